@@ -19,6 +19,8 @@ Extra legs of the pipeline workload (all outside the timed region of `value`):
   parity        tests/accuracy.py on a bounded sample: HIP pipeline (product defaults) vs the fp32 oracle (AP / AR300 / top-1)
   cpu_baseline  the oracle timed on this box's host cores
   --verify      per-image SHA-256 of (boxes, scores, matched indices) gathered to rank 0: identical for 1/2/4/8-GPU runs
+  --dump-outputs DIR   the arrays the last timed step returned, as DIR/<name>.npy (seeded inputs: comparable across builds)
+`--steps` is the number of timed steps of `value` (split into `--windows` windows); `ms_per_step` is one step at the median window's rate.
 """
 import argparse
 import hashlib
@@ -55,7 +57,8 @@ def parse():
     ap.add_argument('--detector-precision', default='fp16', choices=['bf16', 'fp16'],
                     help="storage type of the detector's weights / activations: fp16 (the product default: the mode that meets north_star's 0.1 pt "
                          "tolerance, same MFMA rate) or bf16 (opt-in; the embedder and the matcher compute in bf16 in both)")
-    ap.add_argument('--windows', type=int, default=3, help='timed windows of --steps steps each; value = the median window')
+    ap.add_argument('--windows', type=int, default=3, help='the --steps timed steps are split into this many back-to-back windows '
+                                                            '(fewer when --steps is smaller); value = the median window')
     ap.add_argument('--no-workloads', action='store_true', help='skip the configs[1] / configs[3] figures appended to the pipeline line')
     ap.add_argument('--verify', action='store_true', help='gather per-image result digests to rank 0 (8e: identical across world sizes)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -69,7 +72,16 @@ def parse():
     ap.add_argument('--allow-stub', action='store_true', help='tests only: honour CVPCE_BENCH_STUB (a CPU stand-in for the HIP pipeline; the line is stamped "stub")')
     ap.add_argument('--details', default=None, help='where rank 0 writes the FULL result object (per-layer tables, stages, every co-headline object); '
                                                     'default bench_details.json beside bench.py.  The printed line is the compact form (< 4 KB) and names this file')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the arrays the timed path returned in its last step to DIR/<name>.npy (float32 / '
+                         'float64, at most 64 MB in all; pipeline and detector workloads).  The inputs are seeded: two builds run with '
+                         'the same arguments can be compared output for output.  Under N ranks rank r writes DIR/rank<r>/')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.workload == 'match-stress':
+        ap.error('--dump-outputs: the match-stress workload times graph replays of kernels only and returns no arrays to a caller')
+    return args
 
 
 def spawn_launcher(args):
@@ -331,37 +343,77 @@ def gather_digests(local, world):
     return merged
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, dirname, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: {name: tensor / list} -> dirname/<name>.npy.  Floating arrays are written as float32 (float64 stays float64),
+    integer and boolean ones as float64 (exact below 2**53).  When the whole exceeds `budget` bytes, each array larger than its equal
+    share keeps a fixed seeded sample of its rows (first dimension), in order, and the row numbers kept go to <name>_rows.npy.
+    -> {name: shape written}."""
+    import numpy as np
+    conv = {}
+    for name, v in arrays.items():
+        t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+        conv[name] = (t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).numpy()
+    share = budget // max(1, len(conv))
+    sample = sum(a.nbytes for a in conv.values()) > budget
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, a in conv.items():
+        if sample and a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, min(a.shape[0], share // max(1, a.nbytes // a.shape[0])))
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, f'{name}_rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(dirname, f'{name}.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def _dump_dir(args, rank, world):
+    return args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f'rank{rank}')
+
+
 def _sync(dev):
     if dev.type == 'cuda':
         torch.cuda.synchronize()
 
 
+def window_sizes(steps, windows):
+    """`steps` split into `windows` back-to-back windows of near-equal length (fewer windows when there are fewer steps)."""
+    nw = max(1, min(windows, steps))
+    return [steps // nw + (i < steps % nw) for i in range(nw)]
+
+
 def timed_windows(step, steps, windows, dev, collective=True):
-    """`windows` back-to-back timed regions of EXACTLY `steps` calls of `step()`, each bracketed by barrier +
-    torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  -> (median seconds, [seconds per window]).
-    One window of ~1 s decides little on a power-limited part with +-3 % box-to-box spread; the line reports the median
-    and the spread.  collective=False: a rank-0-only side leg (no barrier, no reduction: the other ranks are not there)."""
+    """EXACTLY `steps` calls of `step()` in all, timed as `windows` back-to-back regions (window_sizes), each bracketed by barrier +
+    torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  -> (seconds of `steps` steps at the median window's
+    rate, [seconds per step of each window]).  One window of ~1 s decides little on a power-limited part with +-3 % box-to-box
+    spread; the line reports the median and the spread.  collective=False: a rank-0-only side leg (no barrier, no reduction: the
+    other ranks are not there)."""
     from cvpce_amd import dist as cdist
-    secs = []
-    for _ in range(max(1, windows)):
+    per_step = []
+    for n in window_sizes(steps, windows):
         _sync(dev)
         if collective:
             cdist.barrier()
             _sync(dev)
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n):
             step()
         _sync(dev)
         if collective:
             cdist.barrier()
         dt = time.perf_counter() - t0
-        secs.append(cdist.max_over_ranks(dt, dev) if collective else dt)
-    return sorted(secs)[len(secs) // 2], secs
+        per_step.append((cdist.max_over_ranks(dt, dev) if collective else dt) / n)
+    return sorted(per_step)[len(per_step) // 2] * steps, per_step
 
 
-def window_stats(secs, steps):
-    ms = [round(t / steps * 1e3, 3) for t in secs]
-    return {'n': len(ms), 'steps_each': steps, 'ms_per_step': ms, 'min': min(ms), 'max': max(ms), 'value': 'median window'}
+def window_stats(per_step, steps):
+    ms = [round(t * 1e3, 3) for t in per_step]
+    return {'n': len(ms), 'steps_each': window_sizes(steps, len(ms)), 'ms_per_step': ms, 'min': min(ms), 'max': max(ms),
+            'value': 'median window'}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -565,6 +617,9 @@ def run_pipeline(args, rank, local_rank, world, dev):
     elapsed, window_secs = timed_windows(step, args.steps, args.windows, dev)
     coll_after = dict(cdist.STATS)
     out = outs[0]
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs({k: v for k, v in out.items() if v is not None}, _dump_dir(args, rank, world))
     proposals = float(sum(out['counts_host'])) / max(1, len(images))
 
     # ---- the legs EVERY rank takes part in come first (their barriers must not wait for rank 0's side legs) -----------------------
@@ -590,10 +645,10 @@ def run_pipeline(args, rank, local_rank, world, dev):
         # boundaries -- nothing between the steps (no steady-state collectives)
         collectives['in_timed_windows'] = {k: coll_after[k] - coll_before[k] for k in ('all_gather', 'all_reduce', 'barrier')}
         # derived, not asserted: what the windows issued beyond their own boundary operations, per timed step
-        nw = max(1, args.windows)
+        nw = len(window_secs)
         itw = collectives['in_timed_windows']
         extra = itw['all_gather'] + max(0, itw['all_reduce'] - nw) + max(0, itw['barrier'] - 2 * nw)
-        collectives['data_path_collectives_per_step'] = extra / (nw * args.steps) if extra else 0
+        collectives['data_path_collectives_per_step'] = extra / args.steps if extra else 0
         collectives['gallery_all_gather_mb'] = round(collectives['all_gather_bytes_received'] / 1e6, 2)
 
     # ---- rank-0-only side legs (no collectives below this line: the other ranks are on their way out) -----------------------------
@@ -768,6 +823,8 @@ def run_pipeline(args, rank, local_rank, world, dev):
                      ('cpu_baseline', cpu), ('workloads', workloads), ('verify', verify)):
         if val is not None:
             line[key] = val
+    if dumped is not None:
+        line['dumped_outputs'] = dumped
     if leg_errors:
         line['leg_errors'] = leg_errors
     if stub is not None:
@@ -914,6 +971,7 @@ def detector_workload(dev, ipg, dpi, image_size, steps, warmup, precision='bf16'
     for _ in range(warmup):
         step()
     elapsed, secs = timed_windows(step, steps, windows, dev, collective)
+    last = outs[0]                     # (the profile pass below runs the step again)
     ms = elapsed / steps * 1e3
     gf = 298.4 * ipg
     res = {'images': ipg, 'image_size': image_size, 'detections_per_img': dpi, 'precision': precision, 'ms_per_step': round(ms, 3),
@@ -931,6 +989,7 @@ def detector_workload(dev, ipg, dpi, image_size, steps, warmup, precision='bf16'
         if want_layers:
             res['layers'] = detector_layers(layers, steps, ms)
     res['_elapsed'] = elapsed
+    res['_out'] = last
     return res
 
 
@@ -942,6 +1001,10 @@ def run_detector(args, rank, local_rank, world, dev):
     w = detector_workload(dev, ipg, dpi, args.image_size, args.steps, args.warmup, args.detector_precision, ids=ids, windows=args.windows,
                           want_profile=(not args.no_roofline and rank == 0))
     elapsed = w.pop('_elapsed')
+    last = w.pop('_out')
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(dict(zip(('boxes', 'scores', 'labels', 'det_count', 'count', 'gaussians'), last)), _dump_dir(args, rank, world))
     summ = w.pop('_conv_summary', None)
     roofline = None
     if summ is not None:
@@ -964,6 +1027,8 @@ def run_detector(args, rank, local_rank, world, dev):
         line['roofline'] = roofline
     if cpu is not None:
         line['cpu_baseline'] = cpu
+    if dumped is not None:
+        line['dumped_outputs'] = dumped
     return line
 
 

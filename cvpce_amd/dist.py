@@ -100,7 +100,9 @@ def barrier():
         if dist.get_backend() == 'nccl':
             dist.barrier(device_ids=[torch.cuda.current_device()])     # RCCL: the barrier's all_reduce runs on THIS rank's GPU
         else:
-            dist.barrier()
+            # gloo: a host all_reduce is the barrier.  torch's barrier() first asks the runtime which accelerator the machine has,
+            # and that query opens the GPU in every rank, the CPU-only ranks of a gloo rehearsal included
+            dist.all_reduce(torch.zeros(1))
 
 
 def backend_name():

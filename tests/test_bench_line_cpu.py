@@ -67,3 +67,37 @@ def test_stub_hook_refused_without_flag():
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '0'], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode != 0 and '--allow-stub' in r.stderr and '{"metric"' not in r.stdout
+
+
+def test_timed_windows_run_exactly_steps():
+    """--steps is the number of timed steps in all: the windows split it, they do not each run it."""
+    import torch
+    for steps, windows, n_windows in ((10, 3, 3), (2, 3, 2), (1, 3, 1), (7, 1, 1)):
+        calls = []
+        elapsed, per_step = bench.timed_windows(lambda: calls.append(1), steps, windows, torch.device('cpu'), collective=False)
+        assert len(calls) == steps and len(per_step) == n_windows and sum(bench.window_sizes(steps, windows)) == steps
+        assert elapsed == sorted(per_step)[len(per_step) // 2] * steps
+        st = bench.window_stats(per_step, steps)
+        assert st['n'] == n_windows and sum(st['steps_each']) == steps
+
+
+def test_dump_outputs_types_budget_and_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files (integers exactly, as float64), and a fixed seeded row sample when the
+    whole would exceed the budget."""
+    import numpy as np
+    import torch
+    out = {'boxes': torch.arange(24, dtype=torch.float32).view(2, 3, 4), 'emb': torch.ones(5, 2, dtype=torch.bfloat16),
+           'indices': torch.tensor([[2 ** 40, -1]]), 'counts_host': [3, 1]}
+    shapes = bench.dump_outputs(out, str(tmp_path / 'a'))
+    assert shapes == {'boxes': [2, 3, 4], 'emb': [5, 2], 'indices': [1, 2], 'counts_host': [2]}
+    got = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in shapes}
+    assert got['boxes'].dtype == np.float32 and got['emb'].dtype == np.float32 and got['indices'].dtype == np.float64
+    assert np.array_equal(got['boxes'], out['boxes'].numpy()) and got['indices'][0, 0] == 2 ** 40 and list(got['counts_host']) == [3, 1]
+    big = {'x': torch.randn(1000, 64), 'n': torch.arange(4)}
+    for d in ('b', 'c'):
+        bench.dump_outputs(big, str(tmp_path / d), budget=64 * 1024)
+    total = sum(f.stat().st_size for f in (tmp_path / 'b').iterdir())
+    assert total <= 64 * 1024 + 4 * 128                               # (+ the .npy headers)
+    rows = np.load(tmp_path / 'b' / 'x_rows.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 'b' / 'x.npy'), big['x'].numpy()[rows]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / 'c' / 'x_rows.npy')) and not (tmp_path / 'b' / 'n_rows.npy').exists()

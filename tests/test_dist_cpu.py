@@ -146,3 +146,47 @@ def test_bench_main_under_8_gloo_ranks():
     d2 = _bench_stub(2)
     assert d2['n_gpus'] == 2 and d2['config']['collectives']['world_size'] == 2 and d2['verify']['images'] == 16
     assert all(d2['verify']['per_image'][g] == v8['per_image'][g] for g in d2['verify']['per_image'])     # image g: same result at any world size
+
+
+def test_bench_dump_outputs_identical_across_runs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned; with the same arguments two runs write the same arrays
+    (the inputs are seeded), so two builds can be compared output for output."""
+    import numpy as np
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CVPCE_BENCH_STUB='bench_stub:build', OMP_NUM_THREADS='1',
+               PYTHONPATH=os.pathsep.join([os.path.join(root, 'tests'), root, os.environ.get('PYTHONPATH', '')]))
+    runs = []
+    for name in ('a', 'b'):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--gallery', '20',
+                            '--images-per-gpu', '4', '--allow-stub', '--details', str(tmp_path / f'{name}.json'), '--dump-outputs', str(d)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        full = json.load(open(tmp_path / f'{name}.json'))
+        assert full['steps'] == 3 and full['windows']['n'] == 3 and sum(full['windows']['steps_each']) == 3
+        runs.append({p.name: np.load(p) for p in d.iterdir()})
+        assert set(full['dumped_outputs']) == {n[:-4] for n in runs[-1]}
+    assert {'boxes.npy', 'scores.npy', 'indices.npy', 'embeddings.npy', 'counts_host.npy'} <= set(runs[0])
+    assert all(a.dtype in (np.float32, np.float64) for a in runs[0].values())
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+
+
+def test_gloo_barrier_leaves_the_gpu_alone(monkeypatch, tmp_path):
+    """A gloo rank's barrier synchronises on the host: torch's barrier() asks the runtime for the machine's accelerator, which opens
+    the GPU in every CPU-only rank of a rehearsal (eight ranks: eight processes holding the device)."""
+    import torch.distributed as dist
+    from cvpce_amd import dist as cdist
+
+    def no_query():
+        raise AssertionError('the gloo barrier queried the accelerator')
+    monkeypatch.setattr(torch._C, '_get_accelerator', no_query)
+    dist.init_process_group('gloo', init_method=f'file://{tmp_path}/store', rank=0, world_size=1)
+    try:
+        before = cdist.STATS['barrier']
+        cdist.barrier()
+        assert cdist.STATS['barrier'] == before + 1
+    finally:
+        dist.destroy_process_group()

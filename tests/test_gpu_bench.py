@@ -43,7 +43,7 @@ def _check_compact(c, d):
 
 
 def test_pipeline_line_small(cuda, tmp_path):
-    c, d = _run(tmp_path, '--steps', '2', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--gallery', '128', '--no-peaks')
+    c, d = _run(tmp_path, '--steps', '3', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--gallery', '128', '--no-peaks')
     _check_compact(c, d)
     assert BASE <= set(c) and c['config']['detector_precision'] == 'fp16' and c['config']['collectives'] is None
     assert c['value_lists_off'] == d['value_lists_off'] and c['value_planted_boxes'] == d['value_planted_boxes'] and c['value_with_h2d'] == d['value_with_h2d']
