@@ -13,7 +13,8 @@
 // staged double buffer (same pipeline as conv_igemm).  Epilogue: the tile's
 // distances go to LDS as [g][q] (conflict-free both ways), every query finds
 // its k smallest (distance, index) pairs lexicographically (ties -> lowest
-// index), partials [Q][tiles_g][k] are merged by a second tiny kernel.
+// index), partials [Q][tiles_g][k] are merged by a second tiny kernel.  k > 16 (up to the gallery size): the
+// distances go to a block in the workspace instead, followed by an exact per-query select and sort (match_select_kernel).
 #include "common.h"
 #include "../../include/cvpce_amd.h"
 #include <math.h>
@@ -23,7 +24,7 @@
 #define MT_TG 128
 #define MT_TQ 128
 #define MT_BK 64
-#define MATCH_KMAX 16
+#define MATCH_KMAX 16          // k above this takes the large-k path (distance block + per-query select + sort, below)
 
 struct MatchArgs {
     const void* q; const void* g;
@@ -33,14 +34,17 @@ struct MatchArgs {
     // one-launch form of match_big_kernel (k = 1): per-query 64-bit (distance, row) keys combined by agent-scope atomic minima, the
     // last workgroup to finish (ticket) writes the results and restores the state block (cvpce_match_state_init)
     unsigned long long* keys; int* ticket; long long* out_idx; float* out_dist;
+    float* dist; int ldd;                 // large k: the distance block [Qn][ldd] (match_kernel<F32, TQ, true>)
 };
 
 // (distance, row) as ONE unsigned 64-bit key whose integer order is the lexicographic order: the float's bits made monotone
 // (negative: all bits flipped, non-negative: sign bit set) above the row index
-__device__ __forceinline__ unsigned long long match_key(float d, int i) {
+__device__ __forceinline__ unsigned match_key32(float d) {
     const unsigned b = __float_as_uint(d);
-    const unsigned o = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return ((unsigned long long)o << 32) | (unsigned)i;
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long match_key(float d, int i) {
+    return ((unsigned long long)match_key32(d) << 32) | (unsigned)i;
 }
 __device__ __forceinline__ float match_key_distance(unsigned long long key) {
     const unsigned o = (unsigned)(key >> 32);
@@ -100,7 +104,8 @@ __device__ __forceinline__ bool lex_lt(float d, int i, float e, int j) { return 
 // TQ = queries per tile: 128 (waves 2 x 2, 64 gallery rows x 64 queries each) or 64 (64 x 32 each; 48 KiB of LDS, three
 // workgroups per CU).  Which one a launch takes is a question of tile COUNT, not of kernel quality: 1 600 x 10 000 gives
 // 13 x 79 = 1 027 tiles of 128 x 128 -- on 512 workgroup slots a third round for three tiles.
-template <bool F32, int TQ>
+// STORE (the large-k path): the epilogue writes the tile's distances to the block a.dist [Qn][a.ldd] instead of selecting.
+template <bool F32, int TQ, bool STORE = false>
 __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs a) {
     static_assert(TQ == 128 || TQ == 64, "query tile");
     constexpr int NT = TQ / 64;                      // 32-query MFMA blocks per wave
@@ -265,6 +270,44 @@ __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs 
     if constexpr (NS > 1) {                                         // the K-steps left over
         if (kt < nk) k_step(kt, std::integral_constant<int, 1 % NS>{});
         if constexpr (NS > 2) { if (kt + 1 < nk) k_step(kt + 1, std::integral_constant<int, 2 % NS>{}); }
+    }
+
+    if constexpr (STORE) {
+        // ---- epilogue of the large-k path: distances -> LDS [q][g] (rows padded to 129 floats: the fragment writes of a lane
+        // half hit 32 different banks), then every query's 128 distances to its row of the block, coalesced along g.  The
+        // distance expression, the NaN rule and the rows past the gallery (+inf) are those of the selecting epilogue below.
+        constexpr int LD = MT_TG + 1;
+        float* Ts = reinterpret_cast<float*>(smem);                    // TQ x 129 f32 = 66 | 33 KiB (the staging is free: the
+        float* s_gn = reinterpret_cast<float*>(smem + TQ * LD * 4);    // last K-step ended on a barrier)
+        if (tid < MT_TG) {
+            const int gg = tile_g * MT_TG + tid;
+            s_gn[tid] = match_norm_term<F32>((gg < a.Gn) ? a.gn[gg] : 1.f);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int ql = wp * 32 * NT + nt * 32 + lr;
+            const int qg = tile_q * TQ + ql;
+            const float qn = match_norm_term<F32>((qg < a.Qn) ? a.qn[qg] : 1.f);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int gl = wc * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int gg = tile_g * MT_TG + gl;
+                    float d = INFINITY;
+                    if (gg < a.Gn) {
+                        d = match_distance<F32>(acc[mt][nt][r], qn, s_gn[gl]);
+                        if (!(d == d)) d = INFINITY;
+                    }
+                    Ts[ql * LD + gl] = d;
+                }
+        }
+        __syncthreads();
+        const int qv = min(TQ, a.Qn - tile_q * TQ);                   // query rows of this tile inside the block
+        float* out = a.dist + (size_t)tile_q * TQ * a.ldd + (size_t)tile_g * MT_TG;
+        for (int i = tid; i < qv * MT_TG; i += 256) out[(size_t)(i >> 7) * a.ldd + (i & 127)] = Ts[(i >> 7) * LD + (i & 127)];
+        return;
     }
 
     // ---- epilogue: distances -> LDS [g][q], then per-query top-k -------------
@@ -737,6 +780,246 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Large k (MATCH_KMAX < k <= Gn).  The fused epilogues above cost O(k) selection rounds per tile and O(k^2 tiles) in the merge,
+// so past k = 16 the search changes algorithm, per query chunk of the call:
+//   1. match_kernel<F32, TQ, true> writes the chunk's distances [Qc][Gpad] (fp32, Gpad = Gn rounded up to the 128-row tile);
+//   2. match_select_kernel, one workgroup per query: an exact radix select of the k smallest (distance, row) pairs, written
+//      unordered as 64-bit keys [Qc][k];
+//   3. match_sort_kernel sorts them in LDS (bitonic, runs of MATCH_SORT_RUN keys) and writes the results; k above one run:
+//      match_merge_runs_kernel merges sorted runs pairwise through the workspace until one run is left.
+//
+// Keys: the 32-bit monotone image of the distance (match_key32) above the row index.  The epilogue's distances are
+// 1 - dot / (|q| |g|) or fma(-dot, 1/|q| 1/|g|, 1): an exact zero of `1 - x` is +0 in round-to-nearest, so -0.0 never occurs,
+// and NaN was made +inf -- on these values the integer order of the keys IS the lexicographic order lex_lt, ties to the
+// lower row included.  Distances come back from the keys bit for bit (match_key_distance).
+// ---------------------------------------------------------------------------------------------------------------------
+#define MATCH_LK_BUDGET (256ull << 20)    // workspace of the large-k path: queries are processed in chunks that fit this
+#define MATCH_SORT_RUN 16384              // keys sorted in LDS by one workgroup (128 KiB of 64-bit keys)
+#define MATCH_SEL_THREADS 512
+#define MATCH_SEL_BINS 2048               // histogram of one select pass: 11 bits of the key
+#define MATCH_SEL_STAGE 32768             // rows of a query kept in LDS during the select (128 KiB); longer rows stream from L2
+
+struct MatchLargeK {
+    int qc;                                // queries per chunk
+    size_t gpad;                           // row stride of the distance block
+    size_t dist_bytes, surv_bytes;         // distance block, survivor keys (twice when the merge passes need a ping-pong buffer)
+    size_t bytes;
+};
+static MatchLargeK match_large_k_plan(int Qn, int Gn, int k) {
+    MatchLargeK p;
+    p.gpad = ((size_t)Gn + MT_TG - 1) / MT_TG * MT_TG;
+    const int nsurv = k > MATCH_SORT_RUN ? 2 : 1;
+    const size_t per = p.gpad * 4 + (size_t)k * 8 * nsurv;
+    size_t qc = MATCH_LK_BUDGET / per;
+    if (qc >= MT_TQ) qc = qc / MT_TQ * MT_TQ;       // whole query tiles where the budget allows
+    if (qc < 1) qc = 1;
+    if (qc > (size_t)Qn) qc = Qn;
+    p.qc = (int)qc;
+    p.dist_bytes = (qc * p.gpad * 4 + 255) / 256 * 256;
+    p.surv_bytes = (qc * (size_t)k * 8 + 255) / 256 * 256;
+    p.bytes = p.dist_bytes + nsurv * p.surv_bytes;
+    return p;
+}
+
+// block-wide exclusive prefix sum of one unsigned per thread (MATCH_SEL_THREADS threads) -> (prefix, total); `red` holds 8 + 1 words
+__device__ __forceinline__ unsigned sel_block_scan(unsigned v, unsigned* red, unsigned& total) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) red[wid] = x;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < MATCH_SEL_THREADS / 64; ++w) {
+        const unsigned t = red[w];
+        before += w < wid ? t : 0u;
+        all += t;
+    }
+    __syncthreads();                       // (red is reused by the next scan)
+    total = all;
+    return before + x - v;
+}
+
+// One workgroup per query row of the distance block: the threshold key T with #(key < T) < k <= #(key <= T) by radix passes
+// over the key range [min, max] (11 bits per pass, histogram in LDS), then every row below T and the lowest-index rows equal to T
+// (an ordered block scan, no atomics) -> surv[q][0..k) = (key << 32 | row), unordered.
+template <bool STAGED>
+__global__ __launch_bounds__(MATCH_SEL_THREADS) void match_select_kernel(const float* __restrict__ dist, int ldd, int Gn, int k,
+                                                                         unsigned long long* __restrict__ surv) {
+    extern __shared__ __attribute__((aligned(16))) unsigned sel_smem[];
+    unsigned* hist = sel_smem;                            // [MATCH_SEL_BINS]
+    unsigned* red = sel_smem + MATCH_SEL_BINS;            // [64] scan / reduction scratch
+    unsigned* keys = sel_smem + MATCH_SEL_BINS + 64;      // [Gn] (STAGED)
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float* row = dist + (size_t)blockIdx.x * ldd;
+    unsigned long long* out = surv + (size_t)blockIdx.x * k;
+    auto key_at = [&](int i) -> unsigned {
+        if constexpr (STAGED) return keys[i];
+        else return match_key32(row[i]);
+    };
+
+    // pass 0: the key range (and the row into LDS)
+    unsigned mn = 0xFFFFFFFFu, mx = 0u;
+    for (int i = tid; i < Gn; i += MATCH_SEL_THREADS) {
+        const unsigned u = match_key32(row[i]);
+        if constexpr (STAGED) keys[i] = u;
+        mn = min(mn, u);
+        mx = max(mx, u);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = min(mn, (unsigned)__shfl_xor(mn, off));
+        mx = max(mx, (unsigned)__shfl_xor(mx, off));
+    }
+    if (lane == 0) { red[wid] = mn; red[16 + wid] = mx; }
+    __syncthreads();
+    unsigned lo = red[0], hi = red[16];
+#pragma unroll
+    for (int w = 1; w < MATCH_SEL_THREADS / 64; ++w) { lo = min(lo, red[w]); hi = max(hi, red[16 + w]); }
+    __syncthreads();
+
+    // the k-th smallest key lies in [lo, hi]; kk = its rank among the keys in [lo, hi] (invariant: 1 <= kk <= their count)
+    unsigned kk = (unsigned)k;
+    while (lo != hi) {                                    // (block-uniform: lo, hi, kk live in every thread alike)
+        const unsigned width = hi - lo;
+        const int bits = 32 - __builtin_clz(width);
+        const int shift = bits > 11 ? bits - 11 : 0;      // (width >> shift) < MATCH_SEL_BINS
+        for (int b = tid; b < MATCH_SEL_BINS; b += MATCH_SEL_THREADS) hist[b] = 0u;
+        __syncthreads();
+        for (int i = tid; i < Gn; i += MATCH_SEL_THREADS) {
+            const unsigned u = key_at(i);
+            if (u >= lo && u <= hi) atomicAdd(&hist[(u - lo) >> shift], 1u);
+        }
+        __syncthreads();
+        constexpr int BPT = MATCH_SEL_BINS / MATCH_SEL_THREADS;   // 4 bins per thread
+        unsigned h[BPT], s = 0;
+#pragma unroll
+        for (int j = 0; j < BPT; ++j) { h[j] = hist[tid * BPT + j]; s += h[j]; }
+        unsigned total;
+        const unsigned before = sel_block_scan(s, red, total);
+        if (before < kk && kk <= before + s) {            // exactly one thread: the bin holding rank kk
+            unsigned c = before;
+            int b = 0;
+#pragma unroll
+            for (int j = 0; j < BPT; ++j)
+                if (c + h[j] < kk) { c += h[j]; b = j + 1; }
+                else break;
+            red[32] = (unsigned)(tid * BPT + b);
+            red[33] = kk - c;
+        }
+        __syncthreads();
+        const unsigned bin = red[32];
+        kk = red[33];
+        __syncthreads();
+        const unsigned nlo = lo + (bin << shift);
+        const unsigned span = shift ? ((1u << shift) - 1u) : 0u;
+        hi = (hi - nlo) <= span ? hi : nlo + span;
+        lo = nlo;
+    }
+    const unsigned T = lo, need = kk;                     // take every key < T (k - need of them) and the first `need` keys == T
+    const unsigned nlt = (unsigned)k - need;
+    unsigned lt_base = 0, eq_base = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int base = 0; base < Gn; base += MATCH_SEL_THREADS) {
+        const int i = base + tid;
+        const unsigned u = i < Gn ? key_at(i) : 0xFFFFFFFFu;
+        const bool lt = i < Gn && u < T, eq = i < Gn && u == T;
+        const unsigned long long mlt = __ballot(lt), meq = __ballot(eq);
+        if (lane == 0) { red[wid] = (unsigned)__popcll(mlt); red[16 + wid] = (unsigned)__popcll(meq); }
+        __syncthreads();
+        unsigned olt = 0, oeq = 0, tlt = 0, teq = 0;
+#pragma unroll
+        for (int w = 0; w < MATCH_SEL_THREADS / 64; ++w) {
+            const unsigned a = red[w], b = red[16 + w];
+            olt += w < wid ? a : 0u;
+            oeq += w < wid ? b : 0u;
+            tlt += a;
+            teq += b;
+        }
+        const unsigned long long key = ((unsigned long long)u << 32) | (unsigned)i;
+        if (lt) {
+            const unsigned p = lt_base + olt + (unsigned)__popcll(mlt & below);
+            if (p < nlt) out[p] = key;                    // (always: exactly nlt keys lie below T)
+        }
+        if (eq) {
+            const unsigned p = eq_base + oeq + (unsigned)__popcll(meq & below);
+            if (p < need) out[nlt + p] = key;
+        }
+        lt_base += tlt;
+        eq_base += teq;
+        if (lt_base == nlt && eq_base >= need) break;     // (block-uniform)
+        __syncthreads();
+    }
+}
+
+// Bitonic sort of one run (P keys, a power of two, padded with all-ones keys that sort last) in LDS.  grid (queries, runs): run r of
+// query q = keys [r RUN, min(k, (r + 1) RUN)) of surv[q].  One run: the results are written; several: the sorted run goes back in place.
+__global__ __launch_bounds__(1024) void match_sort_kernel(unsigned long long* __restrict__ surv, int k, int P,
+                                                          long long* __restrict__ out_idx, float* __restrict__ out_dist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int r0 = blockIdx.y * MATCH_SORT_RUN;
+    const int n = min(MATCH_SORT_RUN, k - r0);
+    unsigned long long* run = surv + (size_t)blockIdx.x * k + r0;
+    for (int i = tid; i < P; i += nt) sk[i] = i < n ? run[i] : ~0ull;
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < P / 2; t += nt) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const unsigned long long x = sk[i], y = sk[j];
+                if ((x > y) == ((i & size) == 0)) { sk[i] = y; sk[j] = x; }
+            }
+            __syncthreads();
+        }
+    if (gridDim.y == 1) {
+        for (int i = tid; i < n; i += nt) {
+            const unsigned long long key = sk[i];
+            out_idx[(size_t)blockIdx.x * k + i] = (long long)(unsigned)(key & 0xFFFFFFFFull);
+            if (out_dist) out_dist[(size_t)blockIdx.x * k + i] = match_key_distance(key);
+        }
+    } else {
+        for (int i = tid; i < n; i += nt) run[i] = sk[i];
+    }
+}
+
+// One merge pass over sorted runs of w keys: runs 2j and 2j + 1 become one.  Every key finds its place by its rank in the partner
+// run (binary search; keys are distinct: the row index is part of the key).  grid (ceil(k / 256), queries).  out_idx set: the
+// last pass, which writes the results instead of dst.
+__global__ __launch_bounds__(256) void match_merge_runs_kernel(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst,
+                                                               int k, int w, long long* __restrict__ out_idx, float* __restrict__ out_dist) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= k) return;
+    const size_t qo = (size_t)blockIdx.y * k;
+    const unsigned long long* s = src + qo;
+    const long long pair = (long long)i / (2ll * w) * (2ll * w);
+    const long long off = i - pair;
+    const unsigned long long key = s[i];
+    long long p0, p1;                                     // the partner run [p0, p1)
+    if (off < w) { p0 = pair + w; p1 = pair + 2ll * w; }
+    else { p0 = pair; p1 = pair + w; }
+    if (p1 > k) p1 = k;
+    if (p0 > k) p0 = k;
+    long long a = p0, b = p1;                             // first partner key not below `key`
+    while (a < b) {
+        const long long m = (a + b) >> 1;
+        if (s[m] < key) a = m + 1;
+        else b = m;
+    }
+    const long long pos = pair + (off < w ? off : off - w) + (a - p0);
+    if (out_idx) {
+        out_idx[qo + pos] = (long long)(unsigned)(key & 0xFFFFFFFFull);
+        if (out_dist) out_dist[qo + pos] = match_key_distance(key);
+    } else {
+        dst[qo + pos] = key;
+    }
+}
+
 // which bf16 core a launch takes: 0 = by the cost model below, 1 = always the 128-row kernel, 2 = always the 256-row LDS-DMA kernel;
 // g_match_nq = 2..5 pins the 256-row kernel's query-tile width (0 = by the model).  Test / measurement switch: results never depend on it.
 static int g_match_core = []() { const char* e = getenv("CVPCE_MATCH_CORE"); return !e ? 0 : (e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : 0)); }();
@@ -771,8 +1054,75 @@ extern "C" int cvpce_match_state_init(void* state, size_t state_bytes, void* str
 }
 
 extern "C" size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k) {
+    if (k > MATCH_KMAX) return (Qn > 0 && Gn > 0 ? match_large_k_plan(Qn, Gn, k).bytes : 0) + 512;
     const size_t tiles_g = (Gn + MT_TG - 1) / MT_TG;
     return (size_t)Qn * tiles_g * k * 8 + 512;
+}
+
+// query tile of the 128-row bf16 kernel: 64-query tiles cost ~0.6 of a 128-query tile and run three to a CU instead of two; the
+// cheaper schedule in whole rounds of the chip wins (CVPCE_MATCH_TQ = 64 | 128 forces one: dev A/B)
+static int match_small_tq(int tiles_g, int Qn) {
+    static const int forced = []() { const char* e = getenv("CVPCE_MATCH_TQ"); return e ? atoi(e) : 0; }();
+    const long long cus = g_cvpce_persistent_wgs;
+    const long long t128 = (long long)tiles_g * ((Qn + 127) / 128), t64 = (long long)tiles_g * ((Qn + 63) / 64);
+    const double c128 = (double)((t128 + 2 * cus - 1) / (2 * cus)) * 1.0, c64 = (double)((t64 + 3 * cus - 1) / (3 * cus)) * 0.6;
+    return forced == 64 || forced == 128 ? forced : (c64 < c128 ? 64 : 128);
+}
+
+// The large-k search (see match_select_kernel): per chunk of p.qc queries, distance block -> select -> sort [-> merge passes], all on
+// the caller's stream.  The distances come from match_kernel (the 128-row core; its bf16 instances form the same distances as the
+// LDS-DMA core), so a query's first 16 results equal those of the fused path bit for bit.
+static int match_large_k(MatchArgs a, int is_f32, void* workspace, hipStream_t s) {
+    const int Qn = a.Qn, Gn = a.Gn, k = a.k;
+    const MatchLargeK p = match_large_k_plan(Qn, Gn, k);
+    const int lds_store_f32 = 2 * 2 * 128 * 256, lds_store_128 = 128 * (MT_TG + 1) * 4 + 512, lds_store_64 = 2 * (128 + 64) * 128;
+    const bool staged = Gn <= MATCH_SEL_STAGE;
+    const int lds_sel = (MATCH_SEL_BINS + 64 + (staged ? Gn : 0)) * 4;
+    if (!cvpce_smem_attr_done<match_kernel<true, 128, true>>((const void*)match_kernel<true, 128, true>, lds_store_f32) ||
+        !cvpce_smem_attr_done<match_kernel<false, 128, true>>((const void*)match_kernel<false, 128, true>, lds_store_128) ||
+        !cvpce_smem_attr_done<match_kernel<false, 64, true>>((const void*)match_kernel<false, 64, true>, lds_store_64) ||
+        !cvpce_smem_attr_done<match_select_kernel<true>>((const void*)match_select_kernel<true>, (MATCH_SEL_BINS + 64 + MATCH_SEL_STAGE) * 4) ||
+        !cvpce_smem_attr_done<match_sort_kernel>((const void*)match_sort_kernel, MATCH_SORT_RUN * 8))
+        return CVPCE_ERR_LAUNCH;
+    float* dist = (float*)workspace;
+    unsigned long long* surv = (unsigned long long*)((char*)workspace + p.dist_bytes);
+    unsigned long long* tmp = (unsigned long long*)((char*)workspace + p.dist_bytes + p.surv_bytes);
+    const int runs = (k + MATCH_SORT_RUN - 1) / MATCH_SORT_RUN;
+    int P = 64;
+    while (P < k && P < MATCH_SORT_RUN) P <<= 1;
+    const int sort_threads = P / 2 < 64 ? 64 : (P / 2 > 1024 ? 1024 : P / 2);
+    const size_t es = is_f32 ? 4 : 2;
+    a.tiles_g = (Gn + MT_TG - 1) / MT_TG;
+    a.dist = dist;
+    a.ldd = (int)p.gpad;
+    for (int c0 = 0; c0 < Qn; c0 += p.qc) {
+        const int qc = min(p.qc, Qn - c0);
+        MatchArgs c = a;
+        c.q = (const char*)a.q + (size_t)c0 * a.D * es;
+        c.qn = a.qn + c0;
+        c.Qn = qc;
+        long long* oi = a.out_idx + (size_t)c0 * k;
+        float* od = a.out_dist ? a.out_dist + (size_t)c0 * k : nullptr;
+        const int tq = is_f32 ? MT_TQ : match_small_tq(c.tiles_g, qc);
+        c.tiles_q = (qc + tq - 1) / tq;
+        const dim3 grid(c.tiles_g * c.tiles_q);
+        if (is_f32) hipLaunchKernelGGL((match_kernel<true, 128, true>), grid, dim3(256), lds_store_f32, s, c);
+        else if (tq == 128) hipLaunchKernelGGL((match_kernel<false, 128, true>), grid, dim3(256), lds_store_128, s, c);
+        else hipLaunchKernelGGL((match_kernel<false, 64, true>), grid, dim3(256), lds_store_64, s, c);
+        if (staged) hipLaunchKernelGGL(match_select_kernel<true>, dim3(qc), dim3(MATCH_SEL_THREADS), lds_sel, s, (const float*)dist, a.ldd, Gn, k, surv);
+        else hipLaunchKernelGGL(match_select_kernel<false>, dim3(qc), dim3(MATCH_SEL_THREADS), lds_sel, s, (const float*)dist, a.ldd, Gn, k, surv);
+        hipLaunchKernelGGL(match_sort_kernel, dim3(qc, runs), dim3(sort_threads), (size_t)P * 8, s, surv, k, P, oi, od);
+        unsigned long long *src = surv, *dst = tmp;
+        for (long long w = MATCH_SORT_RUN; w < k; w *= 2) {
+            const bool last = 2 * w >= k;
+            hipLaunchKernelGGL(match_merge_runs_kernel, dim3((k + 255) / 256, qc), dim3(256), 0, s, (const unsigned long long*)src, dst, k, (int)w,
+                               last ? oi : nullptr, last ? od : nullptr);
+            unsigned long long* t = src; src = dst; dst = t;
+        }
+        const int rc = cvpce_check_launch();
+        if (rc != CVPCE_OK) return rc;
+    }
+    return CVPCE_OK;
 }
 
 static int match_topk_impl(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
@@ -795,7 +1145,7 @@ static int match_topk_impl(const void* queries, const void* gallery, const float
                            int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
                            void* state, size_t state_bytes, long long* out_idx, float* out_dist, void* stream) {
     if (!queries || !gallery || !q_norms || !g_norms || !workspace || !out_idx) return CVPCE_ERR_ARG;
-    if (D <= 0 || D % MT_BK != 0 || k < 1 || k > MATCH_KMAX || Gn < k) return CVPCE_ERR_ARG;
+    if (D <= 0 || D % MT_BK != 0 || k < 1 || Gn < k) return CVPCE_ERR_ARG;
     if (Qn <= 0) return CVPCE_OK;
     if (workspace_bytes < cvpce_match_workspace_bytes(Qn, Gn, k)) return CVPCE_ERR_ARG;
     {   // 32-bit buffer offsets (rows rounded up to whole tiles stay below 2^32)
@@ -805,17 +1155,10 @@ static int match_topk_impl(const void* queries, const void* gallery, const float
     MatchArgs a;
     a.q = queries; a.g = gallery; a.qn = q_norms; a.gn = g_norms; a.Qn = Qn; a.Gn = Gn; a.D = D; a.k = k;
     a.keys = nullptr; a.ticket = nullptr; a.out_idx = out_idx; a.out_dist = out_dist;
+    a.dist = nullptr; a.ldd = 0;
+    if (k > MATCH_KMAX) return match_large_k(a, is_f32, workspace, (hipStream_t)stream);
     a.tiles_g = (Gn + MT_TG - 1) / MT_TG;
-    // query tile of the bf16 kernel: 64-query tiles cost ~0.6 of a 128-query tile and run three to a CU instead of two; the
-    // cheaper schedule in whole rounds of the chip wins (CVPCE_MATCH_TQ = 64 | 128 forces one: dev A/B)
-    int tq = MT_TQ;
-    if (!is_f32) {
-        static const int forced = []() { const char* e = getenv("CVPCE_MATCH_TQ"); return e ? atoi(e) : 0; }();
-        const long long cus = g_cvpce_persistent_wgs;
-        const long long t128 = (long long)a.tiles_g * ((Qn + 127) / 128), t64 = (long long)a.tiles_g * ((Qn + 63) / 64);
-        const double c128 = (double)((t128 + 2 * cus - 1) / (2 * cus)) * 1.0, c64 = (double)((t64 + 3 * cus - 1) / (3 * cus)) * 0.6;
-        tq = forced == 64 || forced == 128 ? forced : (c64 < c128 ? 64 : 128);
-    }
+    const int tq = is_f32 ? MT_TQ : match_small_tq(a.tiles_g, Qn);
     // Which bf16 core and tile: the LDS-DMA kernel (match_big_kernel, 128 MG gallery rows x 64 NQ queries per workgroup) or the 128-row
     // register-staged one, by estimated time.  Model (microseconds; least-squares fit to tools/dev/bench_match.py on MI355X, 63 launches of
     // 200 ... 3 200 queries x 1 000 ... 10 000 rows x 512 | 1 024, rms error 8 %, picks the fastest variant or one within 1 % of it on all nine

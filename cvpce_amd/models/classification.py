@@ -400,9 +400,11 @@ def distance(emb1, emb2, dim=1):
 def nearest_neighbors(anchors, queries, k=1, dtype=torch.float32):
     """classification.py:90-95 -> (Q,k) int64 indices into `anchors`, ascending cosine distance.
 
-    One MFMA GEMM with a fused top-k epilogue (csrc/match.hip).  dtype=float32 uses the exact-f32
-    matrix pipe (index-exact vs the fp32 oracle on tie-free data); bfloat16 is the fast path.
-    Ties resolve to the lower index (the reference's unstable argsort leaves them unspecified).
+    One MFMA GEMM with a fused top-k epilogue (csrc/match.hip); any k up to len(anchors) -- above 16 the
+    distances go through a block in the workspace and an exact per-query select + sort (same results).
+    dtype=float32 uses the exact-f32 matrix pipe (index-exact vs the fp32 oracle on tie-free data);
+    bfloat16 is the fast path.  Ties resolve to the lower index (the reference's unstable argsort leaves
+    them unspecified).
     """
     if not anchors.is_cuda or not queries.is_cuda:
         raise RuntimeError('nearest_neighbors runs on an MI355X (HIP) device only (no CPU fallback)')

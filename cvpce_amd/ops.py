@@ -971,7 +971,11 @@ def row_norms(x, eps=1e-8):
 
 
 def match_topk(queries, gallery, k=1, q_norms=None, g_norms=None, return_distance=False):
-    """(Q,D), (G,D) same dtype (bf16 | f32), D % 64 == 0 -> (Q,k) int64 [+ (Q,k) f32 distances]."""
+    """(Q,D), (G,D) same dtype (bf16 | f32), D % 64 == 0 -> (Q,k) int64 [+ (Q,k) f32 distances].
+
+    Any k (clamped to G): k <= 16 runs the fused GEMM + top-k, k > 16 the library's large-k path (distance block in query chunks,
+    per-query radix select, LDS sort; workspace under 256 MiB).  Same order either way -- ascending (distance, row) -- and a
+    query's first 16 results equal its k = 16 result bit for bit."""
     _need_cuda(queries, gallery)
     assert queries.dtype == gallery.dtype and queries.dtype in (BF16, torch.float32)
     assert queries.is_contiguous() and gallery.is_contiguous() and queries.shape[1] == gallery.shape[1]

@@ -188,12 +188,13 @@ class Classifier:
         return idx['embedding'], idx['annotations']
 
     def match(self, emb):
-        """(P,1024) f32 unit-norm on device -> (P,k) int64 gallery indices."""
+        """(P,1024) f32 unit-norm on device -> (P,min(k,G)) int64 gallery indices, nearest first (any k: ops.match_topk)."""
         q = ops.pad_features(emb.to(self.match_dtype))
         return ops.match_topk(q, self._gallery, self.k, g_norms=self._gallery_norms)
 
     def classify(self, images, return_embedding=False):
-        """production.py:57-74: images (P,3,256,256) in [0,1] -> list[list[str]] (P x k)."""
+        """production.py:57-74: images (P,3,256,256) in [0,1] -> list[list[str]] (P x k).  (One device-to-host copy of the
+        (P,k) indices per batch -- `.tolist()` -- whatever k is.)"""
         res, embs = [], []
         eng = self.encoder.engine()
         step = max(self.batch_size, ENGINE_BATCH)

@@ -321,7 +321,11 @@ int cvpce_detect_postprocess(const float* const* logits, const float* const* reg
 
 /* classification.py:87-95: nearest_neighbors(anchors=gallery, queries, k) -> (Q,k) int64, ascending
  * cosine distance, ties to the lower index.  Rows bf16 (is_f32 = 0) or f32 (is_f32 = 1), D % 64 == 0;
- * norms from cvpce_row_norms (already clamped at eps). */
+ * norms from cvpce_row_norms (already clamped at eps).  1 <= k <= Gn.  k <= 16: one GEMM with a fused per-tile top-k
+ * + a merge launch.  k > 16: per chunk of queries a distance block [chunk][Gn rounded up to 128] in the workspace, an exact
+ * per-query radix select and an LDS sort (+ merge passes for k > 16 384); the workspace then stays under 256 MiB (one
+ * query's distance row and survivor keys at the least).  Either way the same results: a query's first 16 entries are
+ * its k = 16 result bit for bit.  No host synchronisation, no device allocation: everything runs on `stream`. */
 int cvpce_row_norms(const void* x, float* out, int rows, int D, int is_f32, float eps, void* stream);
 size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k);
 int cvpce_match_topk(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
