@@ -27,6 +27,13 @@
 // Ordering rule: the reference sorts on sigmoid scores with an unstable sort,
 // leaving ties unspecified.  Here every ordering uses the fp32 *logit* (a
 // monotone refinement of the score order) and then the lower index.
+//
+// Capacity.  Every kernel is instantiated for CAP = the largest per-level top-k it holds: CAP 1024 (topk <= 1024, L * topk <=
+// 8192 candidates: torchvision's default topk_candidates 1000) and CAP 4096 (topk <= 4096, L * topk <= 20 480), chosen on the
+// host from topk.  The CAP 1024 instantiations are the original kernels with the original launch shapes and workspace.  At
+// CAP 4096 a level's survivors are sorted by the LDS bitonic network, decode_merge holds 8 runs of 4096 (the same 32 keys per
+// thread) so larger levels take the one-kernel decode, nms_sort holds L * topk keys in dynamic LDS (<= 80 KiB) and nms_scan
+// keeps 20 480 indices (80 KiB of static LDS) and fetches the rows of kept boxes after each chunk resolves.
 #include "common.h"
 #include "../../include/cvpce_amd.h"
 #include <math.h>
@@ -34,7 +41,13 @@
 #pragma clang fp contract(off)
 
 #define MAX_LEVELS 8
-#define SORT_CAP 8192
+#define SORT_CAP 8192            // candidates per image at CAP 1024 (8 levels x 1024)
+#define TOPK_CAP_WIDE 4096       // largest topk (CAP of the wide instantiations)
+#define SORT_CAP_WIDE 20480      // candidates per image at CAP 4096 (5 levels x 4096)
+
+template <int CAP> struct Cap;
+template <> struct Cap<1024> { static constexpr int sort = SORT_CAP; };
+template <> struct Cap<TOPK_CAP_WIDE> { static constexpr int sort = SORT_CAP_WIDE; };
 
 struct DecodeArgs {
     const float* logits[MAX_LEVELS];   // [N][gh*gw*A*K]
@@ -51,7 +64,7 @@ struct DecodeArgs {
     int* cand_count;                   // [N][L]
     // chunked form (decode_select_kernel + decode_merge_kernel)
     int chunk_first[MAX_LEVELS + 1];   // first chunk of each level in an image's chunk list; [L] = chunks per image
-    unsigned long long* runs;          // [N][chunks per image][1024] (logit key << 32 | ~index in level), unsorted, 0 = empty
+    unsigned long long* runs;          // [N][chunks per image][CAP] (logit key << 32 | ~index in level), unsorted, 0 = empty
     float t_lo, t_hi;                  // score_passes: logits outside [t_lo, t_hi] are decided without evaluating the sigmoid
 };
 
@@ -60,6 +73,37 @@ __device__ __forceinline__ unsigned ordered_key(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.f / (1.f + expf(-x)); }
+
+// candidate t (rank t of its level) from its composite: anchor synthesis, box decode and clip (BoxCoder.decode_single,
+// clip_boxes_to_image), written to slot level * topk + t of the image's candidate list
+__device__ __forceinline__ void decode_candidate(const DecodeArgs& a, int level, int img, int t, unsigned long long comp,
+                                                 const float* lg, const float* rg) {
+    const int gw = a.gw[level];
+    const int slot = a.L * a.topk;
+    const int idx = (int)(0xFFFFFFFFu - (unsigned)(comp & 0xFFFFFFFFull));
+    const float l = lg[idx];
+    const int aidx = idx / a.K, label = idx - aidx * a.K;
+    const int cell = aidx / a.A, an = aidx - cell * a.A;
+    const int y = cell / gw, x = cell - y * gw;
+    const float shx = (float)x * (float)a.sw[level], shy = (float)y * (float)a.sh[level];
+    const float* ba = a.base_anchors + ((size_t)level * a.A + an) * 4;
+    const float ax1 = shx + ba[0], ay1 = shy + ba[1], ax2 = shx + ba[2], ay2 = shy + ba[3];
+    const float w = ax2 - ax1, h = ay2 - ay1;
+    const float cx = ax1 + 0.5f * w, cy = ay1 + 0.5f * h;
+    const float4 r = *reinterpret_cast<const float4*>(rg + (size_t)aidx * 4);
+    const float dw = fminf(r.z, a.xform_clip), dh = fminf(r.w, a.xform_clip);
+    const float pcx = r.x * w + cx, pcy = r.y * h + cy;
+    const float pw = expf(dw) * w, ph = expf(dh) * h;
+    float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
+    const float ih = (float)a.image_hw[img * 2 + 0], iw = (float)a.image_hw[img * 2 + 1];
+    x1 = fminf(fmaxf(x1, 0.f), iw); x2 = fminf(fmaxf(x2, 0.f), iw);
+    y1 = fminf(fmaxf(y1, 0.f), ih); y2 = fminf(fmaxf(y2, 0.f), ih);
+    const size_t o = (size_t)img * slot + (size_t)level * a.topk + t;
+    *reinterpret_cast<float4*>(a.cand_boxes + o * 4) = make_float4(x1, y1, x2, y2);
+    a.cand_scores[o] = sigmoidf_ref(l);
+    a.cand_logits[o] = l;
+    a.cand_labels[o] = label;
+}
 
 // descending bitonic sort of n (power of two) 64-bit keys in LDS by `nthreads` threads
 __device__ void bitonic_sort_desc(unsigned long long* s, int n, int tid, int nthreads) {
@@ -104,8 +148,9 @@ __device__ __forceinline__ void bitonic_sort1024_desc(unsigned long long* s, int
     __syncthreads();
 }
 
+template <int CAP>
 __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
-    __shared__ unsigned long long sel[1024];
+    __shared__ unsigned long long sel[CAP];
     __shared__ int hist[256];
     __shared__ int wtot[16];
     __shared__ int s_cnt, s_prefix, s_need, s_nsel, s_eqbase, s_eqtotal;
@@ -117,7 +162,7 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
     const float* rg = a.regs[level] + (size_t)img * (size_t)(gh * gw * a.A) * 4;
 
     if (tid == 0) { s_cnt = 0; s_nsel = 0; s_eqbase = 0; s_eqtotal = 0; }
-    sel[tid] = 0ull;
+    for (int i = tid; i < CAP; i += 1024) sel[i] = 0ull;
     __syncthreads();
     // The first R * 1024 logits of a level are read from memory ONCE: every thread keeps R keys in registers (0 = not a
     // candidate) and the count, the four radix passes and the compaction run on them; what lies beyond (P3 of an 800 x 800
@@ -144,7 +189,7 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
     };
     auto take = [&](unsigned key, int i) {
         const int pos = atomicAdd(&s_nsel, 1);
-        if (pos < 1024) sel[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
+        if (pos < CAP) sel[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
     };
     // count candidates above the score threshold
     int local = 0;
@@ -263,36 +308,10 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
         }
     }
     __syncthreads();
-    bitonic_sort_desc(sel, 1024, tid, 1024);
+    bitonic_sort_desc(sel, CAP, tid, 1024);
 
-    const int slot = a.L * a.topk;
     if (tid == 0) a.cand_count[img * a.L + level] = k;
-    if (tid < k) {
-        const unsigned long long comp = sel[tid];
-        const int idx = (int)(0xFFFFFFFFu - (unsigned)(comp & 0xFFFFFFFFull));
-        const float l = lg[idx];
-        const int aidx = idx / a.K, label = idx - aidx * a.K;
-        const int cell = aidx / a.A, an = aidx - cell * a.A;
-        const int y = cell / gw, x = cell - y * gw;
-        const float shx = (float)x * (float)a.sw[level], shy = (float)y * (float)a.sh[level];
-        const float* ba = a.base_anchors + ((size_t)level * a.A + an) * 4;
-        const float ax1 = shx + ba[0], ay1 = shy + ba[1], ax2 = shx + ba[2], ay2 = shy + ba[3];
-        const float w = ax2 - ax1, h = ay2 - ay1;
-        const float cx = ax1 + 0.5f * w, cy = ay1 + 0.5f * h;
-        const float4 r = *reinterpret_cast<const float4*>(rg + (size_t)aidx * 4);
-        const float dw = fminf(r.z, a.xform_clip), dh = fminf(r.w, a.xform_clip);
-        const float pcx = r.x * w + cx, pcy = r.y * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
-        const float ih = (float)a.image_hw[img * 2 + 0], iw = (float)a.image_hw[img * 2 + 1];
-        x1 = fminf(fmaxf(x1, 0.f), iw); x2 = fminf(fmaxf(x2, 0.f), iw);
-        y1 = fminf(fmaxf(y1, 0.f), ih); y2 = fminf(fmaxf(y2, 0.f), ih);
-        const size_t o = (size_t)img * slot + (size_t)level * a.topk + tid;
-        *reinterpret_cast<float4*>(a.cand_boxes + o * 4) = make_float4(x1, y1, x2, y2);
-        a.cand_scores[o] = sigmoidf_ref(l);
-        a.cand_logits[o] = l;
-        a.cand_labels[o] = label;
-    }
+    for (int t = tid; t < k; t += 1024) decode_candidate(a, level, img, t, sel[t], lg, rg);
 }
 
 // ---------------------------------------------------------------------------
@@ -305,25 +324,26 @@ __device__ __forceinline__ bool score_passes(float l, float thresh, float t_lo, 
 }
 
 #define DECODE_CHUNK 8192          // logits per decode_select workgroup (8 per thread, in registers)
-#define DECODE_MAX_RUNS 32         // runs one decode_merge workgroup holds in registers (one entry per thread and run)
+#define DECODE_MAX_RUNS 32         // 1024-entry runs one decode_merge workgroup holds in registers (one entry per thread and run)
 #define DECODE_RUNS_PER_LEVEL 12   // workspace room: N * L * 12 runs (800^2: 17 per image; 1333^2: 43)
 
+template <int CAP>
 struct SelectShared {
-    unsigned long long sel[1024];
+    unsigned long long sel[CAP];
     unsigned long long prefix;
     int hist[256];
     int cnt, nsel, need, eqtotal;
 };
 
 // Exact top-k of the composites comp[u] != 0 (u < nslots; unique 64-bit values) held in the registers of a 1024-thread
-// workgroup: k = min(count, topk) of them end up in sh.sel[0 .. k) (unsorted, the rest of sel is zero); returns k.
+// workgroup: k = min(count, topk) of them end up in sh.sel[0 .. k) (unsorted, the rest of sel is zero); returns k (topk <= CAP).
 // Radix select from the top byte down; it stops at the first byte where every composite sharing the prefix fits (on random
 // logits after 3 of 8 bytes; ties of the logit are resolved by the index bytes, lowest index first, with no special case).
-template <int R>
-__device__ __forceinline__ int select_topk_regs(const unsigned long long (&comp)[R], int nslots, int topk, SelectShared& sh, int tid) {
+template <int R, int CAP>
+__device__ __forceinline__ int select_topk_regs(const unsigned long long (&comp)[R], int nslots, int topk, SelectShared<CAP>& sh, int tid) {
     const int lane = tid & 63;
     if (tid == 0) { sh.cnt = 0; sh.nsel = 0; }
-    sh.sel[tid] = 0ull;
+    for (int i = tid; i < CAP; i += 1024) sh.sel[i] = 0ull;
     __syncthreads();
     int local = 0;
 #pragma unroll
@@ -408,7 +428,7 @@ __device__ __forceinline__ int select_topk_regs(const unsigned long long (&comp)
                 if (lane == leader) base = atomicAdd(&sh.nsel, __popcll(bal));
                 base = __builtin_amdgcn_readlane(base, leader);
                 const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
-                if (pred && pos < 1024) sh.sel[pos] = c;
+                if (pred && pos < CAP) sh.sel[pos] = c;
             }
         }
     }
@@ -416,8 +436,9 @@ __device__ __forceinline__ int select_topk_regs(const unsigned long long (&comp)
     return k;
 }
 
+template <int CAP>
 __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeArgs a) {
-    __shared__ SelectShared sh;
+    __shared__ SelectShared<CAP> sh;
     const int chunk = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     int level = 0;
     while (level + 1 < a.L && chunk >= a.chunk_first[level + 1]) ++level;
@@ -435,59 +456,37 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeArgs a) {
         // ordered_key is 0 only for one NaN pattern, never a candidate
         comp[u] = ok ? (((unsigned long long)ordered_key(l) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
     }
-    const int k = select_topk_regs<R>(comp, R, a.topk, sh, tid);
+    const int k = select_topk_regs<R, CAP>(comp, R, a.topk, sh, tid);
     (void)k;
-    // the whole 1024-entry run is written (zeros past the chunk's survivors): the merge kernel loads its runs without waiting
+    // the whole CAP-entry run is written (zeros past the chunk's survivors): the merge kernel loads its runs without waiting
     // for their counts
-    a.runs[((size_t)img * a.chunk_first[a.L] + chunk) * 1024 + tid] = sh.sel[tid];
+    for (int i = tid; i < CAP; i += 1024) a.runs[((size_t)img * a.chunk_first[a.L] + chunk) * CAP + i] = sh.sel[i];
 }
 
+template <int CAP>
 __global__ __launch_bounds__(1024) void decode_merge_kernel(DecodeArgs a) {
-    __shared__ SelectShared sh;
+    __shared__ SelectShared<CAP> sh;
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     const int gh = a.gh[level], gw = a.gw[level];
     const int n = gh * gw * a.A * a.K;
     const float* lg = a.logits[level] + (size_t)img * n;
     const float* rg = a.regs[level] + (size_t)img * (size_t)(gh * gw * a.A) * 4;
-    const int nch = a.chunk_first[level + 1] - a.chunk_first[level];         // <= DECODE_MAX_RUNS (host)
-    const size_t run0 = (size_t)img * a.chunk_first[a.L] + a.chunk_first[level];
+    // the level's runs are contiguous: nch * CAP entries, CAP / 1024 slots per run (nch <= DECODE_MAX_RUNS * 1024 / CAP, host)
+    const int nch = a.chunk_first[level + 1] - a.chunk_first[level];
+    const int nslots = nch * (CAP / 1024);
+    const unsigned long long* run = a.runs + ((size_t)img * a.chunk_first[a.L] + a.chunk_first[level]) * CAP;
     unsigned long long comp[DECODE_MAX_RUNS];
 #pragma unroll
     for (int u = 0; u < DECODE_MAX_RUNS; ++u) {
         comp[u] = 0ull;
-        if (u < nch) comp[u] = a.runs[(run0 + u) * 1024 + tid];    // (independent loads, all in flight together)
+        if (u < nslots) comp[u] = run[(size_t)u * 1024 + tid];    // (independent loads, all in flight together)
     }
-    const int k = select_topk_regs<DECODE_MAX_RUNS>(comp, nch, a.topk, sh, tid);
-    bitonic_sort1024_desc(sh.sel, tid);
+    const int k = select_topk_regs<DECODE_MAX_RUNS, CAP>(comp, nslots, a.topk, sh, tid);
+    if constexpr (CAP == 1024) bitonic_sort1024_desc(sh.sel, tid);
+    else bitonic_sort_desc(sh.sel, CAP, tid, 1024);
 
-    const int slot = a.L * a.topk;
     if (tid == 0) a.cand_count[img * a.L + level] = k;
-    if (tid < k) {
-        const unsigned long long c = sh.sel[tid];
-        const int idx = (int)(0xFFFFFFFFu - (unsigned)(c & 0xFFFFFFFFull));
-        const float l = lg[idx];
-        const int aidx = idx / a.K, label = idx - aidx * a.K;
-        const int cell = aidx / a.A, an = aidx - cell * a.A;
-        const int y = cell / gw, x = cell - y * gw;
-        const float shx = (float)x * (float)a.sw[level], shy = (float)y * (float)a.sh[level];
-        const float* ba = a.base_anchors + ((size_t)level * a.A + an) * 4;
-        const float ax1 = shx + ba[0], ay1 = shy + ba[1], ax2 = shx + ba[2], ay2 = shy + ba[3];
-        const float w = ax2 - ax1, h = ay2 - ay1;
-        const float cx = ax1 + 0.5f * w, cy = ay1 + 0.5f * h;
-        const float4 r = *reinterpret_cast<const float4*>(rg + (size_t)aidx * 4);
-        const float dw = fminf(r.z, a.xform_clip), dh = fminf(r.w, a.xform_clip);
-        const float pcx = r.x * w + cx, pcy = r.y * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
-        const float ih = (float)a.image_hw[img * 2 + 0], iw = (float)a.image_hw[img * 2 + 1];
-        x1 = fminf(fmaxf(x1, 0.f), iw); x2 = fminf(fmaxf(x2, 0.f), iw);
-        y1 = fminf(fmaxf(y1, 0.f), ih); y2 = fminf(fmaxf(y2, 0.f), ih);
-        const size_t o = (size_t)img * slot + (size_t)level * a.topk + tid;
-        *reinterpret_cast<float4*>(a.cand_boxes + o * 4) = make_float4(x1, y1, x2, y2);
-        a.cand_scores[o] = sigmoidf_ref(l);
-        a.cand_logits[o] = l;
-        a.cand_labels[o] = label;
-    }
+    for (int t = tid; t < k; t += 1024) decode_candidate(a, level, img, t, sh.sel[t], lg, rg);
 }
 
 // ---------------------------------------------------------------------------
@@ -509,8 +508,11 @@ struct NmsArgs {
     int* done;                         // [N]
 };
 
+template <int CAP>
 __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned keys[];   // L segments of 1024 logit keys (<= 32 KiB)
+    // L segments of `seg` logit keys: 1024 at CAP 1024 (<= 32 KiB), topk at CAP 4096 (L * topk <= 20 480: <= 80 KiB)
+    extern __shared__ __attribute__((aligned(16))) unsigned keys[];
+    const int seg = CAP == 1024 ? 1024 : a.topk;
     __shared__ int offs[MAX_LEVELS + 1];
     __shared__ float s_max[16];
     const int img = blockIdx.x, tid = threadIdx.x;
@@ -523,15 +525,15 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
     __syncthreads();
     const int T = offs[a.L];
     // Each level's candidates arrive sorted (decode: logit descending, then lower anchor index): the keys of level l are laid
-    // into the 1024-entry segment l of LDS and every candidate computes its RANK in the merged order -- its rank in its own
+    // into the segment l of LDS and every candidate computes its RANK in the merged order -- its rank in its own
     // level plus, by binary search, the number of candidates of every other level that precede it -- and is copied straight to
     // that position (a bitonic merge of the segments took 36 network stages over 8192 64-bit keys).  Equal logits: the lower
     // level first, then the lower rank, which is the order of the concatenated candidate list -- so a candidate of level l
     // counts the keys >= its own in the levels below l and the keys > its own in the levels above.
     float mx = -INFINITY;
-    for (int i = tid; i < a.L * 1024; i += 1024) {
+    for (int i = tid; i < a.L * seg; i += 1024) {
         unsigned kv = 0u;
-        const int l = i >> 10, r = i & 1023;
+        const int l = i / seg, r = i - l * seg;
         if (r < offs[l + 1] - offs[l]) {
             const int src = l * a.topk + r;
             kv = ordered_key(a.cand_logits[(size_t)img * slot + src]);
@@ -547,19 +549,18 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
     mx = s_max[0];
     for (int w = 1; w < 16; ++w) mx = fmaxf(mx, s_max[w]);
     if (tid == 0) a.s_total[img] = T;
-    for (int l = 0; l < a.L; ++l) {                                  // (i = l * 1024 + tid: the level is uniform per iteration)
-        const int r = tid;
-        if (r >= offs[l + 1] - offs[l]) continue;
-        const unsigned kv = keys[l * 1024 + r];
+    for (int l = 0; l < a.L; ++l)                                    // (the level is uniform per iteration)
+    for (int r = tid; r < offs[l + 1] - offs[l]; r += 1024) {
+        const unsigned kv = keys[l * seg + r];
         int rank = r;
         for (int m = 0; m < a.L; ++m) {
             if (m == l) continue;
-            const unsigned* seg = keys + m * 1024;
+            const unsigned* keys_m = keys + m * seg;
             const unsigned bound = m < l ? kv - 1u : kv;             // count keys > bound (kv >= 1: ordered_key of a candidate)
             int lo = 0, hi = offs[m + 1] - offs[m];
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
-                if (seg[mid] > bound) lo = mid + 1; else hi = mid;
+                if (keys_m[mid] > bound) lo = mid + 1; else hi = mid;
             }
             rank += lo;
         }
@@ -634,16 +635,22 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(NmsArgs a) {
 //   * all 16 waves then OR the kept rows into the removed-bits of the later words: thread (g, w) owns word w and the kept
 //     boxes 8g .. 8g+7 of the chunk, issues its 8 row loads together (independent, coalesced over w) and merges with one
 //     LDS atomic OR -- the one-wave version fetched the kept rows one after the other, ~0.5 us of L2 latency each.
+// At CAP 4096 (up to 320 words) thread (g, w) owns the words w, w + 128, w + 256 and loads the rows of KEPT boxes only, after
+// the chunk resolves: a ring three chunks deep would take 72 row registers per thread.
+template <int CAP>
 __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
+    constexpr int SCAP = Cap<CAP>::sort;
+    constexpr bool WIDE = SCAP / 64 > 128;
+    constexpr int WPT = (SCAP / 64 + 127) / 128;           // words per thread in the propagation step
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (a.phase == 2 && a.done[img]) return;
     const int T = a.s_total[img] < a.limit ? a.s_total[img] : a.limit;
     const int nw = (T + 63) / 64;
-    __shared__ int keep[SORT_CAP];
-    __shared__ unsigned long long rem[SORT_CAP / 64];      // removed bits per 64-box word
+    __shared__ int keep[SCAP];
+    __shared__ unsigned long long rem[SCAP / 64];          // removed bits per 64-box word
     __shared__ unsigned long long s_kept;
     __shared__ int s_nkept;
-    if (tid < SORT_CAP / 64) rem[tid] = 0ull;
+    for (int i = tid; i < SCAP / 64; i += 1024) rem[i] = 0ull;
     if (tid == 0) s_nkept = 0;
     __syncthreads();
     const unsigned long long* M = a.mask + (size_t)img * a.Tmax * a.words;
@@ -653,7 +660,7 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
     // The rows a chunk may have to propagate -- thread (g, w): word w of its rows 8 g .. 8 g + 7 -- are fetched THREE chunks ahead
     // into a register ring, whether the boxes turn out kept or not (40 KiB of L2 reads per chunk): fetched after the chunk was
     // resolved, their ~1 us round trip was the length of a chunk step (105 us for the 79 chunks of dpi 1000).
-    unsigned long long pv[4][8];
+    unsigned long long pv[WIDE ? 1 : 4][8];
     auto fetch_rows = [&](int bb, unsigned long long (&dst)[8]) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -662,16 +669,18 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
             dst[j] = (bb < nw && w > bb && w < nw) ? M[(size_t)r * a.words + w] : 0ull;
         }
     };
-    fetch_rows(0, pv[0]);
-    fetch_rows(1, pv[1]);
-    fetch_rows(2, pv[2]);
+    if constexpr (!WIDE) {
+        fetch_rows(0, pv[0]);
+        fetch_rows(1, pv[1]);
+        fetch_rows(2, pv[2]);
+    }
     bool full = false;
     for (int b4 = 0; b4 < nw && !full; b4 += 4) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
             const int b = b4 + s4;
             if (b >= nw) break;
-            fetch_rows(b + 3, pv[(s4 + 3) & 3]);
+            if constexpr (!WIDE) fetch_rows(b + 3, pv[(s4 + 3) & 3]);
             if (wave == 0) {
                 const int row = b * 64 + lane;
                 const unsigned long long diag = diag_next;
@@ -697,7 +706,7 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
                 const int nkept = s_nkept;
                 if ((kept >> lane) & 1ull) {
                     const int pos = nkept + __popcll(kept & ((1ull << lane) - 1ull));
-                    if (pos < SORT_CAP) keep[pos] = row;
+                    if (pos < SCAP) keep[pos] = row;
                 }
                 if (lane == 0) { s_kept = kept; s_nkept = nkept + __popcll(kept); }
             }
@@ -705,12 +714,30 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
             const unsigned long long kept = s_kept;
             if (s_nkept >= a.max_keep) { full = true; break; }
             // propagate the kept rows of this chunk to the later words
-            if (w > b && w < nw) {
-                const unsigned sub = (unsigned)(kept >> (8 * g)) & 0xFFu;
-                unsigned long long acc = 0ull;
+            if constexpr (!WIDE) {
+                if (w > b && w < nw) {
+                    const unsigned sub = (unsigned)(kept >> (8 * g)) & 0xFFu;
+                    unsigned long long acc = 0ull;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc |= ((sub >> j) & 1u) ? pv[s4][j] : 0ull;
-                if (acc) atomicOr(&rem[w], acc);
+                    for (int j = 0; j < 8; ++j) acc |= ((sub >> j) & 1u) ? pv[s4][j] : 0ull;
+                    if (acc) atomicOr(&rem[w], acc);
+                }
+            } else {
+                const unsigned sub = (unsigned)(kept >> (8 * g)) & 0xFFu;     // kept rows lie below T
+                if (sub) {
+                    unsigned long long acc[WPT];
+#pragma unroll
+                    for (int m = 0; m < WPT; ++m) {
+                        const int ww = w + 128 * m;
+                        acc[m] = 0ull;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (ww > b && ww < nw && ((sub >> j) & 1u)) acc[m] |= M[(size_t)(b * 64 + 8 * g + j) * a.words + ww];
+                    }
+#pragma unroll
+                    for (int m = 0; m < WPT; ++m)
+                        if (acc[m]) atomicOr(&rem[w + 128 * m], acc[m]);
+                }
             }
             __syncthreads();
         }
@@ -746,18 +773,62 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
     if (tid == 0) { a.out_count[img] = nout; a.out_conf_count[img] = s_conf; }
 }
 
+// per-level top-k capacity of the kernels the host selects for `topk` (0: beyond every instantiation)
+static int topk_capacity(int topk) { return topk <= 1024 ? 1024 : topk <= TOPK_CAP_WIDE ? TOPK_CAP_WIDE : 0; }
+
 extern "C" size_t cvpce_detect_workspace_bytes(int N, int L, int topk) {
     const size_t slot = (size_t)L * topk;
     const size_t Tmax = (slot + 63) / 64 * 64, words = Tmax / 64;
+    const size_t cap = topk_capacity(topk) ? topk_capacity(topk) : 1024;
     size_t b = 0;
     b += (size_t)N * slot * (4 + 1 + 1 + 1) * 4;      // cand boxes/scores/logits/labels
     b += (size_t)N * L * 4;                            // cand_count
     b += (size_t)N * Tmax * (4 + 1 + 1 + 1) * 4;       // sorted boxes/scores/labels/off
     b += (size_t)N * 4;                                // s_total
     b += (size_t)N * Tmax * words * 8;                 // mask
-    b += (size_t)N * L * DECODE_RUNS_PER_LEVEL * 1024 * 8;   // chunk runs
+    b += (size_t)N * L * DECODE_RUNS_PER_LEVEL * cap * 8;   // chunk runs (CAP entries each)
     b += (size_t)N * 4;                                // done flags of the two-phase NMS
     return b + 16 * 256;   // every sub-allocation is rounded up to 256 B
+}
+
+// the five launches of one post-processing call at capacity CAP
+template <int CAP>
+static int launch_postprocess(const DecodeArgs& d, NmsArgs n, bool chunked, int chunks, size_t limit, hipStream_t s) {
+    const int L = d.L, N = d.N;
+    if (chunked && !getenv("CVPCE_DECODE_ONE_KERNEL")) {
+        hipLaunchKernelGGL(decode_select_kernel<CAP>, dim3(chunks, N), dim3(1024), 0, s, d);
+        hipLaunchKernelGGL(decode_merge_kernel<CAP>, dim3(L, N), dim3(1024), 0, s, d);
+    } else {
+        hipLaunchKernelGGL(decode_topk_kernel<CAP>, dim3(L, N), dim3(1024), 0, s, d);
+    }
+    const size_t sort_lds = (size_t)L * (CAP == 1024 ? 1024 : d.topk) * 4;
+    if (sort_lds > 64 * 1024) {
+        // above 64 KiB of dynamic LDS the kernel's limit is raised once per process (gfx950: 160 KiB per CU); the first call of a
+        // geometry runs eagerly, so this never happens inside a graph capture
+        static bool raised = false;
+        if (!raised) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_sort_kernel<CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    SORT_CAP_WIDE * 4) != hipSuccess)
+                return CVPCE_ERR_LAUNCH;
+            raised = true;
+        }
+    }
+    hipLaunchKernelGGL(nms_sort_kernel<CAP>, dim3(N), dim3(1024), sort_lds, s, n);
+    const size_t Tmax = (size_t)n.Tmax, words = (size_t)n.words;
+    if (limit >= Tmax || getenv("CVPCE_NMS_ONE_PHASE")) {
+        n.limit = (int)Tmax; n.phase = 0;
+        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
+        hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
+    } else {
+        const unsigned w1 = (unsigned)(limit / 64);
+        n.limit = (int)limit; n.phase = 1;
+        hipLaunchKernelGGL(nms_mask_kernel, dim3(w1, w1, N), dim3(64), 0, s, n);
+        hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
+        n.limit = (int)Tmax; n.phase = 2;
+        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
+        hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
+    }
+    return cvpce_check_launch();
 }
 
 extern "C" int cvpce_detect_postprocess(const float* const* logits, const float* const* regs, const int* gh,
@@ -770,9 +841,12 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
     if (!logits || !regs || !gh || !gw || !stride_h || !stride_w || !base_anchors || !image_hw || !ratios ||
         !workspace || !out_boxes || !out_scores || !out_labels || !out_count || !out_conf_count)
         return CVPCE_ERR_ARG;
-    if (L < 1 || L > MAX_LEVELS || A < 1 || K < 1 || topk < 1 || topk > 1024 || detections_per_img < 1)
+    // topk <= 1024: at most 8192 candidates per image (CAP 1024); topk <= 4096: at most 20 480 (CAP 4096)
+    const int cap = topk_capacity(topk);
+    if (L < 1 || L > MAX_LEVELS || A < 1 || K < 1 || topk < 1 || cap == 0 || detections_per_img < 1)
         return CVPCE_ERR_ARG;
-    if ((size_t)L * topk > SORT_CAP || detections_per_img > SORT_CAP) return CVPCE_ERR_ARG;
+    const size_t sort_cap = cap == 1024 ? SORT_CAP : SORT_CAP_WIDE;
+    if ((size_t)L * topk > sort_cap || (size_t)detections_per_img > sort_cap) return CVPCE_ERR_ARG;
     if (N <= 0) return CVPCE_OK;
     if (workspace_bytes < cvpce_detect_workspace_bytes(N, L, topk)) return CVPCE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -793,7 +867,7 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
     float* s_off = (float*)take((size_t)N * Tmax * 4);
     int* s_total = (int*)take((size_t)N * 4);
     const size_t max_runs = (size_t)L * DECODE_RUNS_PER_LEVEL;          // per image
-    unsigned long long* runs = (unsigned long long*)take((size_t)N * max_runs * 1024 * 8);
+    unsigned long long* runs = (unsigned long long*)take((size_t)N * max_runs * cap * 8);
     int* done = (int*)take((size_t)N * 4);
     if ((size_t)(p - (char*)workspace) > workspace_bytes) return CVPCE_ERR_ARG;
 
@@ -807,16 +881,18 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
     d.score_thresh = score_thresh; d.xform_clip = xform_clip;
     d.cand_boxes = cand_boxes; d.cand_scores = cand_scores; d.cand_logits = cand_logits; d.cand_labels = cand_labels;
     d.cand_count = cand_count;
-    // chunked form unless a level is too large for one merge workgroup or the image's chunks exceed the workspace's runs
+    // chunked form unless a level is too large for one merge workgroup (DECODE_MAX_RUNS runs of 1024, 8 runs of 4096) or the
+    // image's chunks exceed the workspace's runs
+    const int max_merge = DECODE_MAX_RUNS * 1024 / cap;
     bool chunked = true;
     int chunks = 0;
     for (int l = 0; l < L; ++l) {
         const long long n = (long long)gh[l] * gw[l] * A * K;
         const long long nch = (n + DECODE_CHUNK - 1) / DECODE_CHUNK;
         if (n > 0x7FFFFFFFll) return CVPCE_ERR_ARG;
-        if (nch > DECODE_MAX_RUNS) chunked = false;
+        if (nch > max_merge) chunked = false;
         d.chunk_first[l] = chunks;
-        chunks += (int)(nch < DECODE_MAX_RUNS ? nch : DECODE_MAX_RUNS);
+        chunks += (int)(nch < max_merge ? nch : max_merge);
     }
     d.chunk_first[L] = chunks;
     if ((size_t)chunks > max_runs) chunked = false;
@@ -826,12 +902,6 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
         const double t = log((double)score_thresh / (1.0 - (double)score_thresh)), m = 1e-3 * (1.0 + fabs(t));
         d.t_lo = (float)(t - m); d.t_hi = (float)(t + m);
     }
-    if (chunked && !getenv("CVPCE_DECODE_ONE_KERNEL")) {
-        hipLaunchKernelGGL(decode_select_kernel, dim3(chunks, N), dim3(1024), 0, s, d);
-        hipLaunchKernelGGL(decode_merge_kernel, dim3(L, N), dim3(1024), 0, s, d);
-    } else {
-        hipLaunchKernelGGL(decode_topk_kernel, dim3(L, N), dim3(1024), 0, s, d);
-    }
 
     NmsArgs n;
     n.cand_boxes = cand_boxes; n.cand_scores = cand_scores; n.cand_logits = cand_logits; n.cand_labels = cand_labels;
@@ -840,23 +910,10 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
     n.s_boxes = s_boxes; n.s_scores = s_scores; n.s_labels = s_labels; n.s_off = s_off; n.s_total = s_total;
     n.mask = mask; n.out_boxes = out_boxes; n.out_scores = out_scores; n.out_labels = out_labels;
     n.out_count = out_count; n.out_conf_count = out_conf_count;
-    hipLaunchKernelGGL(nms_sort_kernel, dim3(N), dim3(1024), (size_t)L * 1024 * 4, s, n);
+    n.done = done;
     // phase 1 on the first 8 x detections_per_img candidates (>= 1024), phase 2 on all of them for the images that need it
     size_t limit = (size_t)detections_per_img * 8;
     limit = ((limit < 1024 ? 1024 : limit) + 63) / 64 * 64;
-    n.done = done;
-    if (limit >= Tmax || getenv("CVPCE_NMS_ONE_PHASE")) {
-        n.limit = (int)Tmax; n.phase = 0;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
-        hipLaunchKernelGGL(nms_scan_kernel, dim3(N), dim3(1024), 0, s, n);
-    } else {
-        const unsigned w1 = (unsigned)(limit / 64);
-        n.limit = (int)limit; n.phase = 1;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3(w1, w1, N), dim3(64), 0, s, n);
-        hipLaunchKernelGGL(nms_scan_kernel, dim3(N), dim3(1024), 0, s, n);
-        n.limit = (int)Tmax; n.phase = 2;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
-        hipLaunchKernelGGL(nms_scan_kernel, dim3(N), dim3(1024), 0, s, n);
-    }
-    return cvpce_check_launch();
+    if (cap == 1024) return launch_postprocess<1024>(d, n, chunked, chunks, limit, s);
+    return launch_postprocess<TOPK_CAP_WIDE>(d, n, chunked, chunks, limit, s);
 }

@@ -13,7 +13,9 @@ FrozenBN/BN and fused residual / upsample-add / ReLU epilogues, LDS radix-select
 top-k, bitmask NMS.  There is no CPU path: tensors must live on a HIP device.
 """
 import math
+import numbers
 import os
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -30,6 +32,11 @@ BBOX_XFORM_CLIP = math.log(1000.0 / 16)
 ANCHOR_SIZES = tuple((x, int(x * 2 ** (1.0 / 3)), int(x * 2 ** (2.0 / 3))) for x in (32, 64, 128, 256, 512))
 ASPECT_RATIOS = (0.5, 1.0, 2.0)
 FPN_CHANNELS = 256
+NUM_LEVELS = len(ANCHOR_SIZES)   # P3 .. P7
+# bounds of torchvision RetinaNet's inference keywords on the HIP path (GaussianLayerNetwork(**kwargs))
+MAX_MIN_SIZE, MAX_MAX_SIZE = 1600, 2667   # largest transform sizes the kernels' index arithmetic is checked for
+MAX_TOPK_CANDIDATES = 4096                # csrc/detect.hip: per-level top-k capacity (L * topk <= 20 480)
+MAX_HEAD_OUT_CHANNELS = 128               # A * num_classes and 4 * A: the head's output convs
 USE_HEAD_ATLAS = True   # head towers on ONE atlas of the 5 pyramid levels (one launch per tower layer) instead of per level
 N_SIDE_STREAMS = 4   # head towers of the 5 levels run concurrently on side HIP streams (0 = everything on one stream)
 USE_DETECT_GRAPH = os.environ.get('CVPCE_DETECT_GRAPH', '1') != '0'   # replay the static launch schedule of a batch shape from a hipGraph (captured on the shape's 2nd call)
@@ -223,11 +230,16 @@ class _RetinaNetHead(nn.Module):
 # ---------------------------------------------------------------------------
 # the HIP execution plan
 # ---------------------------------------------------------------------------
-def _base_anchors():
+def _base_anchors(anchor_sizes=None, aspect_ratios=None):
+    """torchvision AnchorGenerator.cell_anchors -> (L, A, 4).  anchor_sizes: one tuple of sizes per level (default ANCHOR_SIZES);
+    aspect_ratios: one tuple per level (default ASPECT_RATIOS on every level); every level must give the same A."""
+    anchor_sizes = ANCHOR_SIZES if anchor_sizes is None else anchor_sizes
+    if aspect_ratios is None:
+        aspect_ratios = (ASPECT_RATIOS,) * len(anchor_sizes)
     out = []
-    for sizes in ANCHOR_SIZES:
+    for sizes, level_ratios in zip(anchor_sizes, aspect_ratios):
         scales = torch.as_tensor(sizes, dtype=torch.float32)
-        ratios = torch.as_tensor(ASPECT_RATIOS, dtype=torch.float32)
+        ratios = torch.as_tensor(level_ratios, dtype=torch.float32)
         h_r = torch.sqrt(ratios)
         w_r = 1 / h_r
         ws = (w_r[:, None] * scales[None, :]).view(-1)
@@ -236,10 +248,14 @@ def _base_anchors():
     return torch.stack(out)  # (L, A, 4)
 
 
-def resized_hw(h, w):
-    scale = float(MIN_SIZE) / float(min(h, w))
-    if float(max(h, w)) * scale > MAX_SIZE:
-        scale = float(MAX_SIZE) / float(max(h, w))
+def resized_hw(h, w, min_size=None, max_size=None):
+    """GeneralizedRCNNTransform.resize (eval): the short side to min_size unless the long side would exceed max_size
+    (defaults MIN_SIZE, MAX_SIZE)."""
+    min_size = MIN_SIZE if min_size is None else min_size
+    max_size = MAX_SIZE if max_size is None else max_size
+    scale = float(min_size) / float(min(h, w))
+    if float(max(h, w)) * scale > max_size:
+        scale = float(max_size) / float(max(h, w))
     return int(math.floor(float(h) * scale)), int(math.floor(float(w) * scale))
 
 
@@ -283,10 +299,26 @@ class GLNEngine:
         # layer i of BOTH towers as one conv with Cout = 512 (cout tile 0 = the classification tower, 1 = the regression tower): one masked
         # launch per layer instead of two (ops.conv3x3_atlas_paired)
         self.tower_pairs = self.pack_tower_pairs(model, device) if USE_PAIRED_TOWERS else None
-        self.base_anchors = _base_anchors().to(device)
+        # RetinaNet's transform and anchor options are fixed at the model's construction; the thresholds and top-k are read from
+        # the model on every detect (detect_options)
+        tf, ag = getattr(model, 'transform', None), getattr(model, 'anchor_generator', None)
+        self.min_size = tf.min_size[-1] if tf is not None else MIN_SIZE
+        self.max_size = tf.max_size if tf is not None else MAX_SIZE
+        self.image_mean = tuple(tf.image_mean) if tf is not None else IMAGE_MEAN
+        self.image_std = tuple(tf.image_std) if tf is not None else IMAGE_STD
+        self.base_anchors = (_base_anchors(*_anchor_spec(ag)) if ag is not None else _base_anchors()).to(device)
+        self._model = weakref.ref(model)
         self.side_streams = [torch.cuda.Stream(device=device) for _ in range(4)] if N_SIDE_STREAMS else []
         self.num_anchors = self.base_anchors.shape[1]
         self.device = device
+
+    def detect_options(self):
+        """(topk_candidates, score_thresh, nms_thresh) of the model as they are now (validated), torchvision's defaults without
+        a model."""
+        model = self._model()
+        if model is None:
+            return TOPK_CANDIDATES, SCORE_THRESH, NMS_THRESH
+        return model._detect_options()
 
     def pack_tower_pairs(self, model, device=None):
         """Layer i of BOTH head towers as one conv with Cout = 512 (cout tile 0 = the classification tower, 1 = the regression tower), for
@@ -322,23 +354,24 @@ class GLNEngine:
 
     # -- stages ---------------------------------------------------------------
     @staticmethod
-    def batch_geometry(images):
-        """-> (original sizes, resized sizes, padded (Hp, Wp)) of GeneralizedRCNNTransform for this list of images."""
+    def batch_geometry(images, min_size=None, max_size=None):
+        """-> (original sizes, resized sizes, padded (Hp, Wp)) of GeneralizedRCNNTransform for this list of images
+        (min_size, max_size: resized_hw's)."""
         sizes = [tuple(i.shape[-2:]) for i in images]
-        rs = [resized_hw(h, w) for h, w in sizes]
+        rs = [resized_hw(h, w, min_size, max_size) for h, w in sizes]
         hp = int(math.ceil(max(r[0] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
         wp = int(math.ceil(max(r[1] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
         return sizes, rs, (hp, wp)
 
     def transform(self, images, out=None):
-        sizes, rs, (hp, wp) = self.batch_geometry(images)
+        sizes, rs, (hp, wp) = self.batch_geometry(images, self.min_size, self.max_size)
         batch = out if out is not None else torch.empty((len(images), hp, wp, 8), dtype=self.dtype, device=self.device)
         assert tuple(batch.shape) == (len(images), hp, wp, 8) and batch.dtype == self.dtype
         if USE_BATCHED_TRANSFORM:
-            ops.gln_transform_batch(images, batch, rs, IMAGE_MEAN, IMAGE_STD)
+            ops.gln_transform_batch(images, batch, rs, self.image_mean, self.image_std)
         else:
             for i, (img, (h, w)) in enumerate(zip(images, rs)):
-                ops.gln_transform_into(img.contiguous(), batch, i, h, w, IMAGE_MEAN, IMAGE_STD)
+                ops.gln_transform_into(img.contiguous(), batch, i, h, w, self.image_mean, self.image_std)
         return batch, sizes, rs
 
     def body(self, x):
@@ -556,7 +589,9 @@ class GLNEngine:
             main.wait_event(ev)
         return cls, reg
 
-    def postprocess(self, cls, reg, padded_hw, resized, original, num_classes, detections_per_img, conf_thresh):
+    def postprocess(self, cls, reg, padded_hw, resized, original, num_classes, detections_per_img, conf_thresh, options=None):
+        """options: (topk_candidates, score_thresh, nms_thresh); None = torchvision's defaults."""
+        topk, score_thresh, nms_thresh = options if options is not None else (TOPK_CANDIDATES, SCORE_THRESH, NMS_THRESH)
         n = cls[0].shape[0]
         grids = [(c.shape[1], c.shape[2]) for c in cls]
         strides = [(padded_hw[0] // g[0], padded_hw[1] // g[1]) for g in grids]
@@ -576,7 +611,7 @@ class GLNEngine:
         image_hw, ratios = cache[key]
         self._keep(cache[key])
         return ops.detect_postprocess(logits, regs, grids, strides, self.base_anchors, image_hw, ratios,
-                                      self.num_anchors, num_classes, TOPK_CANDIDATES, SCORE_THRESH, NMS_THRESH,
+                                      self.num_anchors, num_classes, topk, score_thresh, nms_thresh,
                                       BBOX_XFORM_CLIP, detections_per_img, conf_thresh)
 
     def detect(self, images, num_classes, detections_per_img, conf_thresh=0.5, want_intermediates=False):
@@ -584,21 +619,25 @@ class GLNEngine:
 
         The launch schedule after the transform depends only on the batch geometry, so from the second call of a geometry on
         it is captured into a hipGraph and replayed: ~140 kernel launches become one graph launch (the host cost of the
-        Python -> dispatcher -> ctypes path per launch disappears; the kernels and their results are the same, bit for bit)."""
+        Python -> dispatcher -> ctypes path per launch disappears; the kernels and their results are the same, bit for bit).
+        The model's topk_candidates, score_thresh and nms_thresh are read on every call."""
+        options = self.detect_options()
+        _check_detections_per_img(detections_per_img, options[0])
         if USE_DETECT_GRAPH and not want_intermediates and ops.PROFILE is None:
-            return self._detect_graphed(images, num_classes, detections_per_img, conf_thresh)
+            return self._detect_graphed(images, num_classes, detections_per_img, conf_thresh, options)
         batch, original, resized = self.transform(images)
-        return self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates)
+        return self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates, options)
 
-    def _detect_graphed(self, images, num_classes, detections_per_img, conf_thresh):
+    def _detect_graphed(self, images, num_classes, detections_per_img, conf_thresh, options):
         """Graph cache policy (round-2 advisor finding): captured graphs live in an LRU of MAX_DETECT_GRAPHS entries; how often
         a geometry has been seen is counted in a separate (bounded) table, so first sights never push a captured graph out.
         A geometry is captured on its `_capture_on_sight`-th call (2 to begin with).  When a graph is evicted after fewer than
         4 replays -- the mark of a dataset with many image geometries, where capture (synchronise + private pool + eviction
         churn) costs more than it saves -- the threshold doubles (up to MAX_CAPTURE_ON_SIGHT): only geometries that keep
         coming back are then captured, everything else runs eagerly."""
-        original, resized, padded = self.batch_geometry(images)
-        key = (len(images), padded, tuple(resized), tuple(original), num_classes, detections_per_img, float(conf_thresh))
+        original, resized, padded = self.batch_geometry(images, self.min_size, self.max_size)
+        # (the post-processing options are kernel arguments baked into the capture: a change of one is another graph)
+        key = (len(images), padded, tuple(resized), tuple(original), num_classes, detections_per_img, float(conf_thresh), options)
         graphs = self.__dict__.setdefault('_graphs', OrderedDict())
         entry = graphs.get(key)
         if entry is not None:                               # captured: replay
@@ -620,7 +659,7 @@ class GLNEngine:
         need = self.__dict__.setdefault('_capture_on_sight', CAPTURE_ON_SIGHT)
         if seen < need:                                     # not yet: eager (the first call also fills the host-side caches)
             batch, original, resized = self.transform(images)
-            return self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, False)
+            return self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, False, options)
         static_in = torch.empty((len(images), padded[0], padded[1], 8), dtype=self.dtype, device=self.device)
         self.transform(images, out=static_in)
         torch.cuda.current_stream().synchronize()
@@ -629,13 +668,13 @@ class GLNEngine:
         try:
             # (thread-local capture mode: other threads -- e.g. an RCCL watchdog polling its events -- may keep issuing HIP calls)
             with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                static_out = self._detect_tail(static_in, original, resized, num_classes, detections_per_img, conf_thresh, False)
+                static_out = self._detect_tail(static_in, original, resized, num_classes, detections_per_img, conf_thresh, False, options)
         except Exception:
             # e.g. a host-side cache was evicted since the first call and would have to be refilled (an upload) inside the
             # capture: run this call eagerly -- which refills the caches -- and try the capture again next time
             self.__dict__.pop('_capture_refs', None)
             torch.cuda.synchronize()
-            return self._detect_tail(static_in, original, resized, num_classes, detections_per_img, conf_thresh, False)
+            return self._detect_tail(static_in, original, resized, num_classes, detections_per_img, conf_thresh, False, options)
         while len(graphs) >= MAX_DETECT_GRAPHS:            # least recently used captured graph goes
             _, old = graphs.popitem(last=False)
             if old['replays'] < 4:
@@ -660,7 +699,7 @@ class GLNEngine:
                           '65504 on the first batch -- results of this checkpoint are clipped.  Use model.set_precision("bf16") (8 exponent bits, same '
                           'speed) or gln(..., precision="bf16"); model.saturation_report(images) lists the stages.', RuntimeWarning, stacklevel=3)
 
-    def _detect_tail(self, batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates):
+    def _detect_tail(self, batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates, options=None):
         c2, c3, c4, c5 = self.body(batch)
         feats = self.fpn(c3, c4, c5)
         if self.dtype == ops.F16 and FP16_SATURATION_GUARD and '_saturation' not in self.__dict__ and not torch.cuda.is_current_stream_capturing():
@@ -669,7 +708,7 @@ class GLNEngine:
         gauss, gauss_done = self._beside(1, lambda: self.gaussian_branch(c2, feats[0]))
         cls, reg = self.heads_atlas(feats) if USE_HEAD_ATLAS else self.heads(feats)
         out = self.postprocess(cls, reg, tuple(batch.shape[1:3]), resized, original, num_classes,
-                               detections_per_img, conf_thresh)
+                               detections_per_img, conf_thresh, options)
         if gauss_done is not None:
             torch.cuda.current_stream().wait_event(gauss_done)
         gauss = gauss.permute(0, 3, 1, 2)  # (N,1,h,w) view of the NHWC buffer (C == 1)
@@ -679,11 +718,123 @@ class GLNEngine:
 
 
 # ---------------------------------------------------------------------------
+# RetinaNet inference options (torchvision 0.9 keywords, eval semantics)
+# ---------------------------------------------------------------------------
+class TransformOptions:
+    """The eval-mode settings of torchvision's GeneralizedRCNNTransform under its attribute names (min_size is a tuple; the
+    eval resize uses min_size[-1])."""
+
+    def __init__(self, min_size, max_size, image_mean, image_std, size_divisible=SIZE_DIVISIBLE):
+        self.min_size, self.max_size = min_size, max_size
+        self.image_mean, self.image_std = image_mean, image_std
+        self.size_divisible = size_divisible
+
+    def __repr__(self):
+        return (f'TransformOptions(min_size={self.min_size}, max_size={self.max_size}, image_mean={self.image_mean}, '
+                f'image_std={self.image_std})')
+
+
+class AnchorOptions:
+    """Stand-in for torchvision's AnchorGenerator (not installed here): `.sizes` and `.aspect_ratios`, one tuple per level."""
+
+    def __init__(self, sizes=ANCHOR_SIZES, aspect_ratios=(ASPECT_RATIOS,) * NUM_LEVELS):
+        self.sizes, self.aspect_ratios = sizes, aspect_ratios
+
+    def num_anchors_per_location(self):
+        return [len(s) * len(a) for s, a in zip(self.sizes, self.aspect_ratios)]
+
+    def __repr__(self):
+        return f'AnchorOptions(sizes={self.sizes}, aspect_ratios={self.aspect_ratios})'
+
+
+_TRAINING_KEYWORDS = ('fg_iou_thresh', 'bg_iou_thresh')
+_INFERENCE_KEYWORDS = ('min_size', 'max_size', 'image_mean', 'image_std', 'score_thresh', 'nms_thresh', 'topk_candidates',
+                       'anchor_generator')
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _is_real(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(float(v))
+
+
+def _anchor_spec(anchor_generator):
+    """(sizes, aspect_ratios) of an AnchorGenerator-like object, normalised as torchvision does (a flat sequence of sizes is
+    one size per level; a flat sequence of ratios applies to every level)."""
+    sizes, ratios = anchor_generator.sizes, anchor_generator.aspect_ratios
+    sizes = tuple(tuple(s) if isinstance(s, (list, tuple)) else (s,) for s in sizes)
+    if len(ratios) and not isinstance(ratios[0], (list, tuple)):
+        ratios = (tuple(ratios),) * len(sizes)
+    return sizes, tuple(tuple(r) for r in ratios)
+
+
+def _check_anchor_generator(anchor_generator, num_classes):
+    if not (hasattr(anchor_generator, 'sizes') and hasattr(anchor_generator, 'aspect_ratios')):
+        raise TypeError('anchor_generator needs .sizes and .aspect_ratios (torchvision AnchorGenerator)')
+    sizes, ratios = _anchor_spec(anchor_generator)
+    if len(sizes) != NUM_LEVELS or len(ratios) != NUM_LEVELS:
+        raise ValueError(f'anchor_generator: one entry of sizes and aspect_ratios per FPN level ({NUM_LEVELS}), '
+                         f'got {len(sizes)} and {len(ratios)}')
+    for v in [x for level in sizes + ratios for x in level]:
+        if not (_is_real(v) and v > 0):
+            raise ValueError(f'anchor_generator: sizes and aspect ratios must be positive, got {v!r}')
+    per_level = [len(s) * len(r) for s, r in zip(sizes, ratios)]
+    if len(set(per_level)) != 1 or per_level[0] < 1:
+        raise ValueError(f'anchor_generator: the HIP head needs the same number of anchors per location on every level, got {per_level}')
+    a = per_level[0]
+    if a * num_classes > MAX_HEAD_OUT_CHANNELS or 4 * a > MAX_HEAD_OUT_CHANNELS:
+        raise ValueError(f'anchor_generator: {a} anchors per location give head outputs of {a * num_classes} and {4 * a} channels; '
+                         f'the HIP head supports up to {MAX_HEAD_OUT_CHANNELS}')
+    return a
+
+
+def _check_detections_per_img(detections_per_img, topk_candidates):
+    # the post-processing holds up to 8192 candidates per image at topk <= 1024 and 20 480 above (csrc/detect.hip)
+    cap = 8192 if topk_candidates <= 1024 else NUM_LEVELS * MAX_TOPK_CANDIDATES
+    if not (_is_int(detections_per_img) and 1 <= detections_per_img <= cap):
+        raise ValueError(f'detections_per_img must be an int in [1, {cap}] at topk_candidates {topk_candidates}, got {detections_per_img!r}')
+
+
+def _check_detect_options(topk_candidates, score_thresh, nms_thresh, detections_per_img):
+    if not (_is_int(topk_candidates) and 1 <= topk_candidates <= MAX_TOPK_CANDIDATES):
+        raise ValueError(f'topk_candidates must be an int in [1, {MAX_TOPK_CANDIDATES}], got {topk_candidates!r}')
+    if not (_is_real(score_thresh) and 0 <= score_thresh < 1):
+        raise ValueError(f'score_thresh must be in [0, 1), got {score_thresh!r}')
+    if not (_is_real(nms_thresh) and 0 < nms_thresh <= 1):
+        raise ValueError(f'nms_thresh must be in (0, 1], got {nms_thresh!r}')
+    _check_detections_per_img(detections_per_img, topk_candidates)
+
+
+def _transform_options(min_size, max_size, image_mean, image_std):
+    min_size = tuple(min_size) if isinstance(min_size, (list, tuple)) else (min_size,)
+    if not min_size or not all(_is_int(m) and 1 <= m <= MAX_MIN_SIZE for m in min_size):
+        raise ValueError(f'min_size must be a positive int (or a tuple of them) up to {MAX_MIN_SIZE}, got {min_size!r}')
+    if not (_is_int(max_size) and 1 <= max_size <= MAX_MAX_SIZE):
+        raise ValueError(f'max_size must be a positive int up to {MAX_MAX_SIZE}, got {max_size!r}')
+    stats = []
+    for name, v in (('image_mean', image_mean), ('image_std', image_std)):
+        v = [float(x) if _is_real(x) else None for x in v] if isinstance(v, (list, tuple)) or torch.is_tensor(v) else None
+        if v is None or len(v) != 3 or None in v:
+            raise ValueError(f'{name} must be 3 finite floats, got {v!r}')
+        stats.append(v)
+    if min(stats[1]) <= 0:
+        raise ValueError(f'image_std must be positive, got {stats[1]}')
+    return TransformOptions(min_size, int(max_size), stats[0], stats[1])
+
+
+# ---------------------------------------------------------------------------
 # public API
 # ---------------------------------------------------------------------------
 class GaussianLayerNetwork(nn.Module):
     """Drop-in for proposals.py:162-181 (eval mode): `model(list[Tensor(3,H,W)])` ->
-    `list[dict(boxes, scores, labels, gaussians)]`, boxes in original pixels, scores descending."""
+    `list[dict(boxes, scores, labels, gaussians)]`, boxes in original pixels, scores descending.
+
+    `**kwargs` are torchvision 0.9 RetinaNet's inference keywords, stored under its attribute names: `min_size`, `max_size`,
+    `image_mean`, `image_std` (-> `self.transform`) and `anchor_generator` are fixed at construction; `score_thresh`,
+    `nms_thresh`, `topk_candidates` and `detections_per_img` are read on every forward.  `fg_iou_thresh` / `bg_iou_thresh`
+    (training only) are stored and have no effect.  Bounds: DESIGN.md 1."""
 
     def __init__(self, resnet, num_classes, gaussian_loss_params={}, tanh=False, detections_per_img=1000, precision=None, **kwargs):
         super().__init__()
@@ -692,15 +843,31 @@ class GaussianLayerNetwork(nn.Module):
         if precision not in ops.STORAGE_TYPES:
             raise ValueError(f'precision must be one of {sorted(ops.STORAGE_TYPES)}, got {precision!r}')
         self.precision = precision
-        if kwargs:
-            raise TypeError(f'unsupported RetinaNet overrides on the HIP path: {sorted(kwargs)}')
+        unsupported = sorted(k for k in kwargs if k not in _INFERENCE_KEYWORDS + _TRAINING_KEYWORDS)
+        if unsupported:
+            raise TypeError(f'unsupported RetinaNet overrides on the HIP path: {unsupported}')
+        self.transform = _transform_options(kwargs.get('min_size', MIN_SIZE), kwargs.get('max_size', MAX_SIZE),
+                                            kwargs.get('image_mean', IMAGE_MEAN), kwargs.get('image_std', IMAGE_STD))
+        self.anchor_generator = kwargs['anchor_generator'] if kwargs.get('anchor_generator') is not None else AnchorOptions()
+        num_anchors = _check_anchor_generator(self.anchor_generator, num_classes)
+        self.score_thresh = kwargs.get('score_thresh', SCORE_THRESH)
+        self.nms_thresh = kwargs.get('nms_thresh', NMS_THRESH)
+        self.topk_candidates = kwargs.get('topk_candidates', TOPK_CANDIDATES)
+        _check_detect_options(self.topk_candidates, self.score_thresh, self.nms_thresh, detections_per_img)
+        self.fg_iou_thresh = kwargs.get('fg_iou_thresh', 0.5)
+        self.bg_iou_thresh = kwargs.get('bg_iou_thresh', 0.4)
         self.backbone = BackboneWithFPNAndGaussians(resnet, tanh=tanh)
-        self.head = _RetinaNetHead(FPN_CHANNELS, len(ASPECT_RATIOS) * len(ANCHOR_SIZES[0]), num_classes)
+        self.head = _RetinaNetHead(FPN_CHANNELS, num_anchors, num_classes)
         self.num_classes = num_classes
         self.detections_per_img = detections_per_img
         self.gaussian_loss_params = gaussian_loss_params
         self._engine = None
         self.eval()
+
+    def _detect_options(self):
+        """-> (topk_candidates, score_thresh, nms_thresh) as set now; ValueError when one was set out of range."""
+        _check_detect_options(self.topk_candidates, self.score_thresh, self.nms_thresh, self.detections_per_img)
+        return int(self.topk_candidates), float(self.score_thresh), float(self.nms_thresh)
 
     def load_state_dict(self, *args, **kwargs):
         self._engine = None

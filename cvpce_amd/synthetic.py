@@ -21,8 +21,9 @@ def calibrate_head(model, logit_gain=8.0, logit_bias=1.0):
     return model
 
 
-def synthetic_gln(seed=0, detections_per_img=200, tanh=False, calibrate=True, residual_gain=1.0, precision=None):
-    """Seeded GLN (CPU tensors; call .cuda() to run).
+def synthetic_gln(seed=0, detections_per_img=200, tanh=False, calibrate=True, residual_gain=1.0, precision=None, **options):
+    """Seeded GLN (CPU tensors; call .cuda() to run).  `options`: RetinaNet's inference keywords (GaussianLayerNetwork), e.g.
+    min_size, score_thresh or anchor_generator; the backbone's weights do not depend on them.
 
     residual_gain < 1 scales the last FrozenBN of every bottleneck (the residual branch's output gain).  Plain random init
     (gain 1) makes the ResNet body a strongly amplifying map: rounding differences grow ~10x from C2 to C5, which is not how a
@@ -31,7 +32,11 @@ def synthetic_gln(seed=0, detections_per_img=200, tanh=False, calibrate=True, re
     state = torch.random.get_rng_state()
     torch.manual_seed(seed)
     try:
-        model = proposals.gln(pretrained_backbone=False, tanh=tanh, detections_per_img=detections_per_img, precision=precision)
+        if options:       # (what gln() builds, with the options)
+            model = proposals.GaussianLayerNetwork(proposals.gln_backbone(4, False), 1, tanh=tanh, detections_per_img=detections_per_img,
+                                                   precision=precision, **options)
+        else:
+            model = proposals.gln(pretrained_backbone=False, tanh=tanh, detections_per_img=detections_per_img, precision=precision)
         # give the Gaussian-branch BatchNorms non-trivial running statistics
         for m in model.backbone.gaussian_layer.modules():
             if isinstance(m, torch.nn.BatchNorm2d):
