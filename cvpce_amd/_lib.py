@@ -39,9 +39,7 @@ SIGNATURES = {
     'cvpce_conv3x3_halo': (c_int, [_vp, _vp, _fp, _vp] + [c_int] * 9 + [_vp]),
     'cvpce_conv3x3_halo_mac': (c_int, [_vp, _vp, _fp, _vp, _fp, c_int, c_int] + [c_int] * 8 + [_vp]),
     'cvpce_conv3x3_halo_wide': (c_int, [_vp, _vp, _fp, _vp] + [c_int] * 9 + [_vp]),
-    'cvpce_bottleneck_fused': (c_int, [_vp, _vp, _vp, _fp, _vp, _fp, _vp, _fp, _vp] + [c_int] * 11 + [_vp]),
     'cvpce_conv3x3_halo_masked': (c_int, [_vp, _vp, _fp, _vp, _vp, c_int, _vp] + [c_int] * 8 + [_vp]),
-    'cvpce_conv3x3_halo_masked_paired': (c_int, [_vp, _vp, _fp, _vp, _vp, c_int, _vp] + [c_int] * 9 + [_vp]),
     'cvpce_maxpool2d_nhwc_bf16': (c_int, [_vp, _vp] + [c_int] * 9 + [_vp]),
     'cvpce_relu_bf16': (c_int, [_vp, _vp, c_longlong, _vp]),
     'cvpce_pack_halo_weights': (c_int, [_vp, _vp, c_int, c_int]),
@@ -74,10 +72,7 @@ SIGNATURES = {
                                          _vp, c_size_t, _fp, _fp, _vp, _ip, _ip, _vp]),
     'cvpce_row_norms': (c_int, [_vp, _fp, c_int, c_int, c_int, c_float, _vp]),
     'cvpce_match_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
-    'cvpce_match_set_core': (c_int, [c_int, c_int, c_int, c_int]),
-    'cvpce_match_state_bytes': (c_size_t, [c_int]),
-    'cvpce_match_state_init': (c_int, [_vp, c_size_t, _vp]),
-    'cvpce_match_topk_state': (c_int, [_vp, _vp, _fp, _fp, c_int, c_int, c_int, c_int, c_int, _vp, c_size_t, _vp, c_size_t, _vp, _fp, _vp]),
+    'cvpce_match_set_core': (c_int, [c_int, c_int, c_int]),
     'cvpce_probe_l2_stream': (c_int, [_vp, c_longlong, c_int, _fp, c_int, _vp]),
     'cvpce_probe_mfma_bf16': (c_int, [c_int, c_int, _vp, _fp, c_int, _vp]),
     'cvpce_match_topk': (c_int, [_vp, _vp, _fp, _fp, c_int, c_int, c_int, c_int, c_int, _vp, c_size_t, _vp, _fp, _vp]),
@@ -85,8 +80,8 @@ SIGNATURES = {
 # fp16 twins of the detector's kernels (the opt-in accuracy mode): same argument lists as the functions they are named after
 for _base, _twin in (('cvpce_conv2d_nhwc_bf16', 'cvpce_conv2d_nhwc_f16'), ('cvpce_conv2d_splitk_bf16', 'cvpce_conv2d_splitk_f16'), ('cvpce_conv1x1_nhwc_bf16', 'cvpce_conv1x1_nhwc_f16'),
                      ('cvpce_gln_stem_fused', 'cvpce_gln_stem_fused_f16'), ('cvpce_conv3x3_halo', 'cvpce_conv3x3_halo_f16'),
-                     ('cvpce_conv3x3_halo_wide', 'cvpce_conv3x3_halo_wide_f16'), ('cvpce_conv3x3_halo_thin_out', 'cvpce_conv3x3_halo_thin_out_f16'), ('cvpce_conv3x3_halo_masked', 'cvpce_conv3x3_halo_masked_f16'), ('cvpce_conv3x3_halo_masked_paired', 'cvpce_conv3x3_halo_masked_paired_f16'),
-                     ('cvpce_bottleneck_fused', 'cvpce_bottleneck_fused_f16'), ('cvpce_bottleneck_fused_fm', 'cvpce_bottleneck_fused_fm_f16'),
+                     ('cvpce_conv3x3_halo_wide', 'cvpce_conv3x3_halo_wide_f16'), ('cvpce_conv3x3_halo_thin_out', 'cvpce_conv3x3_halo_thin_out_f16'), ('cvpce_conv3x3_halo_masked', 'cvpce_conv3x3_halo_masked_f16'),
+                     ('cvpce_bottleneck_fused_fm', 'cvpce_bottleneck_fused_fm_f16'),
                      ('cvpce_maxpool2d_nhwc_bf16', 'cvpce_maxpool2d_nhwc_f16'), ('cvpce_relu_bf16', 'cvpce_relu_f16'), ('cvpce_gauss_tail_bf16', 'cvpce_gauss_tail_f16'), ('cvpce_gauss_subnet_bf16', 'cvpce_gauss_subnet_f16'), ('cvpce_conv3x3_thin_bf16', 'cvpce_conv3x3_thin_f16'),
                      ('cvpce_gln_transform', 'cvpce_gln_transform_f16'), ('cvpce_gln_transform_batch', 'cvpce_gln_transform_batch_f16')):
     SIGNATURES[_twin] = SIGNATURES[_base]

@@ -33,12 +33,12 @@ constexpr int BN_M1_PIX = 272;    // mid1 pixels in LDS: 16 x 16 + the wrap-arou
 struct BneckArgs {
     const bf16_t* x;      // [N][H][W][Cin]
     const bf16_t* res;    // [N][H][W][4P]  (x itself when Cin == 4P and the block has no projection shortcut)
-    const bf16_t* w1;     // [..][k1_pad]  rows = P couts, k = ci
-    const bf16_t* w2;     // [..][k2_pad]  rows = P couts, chunk-major k = ((ci/64*3 + kh)*3 + kw)*64 + ci%64
-    const bf16_t* w3;     // [..][k3_pad]  rows = 4P couts, k = ci
+    const bf16_t* w1;     // fragment-major P x Cin    (include/cvpce_amd.h cvpce_bottleneck_fused_fm)
+    const bf16_t* w2;     // fragment-major P x 9P
+    const bf16_t* w3;     // fragment-major 4P x P
     const float *b1, *b2, *b3;
     bf16_t* out;          // [N][H][W][4P]
-    int N, H, W, Cin, k1_pad, k2_pad, k3_pad, tiles_x, tiles_y;
+    int N, H, W, Cin, tiles_x, tiles_y;
     unsigned x_bytes, w1_bytes, w2_bytes, w3_bytes, res_bytes;
 };
 
@@ -47,12 +47,11 @@ struct BneckArgs {
 template <int RB>
 __device__ __forceinline__ unsigned lds_swz(unsigned px) { return RB == 128 ? ((px >> 1) & 7u) : (px & 15u); }
 
-// FM (round 5): the three weight tensors are FRAGMENT-MAJOR -- every MFMA weight fragment this kernel loads is one contiguous KiB, lane L's 16
-// bytes at byte 16 L (layouts: include/cvpce_amd.h cvpce_bottleneck_fused_fm; writer: cvpce_amd/ops.py pack_bottleneck_weights).  From the
-// row-major [Cout][K] tensors a fragment is 16 rows x 64 bytes, no two neighbouring lanes share a 64-byte block, and the texture addresser
-// takes such a load one lane per clock (~61 instead of 16 clocks): 94 of the 138 loads a wave issues per tile are weight fragments, and with
-// eight waves on one addresser that was most of a tile's 24 us.
-template <typename E, int P, bool FM>
+// The three weight tensors are FRAGMENT-MAJOR: every MFMA weight fragment this kernel loads is one contiguous KiB, lane L's 16 bytes at
+// byte 16 L (layouts: include/cvpce_amd.h cvpce_bottleneck_fused_fm; writer: cvpce_amd/ops.py pack_bottleneck_weights).  A fragment of a
+// row-major [Cout][K] tensor would be 16 rows x 64 bytes, no two neighbouring lanes would share a 64-byte block, and the texture addresser
+// takes such a load one lane per clock (~61 instead of 16 clocks): 94 of the 138 loads a wave issues per tile are weight fragments.
+template <typename E, int P>
 __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
     constexpr int RB = 2 * P;                      // bytes per LDS pixel row (mid1 and mid2 alike)
     constexpr int CB1 = P / 16;                    // 16-cout blocks of mid1
@@ -82,9 +81,8 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
     const __amdgpu_buffer_rsrc_t srd_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w3, 0, a.w3_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res_bytes, 0x00020000);
 
-    // row of a 32-cout pair of MFMA blocks that lane m = l16 feeds: MFMA row 4q'+j' of block h is cout 8q' + 4h + j', so that
-    // accumulator lane group q ends up with the 8 CONSECUTIVE couts 8q .. 8q+7 of its pixel (one 16-byte chunk)
-    const int pair_row0 = 8 * (l16 >> 2) + (l16 & 3);     // + 4h
+    // (the weight layout makes MFMA row 4q'+j' of block h of a 32-cout pair cout 8q' + 4h + j', so that accumulator lane group q
+    // ends up with the 8 CONSECUTIVE couts 8q .. 8q+7 of its pixel: one 16-byte chunk)
 
     // =====================================================================================================================
     // stage A: mid1 = relu(W1 . x + b1) on the 16 x 16 halo tile; wave w owns halo rows 2w, 2w+1 and all P couts
@@ -105,9 +103,6 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
             xin_t[nt] = (unsigned)iy < (unsigned)a.H && (unsigned)ixt < (unsigned)a.W;
             xoff[nt] = xin_t[nt] ? (unsigned)((((size_t)(n * a.H + iy) * a.W + ixt) * a.Cin + xtq * 8) * 2) : 0xFFFFFFF0u;
         }
-        unsigned woff[CB1];
-#pragma unroll
-        for (int b = 0; b < CB1; ++b) woff[b] = (unsigned)(((32 * (b >> 1) + pair_row0 + 4 * (b & 1)) * a.k1_pad + lq * 8) * 2);
 
         f32x4 acc[CB1][2];
 #pragma unroll
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
         // work items (K-step ks, sub-group sg) in order; the weight loads of item i+1 are issued before the MFMAs of item i
 #define BN_LOAD_A(SLOT, KS, SG)                                                                                \
         _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                       \
-            A[SLOT][i_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd_w1, FM ? (unsigned)((((KS) * CB1 + 4 * (SG) + i_) * 64 + lane) * 16) : woff[4 * (SG) + i_] + (unsigned)((KS) * 64), 0, 0));
+            A[SLOT][i_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd_w1, (unsigned)((((KS) * CB1 + 4 * (SG) + i_) * 64 + lane) * 16), 0, 0));
 #define BN_LOAD_B(SLOT, KS)                                                                                    \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                       \
             B[SLOT][i_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd_x, xin_t[i_] ? xoff[i_] + (unsigned)((KS) * 64) : 0xFFFFFFF0u, 0, 0));
@@ -191,26 +186,19 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
     const int row0 = rg * RW;
     f32x4 acc2[NCB][RW];
     {
-        unsigned w2off[NCB];
 #pragma unroll
         for (int h = 0; h < NCB; ++h) {
-            const int cout = cg * CW + (NCB == 2 ? pair_row0 + 4 * h : l16);
-            w2off[h] = (unsigned)((cout * a.k2_pad + lq * 8) * 2);
             const f32x4 bias = *reinterpret_cast<const f32x4*>(a.b2 + cg * CW + (NCB == 2 ? 8 * lq + 4 * h : 4 * lq));
 #pragma unroll
             for (int r = 0; r < RW; ++r) acc2[h][r] = bias;
         }
         bf16x8 A2[2][3][NCB];
-        // step s = (c64, kw, half): weights of the three kh taps; K offset of tap (kh, kw), chunk c64, half: ((c64*3 + kh)*3 + kw)*64 + half*32
+        // step s = (c64, kw, half): weights of the three kh taps
 #define BN_LOAD_A2(SLOT, S)                                                                                    \
-        {                                                                                                      \
-            const int c64_ = (S) / 6, r6_ = (S) - 6 * c64_, kw_ = r6_ >> 1, hf_ = r6_ & 1;                      \
-            _Pragma("unroll") for (int kh_ = 0; kh_ < 3; ++kh_)                                                \
-                _Pragma("unroll") for (int h_ = 0; h_ < NCB; ++h_)                                             \
-                    A2[SLOT][kh_][h_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(       \
-                        srd_w2, FM ? (unsigned)((((((cg * ((P / 64) * 6) + (S)) * 3 + kh_) * NCB + h_) * 64) + lane) * 16)   \
-                                   : w2off[h_] + (unsigned)((((c64_ * 3 + kh_) * 3 + kw_) * 64 + hf_ * 32) * 2), 0, 0)); \
-        }
+        _Pragma("unroll") for (int kh_ = 0; kh_ < 3; ++kh_)                                                    \
+            _Pragma("unroll") for (int h_ = 0; h_ < NCB; ++h_)                                                 \
+                A2[SLOT][kh_][h_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(           \
+                    srd_w2, (unsigned)((((((cg * ((P / 64) * 6) + (S)) * 3 + kh_) * NCB + h_) * 64) + lane) * 16), 0, 0));
         constexpr int NS = (P / 64) * 6;
         BN_LOAD_A2(0, 0)
         for (int s = 0; s < NS; s += 2) {
@@ -268,18 +256,16 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
     for (int hp = 0; hp < 2 * NG3; ++hp) {
         const int pass = hp >> 1, rbase = (hp & 1) * HR;
         const int c0 = (pass * 8 + wid) * 32;                    // first cout of this pass
-        unsigned w3off[2];
         f32x4 acc3[2][HR];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            w3off[h] = (unsigned)(((c0 + pair_row0 + 4 * h) * a.k3_pad + lq * 8) * 2);
             const f32x4 bias = *reinterpret_cast<const f32x4*>(a.b3 + c0 + 8 * lq + 4 * h);
 #pragma unroll
             for (int r = 0; r < HR; ++r) acc3[h][r] = bias;
         }
         // residual of this pass's 32 couts at its 7 rows of 16 pixels: in flight under the MFMAs.  An accumulator lane (pixel l16, cout
         // group lq) needs 16 bytes of ITS pixel, and neighbouring lanes are neighbouring pixels 8 P bytes apart -- loaded that way no two
-        // neighbouring lanes share a 64-byte block and the texture addresser takes the load one lane per clock (see FM above).  Instead
+        // neighbouring lanes share a 64-byte block and the texture addresser takes the load one lane per clock (see bneck_kernel).  Instead
         // lane 4 p + q loads cout group q of pixel p (four neighbouring lanes = one 64-byte run) and the pieces are exchanged across the
         // wave just before they are added (4 ds_bpermute per row); the stores go the same way round.
         const int tp = lane >> 2, tq = lane & 3;                      // transposed role: pixel tp, cout group tq
@@ -296,7 +282,7 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
         bf16x8 A3[2][2];
 #define BN_LOAD_A3(SLOT, KS)                                                                                   \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                       \
-            A3[SLOT][h_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd_w3, FM ? (unsigned)(((((pass * 8 + wid) * (P / 32) + (KS)) * 2 + h_) * 64 + lane) * 16) : w3off[h_] + (unsigned)((KS) * 64), 0, 0));
+            A3[SLOT][h_] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(srd_w3, (unsigned)(((((pass * 8 + wid) * (P / 32) + (KS)) * 2 + h_) * 64 + lane) * 16), 0, 0));
         constexpr int NK3 = P / 32;
         BN_LOAD_A3(0, 0)
 #pragma unroll
@@ -339,66 +325,49 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BneckArgs a) {
     }
 }
 
-template <typename E, int P, bool FM>
+template <typename E, int P>
 int launch_bneck(const BneckArgs& a, hipStream_t stream) {
     const int smem = BN_M1_PIX * 2 * P;
-    if (!cvpce_smem_attr_done<bneck_kernel<E, P, FM>>((const void*)bneck_kernel<E, P, FM>, smem)) return CVPCE_ERR_LAUNCH;
-    hipLaunchKernelGGL((bneck_kernel<E, P, FM>), dim3((unsigned)(a.N * a.tiles_x * a.tiles_y)), dim3(512), smem, stream, a);
+    if (!cvpce_smem_attr_done<bneck_kernel<E, P>>((const void*)bneck_kernel<E, P>, smem)) return CVPCE_ERR_LAUNCH;
+    hipLaunchKernelGGL((bneck_kernel<E, P>), dim3((unsigned)(a.N * a.tiles_x * a.tiles_y)), dim3(512), smem, stream, a);
     return cvpce_check_launch();
 }
 
-template <typename E, bool FM = false>
+template <typename E>
 int bneck_dispatch(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2, const void* w3,
-                   const float* b3, void* out, int N, int H, int W, int Cin, int P, int k1_pad, int k2_pad, int k3_pad, int c1_pad,
-                   int c2_pad, int c3_pad, void* stream) {
+                   const float* b3, void* out, int N, int H, int W, int Cin, int P, void* stream) {
     if (N <= 0) return CVPCE_OK;
     if (!x || !res || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return CVPCE_ERR_ARG;
     if (P != 64 && P != 128 && P != 256) return CVPCE_ERR_ARG;
-    if (H <= 0 || W <= 0 || Cin <= 0 || Cin % 64 != 0 || k1_pad < Cin || k2_pad != 9 * P || k3_pad < P) return CVPCE_ERR_ARG;
-    if (c1_pad < P || c2_pad < P || c3_pad < 4 * P) return CVPCE_ERR_ARG;
+    if (H <= 0 || W <= 0 || Cin <= 0 || Cin % 64 != 0) return CVPCE_ERR_ARG;
     if ((long long)N * H * W * Cin * 2 >= (1LL << 32) || (long long)N * H * W * 4 * P * 2 >= (1LL << 32)) return CVPCE_ERR_ARG;
     BneckArgs a;
     a.x = (const bf16_t*)x; a.res = (const bf16_t*)res; a.w1 = (const bf16_t*)w1; a.w2 = (const bf16_t*)w2; a.w3 = (const bf16_t*)w3;
     a.b1 = b1; a.b2 = b2; a.b3 = b3; a.out = (bf16_t*)out;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.k1_pad = k1_pad; a.k2_pad = k2_pad; a.k3_pad = k3_pad;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
     a.tiles_x = (W + BT - 1) / BT; a.tiles_y = (H + BT - 1) / BT;
     if ((long long)N * a.tiles_x * a.tiles_y >= (1LL << 31)) return CVPCE_ERR_ARG;
     a.x_bytes = (unsigned)((long long)N * H * W * Cin * 2);
     a.res_bytes = (unsigned)((long long)N * H * W * 4 * P * 2);
-    if (FM) {         // fragment-major tensors hold exactly the P x Cin, P x 9P and 4P x P weights (no padding rows / columns)
-        a.w1_bytes = (unsigned)((long long)P * Cin * 2);
-        a.w2_bytes = (unsigned)((long long)P * 9 * P * 2);
-        a.w3_bytes = (unsigned)((long long)4 * P * P * 2);
-    } else {
-        a.w1_bytes = (unsigned)((long long)c1_pad * k1_pad * 2);
-        a.w2_bytes = (unsigned)((long long)c2_pad * k2_pad * 2);
-        a.w3_bytes = (unsigned)((long long)c3_pad * k3_pad * 2);
-    }
+    // the fragment-major tensors hold exactly the P x Cin, P x 9P and 4P x P weights (no padding rows / columns)
+    a.w1_bytes = (unsigned)((long long)P * Cin * 2);
+    a.w2_bytes = (unsigned)((long long)P * 9 * P * 2);
+    a.w3_bytes = (unsigned)((long long)4 * P * P * 2);
     hipStream_t s = (hipStream_t)stream;
     switch (P) {
-        case 64: return launch_bneck<E, 64, FM>(a, s);
-        case 128: return launch_bneck<E, 128, FM>(a, s);
-        default: return launch_bneck<E, 256, FM>(a, s);
+        case 64: return launch_bneck<E, 64>(a, s);
+        case 128: return launch_bneck<E, 128>(a, s);
+        default: return launch_bneck<E, 256>(a, s);
     }
 }
 
 }  // namespace
 
-extern "C" int cvpce_bottleneck_fused(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
-                                      const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, int k1_pad,
-                                      int k2_pad, int k3_pad, int c1_pad, int c2_pad, int c3_pad, void* stream) {
-    return bneck_dispatch<ElemBF16>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, k1_pad, k2_pad, k3_pad, c1_pad, c2_pad, c3_pad, stream);
-}
 extern "C" int cvpce_bottleneck_fused_fm(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
                                          const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, void* stream) {
-    return bneck_dispatch<ElemBF16, true>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, Cin, 9 * P, P, P, P, 4 * P, stream);
+    return bneck_dispatch<ElemBF16>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, stream);
 }
 extern "C" int cvpce_bottleneck_fused_fm_f16(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
                                              const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, void* stream) {
-    return bneck_dispatch<ElemF16, true>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, Cin, 9 * P, P, P, P, 4 * P, stream);
-}
-extern "C" int cvpce_bottleneck_fused_f16(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
-                                          const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, int k1_pad,
-                                          int k2_pad, int k3_pad, int c1_pad, int c2_pad, int c3_pad, void* stream) {
-    return bneck_dispatch<ElemF16>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, k1_pad, k2_pad, k3_pad, c1_pad, c2_pad, c3_pad, stream);
+    return bneck_dispatch<ElemF16>(x, res, w1, b1, w2, b2, w3, b3, out, N, H, W, Cin, P, stream);
 }

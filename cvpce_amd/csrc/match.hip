@@ -31,9 +31,7 @@ struct MatchArgs {
     const float* qn; const float* gn;     // L2 norms (already clamped by eps)
     int Qn, Gn, D, k, tiles_g, tiles_q;
     float* part_d; int* part_i;           // [Qn][tiles_g][k]
-    // one-launch form of match_big_kernel (k = 1): per-query 64-bit (distance, row) keys combined by agent-scope atomic minima, the
-    // last workgroup to finish (ticket) writes the results and restores the state block (cvpce_match_state_init)
-    unsigned long long* keys; int* ticket; long long* out_idx; float* out_dist;
+    long long* out_idx; float* out_dist;  // large k: the results [Qn][k]
     float* dist; int ldd;                 // large k: the distance block [Qn][ldd] (match_kernel<F32, TQ, true>)
 };
 
@@ -42,9 +40,6 @@ struct MatchArgs {
 __device__ __forceinline__ unsigned match_key32(float d) {
     const unsigned b = __float_as_uint(d);
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long match_key(float d, int i) {
-    return ((unsigned long long)match_key32(d) << 32) | (unsigned)i;
 }
 __device__ __forceinline__ float match_key_distance(unsigned long long key) {
     const unsigned o = (unsigned)(key >> 32);
@@ -692,36 +687,10 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
             wix[tid] = bi;
             const int qg = tile_q * TQ + tid;
             if (qg < a.Qn) {
-                if (a.keys) {
-                    // (the RETURNED old value makes the atomic's completion visible to this thread's vmcnt: it is performed -- at the
-                    // device's coherence point -- before the ticket below is drawn)
-                    const unsigned long long old = __hip_atomic_fetch_min(a.keys + qg, match_key(bd, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("" ::"v"(old));
-                } else {
-                    const size_t o = ((size_t)qg * a.tiles_g + tile_g) * a.k + r;
-                    a.part_d[o] = bd;
-                    a.part_i[o] = bi;
-                }
+                const size_t o = ((size_t)qg * a.tiles_g + tile_g) * a.k + r;
+                a.part_d[o] = bd;
+                a.part_i[o] = bi;
             }
-        }
-        if (a.keys) {
-            // ticket: the workgroup that finishes last has every tile's minima in `keys`; it writes the (Qn, 1) results and puts the
-            // state block back (keys all-ones, ticket 0) for the next launch on this state
-            int* s_last = reinterpret_cast<int*>(smem + 1024 + 10 * TQ * 4);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) *s_last = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            if (*s_last == (int)gridDim.x - 1) {
-                for (int q = tid; q < a.Qn; q += 512) {
-                    const unsigned long long key = __hip_atomic_load(a.keys + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    a.out_idx[q] = (long long)(unsigned)(key & 0xFFFFFFFFull);
-                    if (a.out_dist) a.out_dist[q] = match_key_distance(key);
-                    __hip_atomic_store(a.keys + q, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (tid == 0) __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            return;
         }
         if (r + 1 < a.k) {
             __syncthreads();
@@ -1023,34 +992,14 @@ __global__ __launch_bounds__(256) void match_merge_runs_kernel(const unsigned lo
 // which bf16 core a launch takes: 0 = by the cost model below, 1 = always the 128-row kernel, 2 = always the 256-row LDS-DMA kernel;
 // g_match_nq = 2..5 pins the 256-row kernel's query-tile width (0 = by the model).  Test / measurement switch: results never depend on it.
 static int g_match_core = []() { const char* e = getenv("CVPCE_MATCH_CORE"); return !e ? 0 : (e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : 0)); }();
-// the one-launch form of cvpce_match_topk_state is OPT-IN: measured (tools/dev/bench_match.py) it loses to GEMM launch + merge launch wherever
-// the model picks the fastest tile -- 200 x 10 000 x 512: 10.4 us against 9.6 -- because every workgroup then ends with two dependent
-// device-scope atomic round trips (its keys, then the ticket) where the two-launch form ends with plain stores
-static int g_match_fused = []() { const char* e = getenv("CVPCE_MATCH_FUSED"); return e ? atoi(e) : 0; }();
 static int g_match_mg = []() { const char* e = getenv("CVPCE_MATCH_MG"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2) ? v : 0; }();
 static int g_match_nq = []() { const char* e = getenv("CVPCE_MATCH_NQ"); const int v = e ? atoi(e) : 0; return (v >= 2 && v <= 5) ? v : 0; }();
-extern "C" int cvpce_match_set_core(int core, int nq, int mg, int one_launch) {
+extern "C" int cvpce_match_set_core(int core, int nq, int mg) {
     if (core < 0 || core > 2 || !(nq == 0 || (nq >= 2 && nq <= 5)) || mg < 0 || mg > 2 || (mg == 1 && nq == 5)) return CVPCE_ERR_ARG;
     g_match_core = core;
     g_match_nq = nq;
     g_match_mg = mg;
-    g_match_fused = one_launch != 0;
     return CVPCE_OK;
-}
-
-// ---- state block of the one-launch top-1 form: `max_queries` 64-bit keys (all-ones = no candidate yet) + the ticket counter -----------
-__global__ void match_state_init_kernel(unsigned long long* keys, int n_keys, int* ticket) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_keys) keys[i] = ~0ull;
-    if (i == 0) *ticket = 0;
-}
-extern "C" size_t cvpce_match_state_bytes(int max_queries) { return max_queries <= 0 ? 0 : (size_t)max_queries * 8 + 64; }
-extern "C" int cvpce_match_state_init(void* state, size_t state_bytes, void* stream) {
-    if (!state || state_bytes < 64 + 8 || ((size_t)state & 7)) return CVPCE_ERR_ARG;
-    const int n = (int)((state_bytes - 64) / 8);
-    hipLaunchKernelGGL(match_state_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)state, n,
-                       (int*)((char*)state + (size_t)n * 8));
-    return cvpce_check_launch();
 }
 
 extern "C" size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k) {
@@ -1125,25 +1074,9 @@ static int match_large_k(MatchArgs a, int is_f32, void* workspace, hipStream_t s
     return CVPCE_OK;
 }
 
-static int match_topk_impl(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
-                           int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
-                           void* state, size_t state_bytes, long long* out_idx, float* out_dist, void* stream);
-
 extern "C" int cvpce_match_topk(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
                                 int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
                                 long long* out_idx, float* out_dist, void* stream) {
-    return match_topk_impl(queries, gallery, q_norms, g_norms, Qn, Gn, D, k, is_f32, workspace, workspace_bytes, nullptr, 0, out_idx, out_dist, stream);
-}
-extern "C" int cvpce_match_topk_state(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
-                                      int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
-                                      void* state, size_t state_bytes, long long* out_idx, float* out_dist, void* stream) {
-    if (state && (state_bytes < 64 + 8 || ((size_t)state & 7))) return CVPCE_ERR_ARG;
-    return match_topk_impl(queries, gallery, q_norms, g_norms, Qn, Gn, D, k, is_f32, workspace, workspace_bytes, state, state_bytes, out_idx, out_dist, stream);
-}
-
-static int match_topk_impl(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
-                           int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
-                           void* state, size_t state_bytes, long long* out_idx, float* out_dist, void* stream) {
     if (!queries || !gallery || !q_norms || !g_norms || !workspace || !out_idx) return CVPCE_ERR_ARG;
     if (D <= 0 || D % MT_BK != 0 || k < 1 || Gn < k) return CVPCE_ERR_ARG;
     if (Qn <= 0) return CVPCE_OK;
@@ -1154,7 +1087,7 @@ static int match_topk_impl(const void* queries, const void* gallery, const float
     }
     MatchArgs a;
     a.q = queries; a.g = gallery; a.qn = q_norms; a.gn = g_norms; a.Qn = Qn; a.Gn = Gn; a.D = D; a.k = k;
-    a.keys = nullptr; a.ticket = nullptr; a.out_idx = out_idx; a.out_dist = out_dist;
+    a.out_idx = out_idx; a.out_dist = out_dist;
     a.dist = nullptr; a.ldd = 0;
     if (k > MATCH_KMAX) return match_large_k(a, is_f32, workspace, (hipStream_t)stream);
     a.tiles_g = (Gn + MT_TG - 1) / MT_TG;
@@ -1199,13 +1132,6 @@ static int match_topk_impl(const void* queries, const void* gallery, const float
         a.tiles_q = (Qn + 64 * big_nq - 1) / (64 * big_nq);
         if ((unsigned long long)((unsigned long long)Qn + 64 * big_nq) * D * 2 >= (1ull << 32) || ((unsigned long long)Gn + tg) * D * 2 >= (1ull << 32)) return CVPCE_ERR_ARG;
         const dim3 gridb(a.tiles_g * a.tiles_q);
-        // k = 1 with a state block that holds a key per query: ONE launch (no partials, no merge kernel)
-        const int n_keys = state ? (int)((state_bytes - 64) / 8) : 0;
-        const bool fused = state && k == 1 && Qn <= n_keys && g_match_fused;
-        if (fused) {
-            a.keys = (unsigned long long*)state;
-            a.ticket = (int*)((char*)state + (size_t)n_keys * 8);
-        }
         const size_t smemb = (size_t)2 * (tg + 64 * big_nq) * MB_ROWB;
 #define MB_LAUNCH(NQ_, MG_)                                                                                                    \
         case NQ_ * 4 + MG_:                                                                                                    \
@@ -1217,7 +1143,6 @@ static int match_topk_impl(const void* queries, const void* gallery, const float
             default: return CVPCE_ERR_ARG;
         }
 #undef MB_LAUNCH
-        if (fused) return cvpce_check_launch();
     } else {
     a.tiles_q = (Qn + tq - 1) / tq;
     dim3 grid(a.tiles_g * a.tiles_q);

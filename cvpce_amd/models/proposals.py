@@ -47,10 +47,6 @@ MAX_SIGHT_COUNTS = 512    # geometries whose call counts are remembered (LRU)
 USE_SIDE_BRANCHES = os.environ.get('CVPCE_SIDE_BRANCHES', '1') != '0'   # Gaussian branch beside the heads, projection shortcuts beside conv1 -> conv2
 # the fp16 storage mode checks its first batch for saturated activations once per engine and warns (CVPCE_FP16_GUARD=0 switches the check off)
 FP16_SATURATION_GUARD = os.environ.get('CVPCE_FP16_GUARD', '1') != '0'
-# opt-in: layer i of both head towers in one masked launch (568 tiles in three rounds of the persistent grid).  Built, bit-identical, NOT faster:
-# the two towers' launches already run beside each other on two streams and share the grid's second round (configs[1], same call: 2.475 ms
-# per-tower vs 2.509 ms paired; profiles/r06_rejected_experiments.md)
-USE_PAIRED_TOWERS = os.environ.get('CVPCE_PAIRED_TOWERS', '0') != '0'
 USE_ATLAS_COPY = os.environ.get('CVPCE_ATLAS_COPY', '1') != '0'       # levels <-> atlas in one launch each way (15 slice copies otherwise)
 USE_BATCHED_TRANSFORM = os.environ.get('CVPCE_BATCHED_TRANSFORM', '1') != '0'   # the input transform of a whole batch in one launch
 USE_FUSED_STEM = os.environ.get('CVPCE_FUSED_GLN_STEM', '1') != '0'     # conv1 + bn1 + relu + maxpool in one launch (csrc/gln_stem.hip); False: generic conv + pool kernels
@@ -296,9 +292,6 @@ class GLNEngine:
         self.cls_out = P(ch.cls_logits)
         self.reg_tower = [P(rh.conv[i]) for i in (0, 2, 4, 6)]
         self.reg_out = P(rh.bbox_reg)
-        # layer i of BOTH towers as one conv with Cout = 512 (cout tile 0 = the classification tower, 1 = the regression tower): one masked
-        # launch per layer instead of two (ops.conv3x3_atlas_paired)
-        self.tower_pairs = self.pack_tower_pairs(model, device) if USE_PAIRED_TOWERS else None
         # RetinaNet's transform and anchor options are fixed at the model's construction; the thresholds and top-k are read from
         # the model on every detect (detect_options)
         tf, ag = getattr(model, 'transform', None), getattr(model, 'anchor_generator', None)
@@ -319,15 +312,6 @@ class GLNEngine:
         if model is None:
             return TOPK_CANDIDATES, SCORE_THRESH, NMS_THRESH
         return model._detect_options()
-
-    def pack_tower_pairs(self, model, device=None):
-        """Layer i of BOTH head towers as one conv with Cout = 512 (cout tile 0 = the classification tower, 1 = the regression tower), for
-        `ops.conv3x3_atlas_paired`; None when the towers are not 4 x (256 -> 256)."""
-        ch, rh = model.head.classification_head, model.head.regression_head
-        if not all(c.out_channels == 256 and c.in_channels == 256 for i in (0, 2, 4, 6) for c in (ch.conv[i], rh.conv[i])):
-            return None
-        return [ops.PackedConv(torch.cat((ch.conv[i].weight, rh.conv[i].weight)), torch.cat((ch.conv[i].bias, rh.conv[i].bias)), 1, 1,
-                               device=device if device is not None else self.device, dtype=self.dtype) for i in (0, 2, 4, 6)]
 
     def pack_gaussian(self, gl, subnet, device, dtype=None):
         """Gaussian branch weights (proposals.py:65-107): eval-mode BatchNorm folded into block1/block2."""
@@ -486,43 +470,18 @@ class GLNEngine:
         # the tiles they compute) and skip the tiles that lie wholly in a gap, so the gaps stay zero -- no memset, and about
         # 1/7 of the canvas tiles (the empty ones) are never scheduled.
         bufs = self.__dict__.setdefault('_atlas_bufs', {})
-        bkey = (n, hc, wc, self.tower_pairs is not None)
+        bkey = (n, hc, wc)
         if bkey not in bufs:
             if len(bufs) >= MAX_DETECT_GRAPHS:
                 bufs.pop(next(iter(bufs)))
-            bufs[bkey] = [torch.zeros(n, hc, wc, FPN_CHANNELS, dtype=self.dtype, device=self.device) for _ in range(1 if self.tower_pairs is not None else 5)]
-        atlas, cls_a, cls_b, reg_a, reg_b = (bufs[bkey] + [None] * 4)[:5]
+            bufs[bkey] = [torch.zeros(n, hc, wc, FPN_CHANNELS, dtype=self.dtype, device=self.device) for _ in range(5)]
+        atlas, cls_a, cls_b, reg_a, reg_b = bufs[bkey]
         self._keep(bufs[bkey])
         if USE_ATLAS_COPY:
             ops.atlas_pack(feats, atlas, offs)               # the five levels into the canvas, one launch
         else:
             for f, (h, w), (oy, ox) in zip(feats, shapes, offs):
                 atlas[:, oy:oy + h, ox:ox + w] = f
-
-        def finish(t, final):
-            o = ops.conv2d(t, final, out_f32=True)           # gap pixels hold junk here; they are never read
-            if USE_ATLAS_COPY:
-                return ops.atlas_unpack(o, shapes, offs)
-            return [o[:, oy:oy + h, ox:ox + w].contiguous() for (h, w), (oy, ox) in zip(shapes, offs)]
-
-        if self.tower_pairs is not None:
-            # both towers, layer by layer, in ONE launch each: 2 x 284 tiles in three rounds of the persistent grid instead of 2 + 2
-            pk = ('pair', n, hc, wc)
-            if pk not in bufs:
-                bufs[pk] = [torch.zeros(2, n, hc, wc, FPN_CHANNELS, dtype=self.dtype, device=self.device) for _ in range(2)]
-            ping, pong = bufs[pk]
-            self._keep(bufs[pk])
-            t = atlas
-            for i, pc in enumerate(self.tower_pairs):
-                t = ops.conv3x3_atlas_paired(t, pc, mask, act=1, tile_map=tile_map, out=ping, mask_pixels=npix, in_paired=i > 0)
-                ping, pong = pong, ping
-            if not self.side_streams:
-                return finish(t[0], self.cls_out), finish(t[1], self.reg_out)
-            (reg), reg_done = self._beside(0, lambda: tuple(finish(t[1], self.reg_out)))
-            cls = finish(t[0], self.cls_out)
-            if reg_done is not None:
-                torch.cuda.current_stream().wait_event(reg_done)
-            return cls, list(reg)
 
         def chain(tower, final, ping, pong):
             t = atlas

@@ -84,16 +84,10 @@ class PackedConv:
         w16 = to_storage(packed, dtype)
         self.weight = w16.to(device)
         self.bias = b.to(device) if b is not None else None
-        # the 3x3 halo kernels (csrc/conv3x3_halo2.hip, conv3x3_halo3.hip) read the same values fragment-major
-        self._weight_halo = (self._to_halo_layout(w16, self.cout_pad, self.cin_pad).to(device)
-                             if (kh, kw) == (3, 3) and self.cin_pad % 64 == 0 else None)
-
-    @property
-    def weight_halo(self):
-        """The weights in the fragment-major "halo weight layout" of include/cvpce_amd.h (3x3, Cin % 64 == 0; built with the layer)."""
-        if _os.environ.get('CVPCE_WEIGHT_ROWMAJOR') == '1':     # dev A/B against a library built before the layout change
-            return self.weight
-        return self._weight_halo
+        # the 3x3 halo kernels (csrc/conv3x3_halo2.hip, conv3x3_halo3.hip) read the same values in the fragment-major "halo weight
+        # layout" of include/cvpce_amd.h (3x3, Cin % 64 == 0)
+        self.weight_halo = (self._to_halo_layout(w16, self.cout_pad, self.cin_pad).to(device)
+                            if (kh, kw) == (3, 3) and self.cin_pad % 64 == 0 else None)
 
     @staticmethod
     def _to_halo_layout(weight, cout_pad, cin_pad):
@@ -343,7 +337,7 @@ FUSED_BOTTLENECK_MAX_PLANES = int(_os.environ.get('CVPCE_FUSED_BOTTLENECK_MAXP',
 
 
 def can_fuse_bottleneck(x, c1, c2, c3, residual):
-    """cvpce_bottleneck_fused covers: 1x1 (s1) -> 3x3 (s1, p1) -> 1x1 (s1), planes P in {64, 128, 256}, 4P outputs, a same-size residual.
+    """cvpce_bottleneck_fused_fm covers: 1x1 (s1) -> 3x3 (s1, p1) -> 1x1 (s1), planes P in {64, 128, 256}, 4P outputs, a same-size residual.
     `residual`: the tensor, or just its shape (a caller deciding BEFORE it computes the projection shortcut)."""
     p = c1.cout
     n, h, w, cin = x.shape
@@ -354,9 +348,6 @@ def can_fuse_bottleneck(x, c1, c2, c3, residual):
             and (c3.kh, c3.stride, c3.pad) == (1, 1, 0) and c3.cin == p and c3.cout == 4 * p and c2.k_pad == 9 * p
             and all(c.bias is not None for c in (c1, c2, c3)) and residual is not None and tuple(residual.shape) == (n, h, w, 4 * p)
             and n * h * w * max(cin, 4 * p) * 2 < 2 ** 32)
-
-
-BNECK_FRAGMENT_MAJOR = _os.environ.get('CVPCE_BNECK_FM', '1') != '0'   # A/B switch: the fused bottleneck reads fragment-major weights (round 5)
 
 
 def pack_bottleneck_weights(c1, c2, c3):
@@ -412,16 +403,12 @@ def bottleneck(x, c1, c2, c3, residual):
     n, h, w, cin = x.shape
     p = c1.cout
     out = torch.empty((n, h, w, 4 * p), dtype=x.dtype, device=x.device)
-    fm = pack_bottleneck_weights(c1, c2, c3) if BNECK_FRAGMENT_MAJOR else None      # (built once per block: cached on c1)
+    w1f, w2f, w3f = pack_bottleneck_weights(c1, c2, c3)      # (built once per block: cached on c1)
     prof = PROFILE
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    if fm is not None:
-        T.bottleneck_fused_fm(x, residual, fm[0], c1.bias, fm[1], c2.bias, fm[2], c3.bias, out, p)
-    else:
-        T.bottleneck_fused(x, residual, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias, out, p, c1.k_pad, c2.k_pad, c3.k_pad,
-                           c1.cout_pad, c2.cout_pad, c3.cout_pad)
+    T.bottleneck_fused_fm(x, residual, w1f, c1.bias, w2f, c2.bias, w3f, c3.bias, out, p)
     if prof is not None:
         e1.record()
         prof.records.append(('bneck_kernel', 2.0 * n * h * w * (cin * p + 9 * p * p + 4 * p * p), e0, e1))
@@ -546,35 +533,6 @@ def conv3x3_atlas(x, pc, mask, act=1, tile_map=None, out=None, mask_pixels=None)
         prof.records.append(('conv3x3_halo2_kernel', 2.0 * npix * n * pc.cout * 9 * pc.cin, e0, e1))
         prof.layer(f'conv3x3_halo2 atlas {pc.cin}->{pc.cout} (head tower)', 2.0 * npix * n * pc.cout * 9 * pc.cin,
                    2 * npix * n * (pc.cin + pc.cout) * x.element_size() + _nbytes(pc.weight), e0, e1)
-    return out
-
-
-def conv3x3_atlas_paired(x, pc, mask, act=1, tile_map=None, out=None, mask_pixels=None, in_paired=False):
-    """Layer i of the head's TWO towers (torchvision RetinaNetHead) as ONE masked launch: `pc` packs the towers' layer-i weights
-    concatenated along Cout (256 x towers); x is one atlas (N,H,W,Cin) every tower reads (in_paired=False: the first layer) or the
-    tower-major output of the previous paired launch (towers,N,H,W,Cin); -> (towers,N,H,W,256), tower t's output in part t."""
-    _need_cuda(x, mask, tile_map, out)
-    towers = pc.cout // 256
-    assert pc.cout == 256 * towers and towers >= 2 and x.dtype == pc.dtype and x.is_contiguous() and mask.dtype == torch.uint8 and mask.is_contiguous()
-    n, h, w, cin = x.shape[-4:]
-    assert tuple(x.shape) == ((towers, n, h, w, cin) if in_paired else (n, h, w, cin))
-    assert tuple(mask.shape) == (h, w) and cin == pc.cin_pad and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1) and pc.cin_pad % 64 == 0 and act in (0, 1)
-    if tile_map is not None:
-        assert out is not None and tile_map.dtype == torch.int32 and tile_map.is_contiguous()
-    if out is None:
-        out = torch.empty((towers, n, h, w, 256), dtype=x.dtype, device=x.device)
-    assert tuple(out.shape) == (towers, n, h, w, 256) and out.dtype == x.dtype and out.is_contiguous()
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    T.conv3x3_halo_masked_paired(x, pc.weight_halo, pc.bias, mask, tile_map, out, pc.cout, pc.k_pad, pc.cout_pad, int(act), int(bool(in_paired)))
-    if prof is not None:
-        e1.record()
-        npix = float(mask.sum().item()) if mask_pixels is None else float(mask_pixels)
-        prof.records.append(('conv3x3_halo2_kernel', 2.0 * npix * n * pc.cout * 9 * pc.cin, e0, e1))
-        prof.layer(f'conv3x3_halo2 atlas {pc.cin}->{towers}x256 (both head towers)', 2.0 * npix * n * pc.cout * 9 * pc.cin,
-                   2 * npix * n * ((towers if in_paired else 1) * pc.cin + pc.cout) * x.element_size() + _nbytes(pc.weight), e0, e1)
     return out
 
 
@@ -993,47 +951,14 @@ def match_topk(queries, gallery, k=1, q_norms=None, g_norms=None, return_distanc
     dist = torch.empty((qn, k), dtype=torch.float32, device=queries.device) if return_distance else None
     ws_bytes = lib.cvpce_match_workspace_bytes(qn, gn, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=queries.device)
-    if MATCH_ONE_LAUNCH and k == 1 and queries.dtype == BF16 and qn <= MATCH_STATE_QUERIES and (_match_state_key(queries.device) in _MATCH_STATE or not torch.cuda.is_current_stream_capturing()):
-        # the one-launch form: a state block per (device, stream) -- launches of one stream are ordered, so they can share a block
-        T.match_topk_state(queries, gallery, q_norms, g_norms, k, ws, match_state(queries.device), idx, dist)
-    else:
-        T.match_topk(queries, gallery, q_norms, g_norms, k, ws, idx, dist)
+    T.match_topk(queries, gallery, q_norms, g_norms, k, ws, idx, dist)
     return (idx, dist) if return_distance else idx
 
 
-MATCH_STATE_QUERIES = 16384      # queries per launch the one-launch top-1 search holds keys for (128 KiB per state block)
-_MATCH_STATE = {}
-# The one-launch form of the k = 1 search is an opt-in (measured slower than two launches, profiles/r05_rejected_experiments.md): only
-# when it is on does a launch get a state block (128 KiB per device and stream) and go through cvpce_match_topk_state.  A hipGraph
-# captured with it on must be replayed on its capture stream: the block belongs to that stream's launch order.
-MATCH_ONE_LAUNCH = _os.environ.get('CVPCE_MATCH_FUSED', '0') not in ('', '0')
-
-
-def match_set_core(core=0, nq=0, mg=0, one_launch=0):
-    """`cvpce_match_set_core` (include/cvpce_amd.h): pin the bf16 search's core / tile (0 = the cost model's choice) and switch the
-    one-launch form of k = 1 on or off -- here AND in this module's dispatch.  -> the library's status (0 = ok)."""
-    global MATCH_ONE_LAUNCH
-    rc = int(lib.cvpce_match_set_core(int(core), int(nq), int(mg), int(one_launch)))
-    if rc == 0:
-        MATCH_ONE_LAUNCH = bool(one_launch)
-    return rc
-
-
-def _match_state_key(device):
-    return (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-
-
-def match_state(device):
-    """The persistent state block of the one-launch top-1 search for the CURRENT stream of `device` (include/cvpce_amd.h
-    cvpce_match_topk_state): initialised once, restored by every launch that uses it.  (Never created inside a stream capture -- its
-    memory would belong to that graph's pool: a capture on a stream without a block takes the plain two-launch entry point.)"""
-    key = _match_state_key(device)
-    st = _MATCH_STATE.get(key)
-    if st is None:
-        st = torch.empty(lib.cvpce_match_state_bytes(MATCH_STATE_QUERIES) // 8, dtype=torch.int64, device=device)
-        T.match_state_init(st)
-        _MATCH_STATE[key] = st
-    return st
+def match_set_core(core=0, nq=0, mg=0):
+    """`cvpce_match_set_core` (include/cvpce_amd.h): pin the bf16 search's core / tile (0 = the cost model's choice).
+    -> the library's status (0 = ok)."""
+    return int(lib.cvpce_match_set_core(int(core), int(nq), int(mg)))
 
 
 def pad_features(x, multiple=64):

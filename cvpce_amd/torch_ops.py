@@ -109,18 +109,6 @@ def _conv3x3_halo_mac(x, weight, bias, out, mac, mac_off, cout, k_pad, cout_pad,
                                      cout_pad, pool, _stream()), 'cvpce_conv3x3_halo_mac')
 
 
-@_op('conv3x3_halo_masked_paired(Tensor x, Tensor weight, Tensor? bias, Tensor mask, Tensor? tile_map, Tensor(a!) out, int cout, int k_pad, '
-     'int cout_pad, int relu, int in_paired) -> ()')
-def _conv3x3_halo_masked_paired(x, weight, bias, mask, tile_map, out, cout, k_pad, cout_pad, relu, in_paired):
-    towers = cout // 256
-    n, h, w, cin = x.shape[-4:]
-    assert cout == 256 * towers and towers >= 2 and tuple(out.shape) == (towers, n, h, w, 256)
-    assert tuple(x.shape) == ((towers, n, h, w, cin) if in_paired else (n, h, w, cin))
-    fn = _by_dtype(x, 'cvpce_conv3x3_halo_masked_paired', 'cvpce_conv3x3_halo_masked_paired_f16', weight, out)
-    check(fn(_p(x), _p(weight), _p(bias), _p(mask), _p(tile_map), tile_map.numel() if tile_map is not None else 0,
-             _p(out), n, h, w, cin, cout, k_pad, cout_pad, relu, in_paired, _stream()), 'cvpce_conv3x3_halo_masked_paired')
-
-
 @_op('conv3x3_halo_masked(Tensor x, Tensor weight, Tensor? bias, Tensor mask, Tensor? tile_map, Tensor(a!) out, int cout, int k_pad, '
      'int cout_pad, int relu) -> ()')
 def _conv3x3_halo_masked(x, weight, bias, mask, tile_map, out, cout, k_pad, cout_pad, relu):
@@ -137,15 +125,6 @@ def _bottleneck_fused_fm(x, res, w1f, b1, w2f, b2, w3f, b3, out, planes):
         raise RuntimeError('cvpce_bottleneck_fused_fm: fragment-major weights of the wrong size')
     fn = _by_dtype(x, 'cvpce_bottleneck_fused_fm', 'cvpce_bottleneck_fused_fm_f16', res, w1f, w2f, w3f, out)
     check(fn(_p(x), _p(res), _p(w1f), _p(b1), _p(w2f), _p(b2), _p(w3f), _p(b3), _p(out), n, h, w, cin, planes, _stream()), 'cvpce_bottleneck_fused_fm')
-
-
-@_op('bottleneck_fused(Tensor x, Tensor res, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w3, Tensor b3, Tensor(a!) out, int planes, '
-     'int k1_pad, int k2_pad, int k3_pad, int c1_pad, int c2_pad, int c3_pad) -> ()')
-def _bottleneck_fused(x, res, w1, b1, w2, b2, w3, b3, out, planes, k1_pad, k2_pad, k3_pad, c1_pad, c2_pad, c3_pad):
-    n, h, w, cin = x.shape
-    fn = _by_dtype(x, 'cvpce_bottleneck_fused', 'cvpce_bottleneck_fused_f16', res, w1, w2, w3, out)
-    check(fn(_p(x), _p(res), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3), _p(out), n, h, w, cin, planes, k1_pad, k2_pad, k3_pad,
-             c1_pad, c2_pad, c3_pad, _stream()), 'cvpce_bottleneck_fused')
 
 
 @_op('vgg_stem_fused(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor(a!) out) -> ()')
@@ -379,20 +358,6 @@ def _match_topk(queries, gallery, q_norms, g_norms, k, workspace, idx, dist):
     check(lib.cvpce_match_topk(_p(queries), _p(gallery), _p(q_norms), _p(g_norms), queries.shape[0], gallery.shape[0], queries.shape[1], k,
                                int(queries.dtype == torch.float32), _p(workspace), workspace.numel(), _p(idx), _p(dist), _stream()),
           'cvpce_match_topk')
-
-
-@_op('match_topk_state(Tensor queries, Tensor gallery, Tensor q_norms, Tensor g_norms, int k, Tensor(a!) workspace, Tensor(b!) state, '
-     'Tensor(c!) idx, Tensor(d!)? dist) -> ()')
-def _match_topk_state(queries, gallery, q_norms, g_norms, k, workspace, state, idx, dist):
-    check(lib.cvpce_match_topk_state(_p(queries), _p(gallery), _p(q_norms), _p(g_norms), queries.shape[0], gallery.shape[0], queries.shape[1], k,
-                                     int(queries.dtype == torch.float32), _p(workspace), workspace.numel(), _p(state), state.numel() * state.element_size(),
-                                     _p(idx), _p(dist), _stream()),
-          'cvpce_match_topk_state')
-
-
-@_op('match_state_init(Tensor(a!) state) -> ()')
-def _match_state_init(state):
-    check(lib.cvpce_match_state_init(_p(state), state.numel() * state.element_size(), _stream()), 'cvpce_match_state_init')
 
 
 @_op('probe_mfma_bf16(int shape, int iters, Tensor operands, Tensor(a!) sink, int workgroups) -> ()')

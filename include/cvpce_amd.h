@@ -137,37 +137,18 @@ int cvpce_conv3x3_halo_masked(const void* in, const void* wgt, const float* bias
                               const int* tile_map, int n_tiles, void* out, int N, int H, int W, int Cin, int Cout, int K_pad,
                               int Cout_pad, int relu, void* stream);
 
-/* cvpce_conv3x3_halo_masked for the head's TWO towers in one launch (torchvision RetinaNetHead: classification_head.conv and
- * regression_head.conv are two independent chains of four 3x3 256 -> 256 convs + ReLU over the same features; reached from
- * cvpce/models/proposals.py:166).  Layer i of both towers = one conv with Cout = 256 x towers whose cout tile t is tower t:
- * wgt / bias = the towers' layer-i weights concatenated along Cout (fragment-major halo layout of the [Cout][9 Cin] matrix);
- * in_paired = 0: `in` is ONE atlas [N][H][W][Cin] every tower reads (the first layer); in_paired = 1: `in` is tower-major
- * [towers][N][H][W][Cin], tile t reads part t (the later layers).  `out` is ALWAYS tower-major [towers][N][H][W][256]: part t is
- * tower t's layer-i output, a valid atlas for the next paired launch and contiguous for the tower's output conv.  One launch has
- * towers x the tiles of a per-tower launch on the same persistent grid: 568 tiles in three rounds instead of 2 x (284 in two). */
-int cvpce_conv3x3_halo_masked_paired(const void* in, const void* wgt, const float* bias, const unsigned char* mask,
-                                     const int* tile_map, int n_tiles, void* out, int N, int H, int W, int Cin, int Cout, int K_pad,
-                                     int Cout_pad, int relu, int in_paired, void* stream);
-
 /* One ResNet-50 bottleneck block (torchvision `Bottleneck`, v1.5, STRIDE 1, FrozenBatchNorm2d folded into weights and biases;
  * reached from cvpce/models/proposals.py:202-216) in one launch, the two P-channel intermediates held in LDS:
  *   out = relu( conv1x1_w3( relu( conv3x3_w2( relu( conv1x1_w1(x) + b1 ) ) + b2 ) ) + b3 + res )
  * x: [N][H][W][Cin] (Cin % 64 == 0), res / out: [N][H][W][4P] (res = x for the identity blocks, else the projection
- * shortcut's output), P in {64, 128, 256} (layer1 / layer2 / layer3).  Weights in the layouts of cvpce_conv2d_nhwc_bf16:
- * w1 [c1_pad][k1_pad] (k = ci), w2 [c2_pad][k2_pad = 9P] chunk-major, w3 [c3_pad][k3_pad] (k = ci); biases fp32, required.
- * Same rounding points as the three separate launches (both intermediates are rounded to the storage type). */
-int cvpce_bottleneck_fused(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
-                           const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, int k1_pad, int k2_pad,
-                           int k3_pad, int c1_pad, int c2_pad, int c3_pad, void* stream);
-
-/* The same block with FRAGMENT-MAJOR weights (round 5): every MFMA weight fragment the kernel loads is one contiguous KiB (lane
- * L = 16 lq + l16 at byte 16 L, 8 consecutive k per lane) -- read from the row-major tensors a fragment is 16 rows x 64 bytes, which the
- * texture addresser serves one lane per clock.  No padding rows or columns:
+ * shortcut's output), P in {64, 128, 256} (layer1 / layer2 / layer3); biases fp32, required.  Same rounding points as the three
+ * separate launches (both intermediates are rounded to the storage type).  Weights are FRAGMENT-MAJOR: every MFMA weight fragment
+ * the kernel loads is one contiguous KiB (lane L = 16 lq + l16 at byte 16 L, 8 consecutive k per lane).  No padding rows or columns:
  *   w1 [Cin/32 K-steps ks][P/16 cout blocks b][lane][8]:  cout = 32 (b >> 1) + 8 (l16 >> 2) + (l16 & 3) + 4 (b & 1),  k = 32 ks + 8 lq + e
  *   w2 [P/CW groups cg][6 P/64 steps s = 6 c64 + 2 kw + half][kh][CW/16 blocks h][lane][8]:  CW = 16 at P = 64, else 32;
  *        cout = CW cg + (CW == 32 ? 8 (l16 >> 2) + (l16 & 3) + 4 h : l16),  k = ((3 c64 + kh) 3 + kw) 64 + 32 half + 8 lq + e (chunk-major K)
  *   w3 [4P/32 groups g][P/32 K-steps ks][2 blocks h][lane][8]:  cout = 32 g + 8 (l16 >> 2) + (l16 & 3) + 4 h,  k = 32 ks + 8 lq + e
- * (writer: cvpce_amd/ops.py pack_bottleneck_weights).  Results are bit-identical to cvpce_bottleneck_fused. */
+ * (writer: cvpce_amd/ops.py pack_bottleneck_weights). */
 int cvpce_bottleneck_fused_fm(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
                               const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, void* stream);
 
@@ -331,23 +312,11 @@ size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k);
 int cvpce_match_topk(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
                      int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
                      long long* out_idx, float* out_dist, void* stream);
-/* The same with a caller-owned STATE block (cvpce_match_state_bytes(max_queries) bytes, 8-byte aligned, initialised ONCE by
- * cvpce_match_state_init and restored by every call that uses it): with k = 1, bf16 rows and Qn <= max_queries the whole search is ONE
- * launch -- per-query 64-bit (distance, row) keys combined by device-scope atomic minima, results written by the last workgroup to
- * finish -- instead of a GEMM launch + a merge launch.  One state block per launch that may be in flight at a time (two streams: two
- * blocks).  state = NULL, k > 1, f32 rows or a query count beyond the block: exactly cvpce_match_topk.  Identical results either way.
- * OPT-IN (cvpce_match_set_core(..., one_launch = 1) or CVPCE_MATCH_FUSED=1): measured slower than the two launches at every size
- * (200 x 10 000 x 512: 10.4 us against 9.6 us), so by default this entry point IS cvpce_match_topk. */
-size_t cvpce_match_state_bytes(int max_queries);
-int cvpce_match_state_init(void* state, size_t state_bytes, void* stream);
-int cvpce_match_topk_state(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
-                           int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
-                           void* state, size_t state_bytes, long long* out_idx, float* out_dist, void* stream);
 /* Test / measurement switch of the bf16 path (process-wide; results never depend on it: every bf16 kernel forms identical
  * distances).  core 0 = choose per launch by estimated time (default), 1 = the 128-row register-staged kernel, 2 = the 256-row
  * LDS-DMA kernel; nq = 0 | 2..5 pins that kernel's query tile to 64 nq rows, mg = 0 | 1 | 2 its gallery tile to 128 mg rows
- * (mg = 1 exists for nq <= 4); one_launch = 0 keeps cvpce_match_topk_state on the two-launch form. */
-int cvpce_match_set_core(int core, int nq, int mg, int one_launch);
+ * (mg = 1 exists for nq <= 4). */
+int cvpce_match_set_core(int core, int nq, int mg);
 
 /* 3x3 / stride 1 / pad 1 convolution with FEW, arbitrarily many output channels and fp32 output, no activation: torchvision
  * RetinaNetHead's `cls_logits` (256 -> A * K = 9) and `bbox_reg` (256 -> 4 A = 36) output convs, reached from
@@ -393,15 +362,9 @@ int cvpce_conv3x3_halo_f16(const void* in, const void* wgt, const float* bias, v
                            int Cout, int K_pad, int Cout_pad, int relu, int fuse_pool2, void* stream);
 int cvpce_conv3x3_halo_wide_f16(const void* in, const void* wgt, const float* bias, void* out, int N, int H, int W, int Cin,
                                 int Cout, int K_pad, int Cout_pad, int relu, int fuse_pool2, void* stream);
-int cvpce_conv3x3_halo_masked_paired_f16(const void* in, const void* wgt, const float* bias, const unsigned char* mask,
-                                         const int* tile_map, int n_tiles, void* out, int N, int H, int W, int Cin, int Cout, int K_pad,
-                                         int Cout_pad, int relu, int in_paired, void* stream);
 int cvpce_conv3x3_halo_masked_f16(const void* in, const void* wgt, const float* bias, const unsigned char* mask,
                                   const int* tile_map, int n_tiles, void* out, int N, int H, int W, int Cin, int Cout, int K_pad,
                                   int Cout_pad, int relu, void* stream);
-int cvpce_bottleneck_fused_f16(const void* x, const void* res, const void* w1, const float* b1, const void* w2, const float* b2,
-                               const void* w3, const float* b3, void* out, int N, int H, int W, int Cin, int P, int k1_pad, int k2_pad,
-                               int k3_pad, int c1_pad, int c2_pad, int c3_pad, void* stream);
 int cvpce_maxpool2d_nhwc_f16(const void* in, void* out, int N, int H, int W, int C, int k, int stride, int pad,
                              int Ho, int Wo, void* stream);
 int cvpce_relu_f16(const void* in, void* out, long long n, void* stream);

@@ -36,21 +36,21 @@ def test_workspace_queries_are_host_only():
     assert lib.cvpce_match_workspace_bytes(1600, 3200, 1) >= 1600 * 25 * 8
 
 
-def test_torch_ops_registered_for_the_gpu_only():
+def test_torch_ops_cover_the_abi_on_the_gpu_only():
     """north_star: "exposed to Python through PyTorch-ROCm custom ops".  One dispatcher entry per C-ABI compute entry point,
     CUDA (= HIP) key only: a CPU tensor is refused by the dispatcher itself -- no CPU kernel exists to fall back to."""
     from cvpce_amd import torch_ops
     declared = {s for s in header_symbols() if not s.endswith('_bytes') and s not in ('cvpce_set_persistent_workgroups', 'cvpce_pack_halo_weights', 'cvpce_match_set_core')}   # (host-only helpers)
-    # the fp16 twins of the detector's kernels (round 3) are reached through the SAME ops: the op picks the entry point by the
+    # the fp16 twins of the detector's kernels are reached through the SAME ops: the op picks the entry point by the
     # activations' dtype (torch_ops._by_dtype) -- every twin must have its bf16 original declared too
     twins = {s for s in declared if s.endswith('_f16')}
-    assert len(twins) == 18      # (round 6: + the fused Gaussian subnet, the paired head-tower launch)
+    assert len(twins) == 16
     for t in twins:
         base = t[:-4]
         assert base in declared or base + '_bf16' in declared, t
     declared -= twins
     # (the two 3x3 halo entry points share one op: Cout <= 128 is forwarded to the wide-tile kernel inside the library)
-    assert len(torch_ops.NAMES) == len(declared) == 40   # (round 6: + gauss_subnet, conv3x3_halo_masked_paired) (round 5: + the head's thin-output 3x3, the fragment-major bottleneck, the split-K form of the register-staged conv, the content-only crop) (two halo entry points share an op; atlas_copy has two; round 4: the seven work-list / extent / MAC-start entry points, the Gaussian subnet's tail and its thin 3x3 layers; round 5: the matcher's one-launch form and its state initialiser)
+    assert len(torch_ops.NAMES) == len(declared) == 36   # (two halo entry points share an op; atlas_copy has two)
     for name in torch_ops.NAMES:
         op = getattr(torch.ops.cvpce_amd, name)
         assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')

@@ -568,12 +568,12 @@ def test_match_parity(cuda, dtype, qn, gn, d, k):
 
 
 @pytest.mark.parametrize('qn,gn,d', [(200, 10000, 512), (1600, 10000, 1024), (333, 1357, 256), (5, 40, 64)])
-def test_match_every_core_and_tile_gives_identical_results(cuda, qn, gn, d):
+def test_match_cores_and_tiles_give_identical_results(cuda, qn, gn, d):
     """The bf16 search has two cores (the 128-row register-staged kernel; the LDS-DMA kernel of round 5 with tiles of 128 MG gallery rows x
-    64 NQ queries) and, opt-in, a one-launch form of k = 1 (atomic (distance, row) keys + ticket).  Which one a launch takes is a cost
-    model's choice, so every variant must return the SAME indices and the SAME distances bit for bit -- a query's result must not depend
-    on how many queries it was batched with (classification.py:87-95; BASELINE configs[3] sizes first).  Includes a NaN query, equal rows
-    (ties -> lower index), a ragged last tile in both dimensions, k = 1 and k = 4, and a second call on the restored state block."""
+    64 NQ queries).  Which one a launch takes is a cost model's choice, so every variant must return the SAME indices and the SAME
+    distances bit for bit -- a query's result must not depend on how many queries it was batched with (classification.py:87-95;
+    BASELINE configs[3] sizes first).  Includes a NaN query, equal rows (ties -> lower index), a ragged last tile in both dimensions,
+    k = 1 and k = 4, and a repeated call."""
     from cvpce_amd import ops
     from cvpce_amd._lib import lib
     g = torch.Generator().manual_seed(qn * 7 + gn)
@@ -582,12 +582,11 @@ def test_match_every_core_and_tile_gives_identical_results(cuda, qn, gn, d):
     G[gn // 2] = G[3]                                    # duplicate rows: a tie for every query
     Q[1, 5] = float('nan')
     Gd, Qd = G.to(torch.bfloat16).to(cuda), Q.to(torch.bfloat16).to(cuda)
-    variants = [(1, 0, 0, 0)] + [(2, nq, mg, one) for mg in (1, 2) for nq in (2, 3, 4, 5) if not (mg == 1 and nq == 5) for one in (0, 1)]
+    variants = [(1, 0, 0)] + [(2, nq, mg) for mg in (1, 2) for nq in (2, 3, 4, 5) if not (mg == 1 and nq == 5)]
     ref = None
     try:
-        for core, nq, mg, one in variants:
-            assert ops.match_set_core(core, nq, mg, one) == 0
-            assert ops.MATCH_ONE_LAUNCH == bool(one)
+        for core, nq, mg in variants:
+            assert ops.match_set_core(core, nq, mg) == 0
             got = [ops.match_topk(Qd, Gd, 4, return_distance=True), ops.match_topk(Qd, Gd, 1, return_distance=True),
                    ops.match_topk(Qd, Gd, 1, return_distance=True)]
             torch.cuda.synchronize()
@@ -597,13 +596,12 @@ def test_match_every_core_and_tile_gives_identical_results(cuda, qn, gn, d):
             if ref is None:
                 ref = got
             for (i, x), (ri, rx) in zip(got, ref):
-                assert i.equal(ri), (core, nq, mg, one)
-                assert torch.equal(x.view(torch.int32), rx.view(torch.int32)), (core, nq, mg, one)       # bit for bit (inf rows included)
+                assert i.equal(ri), (core, nq, mg)
+                assert torch.equal(x.view(torch.int32), rx.view(torch.int32)), (core, nq, mg)       # bit for bit (inf rows included)
     finally:
-        ops.match_set_core(0, 0, 0, 0)
-    assert not ops._MATCH_STATE or ops.MATCH_ONE_LAUNCH is False          # (a state block exists only because a one-launch variant ran)
+        ops.match_set_core(0, 0, 0)
     assert ref[0][0][1].tolist() == [0, 1, 2, 3]                                      # the NaN query: all distances +inf, lowest rows first
-    assert lib.cvpce_match_set_core(2, 5, 1, 0) == 1 and lib.cvpce_match_set_core(3, 0, 0, 0) == 1      # no 128-row x 320-query tile; no such core
+    assert lib.cvpce_match_set_core(2, 5, 1) == 1 and lib.cvpce_match_set_core(3, 0, 0) == 1      # no 128-row x 320-query tile; no such core
 
 
 def test_match_k_clamped_and_nan_rows(cuda):
@@ -1042,7 +1040,7 @@ BNECK_CASES = [  # n, cin, planes, h, w, separate residual tensor (the projectio
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('n,cin,p,h,w,sep', BNECK_CASES)
 def test_bottleneck_fused_parity(cuda, dtype, n, cin, p, h, w, sep):
-    """cvpce_bottleneck_fused (1x1 -> 3x3 -> 1x1 + residual, intermediates in LDS) against the three-launch HIP schedule (same
+    """cvpce_bottleneck_fused_fm (1x1 -> 3x3 -> 1x1 + residual, intermediates in LDS) against the three-launch HIP schedule (same
     rounding points: within two ulps of the storage type, almost everywhere identical) and against the oracle ops on the same
     16-bit-rounded operands."""
     from cvpce_amd import ops
@@ -1061,13 +1059,9 @@ def test_bottleneck_fused_parity(cuda, dtype, n, cin, p, h, w, sep):
     ops.FUSED_BOTTLENECK_MAX_PLANES = 256          # the detector only uses P = 64 (the measured win); the kernel is verified for all three widths
     try:
         assert ops.can_fuse_bottleneck(xd, *pcs, rdv)
-        y = ops.bottleneck(xd, *pcs, rdv)                   # fragment-major weights (round 5, the default)
-        ops.BNECK_FRAGMENT_MAJOR = False
-        y_rm = ops.bottleneck(xd, *pcs, rdv)                # the same kernel reading the row-major weights: the same products in the same order
+        y = ops.bottleneck(xd, *pcs, rdv)
     finally:
         ops.FUSED_BOTTLENECK_MAX_PLANES = saved
-        ops.BNECK_FRAGMENT_MAJOR = True
-    assert torch.equal(y.view(torch.int16), y_rm.view(torch.int16))
     ops.USE_FUSED_BOTTLENECK = False
     try:
         m1 = ops.conv2d(xd, pcs[0], act=1)

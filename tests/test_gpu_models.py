@@ -348,7 +348,7 @@ def test_gaussian_branch_vs_reference_golden(cuda, golden_dir, tanh):
 
 
 @pytest.mark.parametrize('hw', [(100, 100), (64, 88), (20, 37)])
-def test_head_atlas_equals_per_level(cuda, gln_model, hw):
+def test_head_atlas_matches_per_level_launches(cuda, gln_model, hw):
     """RetinaNet head on the level atlas (one masked halo launch per tower layer) against the per-level launches."""
     from cvpce_amd.models import proposals as P
     model, _ = gln_model
@@ -371,18 +371,6 @@ def test_head_atlas_equals_per_level(cuda, gln_model, hw):
     for a, b in zip(cls_a + reg_a, cls_l + reg_l):
         assert a.shape == b.shape
         assert (a - b).abs().max() <= 0.02 * b.abs().max() + 1e-3, ((a - b).abs().max(), b.abs().max())
-    # round 6: layer i of BOTH towers as one paired launch (the towers as cout tiles of one conv; opt-in, CVPCE_PAIRED_TOWERS=1): every
-    # tile is computed with the same arithmetic as in the per-tower launches, so the two forms agree bit for bit
-    assert eng.tower_pairs is None
-    eng.tower_pairs = eng.pack_tower_pairs(model)
-    assert eng.tower_pairs is not None and eng.tower_pairs[0].cout == 512
-    try:
-        cls_u, reg_u = eng.heads_atlas(feats)
-    finally:
-        eng.tower_pairs = None
-    torch.cuda.synchronize()
-    for a, b in zip(cls_a + reg_a, cls_u + reg_u):
-        assert torch.equal(a, b)
 
 
 def test_detection_does_not_depend_on_the_batch(cuda):

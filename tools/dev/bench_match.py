@@ -13,7 +13,7 @@ cases = [tuple(int(v) for v in a.split(',')) for a in sys.argv[1:]] or [(200, 10
                                                                         (1600, 10000, 512), (1600, 10000, 1024), (1600, 3200, 1024), (1600, 1000, 1024), (3200, 10000, 1024)]
 
 
-SIDE = torch.cuda.Stream()        # warm-up and capture on ONE stream: the one-launch form's state block is per stream and is never created inside a capture
+SIDE = torch.cuda.Stream()        # warm-up and capture on ONE stream
 
 
 def timed(q, gal, qn, gn, per_graph=20, reps=10):
@@ -45,17 +45,17 @@ for P, G, D in cases:
     gn, qn = ops.row_norms(gal), ops.row_norms(q)
     res = {}
     ref = ref1 = None
-    variants = [('auto', 0, 0, 0, 0), ('small', 1, 0, 0, 0)]
+    variants = [('auto', 0, 0, 0), ('small', 1, 0, 0)]
     for mg in (1, 2):
         for nq in (2, 3, 4, 5):
             if mg == 1 and nq == 5:
                 continue
-            variants += [(f'b{nq}x{mg}', 2, nq, mg, 0), (f'b{nq}x{mg}-1L', 2, nq, mg, 1)]
-    for name, core, nq, mg, one in variants:
-        assert ops.match_set_core(core, nq, mg, one) == 0
+            variants.append((f'b{nq}x{mg}', 2, nq, mg))
+    for name, core, nq, mg in variants:
+        assert ops.match_set_core(core, nq, mg) == 0
         idx, dist = ops.match_topk(q, gal, 3, q_norms=qn, g_norms=gn, return_distance=True)
-        idx1, dist1 = ops.match_topk(q, gal, 1, q_norms=qn, g_norms=gn, return_distance=True)      # (k = 1: the one-launch form where enabled)
-        idx1b, dist1b = ops.match_topk(q, gal, 1, q_norms=qn, g_norms=gn, return_distance=True)    # ... and again on the restored state block
+        idx1, dist1 = ops.match_topk(q, gal, 1, q_norms=qn, g_norms=gn, return_distance=True)
+        idx1b, dist1b = ops.match_topk(q, gal, 1, q_norms=qn, g_norms=gn, return_distance=True)    # (a repeated call)
         torch.cuda.synchronize()
         if ref is None:
             ref, ref1 = (idx.clone(), dist.clone()), (idx1.clone(), dist1.clone())
@@ -63,6 +63,6 @@ for P, G, D in cases:
                     and torch.equal(idx1b, ref1[0]) and torch.equal(dist1b, ref1[1]) and torch.equal(idx1, idx[:, :1]) and torch.equal(dist1, dist[:, :1]))
         us = timed(q, gal, qn, gn)
         res[name] = (round(us, 2), round(2.0 * P * G * D / us / 1e6, 1), 'same' if same else 'DIFFERENT')
-    ops.match_set_core(0, 0, 0, 0)
+    ops.match_set_core(0, 0, 0)
     bad = [k for k, v in res.items() if v[2] != 'same']
     print(f'{P} x {G} x {D}: ' + '  '.join(f'{k} {v[0]}' for k, v in res.items()) + (f'  DIFFERENT: {bad}' if bad else '  (all identical)'), flush=True)

@@ -1,4 +1,4 @@
-"""dev tool: race screen of the distance-GEMM kernels -- every variant (core, tile, one-/two-launch), several shapes, `reps` launches each under
+"""dev tool: race screen of the distance-GEMM kernels -- every variant (core, tile), several shapes, `reps` launches each under
 memory load from a second stream, every result compared bit for bit with the first (LDS-DMA hand-offs are placed by vmcnt / barrier counts:
 a misplaced read passes single runs and fails rarely).  usage: soak_match.py [reps]"""
 import sys, os
@@ -18,8 +18,8 @@ for P, G, D in ((200, 10000, 512), (1600, 10000, 1024), (777, 3333, 256), (320, 
     q = torch.nn.functional.normalize(torch.randn(P, D, generator=g), dim=1).to(dev).to(torch.bfloat16)
     gn, qn = ops.row_norms(gal), ops.row_norms(q)
     ref = None
-    for core, nq, mg, one in [(1, 0, 0, 0)] + [(2, n_, m_, o_) for m_ in (1, 2) for n_ in (2, 3, 4, 5) if not (m_ == 1 and n_ == 5) for o_ in (0, 1)]:
-        assert ops.match_set_core(core, nq, mg, one) == 0
+    for core, nq, mg in [(1, 0, 0)] + [(2, n_, m_) for m_ in (1, 2) for n_ in (2, 3, 4, 5) if not (m_ == 1 and n_ == 5)]:
+        assert ops.match_set_core(core, nq, mg) == 0
         for k in (1, 3):
             first = None
             for r in range(reps):
@@ -36,6 +36,6 @@ for P, G, D in ((200, 10000, 512), (1600, 10000, 1024), (777, 3333, 256), (320, 
             if k == 3 and ref is not None and not (torch.equal(first[0], ref[0]) and torch.equal(first[1].view(torch.int32), ref[1].view(torch.int32))):
                 bad += 1
     torch.cuda.synchronize()
-    print(f'{P} x {G} x {D}: 15 variants x 2 k x {reps} launches, mismatches so far {bad}', flush=True)
-ops.match_set_core(0, 0, 0, 0)
+    print(f'{P} x {G} x {D}: 8 variants x 2 k x {reps} launches, mismatches so far {bad}', flush=True)
+ops.match_set_core(0, 0, 0)
 print('soak_match:', 'OK' if bad == 0 else f'{bad} MISMATCHES')
