@@ -10,7 +10,7 @@ Workloads (`--workload`):
   pipeline      (default) BASELINE configs[2]/[4] per-GPU shape: 8 x 3x2048x2048 -> detect -> crop -> embed -> match, G = 3200
   detector      BASELINE configs[1]: 4 x 3x2048x2048, GLN detector only, detections_per_img = 1000
   match-stress  BASELINE configs[3]: 200 (and 1600) queries x 10 000 gallery rows, D = 512 and 1024, bf16 distance GEMM
-Extra legs of the pipeline workload (all outside the timed region of `value`):
+Extra legs of the pipeline workload, run only with --full (all outside the timed region of `value`; each --no-* option drops one):
   roofline      per-kernel HIP-event timing of the conv kernels + per-stage times
   value_with_h2d  the same K steps with the images uploaded from pinned host memory on a copy stream, batch i+1 during batch i
   value_lists_off / value_planted_boxes / value_fitted_scenes_p200   the same whole pipeline with the constant-padding work lists off,
@@ -18,9 +18,13 @@ Extra legs of the pipeline workload (all outside the timed region of `value`):
                 much of `value` is a property of the random-weight detector's box shapes
   parity        tests/accuracy.py on a bounded sample: HIP pipeline (product defaults) vs the fp32 oracle (AP / AR300 / top-1)
   cpu_baseline  the oracle timed on this box's host cores
+  workloads     configs[1] and configs[3] above, the embedder on planted boxes, the pipeline on fitted scenes
+Options of every run:
   --verify      per-image SHA-256 of (boxes, scores, matched indices) gathered to rank 0: identical for 1/2/4/8-GPU runs
   --dump-outputs DIR   the arrays the last timed step returned, as DIR/<name>.npy (seeded inputs: comparable across builds)
 `--steps` is the number of timed steps of `value` (split into `--windows` windows); `ms_per_step` is one step at the median window's rate.
+Without --full a run does only what `value` needs: set-up, --warmup, the timed steps, --dump-outputs / --verify if asked, the line
+(the detector workload skips its profile pass and CPU baseline, match-stress times its first shape only).
 """
 import argparse
 import hashlib
@@ -41,6 +45,9 @@ import torch  # noqa: E402
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0   # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 MFMA_PEAK_CLOCK_MHZ = 2400.0           # the engine clock that peak is quoted at (same table)
 HBM_PEAK_GBS = 8000.0
+# the side legs: measurements of their own after the timed steps, run only with --full
+SIDE_LEG_FLAGS = ('no_cpu_baseline', 'no_roofline', 'no_clocks', 'no_peaks', 'no_parity', 'no_h2d', 'no_precision_leg', 'no_coheadlines',
+                  'no_workloads')
 
 
 def parse():
@@ -59,6 +66,10 @@ def parse():
                          "tolerance, same MFMA rate) or bf16 (opt-in; the embedder and the matcher compute in bf16 in both)")
     ap.add_argument('--windows', type=int, default=3, help='the --steps timed steps are split into this many back-to-back windows '
                                                             '(fewer when --steps is smaller); value = the median window')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the side legs: CPU baseline, roofline (with clocks and measured peaks), parity, '
+                         'H2D, the other detector precision, the co-headlines, the configs[1] / configs[3] workloads; the detector workload\'s '
+                         'profile pass and CPU baseline; match-stress\'s other three shapes.  The --no-* options below drop legs of a --full run')
     ap.add_argument('--no-workloads', action='store_true', help='skip the configs[1] / configs[3] figures appended to the pipeline line')
     ap.add_argument('--verify', action='store_true', help='gather per-image result digests to rank 0 (8e: identical across world sizes)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -81,6 +92,9 @@ def parse():
         ap.error('--steps must be at least 1')
     if args.dump_outputs and args.workload == 'match-stress':
         ap.error('--dump-outputs: the match-stress workload times graph replays of kernels only and returns no arrays to a caller')
+    if not args.full:
+        for flag in SIDE_LEG_FLAGS:
+            setattr(args, flag, True)
     return args
 
 
@@ -532,8 +546,9 @@ def build_pipeline(args, rank, world, dev, ipg, dpi):
     from cvpce_amd import dist as cdist, production, synthetic
     det = synthetic.synthetic_gln(seed=0, detections_per_img=dpi, precision=args.detector_precision)
     enc = synthetic.synthetic_macvgg(seed=1)
-    det_sd = {k: v.clone() for k, v in det.state_dict().items()} if rank == 0 else None
-    enc_sd = {k: v.clone() for k, v in enc.state_dict().items()} if rank == 0 else None
+    want_sd = rank == 0 and not args.no_cpu_baseline         # (the CPU baseline's copy of the weights)
+    det_sd = {k: v.clone() for k, v in det.state_dict().items()} if want_sd else None
+    enc_sd = {k: v.clone() for k, v in enc.state_dict().items()} if want_sd else None
     det, enc = det.to(dev), enc.to(dev)
 
     # gallery: embedded sharded (G/world rows per rank), assembled by ONE all_gather over RCCL/xGMI
@@ -569,7 +584,7 @@ def stub_factory():
     """CVPCE_BENCH_STUB='module:function' (tests only): a CPU stand-in for `build_pipeline` with the same signature and keys, so that
     main() -- argument parsing, sharding, the gallery all_gather, the timed windows' barriers and MAX reduction, the --verify gather,
     the rank-0-only tail -- can run under N gloo ranks on a box without a GPU.  The stand-in's dict may carry 'rank0_leg', a callable
-    standing for the long rank-0-only side legs.  Every GPU-only leg is off in that mode."""
+    standing for the long rank-0-only side legs (run with --full, like them).  Every GPU-only leg is off in that mode."""
     spec = os.environ.get('CVPCE_BENCH_STUB')
     if not spec:
         return None
@@ -598,8 +613,8 @@ def run_pipeline(args, rank, local_rank, world, dev):
             return None
 
     if stub is not None:
-        args.no_h2d = args.no_roofline = args.no_workloads = args.no_peaks = args.no_parity = args.no_cpu_baseline = True
-        args.no_precision_leg = args.no_coheadlines = True
+        for flag in SIDE_LEG_FLAGS:
+            setattr(args, flag, True)
     else:
         from cvpce_amd import ops, production, synthetic
     built = (stub or build_pipeline)(args, rank, world, dev, ipg, dpi)
@@ -667,7 +682,7 @@ def run_pipeline(args, rank, local_rank, world, dev):
 
     by_precision = leg('precision', precision_leg) if (rank == 0 and not args.no_precision_leg) else None
 
-    if rank == 0 and built.get('rank0_leg') is not None:
+    if rank == 0 and args.full and built.get('rank0_leg') is not None:
         built['rank0_leg']()
     cohead = None
     if rank == 0 and not args.no_coheadlines:
@@ -737,7 +752,7 @@ def run_pipeline(args, rank, local_rank, world, dev):
     roofline = leg('roofline', roofline_leg) if (not args.no_roofline and rank == 0) else None
 
     def workloads_leg():
-        # BASELINE configs[1] and configs[3] on this same box (a few hundred ms of GPU time): the driver only runs the default line
+        # BASELINE configs[1] and configs[3] on this same box (a few hundred ms of GPU time): one --full run of the default workload has them
         # (taken BEFORE the CPU-heavy legs: the oracle's OpenMP threads keep spinning for a while and slow the launch path)
         w = detector_workload(dev, 4, 1000, args.image_size, max(10, args.steps), max(3, args.warmup), args.detector_precision, collective=False, want_layers=True)
         workloads = {'detector_configs1': {k: v for k, v in w.items() if not k.startswith('_')}}
@@ -1035,13 +1050,16 @@ def run_detector(args, rank, local_rank, world, dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # workload: distance-GEMM stress (BASELINE configs[3])
 # ---------------------------------------------------------------------------------------------------------------------
-def match_stress_cases(dev, iters, warmup):
+MATCH_STRESS_SHAPES = ((200, 512), (200, 1024), (1600, 512), (1600, 1024))      # (P, D); the first is match-stress's `value`
+
+
+def match_stress_cases(dev, iters, warmup, shapes=MATCH_STRESS_SHAPES):
     """BASELINE configs[3]: P queries x 10 000 gallery rows x D, bf16 distance GEMM + fused top-1, per launch (graph-replayed)."""
     from cvpce_amd import ops
     G = 10000
     cases = []
     g = torch.Generator().manual_seed(0)
-    for P, D in ((200, 512), (200, 1024), (1600, 512), (1600, 1024)):
+    for P, D in shapes:
         gal = torch.nn.functional.normalize(torch.randn(G, D, generator=g), dim=1).to(dev).to(torch.bfloat16)
         q = torch.nn.functional.normalize(torch.randn(P, D, generator=torch.Generator().manual_seed(1)), dim=1).to(dev).to(torch.bfloat16)
         gn, qn = ops.row_norms(gal), ops.row_norms(q)
@@ -1080,7 +1098,8 @@ def match_stress_cases(dev, iters, warmup):
 
 def run_match_stress(args, rank, local_rank, world, dev):
     iters = max(20, args.steps * 10)
-    cases = match_stress_cases(dev, iters, args.warmup)
+    shapes = MATCH_STRESS_SHAPES if args.full else MATCH_STRESS_SHAPES[:1]
+    cases = match_stress_cases(dev, iters, args.warmup, shapes)
     if rank != 0:
         return None
     head = cases[0]
@@ -1088,7 +1107,8 @@ def run_match_stress(args, rank, local_rank, world, dev):
             'unit': 'queries/s', 'n_gpus': world, 'steps': iters, 'warmup': max(3, args.warmup), 'ms_per_step': round(head['us_per_launch'] / 1e3, 5),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
             'config': {'workload': 'distance GEMM + fused top-1 (cvpce_match_topk), P = 200 queries (one image), G = 10 000 gallery rows, D = 512 '
-                                   '(BASELINE configs[3]); cases: P in {200, 1600} x D in {512, 1024}', 'parallelism': f'dp{world} (replicas)'},
+                                   '(BASELINE configs[3]); cases (P x D): ' + ', '.join(f'{p} x {d}' for p, d in shapes),
+                       'parallelism': f'dp{world} (replicas)'},
             'roofline': {'bound': head['bound'], 'achieved': head['algorithmic_gbs'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': head['frac_of_hbm_peak'], 'traffic': None, 'kernel': 'match_kernel<bf16> + match_merge_kernel',
                          'avg_launch_us': head['us_per_launch'], 'cases': cases}}

@@ -101,3 +101,18 @@ def test_dump_outputs_types_budget_and_sample(tmp_path):
     rows = np.load(tmp_path / 'b' / 'x_rows.npy').astype(np.int64)
     assert np.array_equal(np.load(tmp_path / 'b' / 'x.npy'), big['x'].numpy()[rows]) and np.all(np.diff(rows) > 0)
     assert np.array_equal(rows, np.load(tmp_path / 'c' / 'x_rows.npy')) and not (tmp_path / 'b' / 'n_rows.npy').exists()
+
+
+def test_side_legs_run_only_with_full(monkeypatch):
+    """A plain run does only what `value` needs: every side leg's --no-* flag is set unless --full is given; under --full each --no-*
+    option still drops its leg.  SIDE_LEG_FLAGS names every --no-* option, so a new leg cannot join plain runs unnoticed."""
+    def parsed(*argv):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', *argv])
+        return bench.parse()
+    plain = parsed('--gpus', '1', '--steps', '5', '--warmup', '2')
+    assert not plain.full and all(getattr(plain, f) for f in bench.SIDE_LEG_FLAGS)
+    full = parsed('--gpus', '1', '--steps', '5', '--warmup', '2', '--full')
+    assert {k for k in vars(full) if k.startswith('no_')} == set(bench.SIDE_LEG_FLAGS)
+    assert not any(getattr(full, f) for f in bench.SIDE_LEG_FLAGS)
+    some = parsed('--full', '--no-peaks', '--no-parity')
+    assert {f for f in bench.SIDE_LEG_FLAGS if getattr(some, f)} == {'no_peaks', 'no_parity'}

@@ -113,7 +113,7 @@ def _bench_stub(gpus, extra=()):
     with tempfile.TemporaryDirectory() as tmp:
         det = os.path.join(tmp, 'details.json')
         r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '3', '--warmup', '1', '--gallery', '203',
-                            '--images-per-gpu', '8', '--verify', '--allow-stub', '--details', det, *extra], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                            '--images-per-gpu', '8', '--verify', '--full', '--allow-stub', '--details', det, *extra], capture_output=True, text=True, timeout=600, env=env, cwd=root)
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
         lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
         assert len(lines) == 1, r.stdout[-2000:]                      # rank 0 prints ONE line, the other ranks nothing

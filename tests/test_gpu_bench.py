@@ -1,6 +1,6 @@
 """bench.py's JSON contract on small inputs: every workload prints ONE COMPACT line (< 4 KB: round 5's 23 KB line could not be parsed by the
-driver) with the fields the driver reads, the roofline and cpu_baseline objects, and writes the full result object (tables, stages,
-co-headline objects) to the details file the line names."""
+driver) with the fields the driver reads, with --full the roofline and cpu_baseline objects, and writes the full result object (tables,
+stages, co-headline objects) to the details file the line names.  Without --full a run measures its headline only."""
 import json
 import os
 import subprocess
@@ -43,7 +43,7 @@ def _check_compact(c, d):
 
 
 def test_pipeline_line_small(cuda, tmp_path):
-    c, d = _run(tmp_path, '--steps', '3', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--gallery', '128', '--no-peaks')
+    c, d = _run(tmp_path, '--full', '--steps', '3', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--gallery', '128', '--no-peaks')
     _check_compact(c, d)
     assert BASE <= set(c) and c['config']['detector_precision'] == 'fp16' and c['config']['collectives'] is None
     assert c['value_lists_off'] == d['value_lists_off'] and c['value_planted_boxes'] == d['value_planted_boxes'] and c['value_with_h2d'] == d['value_with_h2d']
@@ -68,7 +68,7 @@ def test_pipeline_line_small(cuda, tmp_path):
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['cores'] >= 1 and c['value'] > 0 and 'sample' in c
     assert d['windows']['n'] == 3 and len(d['windows']['ms_per_step']) == 3 and d['windows']['min'] <= d['ms_per_step'] <= d['windows']['max']
-    w = d['workloads']                                   # BASELINE configs[1] and configs[3] ride on the default (driver-run) line
+    w = d['workloads']                                   # BASELINE configs[1] and configs[3] ride on the --full pipeline line
     assert w['detector_configs1']['images'] == 4 and w['detector_configs1']['detections_per_img'] == 1000 and w['detector_configs1']['ms_per_step'] > 0
     assert {(c['P'], c['D']) for c in w['match_stress_configs3']} == {(200, 512), (200, 1024), (1600, 512), (1600, 1024)}
     assert set(d['parity']['by_precision']) == {'bf16', 'fp16'}
@@ -112,10 +112,25 @@ def test_pipeline_line_small(cuda, tmp_path):
     assert all(0 < e['frac_of_roof'] <= 1.0 for e in ly['classes'] if e['bound'] != 'latency'), ly['classes']
 
 def test_detector_and_match_stress_lines(cuda, tmp_path):
-    c, d = _run(tmp_path, '--workload', 'detector', '--steps', '2', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--no-cpu-baseline')
+    c, d = _run(tmp_path, '--full', '--workload', 'detector', '--steps', '2', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--no-cpu-baseline')
     _check_compact(c, d)
     assert BASE <= set(d) and 'detector' in d['metric'] and d['roofline']['stages']['detect']['ms_per_step'] > 0
-    cm, m = _run(tmp_path, '--workload', 'match-stress', '--steps', '2')
+    cm, m = _run(tmp_path, '--full', '--workload', 'match-stress', '--steps', '2')
     _check_compact(cm, m)
     assert BASE <= set(m) and m['unit'] == 'queries/s' and m['roofline']['bound'] == 'hbm' and len(m['roofline']['cases']) == 4
     assert {(c['P'], c['D']) for c in m['roofline']['cases']} == {(200, 512), (200, 1024), (1600, 512), (1600, 1024)}
+
+
+def test_plain_run_measures_the_headline_only(cuda, tmp_path):
+    """Without --full every workload prints its headline figures and runs nothing of its own after the timed steps: no side leg, no
+    profile pass, no CPU baseline; match-stress times its first shape only."""
+    c, d = _run(tmp_path, '--steps', '3', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024', '--gallery', '128')
+    assert BASE <= set(c) and all(c[k] == d[k] for k in BASE - {'config'}) and d['value'] > 0 and d['config']['detector_precision'] == 'fp16'
+    assert d['windows']['n'] == 3 and d['windows']['min'] <= d['ms_per_step'] <= d['windows']['max']
+    side = {'roofline', 'cpu_baseline', 'parity', 'workloads', 'measured_peaks', 'value_by_detector_precision', 'co_headlines', 'value_with_h2d',
+            'upload_mb_per_step', 'value_lists_off', 'value_planted_boxes', 'value_fitted_scenes_p200'}
+    assert not side & set(d), side & set(d)
+    c, d = _run(tmp_path, '--workload', 'detector', '--steps', '2', '--warmup', '1', '--images-per-gpu', '2', '--image-size', '1024')
+    assert d['value'] > 0 and 'detector' in d['metric'] and not {'roofline', 'cpu_baseline'} & set(d)
+    c, m = _run(tmp_path, '--workload', 'match-stress', '--steps', '2')
+    assert [(e['P'], e['D']) for e in m['roofline']['cases']] == [(200, 512)] and m['value'] == m['roofline']['cases'][0]['queries_per_s']

@@ -27,7 +27,7 @@ def pick(pred):
 
 passes = d['steps'] * d['windows']['n'] + d['warmup'] + 2 * d['steps'] + 2     # warm-up + timed windows + the roofline leg's two passes (+ 2 clock-leg-free extras tolerated)
 out = [f'# {tag} — `roofline.achieved` reproduced from the profiler\'s own numbers\n',
-       f'Command: the stats pass of `tools/collect_profiles.sh {tag}` (`bench.py --steps {d["steps"]} --warmup {d["warmup"]}`, headline steps + roofline leg only).',
+       f'Command: the stats pass of `tools/collect_profiles.sh {tag}` (`bench.py --full --steps {d["steps"]} --warmup {d["warmup"]}` with every other leg off: headline steps + roofline leg only).',
        'Kernel durations: `' + os.path.basename(stats) + '` of that run (copied as `' + tag + '_bench_kernel_stats.csv`); executed FLOPs: the bench\'s own',
        'ConvProfile records (`roofline.executed_tflop`, `roofline.strip_launches.executed_tflop` in the details file of the same run): work-list launches compute',
        'only the listed tiles, so the FLOPs a launch executes are counted by the list builder (`csrc/skiplist.hip`), not derivable from the trace.\n',
