@@ -1,8 +1,9 @@
 """Embed+match top-k accuracy harness -- counterpart of /root/reference/cvpce/classification_eval.py:6-56.
-`testset` yields `(image (3,H,W) f32 in [0,1], list of target annotations, boxes (T,4) integer xyxy)`."""
+`testset` yields `(image (3,H,W) f32 in [0,1] or (H,W,3) uint8, list of target annotations, boxes (T,4) integer xyxy)`; with
+num_workers > 0 it is read through `feeding.ImageFeeder` (the gallery reader pool of the `Classifier` has the same size)."""
 import torch
 
-from . import ops, production, datautils
+from . import feeding, ops, production, datautils
 
 
 def clip_boxes_to_image(boxes, size):
@@ -19,11 +20,11 @@ def eval_dihe(encoder, sampleset, testset, batch_size, num_workers=0, k=(1,), ve
     classifier = production.Classifier(encoder, sampleset, batch_size=batch_size, num_workers=num_workers, k=max(k))
     total, correct = 0, {knn: 0 for knn in k}
     missed, confusion, per_ann = {}, {}, {}
-    for i, (img, target_anns, boxes) in enumerate(testset):
+    for i, (img, target_anns, boxes) in enumerate(feeding.feed(testset, num_workers, classifier.device)):
         if verbose and i % 10 == 0:
             print(f'{i}...')
-        boxes = clip_boxes_to_image(boxes, (img.shape[1], img.shape[2]))
-        crops = ops.crop_resize(img.to(device=classifier.device, dtype=torch.float32).contiguous(),
+        boxes = clip_boxes_to_image(boxes, datautils.image_hw(img))
+        crops = ops.crop_resize(ops.device_image(img, classifier.device),
                                 boxes.to(classifier.device), datautils.CLASSIFICATION_IMAGE_SIZE, mode=0)
         pred_anns = classifier.classify(crops)
         total += len(target_anns)

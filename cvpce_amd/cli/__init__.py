@@ -5,8 +5,11 @@ reference for
     cvpce gln eval | gln detect | dihe eval | dihe prebuild-index | eval-product-detection | eval-planograms
 
 Training, hyper-parameter search, dataset visualisation and plotting commands are out of scope.  Options that only steer
-the reference's DataLoader / matplotlib (`--dataloader-workers`, `--plots`,
-`--plot-res-reduction`) are accepted and ignored: images are read in-process and every metric is printed.
+the reference's matplotlib (`--plots`, `--plot-res-reduction`) are accepted and ignored: every metric is printed.
+`--dataloader-workers` is the number of reader THREADS of `feeding.ImageFeeder`: the shelf images are opened in the 8-bit
+form, decoded that many at a time ahead of the kernels and uploaded from pinned memory (0 = read serially in the calling
+thread; the printed metrics are the same to the last digit, the inputs being the same bits).  The two whole-pipeline commands
+have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
 
     python -m cvpce_amd.cli --help
 """
@@ -15,7 +18,7 @@ import os
 import click
 import torch
 
-from .. import classification_eval, datautils, detection_eval, production, proposals_eval
+from .. import classification_eval, datautils, detection_eval, feeding, production, proposals_eval
 from ..defaults import (GP_ANN_DIR, GP_PLANO_DIR, GP_TEST_DIR, GP_TEST_VALIDATION_SET_SIZE, GP_TRAIN_FOLDERS, OUT_DIR,
                         SKU110K_ANNOTATION_FILE, SKU110K_IMG_DIR, SKU110K_SKIP)
 from ..models import classification, proposals
@@ -28,6 +31,13 @@ _FILE = dict(exists=True, file_okay=True, dir_okay=False, readable=True)
 
 
 EVAL_WINDOW = 8     # images read ahead and run through the kernels together by the evaluation commands
+
+
+def _reader_threads():
+    """Reader threads of the two whole-pipeline commands.  The reference gives them no --dataloader-workers option (it hard-codes its
+    loaders there) and the option set of every command is the reference's, so the count comes from the environment:
+    CVPCE_DATALOADER_WORKERS, default 8 (the reference's DataLoader default), 0 = read serially in the calling thread."""
+    return max(0, int(os.environ.get('CVPCE_DATALOADER_WORKERS', feeding.DEFAULT_WORKERS)))
 
 
 def _coco_or(thresholds, coco):
@@ -59,7 +69,7 @@ def gln():
 @click.option('--annotations', type=click.Path(exists=True), default=SKU110K_ANNOTATION_FILE, show_default=True,
               help='Path to annotations used for testing')
 @click.option('--batch-size', type=int, default=1, show_default=True, help='Batch size')
-@click.option('--dataloader-workers', type=int, default=4, show_default=True, help='(ignored) Number of data loading processes')
+@click.option('--dataloader-workers', type=int, default=4, show_default=True, help='Number of data loading threads (0 = read in the calling thread)')
 @click.option('--metric-workers', type=int, default=8, show_default=True, help='Number of metric calculating processes (0 = in-process)')
 @click.option('--iou-threshold', '-t', type=float, multiple=True, default=(0.5,), show_default=True,
               help='IoU thresholds to calculate metrics for')
@@ -76,14 +86,14 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
 
     STATE_FILE should point to some GLN weights."""
     if dataset == 'sku110k':
-        data = datautils.SKU110KDataset(imgs, annotations, skip=SKU110K_SKIP, include_gaussians=False, flip_chance=0)
+        data = datautils.SKU110KDataset(imgs, annotations, skip=SKU110K_SKIP, include_gaussians=False, flip_chance=0, image_format='uint8')
     elif dataset == 'gp180':
-        data = datautils.GroceryProductsTestSet(imgs, annotations, retinanet_annotations=True)
+        data = datautils.GroceryProductsTestSet(imgs, annotations, retinanet_annotations=True, image_format='uint8')
     else:
-        data = datautils.GPBaselineDataset(imgs, annotations)
+        data = datautils.GPBaselineDataset(imgs, annotations, image_format='uint8')
     thresholds = _coco_or(iou_threshold, coco)
     evaluation = proposals_eval.evaluate_gln(state_file, data, thresholds=thresholds, batch_size=batch_size,
-                                             num_metric_processes=metric_workers, trim_module_prefix=trim_module_prefix)
+                                             num_workers=dataloader_workers, num_metric_processes=metric_workers, trim_module_prefix=trim_module_prefix)
     ap = ar = 0
     for t in thresholds:
         print(f'{t}:\t{evaluation[t]}')
@@ -107,7 +117,7 @@ def detect(conf_thresh, save, state_file, image_file):
     generator = production.ProposalGenerator(model, confidence_threshold=conf_thresh)
     pil_img = Image.open(image_file).convert('RGB')
     with torch.no_grad():
-        detections = generator.generate_proposals(datautils.pil_to_tensor(pil_img)).cpu()
+        detections = generator.generate_proposals(datautils.pil_to_uint8(pil_img)).cpu()
     for x1, y1, x2, y2 in detections.tolist():
         print(f'{x1:.1f} {y1:.1f} {x2:.1f} {y2:.1f}')
     print(f'--> {len(detections)} detections')
@@ -133,7 +143,7 @@ def dihe():
 @click.option('--resnet-layers', type=int, multiple=True, default=[2, 3], show_default=True, help='(resnet50 only)')
 @click.option('--batch-norm/--no-batch-norm', default=False, show_default=True, help="Use/don't use batch normalization in encoder")
 @click.option('--batch-size', type=int, default=8, show_default=True, help='Batch size')
-@click.option('--dataloader-workers', type=int, default=8, show_default=True, help='(ignored) Number of data loading processes')
+@click.option('--dataloader-workers', type=int, default=8, show_default=True, help='Number of data loading threads (0 = read in the calling thread)')
 @click.option('--enc-weights', help='Path to encoder weights')
 @click.option('--only', type=click.Choice(('none', 'test', 'val')), default='none', show_default=True,
               help='Use all images (none) or only the test- or validation split')
@@ -156,8 +166,8 @@ def dihe_eval(img_dir, test_imgs, annotations, model, resnet_layers, batch_norm,
         skip_list = GP_TEST_VALIDATION_SET_SIZE
     elif only == 'val':
         only_list = GP_TEST_VALIDATION_SET_SIZE
-    testset = datautils.GroceryProductsTestSet(test_imgs, annotations, only=only_list, skip=skip_list)
-    accuracy = classification_eval.eval_dihe(encoder, sampleset, testset, batch_size, 0, k=knn, verbose=True)
+    testset = datautils.GroceryProductsTestSet(test_imgs, annotations, only=only_list, skip=skip_list, image_format='uint8')
+    accuracy = classification_eval.eval_dihe(encoder, sampleset, testset, batch_size, dataloader_workers, k=knn, verbose=True)
     print(f'--> accuracy {accuracy}')
 
 
@@ -196,13 +206,15 @@ def prebuild_index(img_dir, datatype, out_dir, dihe_state):
 @click.argument('dihe-state', type=click.Path(**_FILE))
 def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco, load_classifier_index, gln_state, dihe_state):
     """Evaluate product detection performance."""
+    dataloader_workers = _reader_threads()
     sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True)
-    testset = datautils.GroceryProductsTestSet(test_imgs, annotations, retinanet_annotations=True)
+    testset = datautils.GroceryProductsTestSet(test_imgs, annotations, retinanet_annotations=True, image_format='uint8')
     thresholds = _coco_or(iou_threshold, coco)
     proposal_generator = proposals_eval.load_gln(gln_state, False, detections_per_img=200)
     proposal_generator.requires_grad_(False)
     res, all_res = detection_eval.evaluate_detections(proposal_generator, _load_encoder(dihe_state), testset, sampleset,
-                                                      thresholds=thresholds, load_classifier_index=load_classifier_index)
+                                                      thresholds=thresholds, num_workers=dataloader_workers,
+                                                      load_classifier_index=load_classifier_index)
     mam = detection_eval.mean_average_metrics(res, thresholds)
     m_ap = m_ar = 0
     for t in thresholds:
@@ -230,11 +242,12 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
 def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, load_classifier_index, verbose, gln_state,
                     dihe_state):
     """Evaluate planogram compliance evaluation."""
+    dataloader_workers = _reader_threads()
     if datatype == 'gp':
-        planoset = datautils.PlanogramTestSet(test_imgs, test_annotations, planograms)
+        planoset = datautils.PlanogramTestSet(test_imgs, test_annotations, planograms, image_format='uint8')
         sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True)
     else:
-        planoset = datautils.InternalPlanoSet(planograms)
+        planoset = datautils.InternalPlanoSet(planograms, image_format='uint8')
         sampleset = datautils.InternalTrainSet(img_dir[0], include_annotations=True)
     proposal_generator = proposals_eval.load_gln(gln_state, False)
     proposal_generator.requires_grad_(False)
@@ -242,11 +255,12 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
     evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator())
     total_a = total_e = 0.0
-    # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here EVAL_WINDOW images are read ahead and detected /
-    # embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results, one pass of the kernels per window)
-    for s in range(0, len(planoset), EVAL_WINDOW):
-        data = [planoset[i] for i in range(s, min(s + EVAL_WINDOW, len(planoset)))]
-        pairs = [((d[0], d[3]) if datatype == 'gp' else d) for d in data]
+    # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
+    # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,
+    # one pass of the kernels per window)
+    for s, data in enumerate(proposals_eval._batches(feeding.feed(planoset, dataloader_workers, generator.device), EVAL_WINDOW)):
+        s *= EVAL_WINDOW
+        pairs = [((d[0], d[3]) if datatype == 'gp' else tuple(d)) for d in data]
         accs = evaluator.evaluate_batch([img for img, _ in pairs], [plano for _, plano in pairs])
         for i, ((img, plano), acc) in enumerate(zip(pairs, accs), start=s):
             acc = float(acc)

@@ -9,13 +9,21 @@ CLASSIFICATION_IMAGE_SIZE = 256
 def resize_for_classification(img):
     """datautils.py:234-239: pad (3,h,w) to a square with 0.5 (top-left anchored), bilinear -> 256x256.
 
-    Runs the K9 HIP gather kernel (the whole image is the crop box)."""
+    Runs the K9 HIP gather kernel (the whole image is the crop box).  An 8-bit (h,w,3) image is converted on the device first."""
+    from . import ops          # the only kernel calls in this module: the readers below are host-only
+    ops.check_image_form(img)
     if not img.is_cuda:
         raise RuntimeError('resize_for_classification runs on an MI355X (HIP) device only (no CPU fallback)')
-    _, h, w = img.shape
+    h, w = image_hw(img)
     box = torch.tensor([[0.0, 0.0, float(w), float(h)]], device=img.device)
-    from . import ops          # the only kernel call in this module: the readers below are host-only
-    return ops.crop_resize(img.to(torch.float32).contiguous(), box, CLASSIFICATION_IMAGE_SIZE, mode=0)[0]
+    return ops.crop_resize(ops.device_image(img, img.device), box, CLASSIFICATION_IMAGE_SIZE, mode=0)[0]
+
+
+def image_hw(img):
+    """(H, W) of a shelf image in either form: float (3,H,W) or uint8 (H,W,3)."""
+    if img.dtype == torch.uint8:
+        return int(img.shape[0]), int(img.shape[1])
+    return int(img.shape[-2]), int(img.shape[-1])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -42,6 +50,35 @@ def pil_to_tensor(img):
     return torch.from_numpy(a.copy()).permute(2, 0, 1).to(torch.float32) / 255.0
 
 
+def pil_to_uint8(img):
+    """The same pixels as `pil_to_tensor` as the decoder produces them: contiguous uint8 (H,W,C), no float copy.  It stands for
+    the float image `u.permute(2,0,1).to(float32) / 255.0`; the product path converts it on the device (ops.device_image)."""
+    import numpy as np
+    if img.mode not in ('L', 'RGB', 'RGBA'):
+        img = img.convert('RGB')
+    a = np.asarray(img, dtype=np.uint8)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    return torch.from_numpy(a.copy()).contiguous()
+
+
+IMAGE_FORMATS = ('float', 'uint8')
+
+
+def _image_reader(image_format):
+    """The file -> tensor step of the shelf readers: 'float' = pil_to_tensor (3,H,W) float32, 'uint8' = (H,W,3) uint8."""
+    if image_format not in IMAGE_FORMATS:
+        raise ValueError(f'image_format must be one of {IMAGE_FORMATS}, got {image_format!r}')
+    if image_format == 'float':
+        return pil_to_tensor
+
+    def read(img):
+        if img.mode != 'RGB':            # a shelf image is three planes in the 8-bit form (grey / alpha files: as RGB)
+            img = img.convert('RGB')
+        return pil_to_uint8(img)
+    return read
+
+
 def _open_image(path):
     from PIL import Image
     return Image.open(path)
@@ -49,12 +86,15 @@ def _open_image(path):
 
 class SKU110KDataset:
     """datautils.py:130-189, evaluation use (cli/gln.py:264): 8-column CSV `name,x1,y1,x2,y2,class,width,height`, one
-    row per box, images grouped in order of first appearance.  Items: (image (3,H,W) float, entry dict)."""
+    row per box, images grouped in order of first appearance.  Items: (image (3,H,W) float, entry dict); with
+    image_format='uint8' (every shelf reader takes it) the image is (H,W,3) uint8, everything else the same."""
 
-    def __init__(self, img_dir_path, annotation_file_path, skip=(), include_gaussians=False, flip_chance=0, **_unused):
+    def __init__(self, img_dir_path, annotation_file_path, skip=(), include_gaussians=False, flip_chance=0, image_format='float',
+                 **_unused):
         if include_gaussians or flip_chance:
             raise NotImplementedError('training-time targets / augmentation are out of scope (DESIGN.md 6)')
         self.img_dir = img_dir_path
+        self.read_image = _image_reader(image_format)
         self.index = self.build_index(annotation_file_path, skip)
 
     @staticmethod
@@ -85,7 +125,7 @@ class SKU110KDataset:
     def __getitem__(self, i):
         entry = dict(self.index[i])
         try:
-            return pil_to_tensor(_open_image(_os.path.join(self.img_dir, entry['image_name']))), entry
+            return self.read_image(_open_image(_os.path.join(self.img_dir, entry['image_name']))), entry
         except OSError:
             print(f'WARNING: Malformed image: {entry["image_name"]} - returning image 0 ({self.index[0]["image_name"]}) instead.')
             return self[0]
@@ -94,7 +134,8 @@ class SKU110KDataset:
 class GPBaselineDataset:
     """datautils.py:191-232: one 6-column CSV with a header row, image files under <root>/storeN/images/."""
 
-    def __init__(self, img_dir_path, annotation_file_path):
+    def __init__(self, img_dir_path, annotation_file_path, image_format='float'):
+        self.read_image = _image_reader(image_format)
         self.index = self.build_index(img_dir_path, annotation_file_path)
 
     @staticmethod
@@ -127,7 +168,7 @@ class GPBaselineDataset:
 
     def __getitem__(self, i):
         entry = self.index[i]
-        return pil_to_tensor(_open_image(entry['image_path'])), entry
+        return self.read_image(_open_image(entry['image_path'])), entry
 
 
 class GroceryProductsTestSet:
@@ -137,8 +178,9 @@ class GroceryProductsTestSet:
     reference takes os.scandir order, which is unspecified) and the label ids of `retinanet_annotations` are the sorted
     annotation strings (the reference enumerates a set)."""
 
-    def __init__(self, image_dir, ann_dir, only=None, skip=None, retinanet_annotations=False):
+    def __init__(self, image_dir, ann_dir, only=None, skip=None, retinanet_annotations=False, image_format='float'):
         self.image_dir = image_dir
+        self.read_image = _image_reader(image_format)
         self.toskip = skip if type(skip) == int else 0
         self.tokeep = only if type(only) == int else 9999
         self.index = self.build_index(ann_dir, None if type(only) == int else only, None if type(skip) == int else skip)
@@ -186,7 +228,7 @@ class GroceryProductsTestSet:
 
     def __getitem__(self, i):
         e = self.index[i]
-        img = pil_to_tensor(_open_image(e['path']))
+        img = self.read_image(_open_image(e['path']))
         anns, boxes = e['anns'][self.toskip:self.tokeep], e['boxes'][self.toskip:self.tokeep]
         if self.retinanet_annotations:
             return img, {'labels': torch.tensor([self.ann_to_int[a] for a in anns], dtype=torch.long), 'boxes': boxes}
@@ -196,9 +238,9 @@ class GroceryProductsTestSet:
 class PlanogramTestSet(GroceryProductsTestSet):
     """datautils.py:692-707: GP-180 test images + their Tonioni planograms (s<store>_<image>.json)."""
 
-    def __init__(self, image_dir, ann_dir, plano_dir, only=None, skip=None):
+    def __init__(self, image_dir, ann_dir, plano_dir, only=None, skip=None, image_format='float'):
         self.plano_dir = plano_dir
-        super().__init__(image_dir, ann_dir, only, skip)
+        super().__init__(image_dir, ann_dir, only, skip, image_format=image_format)
 
     def build_index(self, ann_dir, only=None, skip=None):
         from . import planogram_adapters
@@ -218,7 +260,8 @@ class InternalPlanoSet:
     """datautils.py:709-750: index.json -> [{image, planogram, correct, facings}], planogram = [{code, box}] with the
     y axis pointing up (flipped here to detector coordinates)."""
 
-    def __init__(self, dir):
+    def __init__(self, dir, image_format='float'):
+        self.read_image = _image_reader(image_format)
         self.index = self.build_index(dir)
 
     @staticmethod
@@ -242,7 +285,7 @@ class InternalPlanoSet:
 
     def __getitem__(self, i):
         e = self.index[i]
-        return pil_to_tensor(_open_image(e['img'])), {'labels': e['anns'], 'boxes': e['boxes'], 'actual_accuracy': e['actual_accuracy']}
+        return self.read_image(_open_image(e['img'])), {'labels': e['anns'], 'boxes': e['boxes'], 'actual_accuracy': e['actual_accuracy']}
 
 
 class GroceryProductsDataset:

@@ -1,10 +1,11 @@
 """Detect -> crop -> embed -> match -> per-class mAP harness -- counterpart of
 /root/reference/cvpce/detection_eval.py:6-55.  `testset` yields `(image, target dict with 'boxes','labels')` and
-has `ann_to_int` / `int_to_ann` like the reference's GP-180 dataset.  As in the reference there is NO confidence
+has `ann_to_int` / `int_to_ann` like the reference's GP-180 dataset; the image is float (3,H,W) or 8-bit (H,W,3).  num_workers
+sizes the gallery reader pool of the `Classifier` and, above 0, the `feeding.ImageFeeder` the test set is read through.  As in the reference there is NO confidence
 filter here: every kept detection is embedded (detection_eval.py:29); unknown labels map to class -1 (:31)."""
 import torch
 
-from . import metrics, ops, production, datautils
+from . import feeding, metrics, ops, production, datautils
 from .proposals_eval import _batches
 
 
@@ -21,10 +22,10 @@ def evaluate_detections(p_model, c_model, testset, trainset, thresholds=(0.5,), 
     # detect -> crop -> embed -> match of a whole proposal batch in one pass of the kernels (the reference crops and classifies image
     # by image, detection_eval.py:27-30); confidence threshold -1: every kept detection is embedded, as in the reference
     pipe = production.BatchedPipeline(p_model, classifier, confidence_threshold=-1.0) if hasattr(p_model, 'engine') else None
-    for i, batch in enumerate(_batches(testset, proposal_batch_size)):
+    for i, batch in enumerate(_batches(feeding.feed(testset, num_workers, classifier.device), proposal_batch_size)):
         if verbose and i % 10 == 0:
             print(f'{i}...')
-        images = [img.cuda(non_blocking=True).to(torch.float32).contiguous() for img, _ in batch]
+        images = [ops.device_image(img, classifier.device) for img, _ in batch]
         if pipe is not None:
             out = pipe.run(images)
             ob, osc, oix = out['boxes'].cpu(), out['scores'].cpu(), out['indices'][:, :, 0].cpu()

@@ -786,9 +786,22 @@ def _transform_options(min_size, max_size, image_mean, image_std):
 # ---------------------------------------------------------------------------
 # public API
 # ---------------------------------------------------------------------------
+def _image_list(images):
+    """The images of a forward call as a list, each in one of the two accepted forms (ops.IMAGE_FORMS; a list may mix them):
+    a TypeError for anything else comes before the device check.  One tensor is a batch of float images (N,3,H,W), or ONE
+    8-bit image (H,W,3)."""
+    if torch.is_tensor(images):
+        images = [images] if images.dtype == torch.uint8 else list(images)
+    images = list(images)
+    for i in images:
+        ops.check_image_form(i)
+    return images
+
+
 class GaussianLayerNetwork(nn.Module):
     """Drop-in for proposals.py:162-181 (eval mode): `model(list[Tensor(3,H,W)])` ->
-    `list[dict(boxes, scores, labels, gaussians)]`, boxes in original pixels, scores descending.
+    `list[dict(boxes, scores, labels, gaussians)]`, boxes in original pixels, scores descending.  An image may also be 8-bit
+    (H,W,3) as a decoder produces it: it is converted on the device to the float image `to_tensor` makes of it, bit for bit.
 
     `**kwargs` are torchvision 0.9 RetinaNet's inference keywords, stored under its attribute names: `min_size`, `max_size`,
     `image_mean`, `image_std` (-> `self.transform`) and `anchor_generator` are fixed at construction; `score_thresh`,
@@ -853,8 +866,9 @@ class GaussianLayerNetwork(nn.Module):
         the largest magnitude and the fraction of elements at the saturation value.  A checkpoint whose activations come near 65504
         should run with `set_precision('bf16')` (8 exponent bits).  Seeded and fitted weights here stay below 1e3.
         -> {'precision', 'stages': {name: {'max_abs', 'saturated_fraction'}}, 'saturated': bool}"""
+        images = _image_list(images)
         eng = self.engine()
-        images = [i.to(device=eng.device, dtype=torch.float32) for i in (list(images) if torch.is_tensor(images) else images)]
+        images = [ops.device_image(i, eng.device) for i in images]
         _, inter = eng.detect(images, self.num_classes, self.detections_per_img, want_intermediates=True)
         self.backbone.gaussians = None
         limit = 65504.0 if self.precision == 'fp16' else float(torch.finfo(torch.bfloat16).max)
@@ -877,10 +891,9 @@ class GaussianLayerNetwork(nn.Module):
     def forward(self, images, targets=None):
         if self.training:
             raise NotImplementedError('training is out of scope of the MI355X inference path (SURVEY.md 2)')
-        if torch.is_tensor(images):
-            images = list(images)
+        images = _image_list(images)
         eng = self.engine()
-        images = [i.to(device=eng.device, dtype=torch.float32) for i in images]
+        images = [ops.device_image(i, eng.device) for i in images]
         boxes, scores, labels, count, _, gauss = eng.detect(images, self.num_classes, self.detections_per_img)
         self.backbone.gaussians = gauss
         counts = count.tolist()

@@ -774,6 +774,63 @@ def l2_normalize(desc, eps=1e-8, want_bf16=False):
 # ---------------------------------------------------------------------------
 # input side
 # ---------------------------------------------------------------------------
+# A shelf image reaches the product path in one of two forms: float (3,H,W) in [0,1] (`datautils.pil_to_tensor`) or 8-bit (H,W,3)
+# as the decoder produces it (`datautils.pil_to_uint8`).  The 8-bit form MEANS the float image pil_to_tensor makes of the same
+# pixels, `u.permute(2,0,1).to(float32) / 255.0` (the correctly rounded quotient; code * float32(1/255) differs from it for 126 of
+# the 256 codes).  It becomes that float image once, on the device, by a gather from a 256-entry table that is built on the host
+# with exactly that expression -- exact by construction, whatever the device's division does.  The transform and crop kernels keep
+# reading float32 planes: no kernel entry point knows about bytes.
+IMAGE_FORMS = 'float (3,H,W) in [0,1] or uint8 (H,W,3)'
+_UINT8_TABLES = {}
+
+
+def uint8_table(device=None):
+    """The 256 float32 values of the 8-bit codes, `arange(256) / 255` computed on the host; device: uploaded once per device."""
+    key = None if device is None else str(torch.device(device))
+    t = _UINT8_TABLES.get(key)
+    if t is None:
+        t = torch.arange(256, dtype=torch.float32) / 255.0
+        if key is not None and torch.device(device).type != 'cpu':
+            t = t.to(device)
+        _UINT8_TABLES[key] = t
+    return t
+
+
+def is_uint8_image(img):
+    return torch.is_tensor(img) and img.dtype == torch.uint8
+
+
+def check_image_form(img):
+    """TypeError for a tensor that is neither of the two image forms.  An integer tensor of any other shape used to be read as
+    floats 0 ... 255, which no caller can have meant."""
+    if not torch.is_tensor(img):
+        raise TypeError(f'an image is a tensor, {IMAGE_FORMS}; got {type(img).__name__}')
+    if img.dtype == torch.uint8 and (img.dim() != 3 or img.shape[2] != 3):
+        raise TypeError(f'an image is {IMAGE_FORMS}; got uint8 {tuple(img.shape)}')
+    return img
+
+
+def uint8_to_float(u):
+    """uint8 (H,W,3) -> float32 (3,H,W) contiguous on u's device: the table gather.  The index is int32, the narrowest type
+    index_select takes (an int64 index would be 100 MB per 2048^2 image)."""
+    check_image_form(u)
+    h, w, _ = u.shape
+    idx = u.permute(2, 0, 1).to(torch.int32, memory_format=torch.contiguous_format).reshape(-1)
+    return uint8_table(u.device).index_select(0, idx).view(3, h, w)
+
+
+def device_image(img, device):
+    """The one place that turns an input image into the device float image (3,H,W) float32 contiguous.
+    float: today's `to(device, float32).contiguous()`.  uint8 (H,W,3): the bytes are uploaded (non-blocking when the source is
+    pinned) unless they are on a device already, then converted there.  Any other uint8 shape: TypeError."""
+    check_image_form(img)
+    if img.dtype != torch.uint8:
+        return img.to(device=device, dtype=torch.float32).contiguous()
+    if not img.is_cuda:
+        img = img.to(device, non_blocking=img.is_pinned())
+    return uint8_to_float(img)
+
+
 def gln_transform_into(img, batch, index, h, w, mean, std):
     """img (3,H0,W0) f32 cuda -> batch[index] (Hp,Wp,8) bf16 | fp16 (the batch tensor's type)."""
     _need_cuda(img, batch)

@@ -37,6 +37,9 @@ class ProposalGenerator:
         self.condfidence_threshold = confidence_threshold  # (sic) production.py:12
 
     def generate_proposals(self, image):
+        """image: float (3,H,W) or 8-bit (H,W,3) (ops.device_image converts the latter on the device)."""
+        if ops.is_uint8_image(image):
+            image = ops.device_image(image, self.device)
         res = self.detector(image[None].to(self.device))[0]
         return res['boxes'][res['scores'] > self.condfidence_threshold]
 
@@ -65,11 +68,11 @@ class ProposalGenerator:
 
     def generate_proposals_and_images(self, image):
         size = datautils.CLASSIFICATION_IMAGE_SIZE
-        img = image.to(device=self.device, dtype=torch.float32).contiguous()
+        img = ops.device_image(image, self.device)           # (either form; converted once, detected and cropped from)
         if hasattr(self.detector, 'engine') and not getattr(self.detector, 'training', False):
             boxes = self._confident_boxes(img)
         else:                                   # any other detector object with the reference's call signature
-            boxes = self.generate_proposals(image)
+            boxes = self.generate_proposals(img if ops.is_uint8_image(image) else image)
             if len(boxes):
                 boxes = boxes[_nondegenerate(boxes)]
         if not len(boxes):
@@ -229,7 +232,7 @@ class PlanogramComparator:
 
     def compare(self, expected, actual, image=None, classifier=None):
         from . import planograms
-        reproj_threshold = 10 if image is None else min(image.shape[1:]) * 0.01
+        reproj_threshold = 10 if image is None else min(datautils.image_hw(image)) * 0.01
         if not len(actual['boxes']):
             return 0 if len(expected['boxes']) else 1
         ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'],
@@ -244,7 +247,7 @@ class PlanogramComparator:
         if found is None:                       # no homography (production.py:98-99)
             return len(matching) / len(expected['boxes'])
         if classifier is not None and image is not None and len(missing_positions):
-            h, w = image.shape[1:]
+            h, w = datautils.image_hw(image)
             pos = missing_positions.clone()
             pos[:, 0::2] = pos[:, 0::2].clamp(min=0, max=w)
             pos[:, 1::2] = pos[:, 1::2].clamp(min=0, max=h)
@@ -253,7 +256,7 @@ class PlanogramComparator:
                 return found.sum() / len(found)
             idx, pos = missing_indices[valid], pos[valid]
             lbls = [l for l, v in zip(missing_labels, valid) if v]
-            img = image.to(device=classifier.device, dtype=torch.float32).contiguous()
+            img = ops.device_image(image, classifier.device)
             crops = ops.crop_resize(img, pos.to(classifier.device), datautils.CLASSIFICATION_IMAGE_SIZE, mode=0)
             for i, want, got in zip(idx, lbls, classifier.classify(crops)):
                 if want == got[0]:
@@ -269,7 +272,15 @@ class PlanogramEvaluator:
         self.classifier = classifier
         self.planogram_comparator = planogram_comparator
 
+    def _float_image(self, image):
+        """An 8-bit image becomes the device float image here, ONCE: detection, the crops and the comparator's re-classification all
+        read that one.  A float image goes on as it came (the callees upload it as before)."""
+        if ops.is_uint8_image(image):
+            return ops.device_image(image, getattr(self.proposal_generator, 'device', self.classifier.device))
+        return image
+
     def evaluate(self, image, planogram):
+        image = self._float_image(image)
         boxes, images = self.proposal_generator.generate_proposals_and_images(image)
         classes = [ann[0] for ann in self.classifier.classify(images)]
         return self.planogram_comparator.compare(planogram, {'boxes': boxes.detach().cpu(), 'labels': classes},
@@ -290,9 +301,9 @@ class PlanogramEvaluator:
         out = [None] * len(images)
         groups = {}
         for i, img in enumerate(images):
-            groups.setdefault(tuple(img.shape), []).append(i)
+            groups.setdefault(datautils.image_hw(ops.check_image_form(img)), []).append(i)
         for idxs in groups.values():
-            res = pipe.run([images[i].to(device=pg.device, dtype=torch.float32).contiguous() for i in idxs])
+            res = pipe.run([ops.device_image(images[i], pg.device) for i in idxs])
             boxes, indices = res['boxes'].cpu(), res['indices'][:, :, 0].cpu()
             for j, i in enumerate(idxs):
                 c = res['counts_host'][j]
@@ -307,6 +318,7 @@ class PlanogramEvaluator:
         """[evaluate(image, planogram) for image, planogram in zip(...)] with the detect / crop / embed / match half batched
         (`detect_and_classify_batch`); the comparator (CPU graph matching, RANSAC, re-classification of missing positions) runs
         per image as in production.py:123-129."""
+        images = [self._float_image(img) for img in images]
         dets = self.detect_and_classify_batch(images)
         return [self.planogram_comparator.compare(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
                 for img, plano, (b, labels) in zip(images, planograms, dets)]
@@ -319,7 +331,8 @@ class PlanogramEvaluator:
         against 275 batched).  The iterator reads up to `lookahead` pairs ahead and sends consecutive images of one size through
         `detect_and_classify_batch` together; the comparator runs per image as before.  Every yielded value equals what
         `evaluate(image, planogram)` returns for that pair (tests/test_gpu_harness.py): an image's detections and labels do not depend
-        on what it is batched with.  lookahead = 1 is the serial loop."""
+        on what it is batched with.  lookahead = 1 is the serial loop.  `pairs` may be a `feeding.ImageFeeder` over such pairs: its
+        device-resident 8-bit images are converted where they are, never copied again."""
         window = []
 
         def flush():
@@ -329,7 +342,8 @@ class PlanogramEvaluator:
             window.clear()
 
         for image, planogram in pairs:
-            if window and (len(window) >= max(1, lookahead) or tuple(image.shape) != tuple(window[0][0].shape)):
+            image = self._float_image(image)
+            if window and (len(window) >= max(1, lookahead) or datautils.image_hw(image) != datautils.image_hw(window[0][0])):
                 yield from flush()
             window.append((image, planogram))
         if window:
@@ -418,7 +432,7 @@ class BatchedPipeline:
 
     @torch.no_grad()
     def run(self, images, stage_events=None, proposals=None):
-        """images: list of (3,H,W) f32 cuda tensors -> dict of device tensors:
+        """images: list of (3,H,W) f32 cuda tensors (or 8-bit (H,W,3) images, converted on the device first) -> dict of device tensors:
         boxes (N,dpi,4), scores (N,dpi), count (N,) = #scores > confidence, indices (N,dpi,k) (-1 beyond count).
         stage_events: optional list that receives (stage name, start event, end event) for detect / crop / embed / match.
         proposals: optional (boxes (N,dpi,4) f32, counts (N,) int32) device tensors that REPLACE the detector's confident boxes after
@@ -434,6 +448,11 @@ class BatchedPipeline:
             return e
 
         det = self.detector
+        if any(ops.is_uint8_image(i) for i in images):
+            for i in images:
+                ops.check_image_form(i)
+            device = det.engine().device
+            images = [ops.device_image(i, device) if ops.is_uint8_image(i) else i for i in images]
         t0 = mark()
         if ops.PROFILE is not None:
             ops.PROFILE.records.stage = 'detect'           # (per-launch profile: the detector's 3x3 halo launches are filed apart)
