@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/cvpce_amd.h.
+"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -86,10 +86,16 @@ for _base, _twin in (('cvpce_conv2d_nhwc_bf16', 'cvpce_conv2d_nhwc_f16'), ('cvpc
                      ('cvpce_gln_transform', 'cvpce_gln_transform_f16'), ('cvpce_gln_transform_batch', 'cvpce_gln_transform_batch_f16')):
     SIGNATURES[_twin] = SIGNATURES[_base]
 
-for _name, (_res, _args) in SIGNATURES.items():
-    _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
+# include/cvpce_amd_eval.h: the evaluation kernels.  A table of its own -- SIGNATURES mirrors the inference header alone.
+EVAL_SIGNATURES = {
+    'cvpce_eval_match_detections': (c_int, [_fp, _ip, _ip, _ip, _fp, _ip, _ip, _fp] + [c_int] * 5 + [_ip, _vp, _vp]),
+}
+
+for _table in (SIGNATURES, EVAL_SIGNATURES):
+    for _name, (_res, _args) in _table.items():
+        _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
+        _fn.restype = _res
+        _fn.argtypes = _args
 
 _ERR = {1: 'bad argument', 2: 'kernel launch failure'}
 

@@ -10,6 +10,8 @@ the reference's matplotlib (`--plots`, `--plot-res-reduction`) are accepted and 
 form, decoded that many at a time ahead of the kernels and uploaded from pinned memory (0 = read serially in the calling
 thread; the printed metrics are the same to the last digit, the inputs being the same bits).  The two whole-pipeline commands
 have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
+One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
+(default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`).
 
     python -m cvpce_amd.cli --help
 """
@@ -51,6 +53,39 @@ def _load_encoder(dihe_state):
     return encoder.eval().requires_grad_(False)
 
 
+class _DeviceMetricsCommand(click.Command):
+    """A command that also takes --device-metrics / --no-device-metrics (default: off).
+
+    The declared options of every command are the reference's, name by name and default by default; this switch has no
+    counterpart there.  It is therefore not declared among them: it is taken off the argument list before click parses the
+    rest, shown in --help under a heading of its own, and read by the command through `_device_metrics_switch()`."""
+    SWITCH = {'--device-metrics': True, '--no-device-metrics': False}
+    HELP = ('Match detections to the ground truth on the GPU instead of on the host (cvpce_amd.device_metrics). '
+            'No metric process is started: --metric-workers is ignored with it.  [default: off]')
+
+    def parse_args(self, ctx, args):
+        rest = []
+        ctx.meta['cvpce_amd.device_metrics'] = False
+        for i, a in enumerate(args):
+            if a == '--':                        # (everything after it is positional)
+                rest += args[i:]
+                break
+            if a in self.SWITCH:
+                ctx.meta['cvpce_amd.device_metrics'] = self.SWITCH[a]
+            else:
+                rest.append(a)
+        return super().parse_args(ctx, rest)
+
+    def format_options(self, ctx, formatter):
+        super().format_options(ctx, formatter)
+        with formatter.section('Options beyond the reference\'s'):
+            formatter.write_dl([('--device-metrics / --no-device-metrics', self.HELP)])
+
+
+def _device_metrics_switch():
+    return bool(click.get_current_context().meta.get('cvpce_amd.device_metrics', False))
+
+
 @click.group()
 def cli():
     """Computer vision based planogram compliance evaluation -- MI355X inference / evaluation commands."""
@@ -62,7 +97,7 @@ def gln():
     """Product proposal generation (GLN)."""
 
 
-@gln.command()
+@gln.command(cls=_DeviceMetricsCommand)
 @click.option('--dataset', type=click.Choice(('sku110k', 'gp180', 'gpbaseline')), default='sku110k', show_default=True,
               help='Dataset type that --imgs and --annotations points to')
 @click.option('--imgs', type=click.Path(**_DIR), default=SKU110K_IMG_DIR, show_default=True, help='Path to image dir')
@@ -70,7 +105,8 @@ def gln():
               help='Path to annotations used for testing')
 @click.option('--batch-size', type=int, default=1, show_default=True, help='Batch size')
 @click.option('--dataloader-workers', type=int, default=4, show_default=True, help='Number of data loading threads (0 = read in the calling thread)')
-@click.option('--metric-workers', type=int, default=8, show_default=True, help='Number of metric calculating processes (0 = in-process)')
+@click.option('--metric-workers', type=int, default=8, show_default=True,
+              help='Number of metric calculating processes (0 = in-process); ignored with --device-metrics')
 @click.option('--iou-threshold', '-t', type=float, multiple=True, default=(0.5,), show_default=True,
               help='IoU thresholds to calculate metrics for')
 @click.option('--coco/--no-coco', default=False, show_default=True,
@@ -93,7 +129,8 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
         data = datautils.GPBaselineDataset(imgs, annotations, image_format='uint8')
     thresholds = _coco_or(iou_threshold, coco)
     evaluation = proposals_eval.evaluate_gln(state_file, data, thresholds=thresholds, batch_size=batch_size,
-                                             num_workers=dataloader_workers, num_metric_processes=metric_workers, trim_module_prefix=trim_module_prefix)
+                                             num_workers=dataloader_workers, num_metric_processes=metric_workers, trim_module_prefix=trim_module_prefix,
+                                             device_metrics=_device_metrics_switch())
     ap = ar = 0
     for t in thresholds:
         print(f'{t}:\t{evaluation[t]}')
@@ -191,7 +228,7 @@ def prebuild_index(img_dir, datatype, out_dir, dihe_state):
 
 
 # ------------------------------------------------------------------ whole pipeline -------------------------------------
-@cli.command()
+@cli.command(cls=_DeviceMetricsCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to GP training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to GP test image root')
@@ -214,7 +251,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     proposal_generator.requires_grad_(False)
     res, all_res = detection_eval.evaluate_detections(proposal_generator, _load_encoder(dihe_state), testset, sampleset,
                                                       thresholds=thresholds, num_workers=dataloader_workers,
-                                                      load_classifier_index=load_classifier_index)
+                                                      load_classifier_index=load_classifier_index, device_metrics=_device_metrics_switch())
     mam = detection_eval.mean_average_metrics(res, thresholds)
     m_ap = m_ar = 0
     for t in thresholds:

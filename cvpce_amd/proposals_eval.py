@@ -1,7 +1,10 @@
 """Detector-only evaluation harness -- counterpart of /root/reference/cvpce/proposals_eval.py:9-91
 (`load_gln`, `evaluate_gln_sync`, `evaluate_gln_async`, `evaluate_gln`; the multiprocess variant only changes where the
-CPU metric code runs: at > 1 000 detector images/s the single-threaded matching loop is what the harness would wait on).  The per-image triple handed to the metric routine is the reference's: (target boxes, predicted boxes,
-scores).  `dataset` is any of the readers in datautils.py, or any iterable of `(image (3,H,W) f32 in [0,1] or (H,W,3) uint8,
+CPU metric code runs).  The per-image triple handed to the metric routine is the reference's: (target boxes, predicted boxes,
+scores).  By default the matching runs on the host as in the reference, in-process or in worker processes; with
+`device_metrics=True` it runs on the device instead (device_metrics.DetectionMetrics: one kernel launch per batch queued behind
+the detector, no per-image copy to the host, no worker processes, one device-to-host copy when the data set is exhausted) and
+gives the same result wherever an image's confidences are pairwise distinct (equal confidences: see device_metrics).  `dataset` is any of the readers in datautils.py, or any iterable of `(image (3,H,W) f32 in [0,1] or (H,W,3) uint8,
 target dict with 'boxes' (T,4))`.  num_workers > 0 reads it through `feeding.ImageFeeder` with that many threads (the reference's
 DataLoader workers); 0, the default, reads it in the calling thread."""
 import torch
@@ -33,7 +36,9 @@ def _batches(dataset, batch_size):
 
 @torch.no_grad()
 def evaluate_gln_sync(model, dataset, thresholds=(.5,), batch_size=1, num_workers=0, plots=False, silent=True,
-                      plot_res_reduction=1):
+                      plot_res_reduction=1, device_metrics=False):
+    if device_metrics:
+        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent)
     predictions, targets, confidences = [], [], []
     for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
         if not silent and i % 100 == 0:
@@ -47,10 +52,25 @@ def evaluate_gln_sync(model, dataset, thresholds=(.5,), batch_size=1, num_worker
     return {thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}
 
 
+def _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent):
+    from . import device_metrics
+    accumulator = device_metrics.DetectionMetrics(thresholds)
+    for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
+        if not silent and i % 100 == 0:
+            print(f'{i}...')
+        result = model([img.cuda(non_blocking=True) for img, _ in batch])
+        accumulator.update([t['boxes'] for _, t in batch], [r['boxes'] for r in result], [r['scores'] for r in result])
+    res = accumulator.compute()
+    return {thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}
+
+
 @torch.no_grad()
 def evaluate_gln_async(model, dataset, thresholds=(.5,), batch_size=1, num_workers=0, num_metric_processes=4, plots=False,
-                       plot_res_reduction=1, silent=True):
-    """proposals_eval.py:50-87: detections are handed to `num_metric_processes` matching workers as they are produced."""
+                       plot_res_reduction=1, silent=True, device_metrics=False):
+    """proposals_eval.py:50-87: detections are handed to `num_metric_processes` matching workers as they are produced.
+    device_metrics=True: no workers are started, the matching is queued on the device behind each batch."""
+    if device_metrics:
+        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent)
     # (the metric processes are started BEFORE the feeder's reader threads exist: a process forked beside running threads can deadlock)
     queue, mqueue, pipe = metrics.calculate_metrics_async(processes=num_metric_processes, iou_thresholds=thresholds)
     for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
@@ -73,9 +93,12 @@ def evaluate_gln_async(model, dataset, thresholds=(.5,), batch_size=1, num_worke
 
 
 def evaluate_gln(save_file, dataset, thresholds=(.5,), batch_size=1, num_workers=0, num_metric_processes=4, plots=False,
-                 trim_module_prefix=True, resolution_reduction=1):
-    """proposals_eval.py:89-91.  num_metric_processes = 0 runs the matching in-process (evaluate_gln_sync)."""
+                 trim_module_prefix=True, resolution_reduction=1, device_metrics=False):
+    """proposals_eval.py:89-91.  num_metric_processes = 0 runs the matching in-process (evaluate_gln_sync); device_metrics=True
+    runs it on the device and ignores num_metric_processes."""
     model = load_gln(save_file, trim_module_prefix)
+    if device_metrics:
+        return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers, device_metrics=True)
     if num_metric_processes and num_metric_processes > 0:
         return evaluate_gln_async(model, dataset, thresholds, batch_size, num_workers, num_metric_processes)
     return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers)

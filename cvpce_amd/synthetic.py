@@ -174,3 +174,31 @@ def structured_shelf(seed, h, w, products, pool=None, scale=(0.45, 0.95), backgr
         img[:, y + row_h:y + row_h + 10, :] = 0.62                                         # the shelf board
         y += row_h + 10 + int(torch.randint(6, 30, (1,), generator=g))
     return img.clamp(0, 1), torch.tensor(boxes, dtype=torch.float32).reshape(-1, 4), torch.tensor(ids, dtype=torch.int64)
+
+
+def dense_detection_scene(seed, n_pred=1000, n_tgt=150, size=2048.0):
+    """Boxes only (no image): a crowded shelf's ground truth and a detector-like prediction set for the metric code --
+    -> (targets (T,4), predictions (n_pred,4), confidences (n_pred,)), float32 on the host, T within 15 % of n_tgt.
+    A third of the targets overlap another target heavily; 40 % of the predictions are jittered copies of targets (IoU spread over
+    the COCO thresholds), 30 % near-duplicates of those -- so many predictions cover the same target and one prediction often
+    covers two, the cases the matching rule is about -- the rest random boxes; confidences are
+    `torch.rand`, not ordered by quality."""
+    g = torch.Generator().manual_seed(seed)
+    t = n_tgt + int(torch.randint(-n_tgt * 15 // 100, n_tgt * 15 // 100 + 1, (1,), generator=g)) if n_tgt >= 7 else n_tgt
+    xy = torch.rand(t, 2, generator=g) * (size * 0.9)
+    wh = 40 + torch.rand(t, 2, generator=g) * 120
+    targets = torch.cat([xy, xy + wh], dim=1)
+    if t >= 3:                                   # a third of the targets overlap another one heavily: one prediction covers both
+        k = t // 3
+        targets[:k] = targets[k:2 * k] + (torch.rand(k, 1, generator=g) * 0.2 - 0.1) * wh[k:2 * k].repeat(1, 2)
+    n_copy, n_dup = (n_pred * 4) // 10, (n_pred * 3) // 10
+    src = torch.randint(0, max(t, 1), (n_copy,), generator=g)
+    scale = (targets[src, 2:] - targets[src, :2]).repeat(1, 2) if t else torch.ones(n_copy, 4)
+    copies = (targets[src] if t else torch.zeros(n_copy, 4)) + torch.randn(n_copy, 4, generator=g) * 0.06 * scale
+    dup_of = torch.randint(0, max(n_copy, 1), (n_dup,), generator=g)
+    dups = copies[dup_of] + torch.randn(n_dup, 4, generator=g) * 1.5
+    n_noise = n_pred - n_copy - n_dup
+    nxy = torch.rand(n_noise, 2, generator=g) * (size * 0.9)
+    noise = torch.cat([nxy, nxy + 30 + torch.rand(n_noise, 2, generator=g) * 150], dim=1)
+    predictions = torch.cat([copies, dups, noise])[torch.randperm(n_pred, generator=g)]
+    return targets, predictions, torch.rand(n_pred, generator=g)
