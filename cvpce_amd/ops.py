@@ -221,9 +221,12 @@ def conv2d(x, pc, act=0, out_f32=False, residual=None, res_mode=0, in_up_shift=0
     n, h, w, cin = x.shape
     assert cin == pc.cin_pad, (cin, pc.cin_pad)
     ho, wo = pc.out_hw(h, w, in_up_shift)
+    oshape = (n, ho // 2, wo // 2, pc.cout) if pool else (n, ho, wo, pc.cout)
+    odtype = torch.float32 if out_f32 else x.dtype
     if out is None:
-        oshape = (n, ho // 2, wo // 2, pc.cout) if pool else (n, ho, wo, pc.cout)
-        out = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+        out = torch.empty(oshape, dtype=odtype, device=x.device)
+    else:
+        assert tuple(out.shape) == oshape and out.dtype == odtype and out.is_contiguous(), (tuple(out.shape), oshape, out.dtype, odtype)
     hr = wr = 0
     if residual is not None:
         assert residual.dtype == x.dtype and residual.is_contiguous() and residual.shape[0] == n and residual.shape[3] == pc.cout

@@ -21,6 +21,28 @@
  *                 [ci/64][cout/32][kw][(ci%64)/32][kh][mt][lane][8] with lane = 16 q + m, m = 0..15, q = 0..3:
  *                 lane (m, q) of block mt holds cout 32 (cout/32) + 8 (m >> 2) + 4 mt + (m & 3), channels
  *                 64 (ci/64) + 32 ((ci%64)/32) + 8 q .. + 7 of tap (kh, kw).  cvpce_pack_halo_weights converts.
+ *
+ * Footprint
+ *   Every entry point reads only the stated extent of each input (activations, residuals, masks, boxes, counts, work lists,
+ *   weights up to Cout_pad x K_pad, biases up to Cout) and writes only the stated extent of each output and of its workspace,
+ *   whatever the tile size of the kernel behind it: ragged tiles are masked, never rounded up into the neighbouring memory.
+ *   Inputs are never written.  An output is written in full, except under these partial-write contracts, where the rest of the
+ *   buffer is left exactly as it was:
+ *     - work-list and strip launches (cvpce_vgg_stem_fused_list, cvpce_conv3x3_halo_list, cvpce_conv3x3_halo_strips): the listed
+ *       tiles only, and of a tile cut at `rows` only those rows; cvpce_embed_worklists writes counts[l] entries of list row l;
+ *     - cvpce_conv3x3_halo_masked with a tile_map: the tiles on the map only (every pixel of those, zeros on the gaps);
+ *     - count-limited crops (cvpce_crop_resize, cvpce_crop_resize_content): boxes p >= *count_dev are skipped; the content form
+ *       writes rows < ext.rows and columns < ext.cols rounded up to even;
+ *     - descriptor slices (cvpce_conv3x3_halo_mac, the `mac` of the list launches, cvpce_mac_init, cvpce_global_max_nhwc_bf16):
+ *       columns off .. off + C - 1 of every row, nothing else of the wider row;
+ *     - cvpce_atlas_copy into the atlas: the levels' pixels, not the gaps between them;
+ *     - cvpce_detect_postprocess: rows below an image's detection count and both counts (the caller zero-fills the rest).
+ *   A workspace is scratch within its stated size.  Pointers are assumed to have the alignment of a fresh device allocation.
+ *   tests/test_gpu_footprint.py holds the device entry points to this with guard bands around each operand (not the host routine
+ *   cvpce_pack_halo_weights, the cvpce_probe_* launches or cvpce_set_persistent_workgroups, which take no tensors of the product).
+ *   What it exercises: operands that start a multiple of 4 KiB into an allocation, and, as the product passes them, rows of the
+ *   work lists (whole rows: 8 * list_stride bytes apart, 512 bytes in the test), single entries of `counts` (4-byte offsets) and
+ *   descriptor slices at a column offset.  No smaller alignment of an activation, weight or output pointer is tested.
  */
 #ifndef CVPCE_AMD_H
 #define CVPCE_AMD_H
