@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h).
+"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h and the
+8-bit input kernels of include/cvpce_amd_input.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -91,7 +92,16 @@ EVAL_SIGNATURES = {
     'cvpce_eval_match_detections': (c_int, [_fp, _ip, _ip, _ip, _fp, _ip, _ip, _fp] + [c_int] * 5 + [_ip, _vp, _vp]),
 }
 
-for _table in (SIGNATURES, EVAL_SIGNATURES):
+# include/cvpce_amd_input.h: the transform and the crop kernels reading (H,W,3) bytes.  A table of its own, like the header.
+INPUT_SIGNATURES = {
+    'cvpce_gln_transform_batch_u8': (c_int, [POINTER(c_void_p), POINTER(ctypes.c_ubyte), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
+                                             _vp, c_int, c_int, POINTER(c_float), POINTER(c_float), _fp, _vp]),
+    'cvpce_crop_resize_u8': (c_int, [_vp, _fp, _fp, _ip, c_int, _vp, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _vp]),
+    'cvpce_crop_resize_content_u8': (c_int, [_vp, _fp, _fp, _ip, c_int, _vp, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _ip, _vp]),
+}
+INPUT_SIGNATURES['cvpce_gln_transform_batch_u8_f16'] = INPUT_SIGNATURES['cvpce_gln_transform_batch_u8']
+
+for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

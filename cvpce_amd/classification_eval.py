@@ -24,7 +24,7 @@ def eval_dihe(encoder, sampleset, testset, batch_size, num_workers=0, k=(1,), ve
         if verbose and i % 10 == 0:
             print(f'{i}...')
         boxes = clip_boxes_to_image(boxes, datautils.image_hw(img))
-        crops = ops.crop_resize(ops.device_image(img, classifier.device),
+        crops = ops.crop_resize(ops.input_image(img, classifier.device),
                                 boxes.to(classifier.device), datautils.CLASSIFICATION_IMAGE_SIZE, mode=0)
         pred_anns = classifier.classify(crops)
         total += len(target_anns)

@@ -11,6 +11,7 @@
 //       input normalisation (classification.py:41-44) writing NHWC8 bf16.
 #include "common.h"
 #include "../../include/cvpce_amd.h"
+#include "../../include/cvpce_amd_input.h"
 #pragma clang fp contract(off)
 
 // PyTorch area_pixel_compute_source_index (align_corners=False, non-cubic)
@@ -22,6 +23,27 @@ __device__ __forceinline__ void src_index(float scale, int dst, int in_size, int
     i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
     l1 = s - (float)i0;
     l0 = 1.f - l1;
+}
+
+// Pixel sources.  The transform and the crop kernels read an image in one of two forms (include/cvpce_amd_input.h): float32 planes
+// (3,H,W), or the decoder's bytes (H,W,3), where code b MEANS tab[b] = float32(b) / float32(255) (ops.uint8_table, made on the host: the
+// 256 floats stay in the vector L1 -- no multiply by 1/255, which is wrong for 126 codes, and no division per tap).  Everything after
+// the tap load is one set of expressions for both forms.  The byte form decides its hazards here:
+//   * every load is ONE byte of ONE pixel (hipcc joins a pixel's first two into a 2-byte load, which global memory takes at any
+//     address): nothing depends on 3 * W being a multiple of 4, and the last pixel's loads end with the tensor;
+//   * a padding tap's clamped pixel offset 0 is byte 0 ... 2 of the image;
+//   * tap32 forms (pixel * 3 + c) in 32 bits: the entry points refuse H * W * 3 >= 2^31.
+__device__ __forceinline__ float tap64(const float* __restrict__ img, const float* __restrict__, int c, size_t plane, size_t pix) {
+    return img[c * plane + pix];
+}
+__device__ __forceinline__ float tap64(const unsigned char* __restrict__ img, const float* __restrict__ tab, int c, size_t, size_t pix) {
+    return tab[img[pix * 3 + c]];
+}
+__device__ __forceinline__ float tap32(const float* __restrict__ img, const float* __restrict__, int c, int plane, int off) {
+    return img[(size_t)c * plane + off];
+}
+__device__ __forceinline__ float tap32(const unsigned char* __restrict__ img, const float* __restrict__ tab, int c, int, int off) {
+    return tab[img[off * 3 + c]];
 }
 
 template <typename E>
@@ -67,38 +89,59 @@ static int gln_transform_dispatch(const float* img, void* out_nhwc8, int H0, int
 
 // The whole batch in ONE launch (grid.z = image): on the detector's critical chain eight 12-us launches in a row cost 0.1 ms.
 struct TransformBatchArgs {
+    static constexpr bool kBytes = false;
     const float* img[32];
     int H0[32], W0[32], h[32], w[32];
 };
+// ... of images in either form, a form per image (bit i of `bytes`: image i is (H,W,3) bytes): a list that mixes them is still one launch
+struct TransformBatchArgsMixed {
+    static constexpr bool kBytes = true;
+    const void* img[32];
+    int H0[32], W0[32], h[32], w[32];
+    unsigned bytes;
+};
 
-template <typename E>
-__global__ void gln_transform_batch_kernel(TransformBatchArgs a, bf16_t* __restrict__ out, int Hp, int Wp, float m0, float m1, float m2,
-                                           float s0, float s1, float s2) {
+// One output pixel of the transform (the arithmetic of gln_transform_kernel, operation for operation)
+template <typename E, typename PIX>
+__device__ __forceinline__ void transform_pixel(const PIX* __restrict__ img, const float* __restrict__ tab, int H0, int W0, int h, int w,
+                                                int x, int y, const float (&mean)[3], const float (&stdv)[3], bf16x8& o) {
+    const float sy = (float)H0 / (float)h, sx = (float)W0 / (float)w;
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    src_index(sy, y, H0, y0, y1, ly0, ly1);
+    src_index(sx, x, W0, x0, x1, lx0, lx1);
+    const size_t plane = (size_t)H0 * W0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v00 = (tap64(img, tab, c, plane, (size_t)y0 * W0 + x0) - mean[c]) / stdv[c];
+        float v01 = (tap64(img, tab, c, plane, (size_t)y0 * W0 + x1) - mean[c]) / stdv[c];
+        float v10 = (tap64(img, tab, c, plane, (size_t)y1 * W0 + x0) - mean[c]) / stdv[c];
+        float v11 = (tap64(img, tab, c, plane, (size_t)y1 * W0 + x1) - mean[c]) / stdv[c];
+        float v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+        o[c] = E::narrow(v);
+    }
+}
+
+template <typename E, typename ARGS>
+__global__ void gln_transform_batch_kernel(ARGS a, const float* __restrict__ tab, bf16_t* __restrict__ out, int Hp, int Wp, float m0, float m1,
+                                           float m2, float s0, float s1, float s2) {
     const int i = blockIdx.z;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= Wp) return;
-    const float* __restrict__ img = a.img[i];
     const int H0 = a.H0[i], W0 = a.W0[i], h = a.h[i], w = a.w[i];
     bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (bf16_t)0.f;
-    if (y < h && x < w) {                                   // (the arithmetic of gln_transform_kernel, operation for operation)
-        const float sy = (float)H0 / (float)h, sx = (float)W0 / (float)w;
-        int y0, y1, x0, x1;
-        float ly0, ly1, lx0, lx1;
-        src_index(sy, y, H0, y0, y1, ly0, ly1);
-        src_index(sx, x, W0, x0, x1, lx0, lx1);
+    if (y < h && x < w) {
         const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float* p = img + (size_t)c * H0 * W0;
-            float v00 = (p[(size_t)y0 * W0 + x0] - mean[c]) / stdv[c];
-            float v01 = (p[(size_t)y0 * W0 + x1] - mean[c]) / stdv[c];
-            float v10 = (p[(size_t)y1 * W0 + x0] - mean[c]) / stdv[c];
-            float v11 = (p[(size_t)y1 * W0 + x1] - mean[c]) / stdv[c];
-            float v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-            o[c] = E::narrow(v);
+        if constexpr (ARGS::kBytes) {
+            if ((a.bytes >> i) & 1u)                        // (uniform over the workgroup: blockIdx.z)
+                transform_pixel<E>(static_cast<const unsigned char*>(a.img[i]), tab, H0, W0, h, w, x, y, mean, stdv, o);
+            else
+                transform_pixel<E>(static_cast<const float*>(a.img[i]), tab, H0, W0, h, w, x, y, mean, stdv, o);
+        } else {
+            transform_pixel<E>(a.img[i], tab, H0, W0, h, w, x, y, mean, stdv, o);
         }
     }
     *reinterpret_cast<bf16x8*>(out + (((size_t)i * Hp + y) * Wp + x) * 8) = o;
@@ -118,8 +161,8 @@ static int gln_transform_batch_dispatch(const float* const* imgs, const int* H0,
             a.img[i] = imgs[j]; a.H0[i] = H0[j]; a.W0[i] = W0[j]; a.h[i] = h[j]; a.w[i] = w[j];
         }
         dim3 grid((Wp + 127) / 128, Hp, m);
-        hipLaunchKernelGGL(gln_transform_batch_kernel<E>, grid, dim3(128), 0, (hipStream_t)stream, a,
-                           (bf16_t*)out_nhwc8 + (size_t)base * Hp * Wp * 8, Hp, Wp, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gln_transform_batch_kernel<E, TransformBatchArgs>), grid, dim3(128), 0, (hipStream_t)stream, a,
+                           (const float*)nullptr, (bf16_t*)out_nhwc8 + (size_t)base * Hp * Wp * 8, Hp, Wp, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
         const int rc = cvpce_check_launch();
         if (rc != CVPCE_OK) return rc;
     }
@@ -133,6 +176,46 @@ extern "C" int cvpce_gln_transform_batch(const float* const* imgs, const int* H0
 extern "C" int cvpce_gln_transform_batch_f16(const float* const* imgs, const int* H0, const int* W0, const int* h, const int* w, int n,
                                              void* out_nhwc8, int Hp, int Wp, const float* mean3, const float* std3, void* stream) {
     return gln_transform_batch_dispatch<ElemF16>(imgs, H0, W0, h, w, n, out_nhwc8, Hp, Wp, mean3, std3, stream);
+}
+
+// include/cvpce_amd_input.h: the same launch over images in either form
+template <typename E>
+static int gln_transform_batch_mixed_dispatch(const void* const* imgs, const unsigned char* is_bytes, const int* H0, const int* W0, const int* h,
+                                              const int* w, int n, void* out_nhwc8, int Hp, int Wp, const float* mean3, const float* std3,
+                                              const float* table, void* stream) {
+    if (n <= 0) return CVPCE_OK;
+    if (!imgs || !is_bytes || !H0 || !W0 || !h || !w || !out_nhwc8 || !mean3 || !std3 || !table || Hp <= 0 || Wp <= 0) return CVPCE_ERR_ARG;
+    for (int j = 0; j < n; ++j) {                           // (every image is checked before the first launch)
+        if (!imgs[j] || h[j] > Hp || w[j] > Wp || h[j] <= 0 || w[j] <= 0 || H0[j] <= 0 || W0[j] <= 0) return CVPCE_ERR_ARG;
+        if (is_bytes[j] && (long long)H0[j] * W0[j] * 3 >= (1LL << 31)) return CVPCE_ERR_ARG;
+    }
+    for (int base = 0; base < n; base += 32) {
+        const int m = n - base < 32 ? n - base : 32;
+        TransformBatchArgsMixed a;
+        a.bytes = 0;
+        for (int i = 0; i < 32; ++i) {
+            const int j = base + (i < m ? i : 0);
+            a.img[i] = imgs[j]; a.H0[i] = H0[j]; a.W0[i] = W0[j]; a.h[i] = h[j]; a.w[i] = w[j];
+            if (is_bytes[j]) a.bytes |= 1u << i;
+        }
+        dim3 grid((Wp + 127) / 128, Hp, m);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gln_transform_batch_kernel<E, TransformBatchArgsMixed>), grid, dim3(128), 0, (hipStream_t)stream, a,
+                           table, (bf16_t*)out_nhwc8 + (size_t)base * Hp * Wp * 8, Hp, Wp, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+        const int rc = cvpce_check_launch();
+        if (rc != CVPCE_OK) return rc;
+    }
+    return CVPCE_OK;
+}
+
+extern "C" int cvpce_gln_transform_batch_u8(const void* const* imgs, const unsigned char* is_bytes, const int* H0, const int* W0, const int* h,
+                                            const int* w, int n, void* out_nhwc8, int Hp, int Wp, const float* mean3, const float* std3,
+                                            const float* table, void* stream) {
+    return gln_transform_batch_mixed_dispatch<ElemBF16>(imgs, is_bytes, H0, W0, h, w, n, out_nhwc8, Hp, Wp, mean3, std3, table, stream);
+}
+extern "C" int cvpce_gln_transform_batch_u8_f16(const void* const* imgs, const unsigned char* is_bytes, const int* H0, const int* W0, const int* h,
+                                                const int* w, int n, void* out_nhwc8, int Hp, int Wp, const float* mean3, const float* std3,
+                                                const float* table, void* stream) {
+    return gln_transform_batch_mixed_dispatch<ElemF16>(imgs, is_bytes, H0, W0, h, w, n, out_nhwc8, Hp, Wp, mean3, std3, table, stream);
 }
 
 extern "C" int cvpce_gln_transform(const float* img, void* out_nhwc8, int H0, int W0, int h, int w, int Hp, int Wp,
@@ -149,7 +232,9 @@ extern "C" int cvpce_gln_transform_f16(const float* img, void* out_nhwc8, int H0
 // mode 1: bf16 NHWC8, scale_to_tanh + MACVGG normalisation fused
 // mode 2: the same values as bf16 NHWC4 (8 bytes per pixel: half the bytes written here and read back by the fused VGG
 //         stem, which takes 4- or 8-channel pixels)
-__global__ void crop_resize_kernel(const float* __restrict__ img, const float* __restrict__ boxes,
+// PIX: float (planes) or unsigned char (bytes, read through `tab`; see tap64 / tap32).
+template <typename PIX>
+__global__ void crop_resize_kernel(const PIX* __restrict__ img, const float* __restrict__ tab, const float* __restrict__ boxes,
                                    const int* __restrict__ count, void* __restrict__ out, int H0, int W0, int S,
                                    int mode, float m0, float m1, float m2, float s0, float s1, float s2) {
     const int p = blockIdx.z;
@@ -180,9 +265,8 @@ __global__ void crop_resize_kernel(const float* __restrict__ img, const float* _
         if (yy0 < ch && xx0 < cw) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* pl = img + (size_t)c * H0 * W0;
                 auto at = [&](int yy, int xx) -> float {
-                    return (yy < ch && xx < cw) ? pl[(size_t)(y1 + yy) * W0 + (x1 + xx)] : 0.5f;
+                    return (yy < ch && xx < cw) ? tap64(img, tab, c, (size_t)H0 * W0, (size_t)(y1 + yy) * W0 + (x1 + xx)) : 0.5f;
                 };
                 v[c] = ly0 * (lx0 * at(yy0, xx0) + lx1 * at(yy0, xx1)) + ly1 * (lx0 * at(yy1, xx0) + lx1 * at(yy1, xx1));
             }
@@ -221,8 +305,8 @@ __global__ void crop_resize_kernel(const float* __restrict__ img, const float* _
 // on 1 024 SIMDs = 52 us; fetching count / extents / box in one round trip, branch-free gathers and two rows per workgroup each
 // changed nothing (44.0 / 44.1 / 43.3 us).
 #define CROP2_ROWS 1
-template <int MODE>
-__global__ void crop_resize2_kernel(const float* __restrict__ img, const float* __restrict__ boxes, const int* __restrict__ count,
+template <int MODE, typename PIX>
+__global__ void crop_resize2_kernel(const PIX* __restrict__ img, const float* __restrict__ tab, const float* __restrict__ boxes, const int* __restrict__ count,
                                     bf16_t* __restrict__ out, int H0, int W0, int S, float m0, float m1, float m2, float s0,
                                     float s1, float s2, const int* __restrict__ ext, int nbox) {
     // XCD-aware order (one workgroup per row: gridDim.x == 1): workgroups are dealt to the 8 XCDs round-robin in launch order, and
@@ -275,7 +359,7 @@ __global__ void crop_resize2_kernel(const float* __restrict__ img, const float* 
             int yy0, yy1;
             float ly0, ly1;
             src_index(sc, oy, larger, yy0, yy1, ly0, ly1);
-            // the 24 taps: every load is issued (at an address clamped into the plane), padding taps are replaced afterwards -- behind
+            // the 24 taps: every load is issued (at an address clamped into the plane / the byte image), padding taps are replaced afterwards -- behind
             // `tap inside ? load : 0.5` branches the loads went out one exec-mask region at a time
             float t[2][3][4];
             const int plane = H0 * W0;                       // (< 2^31: checked on the host)
@@ -291,7 +375,7 @@ __global__ void crop_resize2_kernel(const float* __restrict__ img, const float* 
                     off = in ? off : 0;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        const float raw = img[(size_t)c * plane + off];
+                        const float raw = tap32(img, tab, c, plane, off);
                         t[u][c][k] = in ? raw : 0.5f;
                     }
                 }
@@ -327,12 +411,14 @@ __global__ void crop_resize2_kernel(const float* __restrict__ img, const float* 
     }
 }
 
-static int crop_resize_launch(const float* img, const float* boxes, const int* count_dev, int max_boxes, void* out,
+template <typename PIX>
+static int crop_resize_launch(const PIX* img, const float* tab, const float* boxes, const int* count_dev, int max_boxes, void* out,
                              int H0, int W0, int S, int mode, const float* mean3, const float* std3, const int* ext, void* stream) {
     if (!img || !boxes || !out || S <= 0 || H0 <= 0 || W0 <= 0) return CVPCE_ERR_ARG;
     if (mode < 0 || mode > 2 || (mode != 0 && (!mean3 || !std3))) return CVPCE_ERR_ARG;
     if (ext && (mode == 0 || S % 2 != 0)) return CVPCE_ERR_ARG;
-    if ((long long)H0 * W0 >= (1LL << 31)) return CVPCE_ERR_ARG;        // (32-bit pixel offsets within a plane)
+    // (32-bit offsets: of a pixel within a plane, of a byte within a byte image)
+    if ((long long)H0 * W0 * (sizeof(PIX) == 1 ? 3 : 1) >= (1LL << 31)) return CVPCE_ERR_ARG;
     if (max_boxes <= 0) return CVPCE_OK;
     if (max_boxes > 65528) return CVPCE_ERR_ARG;          // (grid z, rounded up to a multiple of 8)
     dim3 grid((S + 127) / 128, S, max_boxes);
@@ -341,21 +427,21 @@ static int crop_resize_launch(const float* img, const float* boxes, const int* c
     if (mode != 0 && S % 2 == 0) {
         dim3 grid2((S / 2 + 127) / 128, (S + CROP2_ROWS - 1) / CROP2_ROWS, (max_boxes + 7) / 8 * 8);
         if (mode == 2)
-            hipLaunchKernelGGL(crop_resize2_kernel<2>, grid2, dim3(128, CROP2_ROWS), 0, (hipStream_t)stream, img, boxes, count_dev, (bf16_t*)out,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(crop_resize2_kernel<2, PIX>), grid2, dim3(128, CROP2_ROWS), 0, (hipStream_t)stream, img, tab, boxes, count_dev, (bf16_t*)out,
                                H0, W0, S, m[0], m[1], m[2], s[0], s[1], s[2], ext, max_boxes);
         else
-            hipLaunchKernelGGL(crop_resize2_kernel<1>, grid2, dim3(128, CROP2_ROWS), 0, (hipStream_t)stream, img, boxes, count_dev, (bf16_t*)out,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(crop_resize2_kernel<1, PIX>), grid2, dim3(128, CROP2_ROWS), 0, (hipStream_t)stream, img, tab, boxes, count_dev, (bf16_t*)out,
                                H0, W0, S, m[0], m[1], m[2], s[0], s[1], s[2], ext, max_boxes);
         return cvpce_check_launch();
     }
-    hipLaunchKernelGGL(crop_resize_kernel, grid, dim3(128), 0, (hipStream_t)stream, img, boxes, count_dev, out, H0, W0,
+    hipLaunchKernelGGL(crop_resize_kernel<PIX>, grid, dim3(128), 0, (hipStream_t)stream, img, tab, boxes, count_dev, out, H0, W0,
                        S, mode, m[0], m[1], m[2], s[0], s[1], s[2]);
     return cvpce_check_launch();
 }
 
 extern "C" int cvpce_crop_resize(const float* img, const float* boxes, const int* count_dev, int max_boxes, void* out,
                                  int H0, int W0, int S, int mode, const float* mean3, const float* std3, void* stream) {
-    return crop_resize_launch(img, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, nullptr, stream);
+    return crop_resize_launch<float>(img, nullptr, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, nullptr, stream);
 }
 
 // The crops' CONTENT only (modes 1 / 2, even S): pixels with oy >= ext[p].rows or ox >= ext[p].cols (cvpce_crop_extents of the same
@@ -364,7 +450,20 @@ extern "C" int cvpce_crop_resize_content(const float* img, const float* boxes, c
                                          int H0, int W0, int S, int mode, const float* mean3, const float* std3, const int* ext,
                                          void* stream) {
     if (!ext) return CVPCE_ERR_ARG;
-    return crop_resize_launch(img, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, ext, stream);
+    return crop_resize_launch<float>(img, nullptr, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, ext, stream);
+}
+
+// include/cvpce_amd_input.h: the same crops from the decoder's bytes
+extern "C" int cvpce_crop_resize_u8(const unsigned char* img, const float* table, const float* boxes, const int* count_dev, int max_boxes,
+                                    void* out, int H0, int W0, int S, int mode, const float* mean3, const float* std3, void* stream) {
+    if (!table) return CVPCE_ERR_ARG;
+    return crop_resize_launch<unsigned char>(img, table, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, nullptr, stream);
+}
+extern "C" int cvpce_crop_resize_content_u8(const unsigned char* img, const float* table, const float* boxes, const int* count_dev,
+                                            int max_boxes, void* out, int H0, int W0, int S, int mode, const float* mean3, const float* std3,
+                                            const int* ext, void* stream) {
+    if (!table || !ext) return CVPCE_ERR_ARG;
+    return crop_resize_launch<unsigned char>(img, table, boxes, count_dev, max_boxes, out, H0, W0, S, mode, mean3, std3, ext, stream);
 }
 
 // Content extent of every crop at the crop resolution S (the embedder's constant-padding tile skipping, skiplist.hip):

@@ -9,14 +9,15 @@ CLASSIFICATION_IMAGE_SIZE = 256
 def resize_for_classification(img):
     """datautils.py:234-239: pad (3,h,w) to a square with 0.5 (top-left anchored), bilinear -> 256x256.
 
-    Runs the K9 HIP gather kernel (the whole image is the crop box).  An 8-bit (h,w,3) image is converted on the device first."""
+    Runs the K9 HIP gather kernel (the whole image is the crop box).  An 8-bit (h,w,3) image is read as bytes (ops.U8_KERNELS) or
+    converted on the device first."""
     from . import ops          # the only kernel calls in this module: the readers below are host-only
     ops.check_image_form(img)
     if not img.is_cuda:
         raise RuntimeError('resize_for_classification runs on an MI355X (HIP) device only (no CPU fallback)')
     h, w = image_hw(img)
     box = torch.tensor([[0.0, 0.0, float(w), float(h)]], device=img.device)
-    return ops.crop_resize(ops.device_image(img, img.device), box, CLASSIFICATION_IMAGE_SIZE, mode=0)[0]
+    return ops.crop_resize(ops.input_image(img, img.device), box, CLASSIFICATION_IMAGE_SIZE, mode=0)[0]
 
 
 def image_hw(img):

@@ -60,7 +60,7 @@ def evaluate_detections(p_model, c_model, testset, trainset, thresholds=(0.5,), 
     for i, batch in enumerate(_batches(feeding.feed(testset, num_workers, classifier.device), proposal_batch_size)):
         if verbose and i % 10 == 0:
             print(f'{i}...')
-        images = [ops.device_image(img, classifier.device) for img, _ in batch]
+        images = [(ops.input_image if pipe is not None else ops.device_image)(img, classifier.device) for img, _ in batch]
         if device_metrics:
             boxes, scores, classes = _device_detections(images, p_model, pipe, classifier, class_of, testset)
             accumulator.update([t['boxes'] for _, t in batch], boxes, scores, [t['labels'] for _, t in batch], classes)

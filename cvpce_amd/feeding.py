@@ -2,7 +2,7 @@
 memory on a copy stream while the kernels work on the images before them.
 
     for image, planogram in ImageFeeder(pairs, workers=8, device='cuda'):
-        ...                                  # image: uint8 (H,W,3) on the device; ops.device_image converts it where it is
+        ...                                  # image: uint8 (H,W,3) on the device; the kernels read it there (ops.input_image)
 
 The counterpart of the reference's `DataLoader(num_workers=..., pin_memory=True)` for the evaluation loops, in one process: PIL
 releases the GIL while it decodes, so threads are enough (`Classifier._gallery_items` is the same pattern for the gallery).  One GPU
@@ -200,7 +200,11 @@ class ImageFeeder:
                 if on_device is not None:
                     consumer = torch.cuda.current_stream(self.device)
                     consumer.wait_event(done)
-                    on_device.record_stream(consumer)   # allocated on the copy stream, read on the consumer's: not recycled in flight
+                    # allocated on the copy stream, read on the consumer's: not recycled in flight.  With ops.U8_KERNELS on the bytes are
+                    # read not by one conversion but by the transform and, later, by every crop launch -- all on this stream (the
+                    # detector's side streams read feature maps, never the image), and the allocator holds the block until the work
+                    # queued on this stream WHEN THE TENSOR IS FREED has run: one record covers them all
+                    on_device.record_stream(consumer)
                     item = _with_image(item, on_device)
                 yield item
         finally:

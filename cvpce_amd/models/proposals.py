@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..datautils import image_hw
 
 # ---- torchvision 0.9 RetinaNet / transform constants ----
 MIN_SIZE, MAX_SIZE, SIZE_DIVISIBLE = 800, 1333, 32
@@ -341,7 +342,7 @@ class GLNEngine:
     def batch_geometry(images, min_size=None, max_size=None):
         """-> (original sizes, resized sizes, padded (Hp, Wp)) of GeneralizedRCNNTransform for this list of images
         (min_size, max_size: resized_hw's)."""
-        sizes = [tuple(i.shape[-2:]) for i in images]
+        sizes = [image_hw(i) for i in images]               # (either form: float (3,H,W) or uint8 (H,W,3))
         rs = [resized_hw(h, w, min_size, max_size) for h, w in sizes]
         hp = int(math.ceil(max(r[0] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
         wp = int(math.ceil(max(r[1] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
@@ -355,7 +356,10 @@ class GLNEngine:
             ops.gln_transform_batch(images, batch, rs, self.image_mean, self.image_std)
         else:
             for i, (img, (h, w)) in enumerate(zip(images, rs)):
-                ops.gln_transform_into(img.contiguous(), batch, i, h, w, self.image_mean, self.image_std)
+                if ops.is_uint8_image(img):                 # (bytes are read by the batch kernel only)
+                    ops.gln_transform_batch([img], batch[i:i + 1], [(h, w)], self.image_mean, self.image_std)
+                else:
+                    ops.gln_transform_into(img.contiguous(), batch, i, h, w, self.image_mean, self.image_std)
         return batch, sizes, rs
 
     def body(self, x):
@@ -868,7 +872,7 @@ class GaussianLayerNetwork(nn.Module):
         -> {'precision', 'stages': {name: {'max_abs', 'saturated_fraction'}}, 'saturated': bool}"""
         images = _image_list(images)
         eng = self.engine()
-        images = [ops.device_image(i, eng.device) for i in images]
+        images = [ops.input_image(i, eng.device) for i in images]
         _, inter = eng.detect(images, self.num_classes, self.detections_per_img, want_intermediates=True)
         self.backbone.gaussians = None
         limit = 65504.0 if self.precision == 'fp16' else float(torch.finfo(torch.bfloat16).max)
@@ -893,7 +897,7 @@ class GaussianLayerNetwork(nn.Module):
             raise NotImplementedError('training is out of scope of the MI355X inference path (SURVEY.md 2)')
         images = _image_list(images)
         eng = self.engine()
-        images = [ops.device_image(i, eng.device) for i in images]
+        images = [ops.input_image(i, eng.device) for i in images]
         boxes, scores, labels, count, _, gauss = eng.detect(images, self.num_classes, self.detections_per_img)
         self.backbone.gaussians = gauss
         counts = count.tolist()

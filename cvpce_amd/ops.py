@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from ._lib import lib, check
 from .torch_ops import T
+from . import torch_ops_input  # noqa: F401  (registers torch.ops.cvpce_amd.*_u8, the byte-reading input kernels)
 
 BF16 = torch.bfloat16
 F16 = torch.float16
@@ -781,9 +782,13 @@ def l2_normalize(desc, eps=1e-8, want_bf16=False):
 # as the decoder produces it (`datautils.pil_to_uint8`).  The 8-bit form MEANS the float image pil_to_tensor makes of the same
 # pixels, `u.permute(2,0,1).to(float32) / 255.0` (the correctly rounded quotient; code * float32(1/255) differs from it for 126 of
 # the 256 codes).  It becomes that float image once, on the device, by a gather from a 256-entry table that is built on the host
-# with exactly that expression -- exact by construction, whatever the device's division does.  The transform and crop kernels keep
-# reading float32 planes: no kernel entry point knows about bytes.
+# with exactly that expression -- exact by construction, whatever the device's division does.
+# The transform and the crop kernels read either form: the entry points of include/cvpce_amd.h take float32 planes, those
+# of include/cvpce_amd_input.h the bytes and that table, and give the same bits.  U8_KERNELS chooses what an 8-bit image becomes on
+# the product path: on, it stays bytes from the upload to the last crop (`device_bytes`); off, it becomes the float image once
+# (`device_image`) and the float kernels read that.
 IMAGE_FORMS = 'float (3,H,W) in [0,1] or uint8 (H,W,3)'
+U8_KERNELS = _os.environ.get('CVPCE_U8_KERNELS', '0') != '0'   # default: profiles/r12_u8_kernels.md
 _UINT8_TABLES = {}
 
 
@@ -834,6 +839,23 @@ def device_image(img, device):
     return uint8_to_float(img)
 
 
+def device_bytes(img, device):
+    """An input image on the device in the form the kernels read it in: a uint8 (H,W,3) image stays bytes -- uploaded (non-blocking when
+    the source is pinned) unless it is on a device already, and made contiguous; no float copy.  A float image: as `device_image`.
+    Any other uint8 shape: TypeError."""
+    check_image_form(img)
+    if img.dtype != torch.uint8:
+        return img.to(device=device, dtype=torch.float32).contiguous()
+    if not img.is_cuda:
+        img = img.to(device, non_blocking=img.is_pinned())
+    return img.contiguous()
+
+
+def input_image(img, device):
+    """The product path's one upload step: `device_bytes` with U8_KERNELS on, `device_image` with it off."""
+    return device_bytes(img, device) if U8_KERNELS else device_image(img, device)
+
+
 def gln_transform_into(img, batch, index, h, w, mean, std):
     """img (3,H0,W0) f32 cuda -> batch[index] (Hp,Wp,8) bf16 | fp16 (the batch tensor's type)."""
     _need_cuda(img, batch)
@@ -844,15 +866,25 @@ def gln_transform_into(img, batch, index, h, w, mean, std):
 
 
 def gln_transform_batch(images, batch, sizes, mean, std):
-    """images[i] (3,H0,W0) f32 cuda -> batch[i] (Hp,Wp,8), resized to sizes[i] = (h, w): the whole batch in one launch."""
+    """images[i] (3,H0,W0) f32 | (H0,W0,3) uint8, cuda -> batch[i] (Hp,Wp,8), resized to sizes[i] = (h, w): the whole batch in one launch,
+    whatever forms the list mixes (U8_KERNELS off: 8-bit images become float images first)."""
     _need_cuda(batch, *images)
     assert batch.shape[0] == len(images) == len(sizes) and batch.shape[3] == 8 and batch.is_contiguous()
+    for i in images:
+        check_image_form(i)
+    has_bytes = any(i.dtype == torch.uint8 for i in images)
+    if has_bytes and not U8_KERNELS:
+        images, has_bytes = [uint8_to_float(i) if i.dtype == torch.uint8 else i for i in images], False
     prof = PROFILE
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    T.gln_transform_batch([i.contiguous() for i in images], batch, [int(s[0]) for s in sizes], [int(s[1]) for s in sizes],
-                          [float(v) for v in mean], [float(v) for v in std])
+    if has_bytes:
+        T.gln_transform_batch_u8([i.contiguous() for i in images], uint8_table(batch.device), batch, [int(s[0]) for s in sizes],
+                                 [int(s[1]) for s in sizes], [float(v) for v in mean], [float(v) for v in std])
+    else:
+        T.gln_transform_batch([i.contiguous() for i in images], batch, [int(s[0]) for s in sizes], [int(s[1]) for s in sizes],
+                              [float(v) for v in mean], [float(v) for v in std])
     if prof is not None:
         e1.record()
         prof.byte_records.append(('gln_transform_batch_kernel', _nbytes(batch, *images), e0, e1))
@@ -863,12 +895,18 @@ MAX_CROPS_PER_LAUNCH = 65528   # (the grid z limit, a multiple of 8: the crop ke
 
 
 def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, out=None, content_ext=None):
-    """img (3,H0,W0) f32, boxes (P,4) f32 xyxy (device) -> (P,3,S,S) f32 [mode 0] | (P,S,S,8) bf16 [mode 1] | (P,S,S,4) bf16
+    """img (3,H0,W0) f32 | (H0,W0,3) uint8 (the byte kernels; U8_KERNELS off: converted first), boxes (P,4) f32 xyxy (device)
+    -> (P,3,S,S) f32 [mode 0] | (P,S,S,8) bf16 [mode 1] | (P,S,S,4) bf16
     [mode 2: the 8-byte pixels the fused VGG stem reads; half the bytes of mode 1].
     content_ext (P,2) int32 (`crop_extents` of the same boxes; modes 1 / 2): only the crops' CONTENT is written -- the constant padding
     beyond the extents stays unwritten, which only the work-list embedder may be given (it reads it from the constant crop)."""
     _need_cuda(img, boxes)
-    assert img.dtype == torch.float32 and img.is_contiguous()
+    check_image_form(img)
+    from_bytes = img.dtype == torch.uint8
+    if from_bytes and not U8_KERNELS:
+        img, from_bytes = uint8_to_float(img), False
+    assert (from_bytes or img.dtype == torch.float32) and img.is_contiguous()
+    table = uint8_table(img.device) if from_bytes else None
     boxes = boxes.to(torch.float32).contiguous()
     p = boxes.shape[0]
     if out is None:
@@ -889,7 +927,12 @@ def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, o
             e0.record()
         if content_ext is not None:
             assert mode in (1, 2) and size % 2 == 0
-            T.crop_resize_content(img, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s, content_ext[start:start + nb])
+            if from_bytes:
+                T.crop_resize_content_u8(img, table, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s, content_ext[start:start + nb])
+            else:
+                T.crop_resize_content(img, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s, content_ext[start:start + nb])
+        elif from_bytes:
+            T.crop_resize_u8(img, table, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s)
         else:
             T.crop_resize(img, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s)
         if prof is not None:
@@ -903,7 +946,7 @@ def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, o
                 written = int((e[:, 0] * e[:, 1]).sum()) * out.shape[-1] * out.element_size()
             else:
                 written = v * out[0].numel() * out.element_size()
-            prof.byte_records.append(('crop_resize_kernel', area * 3 * 4 + written, e0, e1))
+            prof.byte_records.append(('crop_resize_kernel', area * 3 * (1 if from_bytes else 4) + written, e0, e1))
     return out
 
 

@@ -37,11 +37,21 @@ class ProposalGenerator:
         self.condfidence_threshold = confidence_threshold  # (sic) production.py:12
 
     def generate_proposals(self, image):
-        """image: float (3,H,W) or 8-bit (H,W,3) (ops.device_image converts the latter on the device)."""
+        """image: float (3,H,W) or 8-bit (H,W,3) (uploaded as bytes; read as bytes by the detector's transform with ops.U8_KERNELS on,
+        converted on the device with it off or for a detector that is not ours)."""
         if ops.is_uint8_image(image):
-            image = ops.device_image(image, self.device)
-        res = self.detector(image[None].to(self.device))[0]
+            image = self._upload(image)
+        if ops.is_uint8_image(image):
+            res = self.detector([image])[0]
+        else:
+            res = self.detector(image[None].to(self.device))[0]
         return res['boxes'][res['scores'] > self.condfidence_threshold]
+
+    def _upload(self, image):
+        """ops.input_image for our detector (its transform reads bytes); any other detector object gets the float image, as before."""
+        if hasattr(self.detector, 'engine'):
+            return ops.input_image(image, self.device)
+        return ops.device_image(image, self.device)
 
     def _confident_boxes(self, img):
         """The confident, non-degenerate boxes of one image with ONE host synchronisation: the detector's kept boxes are sorted by
@@ -68,7 +78,7 @@ class ProposalGenerator:
 
     def generate_proposals_and_images(self, image):
         size = datautils.CLASSIFICATION_IMAGE_SIZE
-        img = ops.device_image(image, self.device)           # (either form; converted once, detected and cropped from)
+        img = self._upload(image)                            # (either form; uploaded once, detected and cropped from)
         if hasattr(self.detector, 'engine') and not getattr(self.detector, 'training', False):
             boxes = self._confident_boxes(img)
         else:                                   # any other detector object with the reference's call signature
@@ -256,7 +266,7 @@ class PlanogramComparator:
                 return found.sum() / len(found)
             idx, pos = missing_indices[valid], pos[valid]
             lbls = [l for l, v in zip(missing_labels, valid) if v]
-            img = ops.device_image(image, classifier.device)
+            img = ops.input_image(image, classifier.device)
             crops = ops.crop_resize(img, pos.to(classifier.device), datautils.CLASSIFICATION_IMAGE_SIZE, mode=0)
             for i, want, got in zip(idx, lbls, classifier.classify(crops)):
                 if want == got[0]:
@@ -273,10 +283,13 @@ class PlanogramEvaluator:
         self.planogram_comparator = planogram_comparator
 
     def _float_image(self, image):
-        """An 8-bit image becomes the device float image here, ONCE: detection, the crops and the comparator's re-classification all
-        read that one.  A float image goes on as it came (the callees upload it as before)."""
+        """An 8-bit image becomes the device image here, ONCE (`ops.input_image`: the bytes themselves with ops.U8_KERNELS on, the float
+        image with it off): detection, the crops and the comparator's re-classification all read that one.  A float image goes on as it
+        came (the callees upload it as before)."""
         if ops.is_uint8_image(image):
-            return ops.device_image(image, getattr(self.proposal_generator, 'device', self.classifier.device))
+            pg = self.proposal_generator
+            device = getattr(pg, 'device', self.classifier.device)
+            return pg._upload(image) if hasattr(pg, '_upload') else ops.device_image(image, device)
         return image
 
     def evaluate(self, image, planogram):
@@ -303,7 +316,7 @@ class PlanogramEvaluator:
         for i, img in enumerate(images):
             groups.setdefault(datautils.image_hw(ops.check_image_form(img)), []).append(i)
         for idxs in groups.values():
-            res = pipe.run([ops.device_image(images[i], pg.device) for i in idxs])
+            res = pipe.run([ops.input_image(images[i], pg.device) for i in idxs])
             boxes, indices = res['boxes'].cpu(), res['indices'][:, :, 0].cpu()
             for j, i in enumerate(idxs):
                 c = res['counts_host'][j]
@@ -388,13 +401,14 @@ class BatchedPipeline:
         # skips the tiles that lie in it) -- only for an encoder whose engine has the work-list schedule
         skip = hasattr(emb_eng, 'skip_plan') and emb_eng.skip_plan(size) is not None
         ext = torch.empty((n * dpi, 2), dtype=torch.int32, device=eng.device) if skip else None
-        same_size = all(img.shape == images[0].shape for img in images)
+        hw = [datautils.image_hw(img) for img in images]    # (either form)
+        same_size = all(s == hw[0] for s in hw)
         partial = bool(content_only and skip and CROP_CONTENT_ONLY and emb_eng.will_skip(size))
         if skip and same_size:                   # (images of one size: the extents of the whole batch in one launch)
-            ops.crop_extents(boxes.reshape(n * dpi, 4), conf_count, images[0].shape[1], images[0].shape[2], size, out=ext, per_image=dpi)
+            ops.crop_extents(boxes.reshape(n * dpi, 4), conf_count, hw[0][0], hw[0][1], size, out=ext, per_image=dpi)
         for i, img in enumerate(images):
             if skip and not same_size:
-                ops.crop_extents(boxes[i], conf_count[i:i + 1], img.shape[1], img.shape[2], size, out=ext[i * dpi:(i + 1) * dpi])
+                ops.crop_extents(boxes[i], conf_count[i:i + 1], hw[i][0], hw[i][1], size, out=ext[i * dpi:(i + 1) * dpi])
             ops.crop_resize(img, boxes[i], size, mode=2 if narrow else 1, mean=mean, std=std, count=conf_count[i:i + 1],
                             out=crops[i * dpi:(i + 1) * dpi], content_ext=ext[i * dpi:(i + 1) * dpi] if partial else None)
         return crops, ext, (emb_eng.const_crop(mean, std, crops.shape[3], size) if skip else None), partial
@@ -432,7 +446,7 @@ class BatchedPipeline:
 
     @torch.no_grad()
     def run(self, images, stage_events=None, proposals=None):
-        """images: list of (3,H,W) f32 cuda tensors (or 8-bit (H,W,3) images, converted on the device first) -> dict of device tensors:
+        """images: list of (3,H,W) f32 cuda tensors (or 8-bit (H,W,3) images: `ops.input_image`) -> dict of device tensors:
         boxes (N,dpi,4), scores (N,dpi), count (N,) = #scores > confidence, indices (N,dpi,k) (-1 beyond count).
         stage_events: optional list that receives (stage name, start event, end event) for detect / crop / embed / match.
         proposals: optional (boxes (N,dpi,4) f32, counts (N,) int32) device tensors that REPLACE the detector's confident boxes after
@@ -452,7 +466,7 @@ class BatchedPipeline:
             for i in images:
                 ops.check_image_form(i)
             device = det.engine().device
-            images = [ops.device_image(i, device) if ops.is_uint8_image(i) else i for i in images]
+            images = [ops.input_image(i, device) if ops.is_uint8_image(i) else i for i in images]
         t0 = mark()
         if ops.PROFILE is not None:
             ops.PROFILE.records.stage = 'detect'           # (per-launch profile: the detector's 3x3 halo launches are filed apart)
