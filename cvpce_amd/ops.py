@@ -5,15 +5,11 @@ PyTorch-ROCm custom ops, CUDA/HIP dispatch key only) -> ctypes -> the C ABI of i
 kernels in libcvpce_hip.so.  torch is plumbing: device memory (tensors), the current HIP stream, the dispatcher.  There is
 no CPU kernel anywhere: CPU tensors are rejected loudly.
 """
-import ctypes
-import math
-
 import os as _os
 
 import torch
 
-from . import _lib
-from ._lib import lib, check
+from ._lib import lib
 from .torch_ops import T
 from . import torch_ops_input  # noqa: F401  (registers torch.ops.cvpce_amd.*_u8, the byte-reading input kernels)
 
@@ -31,19 +27,33 @@ def to_storage(t, dtype):
     return t.clamp(-F16_MAX, F16_MAX).to(F16) if dtype == F16 else t.to(dtype)
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError('cvpce_amd ops run on the GPU only (HIP kernels); got a CPU tensor. '
                                'There is no CPU fallback in the product path.')
+
+
+# ---------------------------------------------------------------------------
+# switches: read as module globals at call time (tests and tools assign to them), most of them A/B switches with an environment variable
+# ---------------------------------------------------------------------------
+FORCE_GENERIC_CONV = False   # A/B switch: route every conv through the register-staged fallback kernel
+USE_HALO_3X3 = True          # A/B switch: 3x3 s1 layers with Cin % 64 == 0 through the halo-patch kernel
+HALO_RAGGED = bool(int(_os.environ.get('CVPCE_HALO_RAGGED', '0')))          # test switch: also send small maps and maps that 16x16 tiles do not cover exactly through the halo kernel
+USE_HALO_THIN_OUT = _os.environ.get('CVPCE_HALO_THIN_OUT', '1') != '0'   # A/B switch: the head's output convs through the thin-output form of the wide halo kernel
+USE_THIN_3X3 = _os.environ.get('CVPCE_THIN_3X3', '1') != '0'   # A/B switch: the thin 3x3 layers through csrc/thin3x3.hip
+USE_CONV1X1 = True           # 1x1 convs with Cin, Cout % 64 == 0 through the LDS-free pointwise GEMM kernel (A/B switch)
+CONV1X1_STRIDE1 = _os.environ.get('CVPCE_CONV1X1_STRIDE1', '1') != '0'   # every stride-1 1x1 conv through the pointwise library entry (its streaming kernel, round 4; A/B switch)
+CONV1X1_MAX_CIN = int(_os.environ.get('CVPCE_CONV1X1_MAX_CIN', '256'))   # expansion convs up to this Cin (512 -- the 25 x 25 stage of ResNet-50 -- measured slower: 3.32 -> 3.36 ms detector only)
+CONV1X1_ANY_SHAPE = bool(int(_os.environ.get('CVPCE_CONV1X1_ANY', '0')))   # test switch: every eligible 1x1 conv through the pointwise kernel
+CONV_SPLITK = _os.environ.get('CVPCE_CONV_SPLITK', '1') != '0'   # A/B switch: split-K launches of the register-staged kernel
+USE_FUSED_BOTTLENECK = _os.environ.get('CVPCE_FUSED_BOTTLENECK', '1') != '0'   # A/B switch: stride-1 ResNet bottlenecks (P <= 256) in one launch (csrc/bneck.hip)
+FUSED_BOTTLENECK_MAX_PLANES = int(_os.environ.get('CVPCE_FUSED_BOTTLENECK_MAXP', '128'))   # measured (tools/dev/bench_bneck.py): with fragment-major weights (round 5) layer1 (P = 64: 66 vs 88 us per 4-image block) AND layer2 (P = 128: 49 vs 70 us) win over three launches; P = 256 still loses (120 vs 67 us: a 50 x 50 map has too few tiles for a 110-us tile chain).  Round 3-4 (row-major weights): only P = 64 won
+USE_FUSED_MAC = True   # A/B switch: MAC descriptor (+ pool4, + no store of conv5_3) fused into the conv epilogue
+USE_GAUSS_TAIL = _os.environ.get('CVPCE_GAUSS_TAIL', '1') != '0'   # A/B switch: the Gaussian subnet's two 1x1 layers in one launch
+USE_GAUSS_SUBNET = _os.environ.get('CVPCE_GAUSS_SUBNET', '1') != '0'   # A/B switch: the whole Gaussian subnet in one launch (csrc/gauss_subnet.hip)
+ONE_OUTPUT_BLOCK = _os.environ.get('CVPCE_ONE_OUTPUT_BLOCK', '1') != '0'   # detect_postprocess outputs as views of one block (A/B switch)
+U8_KERNELS = _os.environ.get('CVPCE_U8_KERNELS', '0') != '0'   # 8-bit images stay bytes up to the last crop ("input side" below); default: profiles/r12_u8_kernels.md
 
 
 # ---------------------------------------------------------------------------
@@ -106,10 +116,25 @@ class PackedConv:
         return ((h + 2 * self.pad - self.kh) // self.stride + 1, (w + 2 * self.pad - self.kw) // self.stride + 1)
 
 
-class ConvProfile:
-    """Opt-in per-launch timing of the conv kernel with HIP events on the launch stream (bench.py roofline leg).
+def igemm_tile(pc, m):
+    """The kernel `cvpce_conv2d_nhwc_*` runs layer `pc` with on m = N Ho Wo output pixels -> (kernel, its template arguments): THE mirror of
+    conv2d_dispatch in csrc/conv_igemm.hip (tile TC x TP, K-step BK).  FORCE_GENERIC_CONV 2 and 3 (A/B variants of the 256 x 256 kernel)
+    count as 1 here."""
+    bk64 = pc.cin_pad % 64 == 0
+    tiles256 = (m + 255) // 256
+    if bk64 and not FORCE_GENERIC_CONV:
+        if pc.cout >= 192 and tiles256 * ((pc.cout + 255) // 256) >= 128:
+            return 'conv_dma16_kernel', (256, 256, 2, 4, 2, 4)
+        if 64 < pc.cout <= 128 and tiles256 >= 128:
+            return 'conv_dma_kernel', (128, 128, 2, 2, 2)
+        if 32 < pc.cout <= 64 and tiles256 >= 128:
+            return 'conv_dma_kernel', (64, 128, 2, 2, 2)
+    tc = 128 if pc.cout > 64 else (32 if (pc.cout <= 32 and bk64) else 64)
+    return 'conv_igemm_kernel', (tc, 128, 64 if bk64 else 32, 1 if tc == 32 else 2, 4 if tc == 32 else 2)
 
-    Kernel variant names mirror the dispatch in csrc/conv_igemm.hip (tile TC x TP, K-step BK)."""
+
+class ConvProfile:
+    """Opt-in per-launch timing of the conv kernel with HIP events on the launch stream (bench.py roofline leg)."""
 
     class _Records(list):
         """The launch records; while `stage == 'detect'` the 3x3 halo kernels' records are filed under '<kernel>[detector]': the detector's
@@ -146,29 +171,8 @@ class ConvProfile:
 
     @staticmethod
     def variant(pc, m):
-        bk64 = pc.cin_pad % 64 == 0
-        tiles256 = (m + 255) // 256
-        if bk64 and not FORCE_GENERIC_CONV:
-            if pc.cout >= 192 and tiles256 * ((pc.cout + 255) // 256) >= 128:
-                return 'conv_dma16_kernel<256,256,2,4,2,4>'
-            if 64 < pc.cout <= 128 and tiles256 >= 128:
-                return 'conv_dma_kernel<128,128,2,2,2>'
-            if 32 < pc.cout <= 64 and tiles256 >= 128:
-                return 'conv_dma_kernel<64,128,2,2,2>'
-        tc = 128 if pc.cout > 64 else (32 if (pc.cout <= 32 and bk64) else 64)
-        return f'conv_igemm_kernel<{tc},128,{64 if bk64 else 32},{1 if tc == 32 else 2},{4 if tc == 32 else 2}>'
-
-    @staticmethod
-    def is_igemm128(pc, m):
-        """whether `variant(pc, m)` is the 128-cout register-staged kernel (the one with a split-K form), without formatting a name on the
-        launch path."""
-        if pc.cout <= 64:
-            return False
-        if pc.cin_pad % 64 == 0 and not FORCE_GENERIC_CONV:
-            tiles256 = (m + 255) // 256
-            if (pc.cout >= 192 and tiles256 * ((pc.cout + 255) // 256) >= 128) or (pc.cout <= 128 and tiles256 >= 128):
-                return False
-        return True
+        kernel, args = igemm_tile(pc, m)
+        return f"{kernel}<{','.join(map(str, args))}>"
 
     def summary(self):
         """per kernel: launches, algorithmic FLOPs (`flops`), EXECUTED FLOPs (`flops_executed`: work-list launches of the embedder
@@ -183,7 +187,6 @@ class ConvProfile:
             d['flops_executed'] += (float(rec[4].item()) * rec[5] if rec[4] is not None else 0.0) if len(rec) > 4 else flops
             d['ms'] += e0.elapsed_time(e1)
         return out
-
 
     def summary_bytes(self):
         """per HBM-bound kernel: launches, ALGORITHMIC bytes (every input and output tensor of the launch once, weights included) and
@@ -201,18 +204,113 @@ class ConvProfile:
 PROFILE = None   # set to a ConvProfile() to record
 
 
+class _Launch:
+    """One launch being timed for a ConvProfile: made just before the launch (`_start`); `stop` right after it, before anything else
+    is computed or enqueued; then `file`."""
+
+    def __init__(self, prof):
+        self.prof = prof
+        self.e0, self.e1 = None, self._mark()
+
+    @staticmethod
+    def _mark():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def stop(self):
+        """The launch is enqueued.  (A launch that follows at once is timed from this one's end: stop again after it.)"""
+        self.e0, self.e1 = self.e1, self._mark()
+
+    def file(self, kernel, flops=None, nbytes=None, layer=None, hbm=False, extras=()):
+        """Files the stopped launch under `kernel`: with the conv records when `flops` is given (`extras`: the work-list fields), with the
+        HBM-bound launches when `hbm`; and, when `layer` is given, under that label with the detector's launch classes."""
+        if flops is not None:
+            self.prof.records.append((kernel, flops, self.e0, self.e1) + extras)
+        if hbm:
+            self.prof.byte_records.append((kernel, nbytes, self.e0, self.e1))
+        if layer is not None:
+            self.prof.layer(layer, flops or 0.0, nbytes, self.e0, self.e1)
+
+
+def _start():
+    """-> a running _Launch, or None when no profile is being recorded: PROFILE is read once per call, and without one no event is made
+    and the caller computes no name, label, FLOP or byte count (`if t is not None: t.stop(); t.file(...)`).  The detector captures its schedule
+    in a graph only while PROFILE is None, so no event is ever recorded into a capture."""
+    prof = PROFILE
+    return None if prof is None else _Launch(prof)
+
+
 def _nbytes(*ts):
     return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
 
-CONV1X1_ANY_SHAPE = bool(int(_os.environ.get('CVPCE_CONV1X1_ANY', '0')))   # test switch: every eligible 1x1 conv through the pointwise kernel
-CONV1X1_STRIDE1 = _os.environ.get('CVPCE_CONV1X1_STRIDE1', '1') != '0'   # every stride-1 1x1 conv through the pointwise library entry (its streaming kernel, round 4; A/B switch)
-CONV1X1_MAX_CIN = int(_os.environ.get('CVPCE_CONV1X1_MAX_CIN', '256'))   # expansion convs up to this Cin (512 -- the 25 x 25 stage of ResNet-50 -- measured slower: 3.32 -> 3.36 ms detector only)
-ONE_OUTPUT_BLOCK = _os.environ.get('CVPCE_ONE_OUTPUT_BLOCK', '1') != '0'   # detect_postprocess outputs as views of one block (A/B switch)
-USE_CONV1X1 = True           # 1x1 convs with Cin, Cout % 64 == 0 through the LDS-free pointwise GEMM kernel (A/B switch)
-HALO_RAGGED = bool(int(_os.environ.get('CVPCE_HALO_RAGGED', '0')))          # test switch: also send small maps and maps that 16x16 tiles do not cover exactly through the halo kernel
-USE_HALO_3X3 = True          # A/B switch: 3x3 s1 layers with Cin % 64 == 0 through the halo-patch kernel
-FORCE_GENERIC_CONV = False   # A/B switch: route every conv through the register-staged fallback kernel
+def splitk_factor(pc, ho, wo):
+    """Workgroups per output tile for a conv that the 128-cout register-staged kernel would run: a function of the LAYER shape only
+    (K-steps, map size), 0 = unsplit.  36+ K-steps on an output map of at most 32 x 32: 4 (tools/dev/prof_splitk.sh, kernel durations on 4 images:
+    layer4's 3x3 62.6 -> 28.8 + 6.4 us, P6 / P7 34 -> 11 + 4 us; a 50 x 50 output map has workgroups enough: 37.8 -> 29.0 + 7-10 us, not split)."""
+    if not CONV_SPLITK or pc.cin_pad % 64 != 0 or pc.cout <= 64 or pc.k_pad // 64 < 32:
+        return 0
+    return 4 if ho * wo <= 1024 else 0
+
+
+def conv_route(pc, n, h, w, act, out_f32, has_residual, in_up_shift, pool):
+    """Which launch `conv2d` makes of layer `pc` on an (n, h, w, pc.cin_pad) input -> (route, split-K factor): 'halo_thin_out' | 'halo' |
+    'thin3x3' | 'conv1x1' | 'splitk' (the only one with a factor, else 0) | 'igemm', the first in that order whose kernel covers the call.
+    A function of its arguments and the module's switches only (read now: tests and tools assign to them); no tensor, no device."""
+    if FORCE_GENERIC_CONV:
+        return 'igemm', 0
+    cin = pc.cin_pad
+    ho, wo = pc.out_hw(h, w, in_up_shift)
+    is_3x3 = (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1)
+    input_fits = n * h * w * cin * 2 < 2 ** 32    # (these kernels address the input with 32-bit byte offsets)
+    # the RetinaNet head's output convs (256 -> 9 | 36, fp32 out, no activation): the 16 x 32-pixel halo-patch kernel with only the waves
+    # that hold a real cout computing (csrc/conv3x3_halo3.hip THIN) -- 72 + 60 us per 4 images as register-staged implicit GEMMs
+    if (USE_HALO_THIN_OUT and is_3x3 and cin % 64 == 0 and pc.cout <= 64 and out_f32 and act == 0 and not has_residual and not in_up_shift
+            and not pool and min(h, w) >= 48 and input_fits):
+        return 'halo_thin_out', 0
+    # the halo-patch kernels (Cout <= 128 is forwarded to the wide-tile kernel, conv3x3_halo3.hip, inside the library).  Ragged (masked)
+    # tiles pay from about 50x50 up (detector: 200x200 -1/3, 100x100 -1/3, 50x50 -5 %, 25x25 +20 %); the choice never depends on the batch
+    # size: a crop's embedding must not change with the crops it is batched with
+    if (USE_HALO_3X3 and is_3x3 and cin % 64 == 0 and pc.cout > 64 and pc.cout % 8 == 0 and not out_f32 and act in (0, 1) and not has_residual
+            and not in_up_shift and (HALO_RAGGED or (h % 16 == 0 and w % 16 == 0) or min(h, w) >= 48) and input_fits):
+        return 'halo', 0
+    # thin 3x3 layers (the Gaussian subnet's 64 -> 32 over an upsampled input, 32 -> 32, 32 -> 16, all on the 400 x 400 map): weights in
+    # registers, input rows streamed through LDS (csrc/thin3x3.hip)
+    thin_shape = ((cin, pc.cin, pc.k_pad) == (32, 32, 288) and pc.cout in (16, 32) and not in_up_shift) or \
+                 ((cin, pc.cin, pc.k_pad) == (64, 64, 576) and pc.cout == 32 and in_up_shift == 1)
+    if (USE_THIN_3X3 and is_3x3 and thin_shape and not out_f32 and act in (0, 1) and not has_residual and not pool
+            and n * ho * wo * 64 < 2 ** 32 - 65536):
+        return 'thin3x3', 0
+    # pointwise GEMM kernel: wins on the expansion convs (short K, 4x wider output: HBM-bound, 1.3-1.8x), loses on long K
+    if (USE_CONV1X1 and (pc.kh, pc.kw, pc.pad) == (1, 1, 0) and cin % 64 == 0 and pc.k_pad == cin and pc.cout % 64 == 0
+            and (CONV1X1_ANY_SHAPE or (pc.stride == 1 and CONV1X1_STRIDE1) or (cin <= CONV1X1_MAX_CIN and pc.cout >= 4 * cin))
+            and not out_f32 and act in (0, 1) and not in_up_shift and not pool and input_fits):
+        return 'conv1x1', 0
+    # small maps with a long K (layer4's 3x3 convs on 25 x 25 maps, the stride-2 3x3s that open layer3 / layer4, P5 / P6 / P7): the
+    # register-staged kernel with K split over `ks` workgroups per output tile (csrc/conv_igemm.hip SPLIT), the 128-cout tile only
+    if not pool:
+        kernel, tile = igemm_tile(pc, n * ho * wo)
+        if kernel == 'conv_igemm_kernel' and tile[0] == 128:
+            ks = splitk_factor(pc, ho, wo)
+            if ks:
+                return 'splitk', ks
+    return 'igemm', 0
+
+
+def _splitk_workspace(pc, n, ho, wo, ks, device):
+    """One fp32 workspace per (launch shape, device), kept with the layer: a layer of an engine runs on ONE stream at a time (the
+    side streams of a schedule run DIFFERENT layers), so its launches are ordered and may share the block.  The key must not
+    depend on the stream: a hipGraph is captured on another stream than the eager first call of its geometry, and a capture that
+    found no workspace would have to take the unsplit kernel -- another fp32 summation order, i.e. replayed results that differ
+    from eager ones (tests/test_gpu_configs1.py).  Captured graphs hold a workspace's address, and nothing here knows which graphs
+    are still alive: an entry is NEVER freed (tens of MB per layer and batch geometry; an engine's graph cache bounds the geometries)."""
+    cache = pc.__dict__.setdefault('_splitk_ws', {})
+    key = (n, ho, wo, ks, device)
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.empty(int(lib.cvpce_conv2d_splitk_workspace_bytes(n * ho * wo, pc.cout, ks)), dtype=torch.uint8, device=device)
+    return ws
 
 
 def conv2d(x, pc, act=0, out_f32=False, residual=None, res_mode=0, in_up_shift=0, out=None, pool=False):
@@ -228,116 +326,47 @@ def conv2d(x, pc, act=0, out_f32=False, residual=None, res_mode=0, in_up_shift=0
         out = torch.empty(oshape, dtype=odtype, device=x.device)
     else:
         assert tuple(out.shape) == oshape and out.dtype == odtype and out.is_contiguous(), (tuple(out.shape), oshape, out.dtype, odtype)
-    hr = wr = 0
     if residual is not None:
         assert residual.dtype == x.dtype and residual.is_contiguous() and residual.shape[0] == n and residual.shape[3] == pc.cout
-        hr, wr = residual.shape[1], residual.shape[2]
         if res_mode == 0:
-            res_mode = 1 if (hr, wr) == (ho, wo) else 2
-    halo = (USE_HALO_3X3 and not FORCE_GENERIC_CONV and pc.cin_pad % 64 == 0 and pc.kh == 3 and pc.kw == 3
-            and pc.stride == 1 and pc.pad == 1 and not out_f32 and residual is None and not in_up_shift
-            and act in (0, 1) and pc.cout % 8 == 0 and pc.cout > 64 and (HALO_RAGGED or (h % 16 == 0 and w % 16 == 0) or min(h, w) >= 48)   # ragged (masked) tiles pay from about 50x50 up (detector: 200x200 -1/3, 100x100 -1/3, 50x50 -5 %, 25x25 +20 %); the choice never depends on the batch size: a crop's embedding must not change with the crops it is batched with
-            and n * h * w * pc.cin_pad * 2 < 2 ** 32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    # the RetinaNet head's output convs (256 -> 9 | 36, fp32 out, no activation): the 16 x 32-pixel halo-patch kernel with only the waves
-    # that hold a real cout computing (csrc/conv3x3_halo3.hip THIN) -- 72 + 60 us per 4 images as register-staged implicit GEMMs
-    if (USE_HALO_THIN_OUT and not FORCE_GENERIC_CONV and out_f32 and act == 0 and residual is None and not in_up_shift and not pool
-            and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1) and pc.cin_pad % 64 == 0 and cin == pc.cin_pad and pc.cout <= 64
-            and min(h, w) >= 48 and n * h * w * pc.cin_pad * 2 < 2 ** 32):
+            res_mode = 1 if tuple(residual.shape[1:3]) == (ho, wo) else 2
+    route, ks = conv_route(pc, n, h, w, act, out_f32, residual is not None, in_up_shift, pool)
+    t = _start()
+    if route == 'halo_thin_out':
         T.conv3x3_halo_thin_out(x, pc.weight_halo, pc.bias, out, pc.cout, pc.k_pad, pc.cout_pad)
-        if prof is not None:
-            e1.record()
-            prof.records.append(('conv3x3_halo3_kernel', 2.0 * n * ho * wo * pc.cout * 9 * pc.cin, e0, e1))
-            prof.layer(f'conv3x3_halo3 thin out {ho}x{wo} {pc.cin}->{pc.cout} f32 out', 2.0 * n * ho * wo * pc.cout * 9 * pc.cin, _nbytes(x, out, pc.weight), e0, e1)
-        return out
-    if halo:
-        # (Cout <= 128 is forwarded to the wide-tile kernel, conv3x3_halo3.hip, inside the library)
+    elif route == 'halo':
         T.conv3x3_halo(x, pc.weight_halo, pc.bias, out, pc.cout, pc.k_pad, pc.cout_pad, int(act), int(pool))
-        if prof is not None:
-            e1.record()
-            prof.records.append(('conv3x3_halo3_kernel' if pc.cout <= 128 else 'conv3x3_halo2_kernel',
-                                 2.0 * n * ho * wo * pc.cout * 9 * pc.cin, e0, e1))
-            prof.layer(f"{'conv3x3_halo3' if pc.cout <= 128 else 'conv3x3_halo2'} {h}x{w} {pc.cin}->{pc.cout}" + (' +pool' if pool else ''),
-                       2.0 * n * ho * wo * pc.cout * 9 * pc.cin, _nbytes(x, out, pc.weight), e0, e1)
-        return out
-    # thin 3x3 layers (the Gaussian subnet's 64 -> 32 over an upsampled input, 32 -> 32, 32 -> 16, all on the 400 x 400 map): weights in
-    # registers, input rows streamed through LDS (csrc/thin3x3.hip)
-    thin_shape = ((cin, pc.cin, pc.k_pad) == (32, 32, 288) and pc.cout in (16, 32) and not in_up_shift) or \
-                 ((cin, pc.cin, pc.k_pad) == (64, 64, 576) and pc.cout == 32 and in_up_shift == 1)
-    if (USE_THIN_3X3 and not FORCE_GENERIC_CONV and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1) and thin_shape
-            and not out_f32 and residual is None and not pool and act in (0, 1) and n * ho * wo * 64 < 2 ** 32 - 65536):
+    elif route == 'thin3x3':
         T.conv3x3_thin(x, pc.weight, pc.bias, out, pc.cout, pc.k_pad, pc.cout_pad, int(act), int(in_up_shift))
-        if prof is not None:
-            e1.record()
-            prof.records.append(('thin3x3_kernel', 2.0 * n * ho * wo * pc.cout * 9 * pc.cin, e0, e1))
-            prof.byte_records.append(('thin3x3_kernel', _nbytes(x, out, pc.weight), e0, e1))
-            prof.layer(f'thin3x3 {ho}x{wo} {pc.cin}->{pc.cout}' + (' (2x upsampled input)' if in_up_shift else ''), 2.0 * n * ho * wo * pc.cout * 9 * pc.cin,
-                       _nbytes(x, out, pc.weight), e0, e1)
-        return out
-    # pointwise GEMM kernel: wins on the expansion convs (short K, 4x wider output: HBM-bound, 1.3-1.8x), loses on long K
-    if (USE_CONV1X1 and not FORCE_GENERIC_CONV and pc.kh == 1 and pc.kw == 1 and pc.pad == 0 and cin % 64 == 0 and pc.k_pad == cin
-            and (CONV1X1_ANY_SHAPE or (pc.stride == 1 and CONV1X1_STRIDE1) or (cin <= CONV1X1_MAX_CIN and pc.cout >= 4 * cin)) and pc.cout % 64 == 0 and not out_f32 and not in_up_shift and not pool and act in (0, 1) and n * h * w * cin * 2 < 2 ** 32):
+    elif route == 'conv1x1':
         T.conv1x1_nhwc(x, pc.weight, pc.bias, residual, out, pc.cout, pc.stride, ho, wo, pc.k_pad, pc.cout_pad, int(act), int(res_mode))
-        if prof is not None:
-            e1.record()
-            prof.records.append(('conv1x1_kernel', 2.0 * n * ho * wo * pc.cout * pc.cin, e0, e1))
-            # a strided 1x1 reads only the pixels it keeps; an upsampled residual (res_mode 2) is read at its stored size
-            prof.byte_records.append(('conv1x1_kernel', n * ho * wo * cin * x.element_size() + _nbytes(out, residual, pc.weight), e0, e1))
-            prof.layer(f'conv1x1 {ho}x{wo} {pc.cin}->{pc.cout} s{pc.stride}' + (' +res' if residual is not None else ''), 2.0 * n * ho * wo * pc.cout * pc.cin,
-                       n * ho * wo * cin * x.element_size() + _nbytes(out, residual, pc.weight), e0, e1)
-        return out
-    # small maps with a long K (layer4's 3x3 convs on 25 x 25 maps, the stride-2 3x3s that open layer3 / layer4, P5 / P6 / P7): the
-    # register-staged kernel with K split over `ks` workgroups per output tile (csrc/conv_igemm.hip SPLIT)
-    ks = splitk_factor(pc, ho, wo) if (not pool and not FORCE_GENERIC_CONV and ConvProfile.is_igemm128(pc, n * ho * wo)) else 0
-    ws = None
-    if ks:
-        # One fp32 workspace per (launch shape, device), kept with the layer: a layer of an engine runs on ONE stream at a time (the
-        # side streams of a schedule run DIFFERENT layers), so its launches are ordered and may share the block.  The key must not
-        # depend on the stream: a hipGraph is captured on another stream than the eager first call of its geometry, and a capture that
-        # found no workspace would have to take the unsplit kernel -- another fp32 summation order, i.e. replayed results that differ
-        # from eager ones (tests/test_gpu_configs1.py).  Captured graphs hold a workspace's address, and nothing here knows which graphs
-        # are still alive: an entry is NEVER freed (tens of MB per layer and batch geometry; an engine's graph cache bounds the geometries).
-        cache = pc.__dict__.setdefault('_splitk_ws', {})
-        key = (n, ho, wo, ks, x.device)
-        ws = cache.get(key)
-        if ws is None:
-            ws = cache[key] = torch.empty(int(lib.cvpce_conv2d_splitk_workspace_bytes(n * ho * wo, pc.cout, ks)), dtype=torch.uint8, device=x.device)
-    if ks:
+    elif route == 'splitk':
         T.conv2d_splitk(x, pc.weight, pc.bias, residual, out, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, ho, wo, pc.k_pad, pc.cout_pad,
-                        int(act), int(out_f32), int(in_up_shift), int(res_mode), ks, ws)
+                        int(act), int(out_f32), int(in_up_shift), int(res_mode), ks, _splitk_workspace(pc, n, ho, wo, ks, x.device))
     else:
         T.conv2d_nhwc(x, pc.weight, pc.bias, residual, out, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, ho, wo, pc.k_pad, pc.cout_pad,
                       int(act), int(out_f32), int(in_up_shift), int(res_mode), int(pool), int(FORCE_GENERIC_CONV))   # FORCE_GENERIC_CONV: False/True or 2, 3 = A/B variants
-    if prof is not None:
-        e1.record()
-        # algorithmic FLOPs: real (unpadded) channels, 2 FLOP per MAC
-        prof.records.append((prof.variant(pc, n * ho * wo), 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin, e0, e1))
-        prof.layer(f"{prof.variant(pc, n * ho * wo).split('<')[0]} {ho}x{wo} {pc.cin}->{pc.cout} k{pc.kh} s{pc.stride}" + (' f32 out' if out_f32 else '') + (f' split-K {ks}' if ks else ''),
-                   2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin, _nbytes(x, out, residual, pc.weight), e0, e1)
+    if t is not None:
+        t.stop()
+        flops = 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin    # algorithmic FLOPs: real (unpadded) channels, 2 FLOP per MAC
+        nbytes = _nbytes(x, out, residual, pc.weight)
+        shape = f'{pc.cin}->{pc.cout}'
+        if route == 'halo_thin_out':
+            t.file('conv3x3_halo3_kernel', flops, nbytes, f'conv3x3_halo3 thin out {ho}x{wo} {shape} f32 out')
+        elif route == 'halo':
+            halo = 'conv3x3_halo3' if pc.cout <= 128 else 'conv3x3_halo2'
+            t.file(halo + '_kernel', flops, nbytes, f'{halo} {h}x{w} {shape}' + (' +pool' if pool else ''))
+        elif route == 'thin3x3':
+            t.file('thin3x3_kernel', flops, nbytes, f'thin3x3 {ho}x{wo} {shape}' + (' (2x upsampled input)' if in_up_shift else ''), hbm=True)
+        elif route == 'conv1x1':
+            # a strided 1x1 reads only the pixels it keeps; an upsampled residual (res_mode 2) is read at its stored size
+            nbytes = n * ho * wo * cin * x.element_size() + _nbytes(out, residual, pc.weight)
+            t.file('conv1x1_kernel', flops, nbytes, f'conv1x1 {ho}x{wo} {shape} s{pc.stride}' + (' +res' if residual is not None else ''), hbm=True)
+        else:
+            variant = ConvProfile.variant(pc, n * ho * wo)
+            t.file(variant, flops, nbytes, f"{variant.split('<')[0]} {ho}x{wo} {shape} k{pc.kh} s{pc.stride}" + (' f32 out' if out_f32 else '')
+                   + (f' split-K {ks}' if ks else ''))
     return out
-
-
-CONV_SPLITK = _os.environ.get('CVPCE_CONV_SPLITK', '1') != '0'   # A/B switch: split-K launches of the register-staged kernel
-
-
-def splitk_factor(pc, ho, wo):
-    """Workgroups per output tile for a conv that the 128-cout register-staged kernel would run: a function of the LAYER shape only
-    (K-steps, map size), 0 = unsplit.  36+ K-steps on an output map of at most 32 x 32: 4 (tools/dev/prof_splitk.sh, kernel durations on 4 images:
-    layer4's 3x3 62.6 -> 28.8 + 6.4 us, P6 / P7 34 -> 11 + 4 us; a 50 x 50 output map has workgroups enough: 37.8 -> 29.0 + 7-10 us, not split)."""
-    if not CONV_SPLITK or pc.cin_pad % 64 != 0 or pc.cout <= 64 or pc.k_pad // 64 < 32:
-        return 0
-    return 4 if ho * wo <= 1024 else 0
-
-
-USE_HALO_THIN_OUT = _os.environ.get('CVPCE_HALO_THIN_OUT', '1') != '0'   # A/B switch: the head's output convs through the thin-output form of the wide halo kernel
-USE_THIN_3X3 = _os.environ.get('CVPCE_THIN_3X3', '1') != '0'   # A/B switch: the thin 3x3 layers through csrc/thin3x3.hip
-USE_FUSED_BOTTLENECK = _os.environ.get('CVPCE_FUSED_BOTTLENECK', '1') != '0'   # A/B switch: stride-1 ResNet bottlenecks (P <= 256) in one launch (csrc/bneck.hip)
-
-
-FUSED_BOTTLENECK_MAX_PLANES = int(_os.environ.get('CVPCE_FUSED_BOTTLENECK_MAXP', '128'))   # measured (tools/dev/bench_bneck.py): with fragment-major weights (round 5) layer1 (P = 64: 66 vs 88 us per 4-image block) AND layer2 (P = 128: 49 vs 70 us) win over three launches; P = 256 still loses (120 vs 67 us: a 50 x 50 map has too few tiles for a 110-us tile chain).  Round 3-4 (row-major weights): only P = 64 won
 
 
 def can_fuse_bottleneck(x, c1, c2, c3, residual):
@@ -408,20 +437,13 @@ def bottleneck(x, c1, c2, c3, residual):
     p = c1.cout
     out = torch.empty((n, h, w, 4 * p), dtype=x.dtype, device=x.device)
     w1f, w2f, w3f = pack_bottleneck_weights(c1, c2, c3)      # (built once per block: cached on c1)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.bottleneck_fused_fm(x, residual, w1f, c1.bias, w2f, c2.bias, w3f, c3.bias, out, p)
-    if prof is not None:
-        e1.record()
-        prof.records.append(('bneck_kernel', 2.0 * n * h * w * (cin * p + 9 * p * p + 4 * p * p), e0, e1))
-        prof.layer(f'bneck {h}x{w} {cin}->{p}->{4 * p}', 2.0 * n * h * w * (cin * p + 9 * p * p + 4 * p * p),
-                   _nbytes(x, out, c1.weight, c2.weight, c3.weight) + (0 if residual.data_ptr() == x.data_ptr() else _nbytes(residual)), e0, e1)
+    if t is not None:
+        t.stop()
+        nbytes = _nbytes(x, out, c1.weight, c2.weight, c3.weight) + (0 if residual.data_ptr() == x.data_ptr() else _nbytes(residual))
+        t.file('bneck_kernel', 2.0 * n * h * w * (cin * p + 9 * p * p + 4 * p * p), nbytes, f'bneck {h}x{w} {cin}->{p}->{4 * p}')
     return out
-
-
-USE_FUSED_MAC = True   # A/B switch: MAC descriptor (+ pool4, + no store of conv5_3) fused into the conv epilogue
 
 
 def can_fuse_mac(x, pc):
@@ -442,14 +464,11 @@ def conv2d_relu_mac(x, pc, mac, mac_off, store=True, pool=False):
     out = None
     if store:
         out = torch.empty((n, h // 2, w // 2, pc.cout) if pool else (n, h, w, pc.cout), dtype=BF16, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.conv3x3_halo_mac(x, pc.weight_halo, pc.bias, out, mac, int(mac_off), pc.cout, pc.k_pad, pc.cout_pad, int(pool and store))
-    if prof is not None:
-        e1.record()
-        prof.records.append(('conv3x3_halo2_kernel', 2.0 * n * h * w * pc.cout * 9 * pc.cin, e0, e1))
+    if t is not None:
+        t.stop()
+        t.file('conv3x3_halo2_kernel', 2.0 * n * h * w * pc.cout * 9 * pc.cin)
     return out
 
 
@@ -491,15 +510,11 @@ def gln_stem(x, ps):
     n, h, w, _ = x.shape
     hc, wc = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     out = torch.empty((n, (hc - 1) // 2 + 1, (wc - 1) // 2 + 1, 64), dtype=x.dtype, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.gln_stem_fused(x, ps.w_frag, ps.bias, out)
-    if prof is not None:
-        e1.record()
-        prof.records.append(('gln_stem_kernel', 2.0 * n * hc * wc * 64 * 147, e0, e1))
-        prof.layer(f'gln_stem {h}x{w} 3->64 k7 s2 +pool', 2.0 * n * hc * wc * 64 * 147, _nbytes(x, out), e0, e1)
+    if t is not None:
+        t.stop()
+        t.file('gln_stem_kernel', 2.0 * n * hc * wc * 64 * 147, _nbytes(x, out), f'gln_stem {h}x{w} 3->64 k7 s2 +pool')
     return out
 
 
@@ -526,17 +541,13 @@ def conv3x3_atlas(x, pc, mask, act=1, tile_map=None, out=None, mask_pixels=None)
     if out is None:
         out = torch.empty((n, h, w, pc.cout), dtype=x.dtype, device=x.device)
     assert tuple(out.shape) == (n, h, w, pc.cout) and out.dtype == x.dtype and out.is_contiguous()
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.conv3x3_halo_masked(x, pc.weight_halo, pc.bias, mask, tile_map, out, pc.cout, pc.k_pad, pc.cout_pad, int(act))
-    if prof is not None:
-        e1.record()
+    if t is not None:
+        t.stop()
         npix = float(mask.sum().item()) if mask_pixels is None else float(mask_pixels)
-        prof.records.append(('conv3x3_halo2_kernel', 2.0 * npix * n * pc.cout * 9 * pc.cin, e0, e1))
-        prof.layer(f'conv3x3_halo2 atlas {pc.cin}->{pc.cout} (head tower)', 2.0 * npix * n * pc.cout * 9 * pc.cin,
-                   2 * npix * n * (pc.cin + pc.cout) * x.element_size() + _nbytes(pc.weight), e0, e1)
+        t.file('conv3x3_halo2_kernel', 2.0 * npix * n * pc.cout * 9 * pc.cin, 2 * npix * n * (pc.cin + pc.cout) * x.element_size() + _nbytes(pc.weight),
+               f'conv3x3_halo2 atlas {pc.cin}->{pc.cout} (head tower)')
     return out
 
 
@@ -563,14 +574,11 @@ def vgg_stem(x, ps):
     assert x.dtype == BF16 and x.is_contiguous() and x.shape[3] in (4, 8)
     n, h, w, c = x.shape
     out = torch.empty((n, h // 2, w // 2, 64), dtype=BF16, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.vgg_stem_fused(x, ps.w1, ps.b1, ps.w2, ps.b2, out)
-    if prof is not None:
-        e1.record()
-        prof.records.append(('vgg_stem2_kernel', ps.flops_per_pixel * n * h * w, e0, e1))
+    if t is not None:
+        t.stop()
+        t.file('vgg_stem2_kernel', ps.flops_per_pixel * n * h * w)
     return out
 
 
@@ -628,14 +636,11 @@ def vgg_stem_list(x, const_in, ps, work, count):
     assert x.dtype == BF16 and x.is_contiguous() and x.shape[3] in (4, 8) and const_in.is_contiguous()
     n1, h, w, c = x.shape
     out = torch.empty((n1 + 1, h // 2, w // 2, 64), dtype=BF16, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.vgg_stem_fused_list(x, const_in, ps.w1, ps.b1, ps.w2, ps.b2, out, work, count)
-    if prof is not None:
-        e1.record()
-        prof.records.append(('vgg_stem2_kernel', ps.flops_per_pixel * n1 * h * w, e0, e1, count, ps.flops_per_pixel * 256, f'stem@{h}'))   # (the stem computes whole tiles)
+    if t is not None:
+        t.stop()
+        t.file('vgg_stem2_kernel', ps.flops_per_pixel * n1 * h * w, extras=(count, ps.flops_per_pixel * 256, f'stem@{h}'))   # (the stem computes whole tiles)
     return out
 
 
@@ -654,27 +659,24 @@ def conv2d_list(x, pc, work, count, act=1, pool=False, mac=None, mac_off=0, stor
         out = torch.empty(oshape, dtype=BF16, device=x.device)
     else:
         assert tuple(out.shape) == oshape and out.dtype == BF16 and out.is_contiguous()
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.conv3x3_halo_list(x, pc.weight_halo, pc.bias, out, mac, int(mac_off), pc.cout, pc.k_pad, pc.cout_pad, int(act), int(pool and store), work, count)
-    if prof is not None:
-        e1.record()
+    if t is not None:
+        t.stop()
         wide = pc.cout <= 128
         tile_flops = 2.0 * 16 * (32 if wide else 16) * pc.cout * 9 * pc.cin
+        tag = f'{pc.cin}->{pc.cout}@{h}' + ('mac' if mac is not None else '')
         # (`units` counts the layer's whole MFMA work in sixteenths of a tile, its strip launch included: a strip-list entry is 4 of
         # them (csrc/skiplist.hip) and is filed with the STRIP launch below, a different template instance with its own duration)
         lunits = (units - 4 * strips[1]) if (units is not None and strips is not None) else units
-        prof.records.append(('conv3x3_halo3_kernel' if wide else 'conv3x3_halo2_kernel', 2.0 * (n - 1) * h * w * pc.cout * 9 * pc.cin, e0, e1)
-                            + ((lunits, tile_flops / 16) if units is not None else (count, tile_flops)) + (f'{pc.cin}->{pc.cout}@{h}' + ('mac' if mac is not None else ''),))
+        t.file('conv3x3_halo3_kernel' if wide else 'conv3x3_halo2_kernel', 2.0 * (n - 1) * h * w * pc.cout * 9 * pc.cin,
+               extras=((lunits, tile_flops / 16) if units is not None else (count, tile_flops)) + (tag,))
     if strips is not None:
         assert pc.cout > 128
         T.conv3x3_halo_strips(x, pc.weight_halo, pc.bias, out, mac, int(mac_off), pc.cout, pc.k_pad, pc.cout_pad, int(act), int(pool and store), strips[0], strips[1])
-        if prof is not None:
-            e2 = torch.cuda.Event(enable_timing=True)
-            e2.record()
-            prof.records.append(('conv3x3_halo2_kernel[strips]', 0.0, e1, e2, strips[1], tile_flops / 4, f'{pc.cin}->{pc.cout}@{h}' + ('mac' if mac is not None else '')))
+        if t is not None:
+            t.stop()
+            t.file('conv3x3_halo2_kernel[strips]', 0.0, extras=(strips[1], tile_flops / 4, tag))     # (timed from the list launch's end)
     return out
 
 
@@ -694,9 +696,6 @@ def relu(x):
     return out
 
 
-USE_GAUSS_TAIL = _os.environ.get('CVPCE_GAUSS_TAIL', '1') != '0'   # A/B switch: the Gaussian subnet's two 1x1 layers in one launch
-
-
 def can_fuse_gauss_tail(x, c4, c5):
     """cvpce_gauss_tail covers conv1x1(16 -> 16) + ReLU followed by conv1x1(16 -> 1) (proposals.py:96-107)."""
     return (USE_GAUSS_TAIL and not FORCE_GENERIC_CONV and x.shape[-1] == 16 and c4.dtype == c5.dtype == x.dtype
@@ -709,20 +708,13 @@ def gauss_tail(x, c4, c5, act):
     _need_cuda(x)
     assert can_fuse_gauss_tail(x, c4, c5) and x.is_contiguous() and act in (0, 1, 2)
     out = torch.empty(x.shape[:3] + (1,), dtype=torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.gauss_tail(x, c4.weight, c4.bias, c5.weight, c5.bias, out, c4.k_pad, int(act))
-    if prof is not None:
-        e1.record()
-        prof.records.append(('gauss_tail_kernel', 2.0 * x.shape[0] * x.shape[1] * x.shape[2] * (16 * 16 + 16), e0, e1))
-        prof.byte_records.append(('gauss_tail_kernel', _nbytes(x, out), e0, e1))
-        prof.layer(f'gauss_tail {x.shape[1]}x{x.shape[2]} 16->16->1', 2.0 * x.shape[0] * x.shape[1] * x.shape[2] * (16 * 16 + 16), _nbytes(x, out), e0, e1)
+    if t is not None:
+        t.stop()
+        t.file('gauss_tail_kernel', 2.0 * x.shape[0] * x.shape[1] * x.shape[2] * (16 * 16 + 16), _nbytes(x, out),
+               f'gauss_tail {x.shape[1]}x{x.shape[2]} 16->16->1', hbm=True)
     return out
-
-
-USE_GAUSS_SUBNET = _os.environ.get('CVPCE_GAUSS_SUBNET', '1') != '0'   # A/B switch: the whole Gaussian subnet in one launch (csrc/gauss_subnet.hip)
 
 
 def can_fuse_gauss_subnet(x, convs):
@@ -745,25 +737,20 @@ def gauss_subnet(x, convs, act):
     c1, c2, c3, c4, c5 = convs
     n, hs, ws, _ = x.shape
     out = torch.empty((n, 2 * hs, 2 * ws, 1), dtype=torch.float32, device=x.device)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.gauss_subnet(x, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias, c4.weight, c4.bias, c4.k_pad, c5.weight, c5.bias, c5.k_pad, out, int(act))
-    if prof is not None:
-        e1.record()
-        flops = 2.0 * n * 4 * hs * ws * (9 * 64 * 32 + 9 * 32 * 32 + 9 * 32 * 16 + 16 * 16 + 16)
-        prof.records.append(('gauss_subnet_kernel', flops, e0, e1))
+    if t is not None:
+        t.stop()
         # (not an HBM-bound stage any more: 46 MB of compulsory traffic for 83 GFLOP at 8 images -- it is filed with the conv kernels and, by
         #  its arithmetic intensity, against the MFMA roof in the detector's per-layer table)
-        prof.layer(f'gauss_subnet {2 * hs}x{2 * ws} 64->32->32->16->16->1 (2x upsampled input)', flops, _nbytes(x, out), e0, e1)
+        t.file('gauss_subnet_kernel', 2.0 * n * 4 * hs * ws * (9 * 64 * 32 + 9 * 32 * 32 + 9 * 32 * 16 + 16 * 16 + 16), _nbytes(x, out),
+               f'gauss_subnet {2 * hs}x{2 * ws} 64->32->32->16->16->1 (2x upsampled input)')
     return out
 
 
 def global_max_into(x, out, out_off):
     """x NHWC bf16 -> out[:, out_off:out_off+C] (f32) = amax over H,W."""
     _need_cuda(x, out)
-    n, h, w, c = x.shape
     T.global_max_nhwc(x, out, out_off)
 
 
@@ -788,7 +775,6 @@ def l2_normalize(desc, eps=1e-8, want_bf16=False):
 # the product path: on, it stays bytes from the upload to the last crop (`device_bytes`); off, it becomes the float image once
 # (`device_image`) and the float kernels read that.
 IMAGE_FORMS = 'float (3,H,W) in [0,1] or uint8 (H,W,3)'
-U8_KERNELS = _os.environ.get('CVPCE_U8_KERNELS', '0') != '0'   # default: profiles/r12_u8_kernels.md
 _UINT8_TABLES = {}
 
 
@@ -875,20 +861,16 @@ def gln_transform_batch(images, batch, sizes, mean, std):
     has_bytes = any(i.dtype == torch.uint8 for i in images)
     if has_bytes and not U8_KERNELS:
         images, has_bytes = [uint8_to_float(i) if i.dtype == torch.uint8 else i for i in images], False
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     if has_bytes:
         T.gln_transform_batch_u8([i.contiguous() for i in images], uint8_table(batch.device), batch, [int(s[0]) for s in sizes],
                                  [int(s[1]) for s in sizes], [float(v) for v in mean], [float(v) for v in std])
     else:
         T.gln_transform_batch([i.contiguous() for i in images], batch, [int(s[0]) for s in sizes], [int(s[1]) for s in sizes],
                               [float(v) for v in mean], [float(v) for v in std])
-    if prof is not None:
-        e1.record()
-        prof.byte_records.append(('gln_transform_batch_kernel', _nbytes(batch, *images), e0, e1))
-        prof.layer('gln_transform_batch', 0.0, _nbytes(batch, *images), e0, e1)
+    if t is not None:
+        t.stop()
+        t.file('gln_transform_batch_kernel', None, _nbytes(batch, *images), 'gln_transform_batch', hbm=True)
 
 
 MAX_CROPS_PER_LAUNCH = 65528   # (the grid z limit, a multiple of 8: the crop kernel deals crops to XCDs in groups of 8)
@@ -922,9 +904,7 @@ def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, o
         if count is not None:
             assert start == 0 and p <= MAX_CROPS_PER_LAUNCH
             cnt = count
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        t = None if prof is None else _Launch(prof)
         if content_ext is not None:
             assert mode in (1, 2) and size % 2 == 0
             if from_bytes:
@@ -935,8 +915,8 @@ def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, o
             T.crop_resize_u8(img, table, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s)
         else:
             T.crop_resize(img, boxes[start:start + nb], cnt, out[start:start + nb], size, mode, m, s)
-        if prof is not None:
-            e1.record()
+        if t is not None:
+            t.stop()
             # algorithmic bytes: every source pixel of every (valid) box once (3 planes of f32) + the crop pixels written
             v = nb if cnt is None else int(cnt.reshape(-1)[0])
             b = boxes[start:start + v].to(torch.long)
@@ -946,7 +926,7 @@ def crop_resize(img, boxes, size=256, mode=0, mean=None, std=None, count=None, o
                 written = int((e[:, 0] * e[:, 1]).sum()) * out.shape[-1] * out.element_size()
             else:
                 written = v * out[0].numel() * out.element_size()
-            prof.byte_records.append(('crop_resize_kernel', area * 3 * (1 if from_bytes else 4) + written, e0, e1))
+            t.file('crop_resize_kernel', None, area * 3 * (1 if from_bytes else 4) + written, hbm=True)
     return out
 
 
@@ -993,16 +973,13 @@ def detect_postprocess(logits, regs, grids, strides, base_anchors, image_hw, rat
         conf = torch.zeros((n,), dtype=torch.int32, device=dev)
     for t in list(logits) + list(regs):
         assert t.dtype == torch.float32 and t.is_contiguous()
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _start()
     T.detect_postprocess(list(logits), list(regs), [int(g[0]) for g in grids], [int(g[1]) for g in grids], [int(s[0]) for s in strides],
                          [int(s[1]) for s in strides], base_anchors, image_hw, ratios, num_anchors, num_classes, topk, float(score_thresh),
                          float(nms_thresh), float(xform_clip), detections_per_img, float(conf_thresh), ws, boxes, scores, labels, count, conf)
-    if prof is not None:
-        e1.record()
-        prof.layer(f'detect_postprocess (top-k {topk}, NMS, dpi {detections_per_img}: 5 launches)', 0.0, _nbytes(*logits, *regs, boxes, scores, labels), e0, e1)
+    if t is not None:
+        t.stop()
+        t.file(None, None, _nbytes(*logits, *regs, boxes, scores, labels), f'detect_postprocess (top-k {topk}, NMS, dpi {detections_per_img}: 5 launches)')
     return boxes, scores, labels, count, conf
 
 
