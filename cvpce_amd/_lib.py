@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h and the
-8-bit input kernels of include/cvpce_amd_input.h).
+"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h, the
+8-bit input kernels of include/cvpce_amd_input.h and the planogram comparator kernels of include/cvpce_amd_planogram.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -101,7 +101,14 @@ INPUT_SIGNATURES = {
 }
 INPUT_SIGNATURES['cvpce_gln_transform_batch_u8_f16'] = INPUT_SIGNATURES['cvpce_gln_transform_batch_u8']
 
-for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES):
+# include/cvpce_amd_planogram.h: the comparator's graph stages.  A table of its own, like the header.
+PLANOGRAM_SIGNATURES = {
+    'cvpce_planogram_graphs': (c_int, [_fp, _ip, _fp] + [c_int] * 4 + [_ip, _fp, _ip, _vp]),
+    'cvpce_planogram_match_workspace_bytes': (c_size_t, [c_longlong]),
+    'cvpce_planogram_match': (c_int, [_ip] * 11 + [c_int] * 6 + [c_longlong, _vp, c_size_t, _ip, _ip, _vp]),
+}
+
+for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

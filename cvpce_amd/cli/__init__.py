@@ -63,15 +63,18 @@ class _DeviceMetricsCommand(click.Command):
     HELP = ('Match detections to the ground truth on the GPU instead of on the host (cvpce_amd.device_metrics). '
             'No metric process is started: --metric-workers is ignored with it.  [default: off]')
 
+    KEY = 'cvpce_amd.device_metrics'
+    LABEL = '--device-metrics / --no-device-metrics'
+
     def parse_args(self, ctx, args):
         rest = []
-        ctx.meta['cvpce_amd.device_metrics'] = False
+        ctx.meta[self.KEY] = False
         for i, a in enumerate(args):
             if a == '--':                        # (everything after it is positional)
                 rest += args[i:]
                 break
             if a in self.SWITCH:
-                ctx.meta['cvpce_amd.device_metrics'] = self.SWITCH[a]
+                ctx.meta[self.KEY] = self.SWITCH[a]
             else:
                 rest.append(a)
         return super().parse_args(ctx, rest)
@@ -79,11 +82,24 @@ class _DeviceMetricsCommand(click.Command):
     def format_options(self, ctx, formatter):
         super().format_options(ctx, formatter)
         with formatter.section('Options beyond the reference\'s'):
-            formatter.write_dl([('--device-metrics / --no-device-metrics', self.HELP)])
+            formatter.write_dl([(self.LABEL, self.HELP)])
 
 
 def _device_metrics_switch():
     return bool(click.get_current_context().meta.get('cvpce_amd.device_metrics', False))
+
+
+class _DeviceGraphsCommand(_DeviceMetricsCommand):
+    """The same arrangement for --device-graphs / --no-device-graphs (default: off) of the planogram command."""
+    SWITCH = {'--device-graphs': True, '--no-device-graphs': False}
+    HELP = ('Build the neighbour graphs and match them on the GPU instead of on the host (cvpce_amd.planograms_device; its order at '
+            'equal distances is the documented device rule).  [default: off]')
+    KEY = 'cvpce_amd.device_graphs'
+    LABEL = '--device-graphs / --no-device-graphs'
+
+
+def _device_graphs_switch():
+    return bool(click.get_current_context().meta.get(_DeviceGraphsCommand.KEY, False))
 
 
 @click.group()
@@ -263,7 +279,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command()
+@cli.command(cls=_DeviceGraphsCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -290,7 +306,7 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     proposal_generator.requires_grad_(False)
     generator = production.ProposalGenerator(proposal_generator)
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
-    evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator())
+    evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch()))
     total_a = total_e = 0.0
     # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
     # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,

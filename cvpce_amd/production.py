@@ -237,18 +237,59 @@ class PlanogramComparator:
     """production.py:76-116: graph matching -> RANSAC homography -> per-label IoU matching -> optional re-classification
     of the expected-but-undetected positions (a second trip through the crop / embed / match kernels)."""
 
-    def __init__(self, graph_threshold=0.5):
+    def __init__(self, graph_threshold=0.5, device_graphs=False):
+        """device_graphs (opt-in): the neighbour graphs and the common subgraph come from the kernels of `planograms_device` (its
+        documented rule at equal distances); the homography and everything after it stay the host's.  `host_routed`
+        counts the images that took the host path with the switch on (a graph of more than 1024 nodes)."""
         self.graph_threshold = graph_threshold
+        self.device_graphs = device_graphs
+        self.host_routed = 0
 
     def compare(self, expected, actual, image=None, classifier=None):
+        if self.device_graphs:
+            return self.compare_batch([expected], [actual], [image], classifier)[0]
+        return self._compare_host(expected, actual, image, classifier)
+
+    def _compare_host(self, expected, actual, image, classifier):
         from . import planograms
-        reproj_threshold = 10 if image is None else min(datautils.image_hw(image)) * 0.01
         if not len(actual['boxes']):
             return 0 if len(expected['boxes']) else 1
         ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'],
                                                                                   self.graph_threshold)
         ga = planograms.build_graph(actual['boxes'], actual['labels'], self.graph_threshold)
-        matching = planograms.large_common_subgraph(ge, ga)
+        return self._finish(planograms.large_common_subgraph(ge, ga), expected, actual, image, classifier)
+
+    def compare_batch(self, expecteds, actuals, images=None, classifier=None):
+        """[compare(e, a, img, classifier) for ...] with the graph stages of the whole batch in two launches (all graphs, all matchings)
+        and one copy back; the host tail (homography, per-label claim, re-classification) runs per image.  With `device_graphs` off it
+        is the plain loop."""
+        images = [None] * len(expecteds) if images is None else images
+        if not self.device_graphs:
+            return [self._compare_host(e, a, img, classifier) for e, a, img in zip(expecteds, actuals, images)]
+        from . import planograms_device as pd
+        results, todo = [None] * len(expecteds), []
+        for i, (e, a, img) in enumerate(zip(expecteds, actuals, images)):
+            if not len(a['boxes']):
+                results[i] = 0 if len(e['boxes']) else 1
+            elif not 1 <= len(e['boxes']) <= pd.MAX_NODES or len(a['boxes']) > pd.MAX_NODES:
+                self.host_routed += 1
+                results[i] = self._compare_host(e, a, img, classifier)
+            else:
+                todo.append(i)
+        if todo:
+            have = {i: pd.cached(expecteds[i], self.graph_threshold) for i in todo}
+            build = [expecteds[i] for i in todo if have[i] is None] + [actuals[i] for i in todo]
+            built = pd.build_graphs([(g['boxes'], g['labels']) for g in build], self.graph_threshold)
+            fresh = iter(built[:len(build) - len(todo)])
+            ge = [have[i] if have[i] is not None else next(fresh) for i in todo]
+            matchings = pd.common_subgraphs(ge, built[len(build) - len(todo):])
+            for i, matching in zip(todo, matchings):
+                results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
+        return results
+
+    def _finish(self, matching, expected, actual, image, classifier):
+        from . import planograms
+        reproj_threshold = 10 if image is None else min(datautils.image_hw(image)) * 0.01
         if not len(matching):
             return 0
         found, missing_indices, missing_positions, missing_labels = planograms.finalize_via_ransac(
@@ -333,8 +374,15 @@ class PlanogramEvaluator:
         per image as in production.py:123-129."""
         images = [self._float_image(img) for img in images]
         dets = self.detect_and_classify_batch(images)
-        return [self.planogram_comparator.compare(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
-                for img, plano, (b, labels) in zip(images, planograms, dets)]
+        return self._compare_all(images, planograms, dets)
+
+    def _compare_all(self, images, planograms, dets):
+        """The comparator over a window: per image, or -- a comparator with `device_graphs` on -- its `compare_batch`."""
+        cmp = self.planogram_comparator
+        actuals = [{'boxes': b, 'labels': labels} for b, labels in dets]
+        if getattr(cmp, 'device_graphs', False) and hasattr(cmp, 'compare_batch'):
+            return cmp.compare_batch(list(planograms), actuals, list(images), self.classifier)
+        return [cmp.compare(plano, actual, img, self.classifier) for img, plano, actual in zip(images, planograms, actuals)]
 
 
     def evaluate_iter(self, pairs, lookahead=4):
@@ -350,8 +398,11 @@ class PlanogramEvaluator:
 
         def flush():
             dets = self.detect_and_classify_batch([img for img, _ in window])
-            for (img, plano), (b, labels) in zip(window, dets):
-                yield self.planogram_comparator.compare(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
+            if getattr(self.planogram_comparator, 'device_graphs', False):
+                yield from self._compare_all([img for img, _ in window], [plano for _, plano in window], dets)
+            else:
+                for (img, plano), (b, labels) in zip(window, dets):
+                    yield self.planogram_comparator.compare(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
             window.clear()
 
         for image, planogram in pairs:

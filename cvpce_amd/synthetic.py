@@ -202,3 +202,31 @@ def dense_detection_scene(seed, n_pred=1000, n_tgt=150, size=2048.0):
     noise = torch.cat([nxy, nxy + 30 + torch.rand(n_noise, 2, generator=g) * 150], dim=1)
     predictions = torch.cat([copies, dups, noise])[torch.randperm(n_pred, generator=g)]
     return targets, predictions, torch.rand(n_pred, generator=g)
+
+
+PLANOGRAM_LABELS = tuple(f'product_{i:02d}' for i in range(12))
+
+
+def planogram_grid(rows, cols, seed, cell=(64, 96), gap=(8, 24), origin=(20, 30), labels=PLANOGRAM_LABELS):
+    """A gridded planogram, boxes only: rows x cols equal boxes at integer positions, row by row -> (boxes (n,4) float32 xyxy, labels).
+    Every row of its distance matrix is full of exact ties -- the case real planograms are."""
+    g = torch.Generator().manual_seed(seed)
+    (w, h), (gx, gy), (x0, y0) = cell, gap, origin
+    boxes = [[x0 + c * (w + gx), y0 + r * (h + gy), x0 + c * (w + gx) + w, y0 + r * (h + gy) + h] for r in range(rows) for c in range(cols)]
+    pick = torch.randint(0, len(labels), (rows * cols,), generator=g).tolist()
+    return torch.tensor(boxes, dtype=torch.float32), [labels[i] for i in pick]
+
+
+def perturbed_detections(boxes, labels, seed, scale=1.7, shift=(30.0, 12.0), jitter=3.0, drop=0.05, mislabel=0.05, names=PLANOGRAM_LABELS):
+    """What a detector + classifier might return for a planogram photographed at another scale: the boxes scaled and shifted, every
+    coordinate jittered by up to `jitter` px, a fraction dropped and a fraction given another label -> (boxes, labels)."""
+    g = torch.Generator().manual_seed(seed)
+    n = len(labels)
+    out = boxes * scale + torch.tensor(list(shift) * 2) + (torch.rand(n, 4, generator=g) * 2 - 1) * jitter
+    keep = torch.rand(n, generator=g) >= drop
+    if not bool(keep.any()):
+        keep[0] = True
+    wrong = torch.rand(n, generator=g) < mislabel
+    other = torch.randint(1, len(names), (n,), generator=g).tolist()
+    lab = [names[(names.index(l) + o) % len(names)] if w and l in names else l for l, w, o in zip(labels, wrong.tolist(), other)]
+    return out[keep].contiguous(), [l for l, k in zip(lab, keep.tolist()) if k]
