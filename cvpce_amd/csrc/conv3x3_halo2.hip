@@ -15,8 +15,8 @@
 //     108 fragment reads per chunk instead of 288 -- the reads were 21 % of conv4_2 (profiles/r01d_ablation_halo2.md).
 // Per chunk and wave: 6 steps x (18 ds_read_b128 + 96 MFMA 16x16x32 + 6 weight loads).
 // Weight layout: the fragment-major "halo weight layout" of include/cvpce_amd.h.  Fused bias / ReLU / MaxPool2d(2,2).
-#include "common.h"
-#include <stdlib.h>
+// The host plan of a launch and the device helpers shared with conv3x3_halo3.hip: halo_common.h; the work-list entry: worklist.h.
+#include "halo_common.h"
 #include "../../include/cvpce_amd.h"
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -24,18 +24,11 @@ typedef __attribute__((address_space(3))) char lds_char;
 
 // compile-time timing experiments (never set in the shipped library; tools/ablate.sh): 1 no s_setprio around the MFMA
 // groups, 2 XCD-aware tile order, 4 no patch DMA in the loop, 8 no weight loads in the loop, 16 no output stores (runtime-false predicate),
-// 32 no fragment reads in the loop, 64 no hand-off barrier (races: timing only), 256 (dispatch) 32-aligned maps to the wide kernel,
-// 512 in-kernel clock stamps (below; results unchanged)
+// 32 no fragment reads in the loop, 64 no hand-off barrier (races: timing only), 512 in-kernel clock stamps (below; results unchanged)
 #ifndef CVPCE_DBG
 #define CVPCE_DBG 0
 #endif
 
-#ifndef G2_LIST_DEEP_WEIGHTS
-#define G2_LIST_DEEP_WEIGHTS 0     // 1: work-list launches prefetch the weight fragments TWO steps ahead (3 slots, 246-256 VGPRs, no spill).
-                                   // Measured with the row cut on, same call, three alternations: 27.92 / 27.92 / 27.97 ms (one step ahead)
-                                   // vs 27.95 / 27.98 / 28.12 ms per 1 600 crops -- the cut tiles are bound by the weight stream's BYTES
-                                   // (conv4_2 without any weight load: 3.99 -> 2.85 ms with the cut; with: 4.81 -> 4.33), not by its latency
-#endif
 #define G2_T 16
 #define G2_P 18
 #define G2_NPIX 324
@@ -57,7 +50,6 @@ typedef __attribute__((address_space(3))) char lds_char;
 // tap's fragment read is conflict-free at any alignment.
 __device__ __forceinline__ int g2_swz0(int u) { return ((u & 3) << 1) | ((u >> 2) & 1); }
 __device__ __forceinline__ int g2_swz(int py, int px) { return g2_swz0(px >> 1) ^ (py & 1); }
-__device__ __forceinline__ int g2_col(int l16) { return l16 < 4 ? 2 * l16 : (l16 >= 12 ? 2 * (l16 - 8) : 2 * (l16 - 4) + 1); }
 
 struct Halo2Args {
     const bf16_t* in;    // [N][H][W][Cin]
@@ -74,8 +66,8 @@ struct Halo2Args {
     int cgroups;         // Cout_pad / 32: 32-cout groups per channel chunk of the fragment-major weights
     int tiles_x, tiles_y, ptiles, ctiles, ntiles;
     unsigned in_bytes, wgt_bytes;
-    // LIST launches: the tiles to compute, ((ey_in << 16 | ex_in) << 32) | (n << 16) | (ty << 8) | tx, crop-major; *list_count
-    // entries (device-resident); input pixels with y >= ey_in or x >= ex_in are read from image N - 1 (the constant crop)
+    // LIST launches: the tiles to compute (entries of worklist.h), crop-major; *list_count entries (device-resident); input pixels
+    // with y >= ey or x >= ex of their entry are read from image N - 1 (the constant crop)
     const unsigned long long* list;
     const int* list_count;
 };
@@ -116,21 +108,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
 
     const int nchunks = a.Cin >> 6;
     const int lbid = (CVPCE_DBG & 2) ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-    // Which tiles this workgroup computes.  Plain launches: tile lbid, lbid + grid, ... (all tiles cost the same).  LIST launches:
-    // a CONTIGUOUS block of the list per workgroup -- listed tiles differ in cost when they are cut at `rows`, and the list is
-    // crop-major with a fixed number of tiles per crop, so a stride that is a multiple of it would hand one workgroup nothing but
-    // bottom-row (cut) tiles and another nothing but full ones.  The cout tile stays fixed per workgroup (lbid % ctiles: one
-    // weight set per workgroup, and with an even grid per XCD), its group's workgroups split the list entries among them.
+    // Which tiles this workgroup computes (halo_common.h): every grid-th tile, or a contiguous block of the list.  The block is
+    // halo_list_span's, spelled out: through the helper the compiler no longer sees that the clamp of the entry staging below is
+    // redundant without STRIP (a v_min_i32 per staged entry, four more VGPRs)
     int my_tiles, l_first = 0, l_entries = 0;
     if constexpr (LIST) {
         l_entries = __builtin_amdgcn_readfirstlane(*a.list_count);             // <= a.ptiles (checked by the list builder)
         const int units = STRIP ? (l_entries + 2) / 3 : l_entries;             // STRIP: three list entries make one tile
-        const int groups = (int)gridDim.x / a.ctiles;                          // workgroups per cout tile (the host launches grid % ctiles == 0)
+        const int groups = (int)gridDim.x / a.ctiles;
         const int per = (units + groups - 1) / groups;
         l_first = (lbid / a.ctiles) * per;
         my_tiles = units - l_first < per ? units - l_first : per;
     } else {
-        my_tiles = (a.ntiles - lbid + (int)gridDim.x - 1) / (int)gridDim.x;
+        my_tiles = halo_plain_tiles(a.ntiles, lbid, (int)gridDim.x);
     }
     if (my_tiles <= 0) return;
     const int total_chunks = my_tiles * nchunks;          // < 2^30: checked on the host
@@ -177,7 +167,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         __syncthreads();
     }
 
-    // tile seq -> (image, tile row, tile column, cout tile); cout tile fastest.  ext (LIST): the crop's extents on the INPUT tensor
+    // tile seq -> (image, tile row, tile column, cout tile); cout tile fastest.  ext (LIST): the entry's high word (worklist.h)
     auto tile_of = [&](int seq, int* n, int* ty, int* tx, int& ct, int* ext) {
         if constexpr (LIST) {
             ct = lbid % a.ctiles;
@@ -185,11 +175,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
             for (int s = 0; s < NS; ++s) {
                 const int k = seq * NS + s, g = l_first * NS + k;
                 const unsigned long long e = k < G2_MAX_SEQ ? llist[k] : a.list[g < l_entries ? g : l_entries - 1];
-                const int lo = __builtin_amdgcn_readfirstlane((int)(unsigned)e);
-                ext[s] = __builtin_amdgcn_readfirstlane((int)(unsigned)(e >> 32));
-                n[s] = lo >> 16;
-                ty[s] = (lo >> 8) & 0xFF;
-                tx[s] = lo & 0xFF;
+                const int lo = __builtin_amdgcn_readfirstlane((int)wl_lo(e));
+                ext[s] = __builtin_amdgcn_readfirstlane((int)wl_hi(e));
+                n[s] = wl_image_signed(lo);
+                ty[s] = wl_ty((unsigned)lo);
+                tx[s] = wl_tx((unsigned)lo);
             }
             return;
         }
@@ -216,8 +206,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     auto issue_patch = [&](const int* n, const int* ty, const int* tx, int c, int buf, const int* ext) {
         // lane id recomputed here (2 VALU ops, once per patch) instead of living in a VGPR across the K loop; the volatile
         // asm also keeps the per-piece constants below from being hoisted out of the chunk loop (18+ VGPRs)
-        int ln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int ln = halo_lane_id();
 #pragma unroll
         for (int i = 0; i < NPP; ++i) {
             if (i < npp) {
@@ -235,7 +224,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
                     stx = st == 0 ? tx[0] : (st == 1 ? tx[1] : tx[2]);
                     sext = st == 0 ? ext[0] : (st == 1 ? ext[1] : ext[2]);
                 }
-                const int ey = (sext >> 12) & 0xFFF, ex = sext & 0xFFF;
+                const int ey = wl_ey((unsigned)sext), ex = wl_ex((unsigned)sext);
                 const int y = sty * G2_T - 1 + ry, x = stx * G2_T - 1 + px;
                 const bool ok = pp < G2_NPIX && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
                 int nn = sn;
@@ -275,11 +264,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     // scalar byte offset of the 36 blocks of (cout tile ct, channel chunk c) of this wave's 32 couts
     auto wbase = [&](int ct, int c) { return __builtin_amdgcn_readfirstlane((int)((unsigned)(c * a.cgroups + ct * (TC / 32) + wc) * 36864u)); };
 
-    // ---- pixel fragments: lane (l16, lq) reads pixel (row p, column g2_col(l16) + kw), K-quarter lq of K-half hf:
+    // ---- pixel fragments: lane (l16, lq) reads pixel (row p, column halo_col(l16) + kw), K-quarter lq of K-half hf:
     //      address = ((c3[kw] ^ (hf << 6) ^ ((p & 1) << 4)) + buffer) + (p * 18 + kw) * 128 ----
     unsigned c3[3];
     {
-        const int col = g2_col(l16);
+        const int col = halo_col(l16);
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) c3[kw] = (unsigned)(col * 128) ^ (unsigned)((lq ^ g2_swz0(((col + kw) >> 1) & 7)) << 4);
     }
@@ -303,10 +292,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
             for (int j = 0; j < NB; ++j) acc[i][j] = b0[i];
     }
 
-    // weight slots: the next step's fragments are fetched while this one computes (2 slots); G2_LIST_DEEP_WEIGHTS = 1 makes it two
-    // steps ahead for work-list launches (3 slots) -- built, measured, not faster (see the macro)
-    constexpr int NA = (LIST && G2_LIST_DEEP_WEIGHTS) ? 3 : 2;
-    bf16x8 af[NA][3][2];      // [step % NA][kh][16-cout block]
+    bf16x8 af[2][3][2];       // [step parity][kh][16-cout block]: the next step's weight fragments are fetched while this one computes
     bf16x8 bfr[4];            // patch-row ring
     unsigned e0, e1;          // fragment base addresses of the step being fetched (even / odd patch rows)
 
@@ -316,16 +302,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         _Pragma("unroll") for (int kh_ = 0; kh_ < 3; ++kh_)                                                    \
             _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_) {                                              \
                 const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(srd_w, voff1, (SBASE) + (((T) * 3 + kh_) * 2 + mt_) * 1024, 0); \
-                af[(T) % NA][kh_][mt_] = __builtin_bit_cast(bf16x8, v_);                                       \
+                af[(T) & 1][kh_][mt_] = __builtin_bit_cast(bf16x8, v_);                                       \
             }                                                                                                  \
     }
-    // at the start of step T: the weights of the step NA - 1 ahead (steps 6, 7 = steps 0, 1 of the next chunk)
+    // at the start of step T: the weights of the next step (step 6 = step 0 of the next chunk)
 #define G2_PREFETCH_A(T)                                                                                       \
-    if constexpr (NA == 2) {                                                                                   \
-        if constexpr ((T) < 5) { G2_LOAD_A((T) + 1, sb_cur) } else { G2_LOAD_A(0, sb_next) }                   \
-    } else {                                                                                                   \
-        if constexpr ((T) < 4) { G2_LOAD_A((T) + 2, sb_cur) } else { G2_LOAD_A((T) - 4, sb_next) }             \
-    }
+    if constexpr ((T) < 5) { G2_LOAD_A((T) + 1, sb_cur) } else { G2_LOAD_A(0, sb_next) }
 #define G2_SET_E(T, BUFB)                                                                                      \
     {                                                                                                          \
         const unsigned x_ = c3[(T) >> 1] ^ (unsigned)(((T) & 1) << 6);                                         \
@@ -347,7 +329,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         constexpr int r_ = STRIP ? 4 * ((P) / 6) + j_ : j_;                                                    \
         if constexpr (j_ >= 0 && j_ < (STRIP ? 4 : NB)) {                                                      \
             _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                \
-                acc[mt_][r_] = E::mfma16(af[(T) % NA][KH][mt_], bfr[((P) + 2 * (T)) & 3], acc[mt_][r_]);       \
+                acc[mt_][r_] = E::mfma16(af[(T) & 1][KH][mt_], bfr[((P) + 2 * (T)) & 3], acc[mt_][r_]);       \
         }                                                                                                      \
     }
     // the MFMAs of patch row P: output rows P (kh = 0), P-1 (kh = 1), P-2 (kh = 2) where they exist.  Waits until the
@@ -402,7 +384,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     // ---- prologue ----
     int seq = 0, cchunk = 0, t_n[NS], t_ty[NS], t_tx[NS], t_ct, t_ext_[NS];
     tile_of(0, t_n, t_ty, t_tx, t_ct, t_ext_);
-    int rows_ = (LIST && !STRIP) ? ((t_ext_[0] >> 24) & 0xFF) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
+    int rows_ = (LIST && !STRIP) ? wl_rows((unsigned)t_ext_[0]) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
     int n_ct = t_ct;                                    // cout tile of the NEXT chunk's tile
     auto next_ct = [&]() {
         if (cchunk + 1 < nchunks) return t_ct;
@@ -423,7 +405,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
                 af[0][kh_][mt_] = __builtin_bit_cast(bf16x8, v_);
                 if (dbg8_) af[1][kh_][mt_] = af[0][kh_][mt_];
             }
-        if constexpr (NA == 3) { G2_LOAD_A(1, sb_cur) }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -443,7 +424,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         G2_STEP(0) G2_STEP(1) G2_STEP(2) G2_STEP(3) G2_STEP(4)
         // ---- last step of the chunk, with the chunk hand-off before its rows 16, 17 prefetch from the NEXT buffer ----
         {
-            G2_PREFETCH_A(5)             // step 0 (NA = 3: step 1) of the next chunk; past the last chunk a harmless reload
+            G2_PREFETCH_A(5)             // step 0 of the next chunk; past the last chunk a harmless reload
             __builtin_amdgcn_sched_barrier(0);
             // After the last chunk the barrier, the reads and the weight loads still run -- on valid, unused data -- so
             // that the loop body has one shape and the accumulators stay in place.
@@ -467,7 +448,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
             auto e_live = [&](int nt) { return STRIP ? nt < 12 : (!LIST || nt < rows_t); };
             f32x4 nbias[2];                      // bias of the NEXT tile's couts: lands while this tile is stored
             load_bias(n_ct, nbias);
-            const int col = g2_col(lp);
+            const int col = halo_col(lp);
             const int co = ct * TC + wc * 32 + 8 * lq;            // this lane's 8 consecutive couts
             if constexpr (GMAX) {
                 // MAC descriptor fused (classification.py:46-49 `x.amax(dim=(-2, -1))` of the post-ReLU map): maximum over
@@ -512,9 +493,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
             if (GMAX && a.out == nullptr) {
                 // the map itself has no consumer (conv5_3: only its MAC descriptor is used): nothing to store
             } else if (POOL) {
-                // rows 2i, 2i+1 are accumulator rows of the same lane; columns 2k, 2k+1 are lanes A[k], B[k] with
-                // A = {0-3,12-15}, B = {4-11}: lane A[k] takes its right neighbour by a row rotate (+4 for lanes 0-3,
-                // -4 for lanes 12-15; bank masks 1 and 8)
+                // rows 2i, 2i+1 are accumulator rows of the same lane; the column pairs meet in lanes {0-3,12-15} (halo_pool2x2)
 #pragma unroll
                 for (int i = 0; i < NB / 2; ++i) {
                     const int ox = e_tx(2 * i) * (G2_T / 2) + (col >> 1);
@@ -525,19 +504,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (a.relu) {
-                                const unsigned v = max(__float_as_uint(relu_bits(acc[mt][2 * i][j])), __float_as_uint(relu_bits(acc[mt][2 * i + 1][j])));
-                                unsigned m = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x1, false));   // row_ror:12 -> lane l reads l+4
-                                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0x8, false));            // row_ror:4  -> lane l reads l-4
-                                r[4 * mt + j] = __uint_as_float(m);
-                            } else {
-                                const float v = fmaxf(acc[mt][2 * i][j], acc[mt][2 * i + 1][j]);
-                                const float up = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x12C, 0xF, 0x1, false));
-                                const float dn = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x124, 0xF, 0x8, false));
-                                r[4 * mt + j] = fmaxf(v, fmaxf(up, dn));
-                            }
-                        }
+                        for (int j = 0; j < 4; ++j) r[4 * mt + j] = halo_pool2x2(acc[mt][2 * i][j], acc[mt][2 * i + 1][j], a.relu);
                     if (lane_ok && oy < (a.H >> 1) && co < a.Cout && e_live(2 * i) && (!(CVPCE_DBG & 16) || a.relu == 12345)) {
                         const uint2 l2 = __builtin_bit_cast(uint2, E::pack4(f32x4{r[0], r[1], r[2], r[3]}));
                         const uint2 h2 = __builtin_bit_cast(uint2, E::pack4(f32x4{r[4], r[5], r[6], r[7]}));
@@ -573,7 +540,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
             ++seq;
             if (seq < my_tiles) {
                 tile_of(seq, t_n, t_ty, t_tx, t_ct, t_ext_);
-                if constexpr (LIST && !STRIP) rows_ = (t_ext_[0] >> 24) & 0xFF;
+                if constexpr (LIST && !STRIP) rows_ = wl_rows((unsigned)t_ext_[0]);
             }
         } else {
             ++cchunk;
@@ -607,25 +574,33 @@ static int launch_halo2(Halo2Args a, hipStream_t stream) {
     a.ntiles = a.ptiles * a.ctiles;
     if constexpr (!POOL && !GMAX && !LIST) {
         // few pixel tiles (the detector's small maps): 128-cout tiles on twice as many workgroups
-        static const bool narrow_ok = !(getenv("CVPCE_HALO_NARROW") && getenv("CVPCE_HALO_NARROW")[0] == '0');   // dev A/B switch
-        if (narrow_ok && !a.mask && a.Cout % 128 == 0 && 2 * a.ntiles <= g_cvpce_persistent_wgs) {
+        if (!a.mask && a.Cout % 128 == 0 && 2 * a.ntiles <= g_cvpce_persistent_wgs) {
             a.ctiles = a.Cout / 128;
             a.ntiles = a.ptiles * a.ctiles;
-            if (!cvpce_smem_attr_done<conv3x3_halo2_kernel<E, false, false, false, false, 4>>((const void*)conv3x3_halo2_kernel<E, false, false, false, false, 4>, 3 * G2_A_BYTES))
-                return CVPCE_ERR_LAUNCH;
-            hipLaunchKernelGGL((conv3x3_halo2_kernel<E, false, false, false, false, 4>), dim3(a.ntiles), dim3(256), 3 * G2_A_BYTES, stream, a);
-            return cvpce_check_launch();
+            return halo_launch<conv3x3_halo2_kernel<E, false, false, false, false, 4>>(a, a.ntiles, 256, 3 * G2_A_BYTES, stream);
         }
     }
     const int smem = a.mask ? G2_SMEM_MASKED : (LIST ? G2_SMEM_LIST : 3 * G2_A_BYTES);
-    if (!cvpce_smem_attr_done<conv3x3_halo2_kernel<E, POOL, GMAX, LIST, STRIP>>((const void*)conv3x3_halo2_kernel<E, POOL, GMAX, LIST, STRIP>, G2_SMEM_MASKED))
-        return CVPCE_ERR_LAUNCH;
-    int grid = a.ntiles < g_cvpce_persistent_wgs ? a.ntiles : g_cvpce_persistent_wgs;
-    if (LIST) grid = grid < a.ctiles ? a.ctiles : grid / a.ctiles * a.ctiles;     // (work-list launches: the same number of workgroups per cout tile)
+    const int grid = halo_grid(a.ntiles, a.ctiles, LIST);
     if (a.mask && (a.ntiles + grid - 1) / grid > G2_MAX_SEQ) return CVPCE_ERR_ARG;   // the workgroup's tile list lives in LDS
-    hipLaunchKernelGGL((conv3x3_halo2_kernel<E, POOL, GMAX, LIST, STRIP>), dim3(grid), dim3(512), smem, stream, a);
-    return cvpce_check_launch();
+    return halo_launch<conv3x3_halo2_kernel<E, POOL, GMAX, LIST, STRIP>>(a, grid, 512, smem, stream, G2_SMEM_MASKED);
 }
+
+// the Halo2Args of a launch without mask, tile map or list (the callers add theirs)
+static Halo2Args halo2_args(const void* in, const void* wgt, const float* bias, void* out, float* gmax, int gmax_stride, int gmax_off,
+                            const HaloShape& sh, int relu) {
+    Halo2Args a;
+    halo_fill(a, in, wgt, bias, out, sh, relu, G2_T, nullptr, nullptr);
+    a.mask = nullptr; a.tile_map = nullptr; a.tiles_per_image = a.tiles_x * a.tiles_y;
+    a.gmax = gmax; a.gmax_stride = gmax_stride; a.gmax_off = gmax_off;
+    return a;
+}
+// a MAC descriptor needs the ReLU'd map of a 256-cout-tile launch and room for its Cout values in a descriptor row
+static bool halo2_gmax_ok(int relu, int Cout, int gmax_stride, int gmax_off) {
+    return relu && Cout > 128 && gmax_off >= 0 && gmax_off + Cout <= gmax_stride;
+}
+
+static constexpr HaloRules G2_RULES = {/* tile_w */ G2_T, /* cout_tile */ 256, /* max_chunks */ 1LL << 30, /* cout_mult8 */ true, /* cout_max */ 0};
 
 template <typename E>
 static int halo2_dispatch(const void* in, const void* wgt, const float* bias, const unsigned char* mask, const int* tile_map,
@@ -633,35 +608,20 @@ static int halo2_dispatch(const void* in, const void* wgt, const float* bias, co
                           int gmax_stride, int gmax_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
                           int fuse_pool2, void* stream) {
     if (N <= 0) return CVPCE_OK;
-    if (!in || !wgt || (!out && !gmax)) return CVPCE_ERR_ARG;
-    if (gmax && (!relu || mask || Cout <= 128 || gmax_off < 0 || gmax_off + Cout > gmax_stride)) return CVPCE_ERR_ARG;
+    if (!out && !gmax) return CVPCE_ERR_ARG;
+    if (gmax && (mask || !halo2_gmax_ok(relu, Cout, gmax_stride, gmax_off))) return CVPCE_ERR_ARG;
     if (tile_map && (!mask || n_map <= 0)) return CVPCE_ERR_ARG;
-    if (H <= 0 || W <= 0 || Cin % 64 != 0 || Cin <= 0 || Cout % 8 != 0 || Cout <= 0) return CVPCE_ERR_ARG;
-    if (fuse_pool2 && ((H & 1) || (W & 1))) return CVPCE_ERR_ARG;
-    if (K_pad != 9 * Cin || Cout_pad % 256 != 0 || Cout_pad < Cout) return CVPCE_ERR_ARG;
-    if ((long long)N * H * W * Cin * 2 >= (1LL << 32) || (long long)N * H * W * Cout >= (1LL << 31)) return CVPCE_ERR_ARG;
-    if ((long long)Cout_pad * K_pad * 2 >= (1LL << 31)) return CVPCE_ERR_ARG;
     if (mask && fuse_pool2) return CVPCE_ERR_ARG;
-    // few output channels: the wide-tile kernel keeps every wave's 32-cout x 256-pixel tile (conv3x3_halo3.hip)
-    // (CVPCE_DBG & 256, dev A/B only: also route every map that 32-pixel-wide tiles cover exactly to the wide-tile kernel --
-    //  measured and not adopted, profiles/r02_ablation_halo2.md)
-    if ((Cout <= 128 || ((CVPCE_DBG & 256) && !gmax && W % 32 == 0 && H % 16 == 0)) && !mask)
+    // few output channels: the wide-tile kernel keeps every wave's 32-cout x 256-pixel tile (conv3x3_halo3.hip; it checks the rest)
+    if (Cout <= 128 && !mask)
         return (E::kF16 ? cvpce_conv3x3_halo_wide_f16 : cvpce_conv3x3_halo_wide)(in, wgt, bias, out, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, stream);
-    Halo2Args a;
-    a.in = (const bf16_t*)in; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.mask = mask; a.out = (bf16_t*)out;
-    a.gmax = gmax; a.gmax_stride = gmax_stride; a.gmax_off = gmax_off;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K_pad = K_pad; a.relu = relu; a.cgroups = Cout_pad / 32;
-    a.tiles_x = (W + G2_T - 1) / G2_T; a.tiles_y = (H + G2_T - 1) / G2_T;
-    a.tile_map = tile_map; a.tiles_per_image = tile_map ? n_map : a.tiles_x * a.tiles_y;
-    a.ptiles = N * a.tiles_per_image;
-    a.in_bytes = (unsigned)((long long)N * H * W * Cin * 2);
-    a.wgt_bytes = (unsigned)((long long)Cout_pad * K_pad * 2);
-    a.ctiles = a.ntiles = 0;
-    a.list = nullptr; a.list_count = nullptr;
-    if ((long long)a.ptiles * ((Cout + 255) / 256) * (Cin / 64) >= (1LL << 30)) return CVPCE_ERR_ARG;
+    const HaloShape sh{N, H, W, Cin, Cout, K_pad, Cout_pad};
+    if (!halo_shape_ok(in, wgt, sh, fuse_pool2, tile_map ? n_map : 0, false, G2_RULES)) return CVPCE_ERR_ARG;
+    Halo2Args a = halo2_args(in, wgt, bias, out, gmax, gmax_stride, gmax_off, sh, relu);
     hipStream_t s = (hipStream_t)stream;
-    if (gmax) return fuse_pool2 ? launch_halo2<E, true, true>(a, s) : launch_halo2<E, false, true>(a, s);
     if (mask) {
+        a.mask = mask;
+        if (tile_map) { a.tile_map = tile_map; a.tiles_per_image = n_map; a.ptiles = N * n_map; }
         // a masked launch keeps every workgroup's tile list in LDS (G2_MAX_SEQ entries): a batch too large for that is split
         // into launches over whole images (the tile sequence restarts with every image, so the results do not change)
         const long long per_image = (long long)a.tiles_per_image * ((Cout + 255) / 256);
@@ -680,7 +640,7 @@ static int halo2_dispatch(const void* in, const void* wgt, const float* bias, co
         }
         return CVPCE_OK;
     }
-    return fuse_pool2 ? launch_halo2<E, true, false>(a, s) : launch_halo2<E, false, false>(a, s);
+    return halo_pick([&](auto pool, auto mac) { return launch_halo2<E, decltype(pool)::value, decltype(mac)::value>(a, s); }, fuse_pool2 != 0, gmax != nullptr);
 }
 
 extern "C" int cvpce_conv3x3_halo(const void* in, const void* wgt, const float* bias, void* out, int N, int H, int W,
@@ -724,37 +684,19 @@ static int halo_list_launch(const void* in, const void* wgt, const float* bias, 
                             int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
                             int fuse_pool2, const unsigned long long* list, const int* count_dev, bool strips, void* stream) {
     if (N <= 0) return CVPCE_OK;
-    if (!in || !wgt || (!out && !mac) || !list || !count_dev) return CVPCE_ERR_ARG;
-    if (mac && (!relu || Cout <= 128 || mac_off < 0 || mac_off + Cout > mac_stride)) return CVPCE_ERR_ARG;
-    if (H <= 0 || W <= 0 || Cin % 64 != 0 || Cin <= 0 || Cout % 8 != 0 || Cout <= 0) return CVPCE_ERR_ARG;
-    if (fuse_pool2 && ((H & 1) || (W & 1))) return CVPCE_ERR_ARG;
-    if (K_pad != 9 * Cin || Cout_pad % 256 != 0 || Cout_pad < Cout) return CVPCE_ERR_ARG;
-    if ((long long)N * H * W * Cin * 2 >= (1LL << 32) || (long long)N * H * W * Cout >= (1LL << 31)) return CVPCE_ERR_ARG;
-    if ((long long)Cout_pad * K_pad * 2 >= (1LL << 31) || N > 65535) return CVPCE_ERR_ARG;
+    if ((!out && !mac) || !list || !count_dev) return CVPCE_ERR_ARG;
+    if (mac && !halo2_gmax_ok(relu, Cout, mac_stride, mac_off)) return CVPCE_ERR_ARG;
     if (Cout <= 128) {
         if (strips) return CVPCE_ERR_ARG;               // (the wide-tile kernel has no strip mode)
         return cvpce_conv3x3_halo_wide_list(in, wgt, bias, out, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, list, count_dev, stream);
     }
-    Halo2Args a;
-    a.in = (const bf16_t*)in; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.mask = nullptr; a.out = (bf16_t*)out;
-    a.gmax = mac; a.gmax_stride = mac_stride; a.gmax_off = mac_off;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K_pad = K_pad; a.relu = relu; a.cgroups = Cout_pad / 32;
-    a.tiles_x = (W + G2_T - 1) / G2_T; a.tiles_y = (H + G2_T - 1) / G2_T;
-    if (a.tiles_x > 255 || a.tiles_y > 255 || H > 65535 || W > 65535) return CVPCE_ERR_ARG;
-    a.tile_map = nullptr; a.tiles_per_image = a.tiles_x * a.tiles_y;
-    a.ptiles = N * a.tiles_per_image;
-    a.in_bytes = (unsigned)((long long)N * H * W * Cin * 2);
-    a.wgt_bytes = (unsigned)((long long)Cout_pad * K_pad * 2);
-    a.ctiles = a.ntiles = 0;
+    const HaloShape sh{N, H, W, Cin, Cout, K_pad, Cout_pad};
+    if (!halo_shape_ok(in, wgt, sh, fuse_pool2, 0, true, G2_RULES)) return CVPCE_ERR_ARG;
+    Halo2Args a = halo2_args(in, wgt, bias, out, mac, mac_stride, mac_off, sh, relu);
     a.list = list; a.list_count = count_dev;
-    if ((long long)a.ptiles * ((Cout + 255) / 256) * (Cin / 64) >= (1LL << 30)) return CVPCE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (strips) {
-        if (mac) return fuse_pool2 ? launch_halo2<ElemBF16, true, true, true, true>(a, s) : launch_halo2<ElemBF16, false, true, true, true>(a, s);
-        return fuse_pool2 ? launch_halo2<ElemBF16, true, false, true, true>(a, s) : launch_halo2<ElemBF16, false, false, true, true>(a, s);
-    }
-    if (mac) return fuse_pool2 ? launch_halo2<ElemBF16, true, true, true>(a, s) : launch_halo2<ElemBF16, false, true, true>(a, s);
-    return fuse_pool2 ? launch_halo2<ElemBF16, true, false, true>(a, s) : launch_halo2<ElemBF16, false, false, true>(a, s);
+    return halo_pick([&](auto pool, auto gm, auto strip) { return launch_halo2<ElemBF16, decltype(pool)::value, decltype(gm)::value, true, decltype(strip)::value>(a, s); },
+                     fuse_pool2 != 0, mac != nullptr, strips);
 }
 
 extern "C" int cvpce_conv3x3_halo_list(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,

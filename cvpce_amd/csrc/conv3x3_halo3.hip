@@ -14,7 +14,8 @@
 // conflict-free for 64-byte pixels under the chunk ^ ((px >> 2) & 3) swizzle; the fused MaxPool2d(2,2) is a plain max
 // of two accumulator rows plus one masked row-rotate per side.
 // K order / weight layout: chunk-major [Cout_pad][K_pad] of include/cvpce_amd.h.  Fused bias / ReLU / MaxPool2d(2,2).
-#include "common.h"
+// The host plan of a launch and the device helpers shared with conv3x3_halo2.hip: halo_common.h; the work-list entry: worklist.h.
+#include "halo_common.h"
 #include "../../include/cvpce_amd.h"
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -33,8 +34,6 @@ typedef __attribute__((address_space(3))) char lds_char;
 #define G3_MAX_SEQ 512
 #define G3_LLIST_OFF (3 * G3_A_BYTES)
 #define G3_SMEM_LIST (G3_LLIST_OFF + G3_MAX_SEQ * 8)
-
-__device__ __forceinline__ int g3_col(int l16) { return l16 < 4 ? 2 * l16 : (l16 >= 12 ? 2 * (l16 - 8) : 2 * (l16 - 4) + 1); }
 
 struct Halo3Args {
     const bf16_t* in;    // [N][H][W][Cin]
@@ -97,16 +96,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
     // fetched again from beyond it: conv2_1 +2.3 %, conv2_2 +1.8 % (same call, three alternations, real activations;
     // CVPCE_DBG & 2 = the plain order, dev A/B)
     const int lbid = (CVPCE_DBG & 2) ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    // LIST launches: a contiguous block of the list per workgroup, the cout tile fixed per workgroup (see conv3x3_halo2.hip)
+    // LIST launches: a contiguous block of the list per workgroup, the cout tile fixed per workgroup (halo_common.h)
     int my_tiles, l_first = 0;
     if constexpr (LIST) {
-        const int entries = __builtin_amdgcn_readfirstlane(*a.list_count);
-        const int groups = (int)gridDim.x / a.ctiles;
-        const int per = (entries + groups - 1) / groups;
-        l_first = (lbid / a.ctiles) * per;
-        my_tiles = entries - l_first < per ? entries - l_first : per;
+        my_tiles = halo_list_span(__builtin_amdgcn_readfirstlane(*a.list_count), (int)gridDim.x, a.ctiles, lbid, l_first);
     } else {
-        my_tiles = (a.ntiles - lbid + (int)gridDim.x - 1) / (int)gridDim.x;
+        my_tiles = halo_plain_tiles(a.ntiles, lbid, (int)gridDim.x);
     }
     if (my_tiles <= 0) return;
     const int total_chunks = my_tiles * nchunks;          // < 2^30: checked on the host
@@ -122,11 +117,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
         if constexpr (LIST) {
             ct = lbid % a.ctiles;
             const unsigned long long e = seq < G3_MAX_SEQ ? llist[seq] : a.list[l_first + seq];
-            const int lo = __builtin_amdgcn_readfirstlane((int)(unsigned)e);
-            ext = __builtin_amdgcn_readfirstlane((int)(unsigned)(e >> 32));
-            n = lo >> 16;
-            ty = (lo >> 8) & 0xFF;
-            tx = lo & 0xFF;
+            const int lo = __builtin_amdgcn_readfirstlane((int)wl_lo(e));
+            ext = __builtin_amdgcn_readfirstlane((int)wl_hi(e));
+            n = wl_image_signed(lo);
+            ty = wl_ty((unsigned)lo);
+            tx = wl_tx((unsigned)lo);
             return;
         }
         ext = 0;
@@ -144,11 +139,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
     const int npp = (wid < 7) ? 5 : 4;
     auto issue_patch = [&](int n, int ty, int tx, int c32, int buf, int ext) {
         const int y0 = ty * G3_TH - 1, x0 = tx * G3_TW - 1;
-        const int ey = (ext >> 12) & 0xFFF, ex = ext & 0xFFF;
-        // lane id recomputed here (2 VALU ops, once per patch) instead of living in a VGPR across the K loop; the empty
+        const int ey = wl_ey((unsigned)ext), ex = wl_ex((unsigned)ext);
+        // lane id recomputed here (2 VALU ops, once per patch) instead of living in a VGPR across the K loop; the volatile
         // asm also keeps the per-piece constants below from being hoisted out of the chunk loop (18+ VGPRs)
-        int ln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int ln = halo_lane_id();
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             if (i < npp) {
@@ -190,11 +184,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
     const unsigned voff1 = (unsigned)(lane * 16);
     auto wbase = [&](int ct, int c) { return __builtin_amdgcn_readfirstlane((int)((unsigned)(c * a.cgroups + ct * (TC / 32) + wc) * 36864u)); };
 
-    // ---- pixel fragments: lane (l16, lq) reads pixel (patch row p, column 16 wp + g3_col(l16) + kw), K-quarter lq:
+    // ---- pixel fragments: lane (l16, lq) reads pixel (patch row p, column 16 wp + halo_col(l16) + kw), K-quarter lq:
     //      address = (c3[kw] + buffer) + (p * 34 + kw) * 64 ----
     unsigned c3[3];
     {
-        const int col = 16 * wp + g3_col(l16);
+        const int col = 16 * wp + halo_col(l16);
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) c3[kw] = (unsigned)(col * 64 + ((lq ^ (((col + kw) >> 2) & 3)) << 4));
     }
@@ -306,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
     // ---- prologue ----
     int seq = 0, cchunk = 0, t_n, t_ty, t_tx, t_ct, t_ext_;
     tile_of(0, t_n, t_ty, t_tx, t_ct, t_ext_);
-    int rows_ = LIST ? ((t_ext_ >> 24) & 0xFF) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
+    int rows_ = LIST ? wl_rows((unsigned)t_ext_) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
     int n_ct = t_ct;                                    // cout tile of the NEXT chunk's tile
     auto next_ct = [&]() {
         if (cchunk + 1 < nchunks) return t_ct;
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
             G3_TIC()
             f32x4 nbias[2];                      // bias of the NEXT tile's couts: lands while this tile is stored
             load_bias(n_ct, nbias);
-            const int col = g3_col(lp);
+            const int col = halo_col(lp);
             if constexpr (THIN) {
                 // fp32 outputs, [pixel][Cout] with any Cout: this lane's (up to) 8 couts of its pixel, 16 bytes at a time where Cout % 4 == 0
                 float* outf = reinterpret_cast<float*>(a.out);
@@ -371,9 +365,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
                     }
                 }
             } else if (POOL) {
-                // rows 2i, 2i+1 are blocks 2i, 2i+1 of the same lane; columns 2k, 2k+1 are lanes A[k], B[k] with
-                // A = {0-3,12-15}, B = {4-11}: lane A[k] takes its right neighbour by a row rotate (+4 for lanes 0-3,
-                // -4 for lanes 12-15; bank masks 1 and 8)
+                // rows 2i, 2i+1 are blocks 2i, 2i+1 of the same lane; the column pairs meet in lanes {0-3,12-15} (halo_pool2x2)
                 const int ox = tx * (G3_TW / 2) + 8 * wp + (col >> 1);
                 const bool lane_ok = (lp < 4 || lp >= 12) && ox < (a.W >> 1);
 #pragma unroll
@@ -385,19 +377,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (a.relu) {
-                                const unsigned v = max(__float_as_uint(relu_bits(acc[mt][2 * i][j])), __float_as_uint(relu_bits(acc[mt][2 * i + 1][j])));
-                                unsigned m = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x1, false));   // row_ror:12 -> lane l reads l+4
-                                m = max(m, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0x8, false));            // row_ror:4  -> lane l reads l-4
-                                r[4 * mt + j] = __uint_as_float(m);
-                            } else {
-                                const float v = fmaxf(acc[mt][2 * i][j], acc[mt][2 * i + 1][j]);
-                                const float up = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x12C, 0xF, 0x1, false));
-                                const float dn = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x124, 0xF, 0x8, false));
-                                r[4 * mt + j] = fmaxf(v, fmaxf(up, dn));
-                            }
-                        }
+                        for (int j = 0; j < 4; ++j) r[4 * mt + j] = halo_pool2x2(acc[mt][2 * i][j], acc[mt][2 * i + 1][j], a.relu);
                     if (lane_ok && oy < (a.H >> 1) && co < a.Cout && (!LIST || 2 * i < rows_t) && (!(CVPCE_DBG & 16) || a.relu == 12345)) {
                         const uint2 l2 = __builtin_bit_cast(uint2, E::pack4(f32x4{r[0], r[1], r[2], r[3]}));
                         const uint2 h2 = __builtin_bit_cast(uint2, E::pack4(f32x4{r[4], r[5], r[6], r[7]}));
@@ -412,7 +392,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
                 // and four neighbouring lanes write one contiguous 64-byte run.
                 const int tp = lane >> 2, tq = lane & 3;                // after the exchange: pixel column index tp, cout group tq
                 const int src4 = (16 * tq + tp) * 4;                    // byte address of the source lane (lq = tq, lp = tp)
-                const int ox = tx * G3_TW + 16 * wp + g3_col(tp);
+                const int ox = tx * G3_TW + 16 * wp + halo_col(tp);
                 const int co = ct * TC + wc * 32 + 8 * tq;
 #pragma unroll
                 for (int nt = 0; nt < NB; ++nt) {
@@ -443,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
             ++seq;
             if (seq < my_tiles) {
                 tile_of(seq, t_n, t_ty, t_tx, t_ct, t_ext_);
-                if constexpr (LIST) rows_ = (t_ext_ >> 24) & 0xFF;
+                if constexpr (LIST) rows_ = wl_rows((unsigned)t_ext_);
             }
         } else {
             ++cchunk;
@@ -468,44 +448,27 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
 #undef G3_LOAD_A
 }
 
-template <typename E, bool POOL, bool LIST = false>
-static int launch_halo3(Halo3Args a, hipStream_t stream) {
-    a.ctiles = (a.Cout + 127) / 128;
-    a.ntiles = a.ptiles * a.ctiles;
-    const int smem = LIST ? G3_SMEM_LIST : 3 * G3_A_BYTES;
-    if (!cvpce_smem_attr_done<conv3x3_halo3_kernel<E, POOL, LIST>>((const void*)conv3x3_halo3_kernel<E, POOL, LIST>, smem)) return CVPCE_ERR_LAUNCH;
-    int grid = a.ntiles < g_cvpce_persistent_wgs ? a.ntiles : g_cvpce_persistent_wgs;
-    if (LIST) grid = grid < a.ctiles ? a.ctiles : grid / a.ctiles * a.ctiles;     // (work-list launches: the same number of workgroups per cout tile)
-    hipLaunchKernelGGL((conv3x3_halo3_kernel<E, POOL, LIST>), dim3(grid), dim3(512), smem, stream, a);
-    return cvpce_check_launch();
-}
+static constexpr HaloRules G3_RULES = {/* tile_w */ G3_TW, /* cout_tile */ 128, /* max_chunks */ 1LL << 29, /* cout_mult8 */ true, /* cout_max */ 0};
+// the thin form: one cout tile, any Cout up to 128
+static constexpr HaloRules G3_THIN_RULES = {/* tile_w */ G3_TW, /* cout_tile */ 0, /* max_chunks */ 1LL << 29, /* cout_mult8 */ false, /* cout_max */ 128};
 
 template <typename E>
 static int halo3_dispatch(const void* in, const void* wgt, const float* bias, void* out, int N, int H, int W,
                           int Cin, int Cout, int K_pad, int Cout_pad, int relu, int fuse_pool2, void* stream,
                           const unsigned long long* list = nullptr, const int* count_dev = nullptr) {
     if (N <= 0) return CVPCE_OK;
-    if (!in || !wgt || !out) return CVPCE_ERR_ARG;
-    if (H <= 0 || W <= 0 || Cin % 64 != 0 || Cin <= 0 || Cout % 8 != 0 || Cout <= 0) return CVPCE_ERR_ARG;
-    if (fuse_pool2 && ((H & 1) || (W & 1))) return CVPCE_ERR_ARG;
-    if (K_pad != 9 * Cin || Cout_pad % 256 != 0 || Cout_pad < Cout) return CVPCE_ERR_ARG;
-    if ((long long)N * H * W * Cin * 2 >= (1LL << 32) || (long long)N * H * W * Cout >= (1LL << 31)) return CVPCE_ERR_ARG;
-    if ((long long)Cout_pad * K_pad * 2 >= (1LL << 31)) return CVPCE_ERR_ARG;
+    if (!out || (list && (E::kF16 || !count_dev))) return CVPCE_ERR_ARG;   // (the list entry exists for the bf16 embedder)
+    const HaloShape sh{N, H, W, Cin, Cout, K_pad, Cout_pad};
+    if (!halo_shape_ok(in, wgt, sh, fuse_pool2, 0, list != nullptr, G3_RULES)) return CVPCE_ERR_ARG;
     Halo3Args a;
-    a.in = (const bf16_t*)in; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.out = (bf16_t*)out;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K_pad = K_pad; a.relu = relu; a.cgroups = Cout_pad / 32;
-    a.tiles_x = (W + G3_TW - 1) / G3_TW; a.tiles_y = (H + G3_TH - 1) / G3_TH; a.ptiles = N * a.tiles_x * a.tiles_y;
-    a.in_bytes = (unsigned)((long long)N * H * W * Cin * 2);
-    a.wgt_bytes = (unsigned)((long long)Cout_pad * K_pad * 2);
-    a.ctiles = a.ntiles = 0;
-    a.list = list; a.list_count = count_dev;
-    if ((long long)a.ptiles * ((Cout + 127) / 128) * (Cin / 64) >= (1LL << 29)) return CVPCE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (list) {
-        if (E::kF16 || !count_dev || N > 65535 || a.tiles_x > 255 || a.tiles_y > 255 || H > 65535 || W > 65535) return CVPCE_ERR_ARG;   // (the list entry exists for the bf16 embedder)
-        if constexpr (!E::kF16) return fuse_pool2 ? launch_halo3<E, true, true>(a, s) : launch_halo3<E, false, true>(a, s);
-    }
-    return fuse_pool2 ? launch_halo3<E, true>(a, s) : launch_halo3<E, false>(a, s);
+    halo_fill(a, in, wgt, bias, out, sh, relu, G3_TW, list, count_dev);
+    a.ctiles = (Cout + 127) / 128;
+    a.ntiles = a.ptiles * a.ctiles;
+    return halo_pick([&](auto pool, auto lst) {
+        constexpr bool LIST = decltype(lst)::value && !E::kF16;
+        return halo_launch<conv3x3_halo3_kernel<E, decltype(pool)::value, LIST>>(a, halo_grid(a.ntiles, a.ctiles, LIST), 512,
+                                                                                 LIST ? G3_SMEM_LIST : 3 * G3_A_BYTES, (hipStream_t)stream);
+    }, fuse_pool2 != 0, list != nullptr);
 }
 
 // the thin-output form: fp32 [N][H][W][Cout] outputs, Cout <= 128 and not necessarily a multiple of 8, no activation
@@ -513,24 +476,13 @@ template <typename E>
 static int halo3_thin_dispatch(const void* in, const void* wgt, const float* bias, float* out, int N, int H, int W, int Cin, int Cout,
                                int K_pad, int Cout_pad, void* stream) {
     if (N <= 0) return CVPCE_OK;
-    if (!in || !wgt || !out) return CVPCE_ERR_ARG;
-    if (H <= 0 || W <= 0 || Cin % 64 != 0 || Cin <= 0 || Cout <= 0 || Cout > 128) return CVPCE_ERR_ARG;
-    if (K_pad != 9 * Cin || Cout_pad % 256 != 0 || Cout_pad < Cout) return CVPCE_ERR_ARG;
-    if ((long long)N * H * W * Cin * 2 >= (1LL << 32) || (long long)N * H * W * Cout >= (1LL << 31)) return CVPCE_ERR_ARG;
-    if ((long long)Cout_pad * K_pad * 2 >= (1LL << 31)) return CVPCE_ERR_ARG;
+    if (!out) return CVPCE_ERR_ARG;
+    const HaloShape sh{N, H, W, Cin, Cout, K_pad, Cout_pad};
+    if (!halo_shape_ok(in, wgt, sh, 0, 0, false, G3_THIN_RULES)) return CVPCE_ERR_ARG;
     Halo3Args a;
-    a.in = (const bf16_t*)in; a.wgt = (const bf16_t*)wgt; a.bias = bias; a.out = reinterpret_cast<bf16_t*>(out);
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K_pad = K_pad; a.relu = 0; a.cgroups = Cout_pad / 32;
-    a.tiles_x = (W + G3_TW - 1) / G3_TW; a.tiles_y = (H + G3_TH - 1) / G3_TH; a.ptiles = N * a.tiles_x * a.tiles_y;
-    a.in_bytes = (unsigned)((long long)N * H * W * Cin * 2);
-    a.wgt_bytes = (unsigned)((long long)Cout_pad * K_pad * 2);
+    halo_fill(a, in, wgt, bias, out, sh, 0, G3_TW, nullptr, nullptr);
     a.ctiles = 1; a.ntiles = a.ptiles;
-    a.list = nullptr; a.list_count = nullptr;
-    if ((long long)a.ptiles * (Cin / 64) >= (1LL << 29)) return CVPCE_ERR_ARG;
-    if (!cvpce_smem_attr_done<conv3x3_halo3_kernel<E, false, false, true>>((const void*)conv3x3_halo3_kernel<E, false, false, true>, 3 * G3_A_BYTES)) return CVPCE_ERR_LAUNCH;
-    const int grid = a.ntiles < g_cvpce_persistent_wgs ? a.ntiles : g_cvpce_persistent_wgs;
-    hipLaunchKernelGGL((conv3x3_halo3_kernel<E, false, false, true>), dim3(grid), dim3(512), 3 * G3_A_BYTES, (hipStream_t)stream, a);
-    return cvpce_check_launch();
+    return halo_launch<conv3x3_halo3_kernel<E, false, false, true>>(a, halo_grid(a.ntiles, 1, false), 512, 3 * G3_A_BYTES, (hipStream_t)stream);
 }
 extern "C" int cvpce_conv3x3_halo_thin_out(const void* in, const void* wgt, const float* bias, float* out, int N, int H, int W,
                                            int Cin, int Cout, int K_pad, int Cout_pad, void* stream) {

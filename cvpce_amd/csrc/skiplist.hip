@@ -13,12 +13,12 @@
 // upwards -- and clamped to the tensor's size.  The op chain of the whole pass is one bit string (cvpce_embed_worklists `pool_mask`);
 // a tensor is named by how many ops precede it, so its producer and its consumers compute the same, exact, extent.
 //
-// This kernel turns the extents into one compacted, crop-major tile list per layer (device-resident counts: no host sync):
-//   entry = ((rows << 24 | ey_in << 12 | ex_in) << 32) | (n << 16) | (ty << 8) | tx
-// rows = how many of the tile's 16 conv-output rows (before a fused pool) are NOT wholly constant, rounded up to 4: the halo
+// This kernel turns the extents into one compacted, crop-major tile list per layer (device-resident counts: no host sync); the
+// entry format and the limits it sets are worklist.h's.  rows = how many of the tile's 16 conv-output rows (before a fused pool) are NOT wholly constant, rounded up to 4: the halo
 // kernels stop streaming patch rows behind them (rows of a tile below the crop's content extent are never read by anyone).
 // Layers with skip == 3 get a second list, the STRIP list: their tiles with rows == 4, which conv3x3_halo2.hip computes three at a time.
 #include "common.h"
+#include "worklist.h"
 #include "../../include/cvpce_amd.h"
 
 #define SKL_MAX_LAYERS 16
@@ -45,7 +45,7 @@ __device__ __forceinline__ int skl_extent(int e0, int S, unsigned pool_mask, int
 __global__ __launch_bounds__(1024) void embed_worklists_kernel(WorklistArgs a) {
     __shared__ int s_cnt[1024];                        // scan scratch
     __shared__ int s_end[1024], s_send[1024];          // per crop of the current chunk: END offset of its entries in the chunk's list / strip list
-    __shared__ unsigned s_geo[1024], s_ext[1024];      // (ny << 16 | nx << 8 | rows of the last tile row), (ey_in << 12 | ex_in)
+    __shared__ unsigned s_geo[1024], s_ext[1024];      // (ny << 16 | nx << 8 | rows of the last tile row), wl_pack_ext(ey_in, ex_in)
     __shared__ int s_base, s_sbase, s_units;
     const cvpce_skip_layer L = a.L[blockIdx.x];
     const int tid = threadIdx.x;
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(1024) void embed_worklists_kernel(WorklistArgs a) {
         // 0 .. rows + 1), a strip 4 (three strips share one pass of 72 MFMAs per step against a full tile's 96)
         if (ny > 0) atomicAdd(&s_units, nx * (16 * (ny - 1) + (strips ? 4 : (last_rows < 16 ? last_rows + 1 : 16))));
         s_geo[tid] = ((unsigned)ny << 16) | ((unsigned)nx << 8) | (unsigned)last_rows;
-        s_ext[tid] = ((unsigned)eiy << 12) | (unsigned)eix;
+        s_ext[tid] = wl_pack_ext((unsigned)eiy, (unsigned)eix);
         const int base0 = s_base, sbase0 = s_sbase;          // (read before the scans' barriers; updated behind them)
         scan(cnt);
         s_end[tid] = s_cnt[tid];
@@ -127,15 +127,13 @@ __global__ __launch_bounds__(1024) void embed_worklists_kernel(WorklistArgs a) {
             const int cny = (int)(geo >> 16), cnx = (int)((geo >> 8) & 0xFF), j = e - (c ? s_end[c - 1] : 0);
             const int ty = j / cnx, tx = j - ty * cnx;
             const unsigned rows = (ty == cny - 1) ? (geo & 0xFF) : 16u;
-            list[base0 + e] = ((unsigned long long)((rows << 24) | s_ext[c]) << 32) |
-                              (unsigned long long)(((unsigned)(n0 + c) << 16) | ((unsigned)ty << 8) | (unsigned)tx);
+            list[base0 + e] = wl_pack(rows, s_ext[c], (unsigned)(n0 + c), (unsigned)ty, (unsigned)tx);
         }
         for (int e = (int)blockIdx.y * 1024 + tid; e < stotal; e += (int)gridDim.y * 1024) {
             const int c = crop_of(s_send, e);
             const unsigned geo = s_geo[c];
             const int cny = (int)(geo >> 16), tx = e - (c ? s_send[c - 1] : 0);
-            slist[sbase0 + e] = ((unsigned long long)((4u << 24) | s_ext[c]) << 32) |
-                                (unsigned long long)(((unsigned)(n0 + c) << 16) | ((unsigned)(cny - 1) << 8) | (unsigned)tx);
+            slist[sbase0 + e] = wl_pack(4u, s_ext[c], (unsigned)(n0 + c), (unsigned)(cny - 1), (unsigned)tx);
         }
         __syncthreads();
         if (tid == 0) { s_base = base0 + total; s_sbase = sbase0 + stotal; }
@@ -152,15 +150,15 @@ extern "C" int cvpce_embed_worklists(const int* ext0, int n_images, int S, unsig
                                      unsigned long long* lists, long long list_stride, int* counts, int* computed, void* stream) {
     if (n_layers <= 0) return CVPCE_OK;
     if (!ext0 && n_images > 1) return CVPCE_ERR_ARG;
-    if (!layers || !lists || !counts || n_layers > SKL_MAX_LAYERS || n_images <= 0 || n_images > 65535 || S <= 0 || S > 32767) return CVPCE_ERR_ARG;
+    if (!layers || !lists || !counts || n_layers > SKL_MAX_LAYERS || n_images <= 0 || n_images > WL_MAX_IMAGES || S <= 0 || S > 32767) return CVPCE_ERR_ARG;
     WorklistArgs a;
     a.ext0 = ext0; a.n = n_images; a.S = S; a.nl = n_layers; a.pool_mask = pool_mask; a.lists = lists; a.stride = list_stride; a.counts = counts; a.computed = computed;
     for (int i = 0; i < n_layers; ++i) {
         const cvpce_skip_layer& l = layers[i];
-        if (l.H <= 0 || l.W <= 0 || l.tile_h <= 0 || l.tile_w <= 0 || l.in_H <= 0 || l.in_W <= 0 || l.in_H > 4095 || l.in_W > 4095) return CVPCE_ERR_ARG;
+        if (l.H <= 0 || l.W <= 0 || l.tile_h <= 0 || l.tile_w <= 0 || l.in_H <= 0 || l.in_W <= 0 || l.in_H > WL_MAX_EXTENT || l.in_W > WL_MAX_EXTENT) return CVPCE_ERR_ARG;
         if (l.in_ops < 0 || l.out_ops < l.in_ops || l.out_ops > 32) return CVPCE_ERR_ARG;
         const long long ty = (l.H + l.tile_h - 1) / l.tile_h, tx = (l.W + l.tile_w - 1) / l.tile_w;
-        if (ty > 255 || tx > 255 || ty * tx * n_images > list_stride) return CVPCE_ERR_ARG;
+        if (ty > WL_MAX_TILES || tx > WL_MAX_TILES || ty * tx * n_images > list_stride) return CVPCE_ERR_ARG;
         a.L[i] = l;
     }
     const int split = n_images >= 64 ? 8 : 1;

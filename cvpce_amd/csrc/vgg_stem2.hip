@@ -20,6 +20,7 @@
 // Biases live in LDS and seed the accumulators (max(x + b) = max(x) + b), which also frees 64 VGPRs.
 // HBM traffic per crop: 0.5 MB in (NHWC4 bf16) + 2.1 MB out instead of 0.5 + 8.4 + 8.4 + 2.1 MB.
 #include "common.h"
+#include "worklist.h"
 #include "../../include/cvpce_amd.h"
 
 // compile-time timing experiments (never set in the shipped library; tools/ablate.sh): 1 no initial de-phasing,
@@ -49,8 +50,8 @@ struct Stem2Args {
     bf16_t* out;         // [N][H/2][W/2][64]
     int N, H, W;
     int tiles_x, tiles_y, ntiles;
-    // LIST launches (the embedder's constant-padding tile skipping, skiplist.hip): the tiles to compute, low word of an entry =
-    // (n << 16) | (ty << 8) | tx, *list_count entries; image N - 1 (the constant crop) is read from const_in, not from `in`
+    // LIST launches (the embedder's constant-padding tile skipping, skiplist.hip): the tiles to compute, entries of worklist.h,
+    // *list_count of them; image N - 1 (the constant crop) is read from const_in, not from `in`
     const unsigned long long* list;
     const int* list_count;
     const bf16_t* const_in;
@@ -124,12 +125,12 @@ __global__ __launch_bounds__(512, 2) void vgg_stem2_kernel(Stem2Args a) {
 
     // input patch staging: 400 pixels of 8 B, two per thread of the team (second one only for qtid < 144)
     unsigned long long preg[2];
-    // work item -> (image, tile row, tile column): a list entry, or the flat tile index itself
+    // work item -> (image, tile row, tile column): the low word of a list entry, or the flat tile index itself
     auto decode = [&](unsigned e, int& n, int& ty, int& tx) {
         if constexpr (LIST) {
-            n = (int)(e >> 16);
-            ty = (int)((e >> 8) & 0xFF);
-            tx = (int)(e & 0xFF);
+            n = wl_image(e);
+            ty = wl_ty(e);
+            tx = wl_tx(e);
         } else {
             n = (int)e / (a.tiles_x * a.tiles_y);
             const int r = (int)e - n * (a.tiles_x * a.tiles_y);
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void vgg_stem2_kernel(Stem2Args a) {
             tx = r - ty * a.tiles_x;
         }
     };
-    // LIST: `ext` = (ey << 12) | ex, the crop's content extent from the entry's high word -- a pixel with y >= ey or x >= ex is the pad
+    // LIST: `ext` = the entry's high word with the crop's content extent (ey, ex) -- a pixel with y >= ey or x >= ex is the pad
     // constant and is read from the constant crop (the crop kernel may not have written it: cvpce_crop_resize_content)
     auto load_patch = [&](unsigned item, unsigned ext) {
         int n, ty, tx;
@@ -146,8 +147,8 @@ __global__ __launch_bounds__(512, 2) void vgg_stem2_kernel(Stem2Args a) {
         int ey = a.H, ex = a.W;
         if constexpr (LIST) {
             if (n == a.N - 1) img = a.const_in;
-            ey = (int)((ext >> 12) & 0xFFFu);
-            ex = (int)(ext & 0xFFFu);
+            ey = wl_ey(ext);
+            ex = wl_ex(ext);
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -179,11 +180,11 @@ __global__ __launch_bounds__(512, 2) void vgg_stem2_kernel(Stem2Args a) {
     if (tile >= ntiles) return;                       // (team-uniform; the other team does not wait for this one)
     // the work items of this and the next two iterations (LIST: list entries, fetched two iterations ahead of their use)
     auto item_at = [&](int t) -> unsigned {
-        if constexpr (LIST) return t < ntiles ? (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a.list[t]) : 0u;
+        if constexpr (LIST) return t < ntiles ? (unsigned)__builtin_amdgcn_readfirstlane((int)wl_lo(a.list[t])) : 0u;
         return (unsigned)t;
     };
     auto ext_at = [&](int t) -> unsigned {
-        if constexpr (LIST) return t < ntiles ? (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a.list[t] >> 32)) : 0u;
+        if constexpr (LIST) return t < ntiles ? (unsigned)__builtin_amdgcn_readfirstlane((int)wl_hi(a.list[t])) : 0u;
         return 0u;
     };
     unsigned it_cur = item_at(tile), it_next = item_at(tile + stride);
@@ -407,7 +408,7 @@ static int stem_launch(const void* in_nhwc, int in_cstride, const void* const_in
                        void* stream) {
     if (N <= 0) return CVPCE_OK;
     if (!in_nhwc || !w1 || !b1 || !w2 || !b2 || !out) return CVPCE_ERR_ARG;
-    if (list && (!count_dev || !const_in || N > 65535 || H / S2_T > 255 || W / S2_T > 255)) return CVPCE_ERR_ARG;
+    if (list && (!count_dev || !const_in || !wl_fits(N, H, W, S2_T))) return CVPCE_ERR_ARG;
     if (in_cstride != 4 && in_cstride != 8) return CVPCE_ERR_ARG;
     if (H % S2_T != 0 || W % S2_T != 0 || H <= 0 || W <= 0) return CVPCE_ERR_ARG;
     if ((long long)N * H * W >= (1LL << 31) / 4) return CVPCE_ERR_ARG;      // in-kernel pixel indices are 32-bit, byte offsets 64-bit
