@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import footprint as fp            # tests/footprint.py
+from footprint import listed_pixels as _listed_pixels, worklist_model as _worklist_model, whole
 
 pytestmark = pytest.mark.gpu
 
@@ -221,56 +222,6 @@ def test_conv3x3_halo_thin_out(cuda, cin, cout, dt):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # work-list and strip launches of the embedder
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _listed_pixels(entries, n, h, w, th, tw):
-    """(n,h,w,1) bool: the output pixels the tiles of a work list cover -- entry = (rows << 56 | ...) | n << 16 | ty << 8 | tx
-    (include/cvpce_amd.h): a tile cut at `rows` of its 16 conv-output rows stores that share of its th output rows."""
-    m = torch.zeros(n, h, w, 1, dtype=torch.bool)
-    for e in entries:
-        rows, img, ty, tx = (e >> 56) & 0xFF, (e >> 16) & 0xFFFF, (e >> 8) & 0xFF, e & 0xFF
-        m[img, ty * th:ty * th + rows * th // 16, tx * tw:(tx + 1) * tw] = True
-    return m
-
-
-def _worklist_model(ext, size, pool_mask, layers):
-    """The work lists of include/cvpce_amd.h (cvpce_embed_worklists) in plain Python, independent of the kernel -- the model of
-    tests/test_gpu_skip.py test_worklists_match_python_model at crop size `size`.  ext: (rows, cols) per crop, the constant crop
-    included -> per layer (list entries, strip-list entries, MFMA work in sixteenths of a tile, [rows computed, tile columns] per crop)."""
-    def extent(e0, nops, dim):
-        if e0 >= size:
-            return dim
-        e = e0
-        for i in range(nops):
-            e = (e + 1) // 2 if (pool_mask >> i) & 1 else e + 1
-        return min(dim, e)
-    model = []
-    for h, w, th, tw, out_ops, ih, iw, in_ops, skip in layers:
-        ty_n, tx_n = -(-h // th), -(-w // tw)
-        want, swant, comp = [], [], []
-        for c, (ey0, ex0) in enumerate(ext):
-            ny, nx = ty_n, tx_n
-            if skip:
-                ny = min(ty_n, -(-extent(ey0, out_ops, h) // th))
-                nx = min(tx_n, -(-extent(ex0, out_ops, w) // tw))
-            if nx == 0:
-                ny = 0                                           # no tile column listed: no tile row either
-            ext_in = (extent(ey0, in_ops, ih) << 12) | extent(ex0, in_ops, iw)
-            last = 16
-            for ty in range(ny):
-                rows = 16
-                if skip >= 2 and ty == ny - 1:
-                    act = min(th, extent(ey0, out_ops, h) - ty * th)
-                    last = rows = min(16, (-(-act * 16 // th) + 3) // 4 * 4)
-                entries = [(((rows << 24) | ext_in) << 32) | (c << 16) | (ty << 8) | tx for tx in range(nx)]
-                if skip >= 3 and rows == 4 and ty == ny - 1:
-                    swant += entries
-                else:
-                    want += entries
-            comp.append([(ny - 1) * 16 + last if ny else 0, nx])
-        work = sum(r + 1 if r < 16 else 16 for r in ((e >> 56) & 0xFF for e in want)) + 4 * len(swant)
-        model.append((want, swant, work, comp))
-    return model
-
-
 def test_list_and_strip_launches(cuda):
     """cvpce_crop_extents -> cvpce_embed_worklists -> cvpce_vgg_stem_fused_list -> cvpce_conv3x3_halo_list (wide tiles; 16x16 tiles with
     the fused pool; with the MAC descriptor and no store) + cvpce_conv3x3_halo_strips + cvpce_mac_init, on three crops (a wide box, a
@@ -327,11 +278,6 @@ def test_list_and_strip_launches(cuda):
     full = ops.crop_resize(img.to(cuda), boxes.to(cuda), S, mode=2, mean=TANH_MEAN, std=TANH_STD)
     assert torch.equal(x0.cpu()[must.expand_as(x0)], full.cpu()[must.expand_as(full)])
     x0in, cstin = fp.put(x0, cuda), fp.put(const, cuda)                              # x0's padding: the prefill NaNs
-
-    def whole(prev, mask):
-        """the tensor a layer's list leaves to the constant crop, filled in from the constant crop's own pixels (image n - 1)"""
-        prev = prev.cpu()
-        return torch.where(mask.expand_as(prev), prev, prev[-1:].expand_as(prev))
 
     # stem over its list
     w1, b1 = torch.randn(64, 3, 3, 3, generator=g) / math.sqrt(27), torch.randn(64, generator=g) * 0.1
