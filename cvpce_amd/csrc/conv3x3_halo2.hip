@@ -18,6 +18,7 @@
 // The host plan of a launch and the device helpers shared with conv3x3_halo3.hip: halo_common.h; the work-list entry: worklist.h.
 #include "halo_common.h"
 #include "../../include/cvpce_amd.h"
+#include "../../include/cvpce_amd_lists.h"
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(3))) char lds_char;
@@ -87,14 +88,20 @@ extern "C" int cvpce_debug_halo2_clock(unsigned long long* host_out) {
 // tile's MFMAs against a full tile's weight stream, which is what bounds them (profiles/r04_rejected_experiments.md); here patch
 // rows 6s .. 6s + 5 of the 18-row patch belong to strip s, accumulator rows 4s .. 4s + 3 are its outputs, and the three share
 // every weight fragment: 72 MFMAs per step and wave for three tiles' worth of useful rows.
+// SH is the strip height: 0 no strips, 4 the above (NS = 3 strips a pass), 2 the THIN strips of the list mode 5 (skiplist.hip): tiles with
+// `rows` == 2, NS = 4 a pass -- patch rows 4s .. 4s + 3 and accumulator rows 2s, 2s + 1 belong to strip s, patch rows 16 and 17 to no
+// strip (no DMA source, never read): 48 MFMAs per step and wave for four tiles.  In general SH + 2 patch rows per strip.
 // NW (waves = 32-cout groups per workgroup): 8 -> a 256-cout tile; 4 -> a 128-cout tile for launches with too few pixel tiles to fill
 // the chip (the detector's 50 x 50 and 25 x 25 maps: 128 / 32 tiles of 16 x 16 pixels for 256 compute units): twice the workgroups,
 // each with half the weight stream and the same patch.
-template <typename E, bool POOL, bool GMAX, bool LIST, bool STRIP = false, int NW = 8>
+template <typename E, bool POOL, bool GMAX, bool LIST, int SH = 0, int NW = 8>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel(Halo2Args a) {
+    constexpr bool STRIP = SH != 0;
+    static_assert(SH == 0 || SH == 2 || SH == 4, "strip height");
     static_assert(!STRIP || LIST, "strips come from a work list");
     static_assert(NW == 8 || NW == 4, "cout waves");   // (two waves on a 64-cout tile for the 25 x 25 maps: measured, no further gain)
-    constexpr int TC = 32 * NW, NB = 16, NS = STRIP ? 3 : 1;
+    constexpr int TC = 32 * NW, NB = 16, NS = SH == 4 ? 3 : (SH == 2 ? 4 : 1);
+    constexpr int SHD = STRIP ? SH : 1, PR = SH + 2;     // (strip height as a divisor; patch rows per strip)
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* Ap = smem;                 // [3][328][64] bf16
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     int my_tiles, l_first = 0, l_entries = 0;
     if constexpr (LIST) {
         l_entries = __builtin_amdgcn_readfirstlane(*a.list_count);             // <= a.ptiles (checked by the list builder)
-        const int units = STRIP ? (l_entries + 2) / 3 : l_entries;             // STRIP: three list entries make one tile
+        const int units = STRIP ? (l_entries + NS - 1) / NS : l_entries;       // STRIP: NS list entries make one tile
         const int groups = (int)gridDim.x / a.ctiles;
         const int per = (units + groups - 1) / groups;
         l_first = (lbid / a.ctiles) * per;
@@ -214,19 +221,28 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
                 const int pp = j * 8 + (ln >> 3);
                 const int py = pp / G2_P, px = pp - py * G2_P;
                 const int lchunk = (ln & 7) ^ g2_swz(py, px);
-                // the tile this patch pixel belongs to: the one tile, or (STRIP) strip py / 6, whose patch rows are 6 s .. 6 s + 5
+                // the tile this patch pixel belongs to: the one tile, or (STRIP) strip py / PR, whose patch rows are PR s .. PR s + PR - 1
                 int sn = n[0], sty = ty[0], stx = tx[0], sext = ext[0], ry = py;
-                if constexpr (STRIP) {
+                bool in_strip = true;
+                if constexpr (SH == 4) {
                     const int st = py >= 12 ? 2 : (py >= 6 ? 1 : 0);
                     ry = py - 6 * st;
                     sn = st == 0 ? n[0] : (st == 1 ? n[1] : n[2]);
                     sty = st == 0 ? ty[0] : (st == 1 ? ty[1] : ty[2]);
                     stx = st == 0 ? tx[0] : (st == 1 ? tx[1] : tx[2]);
                     sext = st == 0 ? ext[0] : (st == 1 ? ext[1] : ext[2]);
+                } else if constexpr (SH == 2) {
+                    const int st = py >> 2;                      // 4 = patch rows 16, 17: no strip, zero-filled like a border
+                    in_strip = st < NS;
+                    ry = py & 3;
+                    sn = st == 0 ? n[0] : (st == 1 ? n[1] : (st == 2 ? n[2] : n[3]));
+                    sty = st == 0 ? ty[0] : (st == 1 ? ty[1] : (st == 2 ? ty[2] : ty[3]));
+                    stx = st == 0 ? tx[0] : (st == 1 ? tx[1] : (st == 2 ? tx[2] : tx[3]));
+                    sext = st == 0 ? ext[0] : (st == 1 ? ext[1] : (st == 2 ? ext[2] : ext[3]));
                 }
                 const int ey = wl_ey((unsigned)sext), ex = wl_ex((unsigned)sext);
                 const int y = sty * G2_T - 1 + ry, x = stx * G2_T - 1 + px;
-                const bool ok = pp < G2_NPIX && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+                const bool ok = pp < G2_NPIX && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W && in_strip;
                 int nn = sn;
                 if constexpr (LIST) nn = (y >= ey || x >= ex) ? a.N - 1 : sn;   // constant region of the crop: the constant crop's pixel
                 const unsigned off = (unsigned)((((size_t)(nn * a.H + y) * a.W + x) * a.Cin + c * 64) * 2) + (unsigned)(lchunk * 16);
@@ -314,30 +330,31 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         e0 = x_ + (BUFB);                                                                                      \
         e1 = (x_ ^ 16u) + (BUFB);                                                                              \
     }
-    // read patch row P of step T into ring slot (P + 2 T) & 3 (a step has 18 rows, 18 = 2 mod 4)
+    // read patch row P of step T into ring slot (P + 2 T) & 3 (a step has 18 rows, 18 = 2 mod 4).  SH == 2: patch rows 16, 17 belong
+    // to no strip and are not read (G2_ROW counts its waits accordingly)
 #define G2_READ(T, P)                                                                                          \
-    if constexpr (!(CVPCE_DBG & 32)) {                                                                         \
+    if constexpr (!(CVPCE_DBG & 32) && !(SH == 2 && (P) >= 16)) {                                              \
         if constexpr (((P) & 1) == 0)                                                                          \
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bfr[((P) + 2 * (T)) & 3]) : "v"(e0), "n"(((P) * G2_P + ((T) >> 1)) * 128)); \
         else                                                                                                   \
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bfr[((P) + 2 * (T)) & 3]) : "v"(e1), "n"(((P) * G2_P + ((T) >> 1)) * 128)); \
     }
-    // patch row P through tap KH feeds output row P - KH -- or (STRIP) row (P % 6) - KH < 4 of strip P / 6 = accumulator row 4 (P / 6) + ...
+    // patch row P through tap KH feeds output row P - KH -- or (STRIP) row (P % PR) - KH < SH of strip P / PR = accumulator row SH (P / PR) + ...
 #define G2_ROW_KH(T, P, KH)                                                                                    \
     {                                                                                                          \
-        constexpr int j_ = STRIP ? (P) % 6 - (KH) : (P) - (KH);                                                \
-        constexpr int r_ = STRIP ? 4 * ((P) / 6) + j_ : j_;                                                    \
-        if constexpr (j_ >= 0 && j_ < (STRIP ? 4 : NB)) {                                                      \
+        constexpr int j_ = STRIP ? (P) % PR - (KH) : (P) - (KH);                                               \
+        constexpr int r_ = STRIP ? SH * ((P) / PR) + j_ : j_;                                                  \
+        if constexpr (j_ >= 0 && j_ < (STRIP ? SH : NB) && (!STRIP || (P) / PR < NS)) {                        \
             _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                \
                 acc[mt_][r_] = E::mfma16(af[(T) & 1][KH][mt_], bfr[((P) + 2 * (T)) & 3], acc[mt_][r_]);       \
         }                                                                                                      \
     }
     // the MFMAs of patch row P: output rows P (kh = 0), P-1 (kh = 1), P-2 (kh = 2) where they exist.  Waits until the
-    // row has landed (the two rows prefetched after it may stay in flight); the "+v" tie keeps the compiler from
-    // hoisting an MFMA above the wait.
+    // row has landed (the two rows prefetched after it may stay in flight: SH == 2 prefetches nothing behind rows 14, 15, its last);
+    // the "+v" tie keeps the compiler from hoisting an MFMA above the wait.
 #define G2_ROW(T, P)                                                                                           \
     {                                                                                                          \
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bfr[((P) + 2 * (T)) & 3]));                                 \
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bfr[((P) + 2 * (T)) & 3]) : "n"(SH == 2 && ((P) == 14 || (P) == 15) ? 15 - (P) : 2)); \
         G2_ROW_KH(T, P, 0) G2_ROW_KH(T, P, 1) G2_ROW_KH(T, P, 2)                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
     }
@@ -352,22 +369,42 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         if (!(CVPCE_DBG & 64)) __builtin_amdgcn_s_barrier();                                                   \
         issue_next_patch();                                                                                    \
     }
-    // LIST launches: a tile computes only its first `rows_` (4 | 8 | 12 | 16) output rows -- the rest lies in the crop's constant
-    // region and is never read by anyone.  Output row r needs patch rows r .. r + 2, so a step streams patch rows 0 .. rows_ + 1
-    // and stops (three uniform branches per step); the two reads it has prefetched beyond are stale and land, in order, before
-    // the next step's rows 0 and 1 that follow them into the same ring slots.  Accumulator rows rows_, rows_ + 1 collect partial
-    // sums nobody stores.  BEFORE / AFTER: what precedes the step's hand-over to the next one (the chunk hand-off in the last step).
+    // LIST launches: a tile computes only its first `rows_` output rows, `rows_` any EVEN number 2 .. 16 -- the rest lies in the crop's
+    // constant region and is never read by anyone.  Output row r needs patch rows r .. r + 2, so a step streams patch rows
+    // 0 .. rows_ + 1 and stops: one uniform branch per row pair (every G2_RP is a scheduling region of its own, so a branch between two
+    // of them splits nothing).  The two reads the step has prefetched beyond, patch rows rows_ + 2 and rows_ + 3, are stale: the cut
+    // step waits for them (G2_STALE_LANDED) before it hands over, so whatever slot they sit in -- relative to 2 T, slots 2, 3 for
+    // rows_ = 0 (mod 4), the slots the next step's rows 0, 1 go to; slots 0, 1 for rows_ = 2 (mod 4), the slots of its rows 2, 3 -- is
+    // free when the next read into it is issued.  The next step's rows 0, 1 go to slots 2, 3: for rows_ = 2 (mod 4) the slots of
+    // patch rows rows_, rows_ + 1, the last two consumed; their MFMAs were issued before the reads that overwrite them, as everywhere
+    // in the ring.  The waits count as in a full step: when G2_ROW(TN, 0) waits for lgkmcnt(2), rows 0, 1, 2 are in flight.
+    // Accumulator rows rows_, rows_ + 1 collect partial sums nobody stores.  A THIN strip pass (SH == 2) streams patch rows 0 .. 15
+    // and never reads rows 16, 17: rows_ = 14 throughout, no stale read.  BEFORE: what precedes the step's hand-over to the next one
+    // (the chunk hand-off in the last step).
+#define G2_MORE(R) (!LIST || SH == 4 || (SH == 2 ? (R) < 14 : rows_ > (R)))
+    // the stale reads' destination registers are dead to the compiler the moment they are issued: it hands them to the next value it
+    // computes (seen: an LDS address of G2_SET_E three instructions behind a short strip row), and the late data would land on that.
+    // So a cut step waits until they have landed before anything else is computed -- they were issued two MFMA groups ago
+#define G2_STALE_LANDED()                                                                                      \
+    {                                                                                                          \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
+    }
 #define G2_ROWS_AND_TAIL(T, TN, BUFB_NEXT, BEFORE)                                                             \
-    G2_RP(T, 0) G2_RP(T, 1) G2_RP(T, 2) G2_RP(T, 3) G2_RP(T, 4) G2_RP(T, 5)                                    \
-    if (!LIST || STRIP || rows_ > 4) { G2_RP(T, 6) G2_RP(T, 7) G2_RP(T, 8) G2_RP(T, 9) }                       \
-    if (!LIST || STRIP || rows_ > 8) { G2_RP(T, 10) G2_RP(T, 11) G2_RP(T, 12) G2_RP(T, 13) }                   \
-    if (!LIST || STRIP || rows_ > 12) {                                                                        \
-        G2_RP(T, 14) G2_RP(T, 15)                                                                              \
+    G2_RP(T, 0) G2_RP(T, 1) G2_RP(T, 2) G2_RP(T, 3)                                                            \
+    if (G2_MORE(2)) { G2_RP(T, 4) G2_RP(T, 5) }                                                                \
+    if (G2_MORE(4)) { G2_RP(T, 6) G2_RP(T, 7) }                                                                \
+    if (G2_MORE(6)) { G2_RP(T, 8) G2_RP(T, 9) }                                                                \
+    if (G2_MORE(8)) { G2_RP(T, 10) G2_RP(T, 11) }                                                              \
+    if (G2_MORE(10)) { G2_RP(T, 12) G2_RP(T, 13) }                                                             \
+    if (G2_MORE(12)) { G2_RP(T, 14) G2_RP(T, 15) }                                                             \
+    if (G2_MORE(14)) {                                                                                         \
         BEFORE                                                                                                 \
         G2_SET_E(TN, BUFB_NEXT)                                                                                \
         G2_READ(TN, 0) G2_ROW(T, 16)                                                                           \
         G2_READ(TN, 1) G2_ROW(T, 17)                                                                           \
     } else {                                                                                                   \
+        G2_STALE_LANDED()                                                                                      \
         BEFORE                                                                                                 \
         G2_SET_E(TN, BUFB_NEXT)                                                                                \
         G2_READ(TN, 0)                                                                                         \
@@ -384,7 +421,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     // ---- prologue ----
     int seq = 0, cchunk = 0, t_n[NS], t_ty[NS], t_tx[NS], t_ct, t_ext_[NS];
     tile_of(0, t_n, t_ty, t_tx, t_ct, t_ext_);
-    int rows_ = (LIST && !STRIP) ? wl_rows((unsigned)t_ext_[0]) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
+    int rows_ = (LIST && !STRIP) ? wl_rows((unsigned)t_ext_[0]) : (SH == 2 ? 14 : NB);   // output rows of the current tile that are computed (LIST: even, 2 .. 16)
     int n_ct = t_ct;                                    // cout tile of the NEXT chunk's tile
     auto next_ct = [&]() {
         if (cchunk + 1 < nchunks) return t_ct;
@@ -439,13 +476,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         if (cchunk + 1 == nchunks) {
             // ---- epilogue of this tile (the next tile's patch, weights and first rows are already in flight) ----
             const int ct = t_ct;
-            const int rows_t = STRIP ? 4 : rows_;   // (LIST) rows of this tile (STRIP: of each strip) that were computed: the others are not stored
-            // accumulator row nt belongs to output row nt of the tile -- or (STRIP) to output row nt % 4 of strip nt / 4
-            auto e_n = [&](int nt) { return STRIP ? t_n[(nt >> 2) < NS ? (nt >> 2) : 0] : t_n[0]; };
-            auto e_ty = [&](int nt) { return STRIP ? t_ty[(nt >> 2) < NS ? (nt >> 2) : 0] : t_ty[0]; };
-            auto e_tx = [&](int nt) { return STRIP ? t_tx[(nt >> 2) < NS ? (nt >> 2) : 0] : t_tx[0]; };
-            auto e_row = [&](int nt) { return STRIP ? (nt & 3) : nt; };
-            auto e_live = [&](int nt) { return STRIP ? nt < 12 : (!LIST || nt < rows_t); };
+            const int rows_t = STRIP ? SH : rows_;  // (LIST) rows of this tile (STRIP: of each strip) that were computed: the others are not stored
+            // accumulator row nt belongs to output row nt of the tile -- or (STRIP) to output row nt % SH of strip nt / SH
+            auto e_n = [&](int nt) { return STRIP ? t_n[(nt / SHD) < NS ? (nt / SHD) : 0] : t_n[0]; };
+            auto e_ty = [&](int nt) { return STRIP ? t_ty[(nt / SHD) < NS ? (nt / SHD) : 0] : t_ty[0]; };
+            auto e_tx = [&](int nt) { return STRIP ? t_tx[(nt / SHD) < NS ? (nt / SHD) : 0] : t_tx[0]; };
+            auto e_row = [&](int nt) { return STRIP ? (nt % SHD) : nt; };
+            auto e_live = [&](int nt) { return STRIP ? nt < NS * SH : (!LIST || nt < rows_t); };
             f32x4 nbias[2];                      // bias of the NEXT tile's couts: lands while this tile is stored
             load_bias(n_ct, nbias);
             const int col = halo_col(lp);
@@ -464,7 +501,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
                     const int n = t_n[sg], ty = t_ty[sg], tx = t_tx[sg];
                     if (tx * G2_T + col < a.W) {
 #pragma unroll
-                        for (int nt = STRIP ? 4 * sg : 0; nt < (STRIP ? 4 * sg + 4 : NB); ++nt)
+                        for (int nt = STRIP ? SH * sg : 0; nt < (STRIP ? SH * sg + SH : NB); ++nt)
                             if (ty * G2_T + e_row(nt) < a.H && e_live(nt)) {  // (LIST: the rows this tile computed; the rest is cvpce_mac_init's)
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
@@ -559,6 +596,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
 #undef G2_STEP
 #undef G2_HANDOFF
 #undef G2_ROWS_AND_TAIL
+#undef G2_MORE
+#undef G2_STALE_LANDED
 #undef G2_RP
 #undef G2_ROW
 #undef G2_ROW_KH
@@ -568,7 +607,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
 #undef G2_LOAD_A
 }
 
-template <typename E, bool POOL, bool GMAX, bool LIST = false, bool STRIP = false>
+template <typename E, bool POOL, bool GMAX, bool LIST = false, int SH = 0>
 static int launch_halo2(Halo2Args a, hipStream_t stream) {
     a.ctiles = (a.Cout + 255) / 256;
     a.ntiles = a.ptiles * a.ctiles;
@@ -577,13 +616,13 @@ static int launch_halo2(Halo2Args a, hipStream_t stream) {
         if (!a.mask && a.Cout % 128 == 0 && 2 * a.ntiles <= g_cvpce_persistent_wgs) {
             a.ctiles = a.Cout / 128;
             a.ntiles = a.ptiles * a.ctiles;
-            return halo_launch<conv3x3_halo2_kernel<E, false, false, false, false, 4>>(a, a.ntiles, 256, 3 * G2_A_BYTES, stream);
+            return halo_launch<conv3x3_halo2_kernel<E, false, false, false, 0, 4>>(a, a.ntiles, 256, 3 * G2_A_BYTES, stream);
         }
     }
     const int smem = a.mask ? G2_SMEM_MASKED : (LIST ? G2_SMEM_LIST : 3 * G2_A_BYTES);
     const int grid = halo_grid(a.ntiles, a.ctiles, LIST);
     if (a.mask && (a.ntiles + grid - 1) / grid > G2_MAX_SEQ) return CVPCE_ERR_ARG;   // the workgroup's tile list lives in LDS
-    return halo_launch<conv3x3_halo2_kernel<E, POOL, GMAX, LIST, STRIP>>(a, grid, 512, smem, stream, G2_SMEM_MASKED);
+    return halo_launch<conv3x3_halo2_kernel<E, POOL, GMAX, LIST, SH>>(a, grid, 512, smem, stream, G2_SMEM_MASKED);
 }
 
 // the Halo2Args of a launch without mask, tile map or list (the callers add theirs)
@@ -682,12 +721,12 @@ int cvpce_conv3x3_halo_wide_list(const void* in, const void* wgt, const float* b
 
 static int halo_list_launch(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,
                             int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
-                            int fuse_pool2, const unsigned long long* list, const int* count_dev, bool strips, void* stream) {
+                            int fuse_pool2, const unsigned long long* list, const int* count_dev, int strip_h, void* stream) {
     if (N <= 0) return CVPCE_OK;
     if ((!out && !mac) || !list || !count_dev) return CVPCE_ERR_ARG;
     if (mac && !halo2_gmax_ok(relu, Cout, mac_stride, mac_off)) return CVPCE_ERR_ARG;
     if (Cout <= 128) {
-        if (strips) return CVPCE_ERR_ARG;               // (the wide-tile kernel has no strip mode)
+        if (strip_h) return CVPCE_ERR_ARG;              // (the wide-tile kernel has no strip mode)
         return cvpce_conv3x3_halo_wide_list(in, wgt, bias, out, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, list, count_dev, stream);
     }
     const HaloShape sh{N, H, W, Cin, Cout, K_pad, Cout_pad};
@@ -695,20 +734,27 @@ static int halo_list_launch(const void* in, const void* wgt, const float* bias, 
     Halo2Args a = halo2_args(in, wgt, bias, out, mac, mac_stride, mac_off, sh, relu);
     a.list = list; a.list_count = count_dev;
     hipStream_t s = (hipStream_t)stream;
-    return halo_pick([&](auto pool, auto gm, auto strip) { return launch_halo2<ElemBF16, decltype(pool)::value, decltype(gm)::value, true, decltype(strip)::value>(a, s); },
-                     fuse_pool2 != 0, mac != nullptr, strips);
+    return halo_pick([&](auto pool, auto gm, auto strip, auto thin) {
+        return launch_halo2<ElemBF16, decltype(pool)::value, decltype(gm)::value, true, decltype(strip)::value ? (decltype(thin)::value ? 2 : 4) : 0>(a, s);
+    }, fuse_pool2 != 0, mac != nullptr, strip_h != 0, strip_h == 2);
 }
 
 extern "C" int cvpce_conv3x3_halo_list(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,
                                        int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
                                        int fuse_pool2, const unsigned long long* list, const int* count_dev, void* stream) {
-    return halo_list_launch(in, wgt, bias, out, mac, mac_stride, mac_off, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, list, count_dev, false, stream);
+    return halo_list_launch(in, wgt, bias, out, mac, mac_stride, mac_off, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, list, count_dev, 0, stream);
 }
 
 extern "C" int cvpce_conv3x3_halo_strips(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,
                                          int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
                                          int fuse_pool2, const unsigned long long* strip_list, const int* count_dev, void* stream) {
-    return halo_list_launch(in, wgt, bias, out, mac, mac_stride, mac_off, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, strip_list, count_dev, true, stream);
+    return halo_list_launch(in, wgt, bias, out, mac, mac_stride, mac_off, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, strip_list, count_dev, 4, stream);
+}
+
+extern "C" int cvpce_conv3x3_halo_strips2(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,
+                                          int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
+                                          int fuse_pool2, const unsigned long long* thin_list, const int* count_dev, void* stream) {
+    return halo_list_launch(in, wgt, bias, out, mac, mac_stride, mac_off, N, H, W, Cin, Cout, K_pad, Cout_pad, relu, fuse_pool2, thin_list, count_dev, 2, stream);
 }
 
 // [host] row-major chunk-major [Cout_pad][9 Cin] -> the fragment-major halo weight layout (include/cvpce_amd.h)

@@ -260,18 +260,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
         { G3_TIC() if (!(CVPCE_DBG & 64)) __builtin_amdgcn_s_barrier(); G3_TOC(2) }     /* (64: timing-only ablation, no hand-off wait / barrier) */ \
         issue_next_patch();                                                                                    \
     }
-    // LIST launches compute only the first `rows_` (4 | 8 | 12 | 16) output rows of a tile: see G2_ROWS_AND_TAIL in conv3x3_halo2.hip
+    // LIST launches compute only the first `rows_` (even, 2 .. 16) output rows of a tile, a branch per row pair: see G2_ROWS_AND_TAIL in
+    // conv3x3_halo2.hip (the same ring, the same argument for rows_ = 0 and = 2 mod 4)
+#define G3_MORE(R) (!LIST || rows_ > (R))
 #define G3_ROWS_AND_TAIL(T, TN, BUFB_NEXT, BEFORE)                                                             \
-    G3_RP(T, 0) G3_RP(T, 1) G3_RP(T, 2) G3_RP(T, 3) G3_RP(T, 4) G3_RP(T, 5)                                    \
-    if (!LIST || rows_ > 4) { G3_RP(T, 6) G3_RP(T, 7) G3_RP(T, 8) G3_RP(T, 9) }                                \
-    if (!LIST || rows_ > 8) { G3_RP(T, 10) G3_RP(T, 11) G3_RP(T, 12) G3_RP(T, 13) }                            \
-    if (!LIST || rows_ > 12) {                                                                                 \
-        G3_RP(T, 14) G3_RP(T, 15)                                                                              \
+    G3_RP(T, 0) G3_RP(T, 1) G3_RP(T, 2) G3_RP(T, 3)                                                            \
+    if (G3_MORE(2)) { G3_RP(T, 4) G3_RP(T, 5) }                                                                \
+    if (G3_MORE(4)) { G3_RP(T, 6) G3_RP(T, 7) }                                                                \
+    if (G3_MORE(6)) { G3_RP(T, 8) G3_RP(T, 9) }                                                                \
+    if (G3_MORE(8)) { G3_RP(T, 10) G3_RP(T, 11) }                                                              \
+    if (G3_MORE(10)) { G3_RP(T, 12) G3_RP(T, 13) }                                                             \
+    if (G3_MORE(12)) { G3_RP(T, 14) G3_RP(T, 15) }                                                             \
+    if (G3_MORE(14)) {                                                                                         \
         BEFORE                                                                                                 \
         G3_SET_E(TN, BUFB_NEXT)                                                                                \
         G3_READ(TN, 0) G3_ROW(T, 16)                                                                           \
         G3_READ(TN, 1) G3_ROW(T, 17)                                                                           \
     } else {                                                                                                   \
+        /* the stale reads have landed before anything else is computed: see G2_STALE_LANDED */                \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
         BEFORE                                                                                                 \
         G3_SET_E(TN, BUFB_NEXT)                                                                                \
         G3_READ(TN, 0)                                                                                         \
@@ -300,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
     // ---- prologue ----
     int seq = 0, cchunk = 0, t_n, t_ty, t_tx, t_ct, t_ext_;
     tile_of(0, t_n, t_ty, t_tx, t_ct, t_ext_);
-    int rows_ = LIST ? wl_rows((unsigned)t_ext_) : NB;     // output rows of the current tile that are computed (LIST: 4 | 8 | 12 | 16)
+    int rows_ = LIST ? wl_rows((unsigned)t_ext_) : NB;     // output rows of the current tile that are computed (LIST: even, 2 .. 16)
     int n_ct = t_ct;                                    // cout tile of the NEXT chunk's tile
     auto next_ct = [&]() {
         if (cchunk + 1 < nchunks) return t_ct;
@@ -441,6 +449,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
 #undef G3_STEP
 #undef G3_HANDOFF
 #undef G3_ROWS_AND_TAIL
+#undef G3_MORE
 #undef G3_RP
 #undef G3_ROW
 #undef G3_READ

@@ -5,7 +5,7 @@
 //
 //   n        image (crop) of the tile; image N - 1 of every tensor is the constant crop
 //   ty, tx   tile row / column in the image, in the tile size of the kernel that walks the list
-//   rows     how many of the tile's 16 conv-output rows are computed (4 | 8 | 12 | 16)
+//   rows     how many of the tile's 16 conv-output rows are computed (even, 2 .. 16; the list modes 2 and 3 of skiplist.hip: 4 | 8 | 12 | 16)
 //   ey, ex   the crop's content extent on the kernel's INPUT tensor: pixels with y >= ey or x >= ex are read from the constant crop
 // The kernels read an entry as its two 32-bit words (one readfirstlane each) and take the fields from those.
 #pragma once

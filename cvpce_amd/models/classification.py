@@ -51,6 +51,26 @@ SKIP_MAC = _os.environ.get('CVPCE_SKIP_MAC', '1') != '0'
 # on the bench's boxes) are computed three at a time (`cvpce_conv3x3_halo_strips`): alone such a tile issues a third of the MFMAs of a
 # full one against the same weight stream, which bounds it.  A/B switch.
 SKIP_STRIPS = _os.environ.get('CVPCE_SKIP_STRIPS', '1') != '0'
+# ... and the lists are built in the FINE modes (csrc/skiplist.hip, skip 4 / 5): listed tiles are cut at their last non-constant row
+# PAIR instead of at a multiple of 4 rows, and last-row tiles with only 2 useful rows go to a thin strip list, computed four at a time
+# (`cvpce_conv3x3_halo_strips2`).  `skip_plan` is unchanged: `_embed_skip` maps its modes 2 -> 4 and 3 -> 5 when it builds the lists.
+# A/B switch; SKIP_FINE_PARTS (dev A/B) names the parts that are on: even rows in the wide-tile kernel (Cout <= 128), even rows in
+# the 16 x 16-tile kernel, the thin strip lists (which need the latter).  Each part is on by default only if it won its own same-call
+# A/B (profiles/r16_fine_lists.md, 1 600 bench-shaped crops): even rows + thin strips in the 16 x 16-tile kernel -0.82 ms of 24.5, every
+# run; even rows alone, in either kernel, inside the 0.2 ms spread -- so the wide-tile kernel's layers keep the 4-row cut.
+SKIP_FINE = _os.environ.get('CVPCE_SKIP_FINE', '1') != '0'
+SKIP_FINE_PARTS = tuple(p for p in _os.environ.get('CVPCE_SKIP_FINE_PARTS', 'halo2,thin').split(',') if p)
+
+
+def _fine_mode(mode, cout):
+    """The list mode `_embed_skip` hands to `ops.embed_worklists` for a layer whose `skip_plan` mode is `mode`."""
+    if not SKIP_FINE or mode not in (2, 3):
+        return mode
+    if cout <= 128:
+        return 4 if (mode == 2 and 'halo3' in SKIP_FINE_PARTS) else mode
+    if 'halo2' not in SKIP_FINE_PARTS:
+        return mode
+    return 4 if mode == 2 else (5 if 'thin' in SKIP_FINE_PARTS else mode)
 
 
 def _passes(n, step, longest):
@@ -222,6 +242,8 @@ class MACVGGEngine:
             tiles per workgroup -- the uneven tail of a launch (workgroups run out of tiles a tile apart) costs half as much."""
         steps, layers, pool_mask = sched
         N, S, nl = x.shape[0], x.shape[1], len(steps)
+        # the fine list modes (SKIP_FINE): layer 0 is the stem, whose mode stays
+        layers = [l if i == 0 else l[:-1] + [_fine_mode(l[-1], steps[i][1].cout)] for i, l in enumerate(layers)]
         early = 1 + sum(1 for st in steps[1:] if st[1].cout <= 128 and not st[3])
         if any(st[1].cout <= 128 for st in steps[early:]):
             early = nl                                     # (not the VGG16 shape: wide-tile layers after halo2 ones -- everything in passes)
@@ -236,6 +258,7 @@ class MACVGGEngine:
             res = ops.embed_worklists(ext_, n_img, S, pool_mask, sub, (S // 16) ** 2 if first == 0 else max(1, (sub[0][5] // 16)) ** 2,
                                       want_computed=mac_skips)
             lists, counts = res[0], res[1]
+            has_thin = any(l[-1] == 5 for l in sub)          # then the thin lists / their counts follow the strip lists / counts
             if mac_skips:
                 o = sum(st[1].cout for st in steps[1:first] if st[3])
                 for j in range(k):
@@ -251,7 +274,8 @@ class MACVGGEngine:
                 kind, pc, pool, mac, store = steps[li]
                 t = ops.conv2d_list(t, pc, lists[j], counts[j:j + 1], act=1, pool=pool, mac=desc if mac else None, mac_off=off, store=store,
                                     units=counts[k + j:k + j + 1], out=out_last if (j == k - 1 and store) else None,
-                                    strips=(lists[k + j], counts[2 * k + j:2 * k + j + 1]) if layers[li][-1] == 3 else None)
+                                    strips=(lists[k + j], counts[2 * k + j:2 * k + j + 1]) if layers[li][-1] in (3, 5) else None,
+                                    thin=(lists[2 * k + j], counts[3 * k + j:3 * k + j + 1]) if (has_thin and layers[li][-1] == 5) else None)
                 if mac:
                     off += pc.cout
             return t

@@ -12,6 +12,7 @@ import torch
 from ._lib import lib
 from .torch_ops import T
 from . import torch_ops_input  # noqa: F401  (registers torch.ops.cvpce_amd.*_u8, the byte-reading input kernels)
+from . import torch_ops_lists  # noqa: F401  (registers torch.ops.cvpce_amd.conv3x3_halo_strips2, the thin-strip launch)
 
 BF16 = torch.bfloat16
 F16 = torch.float16
@@ -614,11 +615,13 @@ def embed_worklists(ext0, n_images, size, pool_mask, layers, max_tiles, want_com
     """ext0 (n_images - 1, 2) int32 (the last image is the implied constant crop); pool_mask: the pass's op chain (bit i: op i is
     a 2x2 pool, else a 3x3 conv); layers: list of `skip_layer` -> (lists (2 L, n_images * max_tiles) int64: the layers' lists, then
     their strip lists; counts (3 L,) int32: tiles per layer, the layers' MFMA work in sixteenths of a tile, strip entries [, computed (L, n_images, 2) int32: conv rows computed /
-    tile columns listed per crop]), all on the device, no synchronisation."""
+    tile columns listed per crop]), all on the device, no synchronisation.  With a layer of skip mode 5 the tensors carry the thin strip
+    lists as well: lists (3 L, ...), rows 2 L .. the thin lists; counts (4 L,), the last L the thin-strip entries."""
     _need_cuda(ext0)
     dev = ext0.device if ext0 is not None else torch.device('cuda', torch.cuda.current_device())
-    lists = torch.empty((2 * len(layers), n_images * max_tiles), dtype=torch.int64, device=dev)       # rows L ..: the layers' strip lists
-    counts = torch.empty((3 * len(layers),), dtype=torch.int32, device=dev)
+    thin = any(l[-1] == 5 for l in layers)
+    lists = torch.empty(((3 if thin else 2) * len(layers), n_images * max_tiles), dtype=torch.int64, device=dev)   # rows L ..: the layers' strip lists
+    counts = torch.empty(((4 if thin else 3) * len(layers),), dtype=torch.int32, device=dev)
     computed = torch.empty((len(layers), n_images, 2), dtype=torch.int32, device=dev) if want_computed else None
     T.embed_worklists(ext0, int(n_images), int(size), int(pool_mask), [v for l in layers for v in l], lists, counts, computed)
     return (lists, counts, computed) if want_computed else (lists, counts)
@@ -644,10 +647,11 @@ def vgg_stem_list(x, const_in, ps, work, count):
     return out
 
 
-def conv2d_list(x, pc, work, count, act=1, pool=False, mac=None, mac_off=0, store=True, units=None, strips=None, out=None):
+def conv2d_list(x, pc, work, count, act=1, pool=False, mac=None, mac_off=0, store=True, units=None, strips=None, out=None, thin=None):
     """3x3 / s1 / p1 conv (+ReLU, + fused MaxPool2d(2,2), + fused MAC descriptor) over a work list; x (N,H,W,Cin) with the
     constant crop as image N - 1.  strips = (strip list, its count): a second launch computes the layer's strip list (tiles with
-    only 4 useful rows, three at a time) into the same output.  Returns the output tensor (None with store=False)."""
+    only 4 useful rows, three at a time) into the same output; thin = (thin strip list, its count): a further launch computes the
+    tiles with only 2 useful rows, four at a time.  Returns the output tensor (None with store=False)."""
     _need_cuda(x, work, count, mac)
     assert x.dtype == BF16 and pc.dtype == BF16 and x.is_contiguous() and x.dim() == 4
     assert pc.cin_pad % 64 == 0 and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1) and pc.cout % 8 == 0 and pc.cout > 64
@@ -668,7 +672,11 @@ def conv2d_list(x, pc, work, count, act=1, pool=False, mac=None, mac_off=0, stor
         tag = f'{pc.cin}->{pc.cout}@{h}' + ('mac' if mac is not None else '')
         # (`units` counts the layer's whole MFMA work in sixteenths of a tile, its strip launch included: a strip-list entry is 4 of
         # them (csrc/skiplist.hip) and is filed with the STRIP launch below, a different template instance with its own duration)
-        lunits = (units - 4 * strips[1]) if (units is not None and strips is not None) else units
+        lunits = units
+        if units is not None and strips is not None:
+            lunits = lunits - 4 * strips[1]
+        if units is not None and thin is not None:
+            lunits = lunits - 2 * thin[1]                       # (a thin-strip entry is 2 of them)
         t.file('conv3x3_halo3_kernel' if wide else 'conv3x3_halo2_kernel', 2.0 * (n - 1) * h * w * pc.cout * 9 * pc.cin,
                extras=((lunits, tile_flops / 16) if units is not None else (count, tile_flops)) + (tag,))
     if strips is not None:
@@ -677,6 +685,12 @@ def conv2d_list(x, pc, work, count, act=1, pool=False, mac=None, mac_off=0, stor
         if t is not None:
             t.stop()
             t.file('conv3x3_halo2_kernel[strips]', 0.0, extras=(strips[1], tile_flops / 4, tag))     # (timed from the list launch's end)
+    if thin is not None:
+        assert pc.cout > 128
+        T.conv3x3_halo_strips2(x, pc.weight_halo, pc.bias, out, mac, int(mac_off), pc.cout, pc.k_pad, pc.cout_pad, int(act), int(pool and store), thin[0], thin[1])
+        if t is not None:
+            t.stop()
+            t.file('conv3x3_halo2_kernel[strips]', 0.0, extras=(thin[1], tile_flops / 8, tag))       # (timed from the launch before it)
     return out
 
 

@@ -259,11 +259,13 @@ def _mac_init(desc, off, row_suffix_max, col_suffix_max, computed):
 @_op('embed_worklists(Tensor? ext0, int n_images, int size, int pool_mask, int[] layers, Tensor(a!) lists, Tensor(b!) counts, '
      'Tensor(c!)? computed) -> ()')
 def _embed_worklists(ext0, n_images, size, pool_mask, layers, lists, counts, computed):
-    """layers: 9 ints per layer in the field order of `cvpce_skip_layer`; lists (2 * n_layers, stride) int64 (lists, then strip lists); counts (3 * n_layers,) int32 (tiles, row units, strip entries)."""
+    """layers: 9 ints per layer in the field order of `cvpce_skip_layer`; lists (2 * n_layers, stride) int64 (lists, then strip lists); counts (3 * n_layers,) int32 (tiles, row units, strip entries).
+    With a layer of skip == 5: lists (3 * n_layers, stride), the thin strip lists last; counts (4 * n_layers,), the thin-strip entries last."""
     nf = len(_lib.SkipLayer._fields_)
     nl = len(layers) // nf
-    if len(layers) != nl * nf or lists.dtype != torch.int64 or not lists.is_contiguous() or lists.shape[0] != 2 * nl or counts.dtype != torch.int32 \
-            or counts.numel() != 3 * nl or (ext0 is not None and (ext0.dtype != torch.int32 or not ext0.is_contiguous() or ext0.numel() < 2 * (n_images - 1))):
+    thin = any(int(layers[i * nf + nf - 1]) == 5 for i in range(nl))
+    if len(layers) != nl * nf or lists.dtype != torch.int64 or not lists.is_contiguous() or lists.shape[0] != (3 if thin else 2) * nl or counts.dtype != torch.int32 \
+            or counts.numel() != (4 if thin else 3) * nl or (ext0 is not None and (ext0.dtype != torch.int32 or not ext0.is_contiguous() or ext0.numel() < 2 * (n_images - 1))):
         raise RuntimeError('embed_worklists: bad argument shapes / types')
     arr = (_lib.SkipLayer * nl)(*[_lib.SkipLayer(*[int(v) for v in layers[i * nf:(i + 1) * nf]]) for i in range(nl)])
     if computed is not None and (computed.dtype != torch.int32 or not computed.is_contiguous() or computed.numel() < 2 * nl * n_images):

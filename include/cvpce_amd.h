@@ -28,7 +28,7 @@
  *   whatever the tile size of the kernel behind it: ragged tiles are masked, never rounded up into the neighbouring memory.
  *   Inputs are never written.  An output is written in full, except under these partial-write contracts, where the rest of the
  *   buffer is left exactly as it was:
- *     - work-list and strip launches (cvpce_vgg_stem_fused_list, cvpce_conv3x3_halo_list, cvpce_conv3x3_halo_strips): the listed
+ *     - work-list and strip launches (cvpce_vgg_stem_fused_list, cvpce_conv3x3_halo_list, cvpce_conv3x3_halo_strips, cvpce_conv3x3_halo_strips2): the listed
  *       tiles only, and of a tile cut at `rows` only those rows; cvpce_embed_worklists writes counts[l] entries of list row l;
  *     - cvpce_conv3x3_halo_masked with a tile_map: the tiles on the map only (every pixel of those, zeros on the gaps);
  *     - count-limited crops (cvpce_crop_resize, cvpce_crop_resize_content): boxes p >= *count_dev are skipped; the content form
@@ -269,18 +269,24 @@ typedef struct {
     int in_H, in_W;            /* the layer's INPUT tensor */
     int in_ops;                /* ... and its name */
     int skip;                  /* 0: list every tile; 1: leave out the tiles that are wholly constant; 2: ... and cut the listed tiles at their
-                                  last non-constant row (`rows`); 3: ... and move the tiles with rows == 4 to the layer's STRIP list */
+                                  last non-constant row (`rows` rounded up to 4); 3: ... and move the tiles with rows == 4 to the layer's STRIP
+                                  list; 4: as 2 with `rows` rounded up to 2; 5: as 3 with `rows` rounded up to 2, and the last-row tiles with
+                                  rows == 2 moved to the layer's THIN strip list */
 } cvpce_skip_layer;
 /* ext0 [n_images - 1][2] (cvpce_crop_extents; the constant crop, image n_images - 1, is implied), layers [host] ->
  * lists[l * list_stride + i] for i < counts[l] (device): the tiles layer l computes, crop-major,
  *   entry = ((rows << 24 | ey_in << 12 | ex_in) << 32) | (n << 16) | (ty << 8) | tx
- * (ey_in / ex_in < 4096: the INPUT tensor's extents of crop n; rows in {4, 8, 12, 16}: the tile's conv-output rows that are not
- * wholly constant, rounded up to 4 -- the halo kernels compute only those, the rest of the tile is neither computed nor stored)
+ * (ey_in / ex_in < 4096: the INPUT tensor's extents of crop n; rows: the tile's conv-output rows that are not wholly constant,
+ * rounded up to 4 (skip 2, 3: rows in {4, 8, 12, 16}) or to 2 (skip 4, 5: any even number 2 .. 16) -- the halo kernels compute the
+ * first `rows` rows of a listed tile for ANY even `rows`, the rest of the tile is neither computed nor stored)
  * list_stride >= n_images * tiles of the largest layer.  No host synchronisation: the kernels read counts[l] themselves.
  * `lists` has 2 * n_layers rows: row n_layers + l is layer l's STRIP list (skip == 3: its tiles with rows == 4, same entry format,
- * for cvpce_conv3x3_halo_strips; empty otherwise).
+ * for cvpce_conv3x3_halo_strips; skip == 5: its last-row tiles with rows == 4; empty otherwise).
+ * When a layer has skip == 5, `lists` has 3 * n_layers rows and counts 4 * n_layers entries: row 2 * n_layers + l is layer l's THIN
+ * strip list (its last-row tiles with rows == 2, for cvpce_conv3x3_halo_strips2 of include/cvpce_amd_lists.h; empty for the other modes) and
+ * counts[3 * n_layers + l] its entries.  Without such a layer the shapes, and every value, are those of modes 0 .. 3.
  * counts has 3 * n_layers entries: counts[n_layers + l] = the MFMA work layer l performs, in sixteenths of a full tile (a tile cut
- * at `rows` < 16 streams rows + 1 of its 16 row groups, a strip counts 4) -- what `roofline` counts as executed FLOPs;
+ * at `rows` < 16 streams rows + 1 of its 16 row groups, a strip counts 4, a thin strip 2) -- what `roofline` counts as executed FLOPs;
  * counts[2 * n_layers + l] = entries of layer l's strip list.
  * computed (optional, [n_layers][n_images][2]): per layer and crop, (conv-output rows computed, tile columns listed) -- the region
  * cvpce_mac_init has to cover from the constant crop. */
@@ -355,6 +361,7 @@ int cvpce_conv3x3_halo_thin_out(const void* in, const void* wgt, const float* bi
 int cvpce_conv3x3_halo_strips(const void* in, const void* wgt, const float* bias, void* out, float* mac, int mac_stride,
                               int mac_off, int N, int H, int W, int Cin, int Cout, int K_pad, int Cout_pad, int relu,
                               int fuse_pool2, const unsigned long long* strip_list, const int* count_dev, void* stream);
+/* (The companion for a layer's THIN strip list, cvpce_skip_layer.skip == 5, is declared in include/cvpce_amd_lists.h.) */
 
 /* ---- fp16 twins: the detector's opt-in accuracy mode ------------------------------------------------------------------
  * `gln(..., precision='fp16')` / `GaussianLayerNetwork.set_precision('fp16')` stores the detector's weights and inter-layer
