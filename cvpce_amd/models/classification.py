@@ -10,6 +10,7 @@ of HIP kernels: 13 MFMA implicit-GEMM 3x3 convolutions with fused bias+ReLU,
 4 max-pools, two global-max (MAC) reductions and an L2 normalisation.
 """
 from collections import OrderedDict
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -63,14 +64,45 @@ SKIP_FINE_PARTS = tuple(p for p in _os.environ.get('CVPCE_SKIP_FINE_PARTS', 'hal
 
 
 def _fine_mode(mode, cout):
-    """The list mode `_embed_skip` hands to `ops.embed_worklists` for a layer whose `skip_plan` mode is `mode`."""
-    if not SKIP_FINE or mode not in (2, 3):
+    """The list mode `_embed_skip` hands to `ops.embed_worklists` for a layer whose `skip_plan` mode is `mode` (the switches are read now)."""
+    M = ops.SkipMode
+    if not SKIP_FINE or mode not in (M.ROWS4, M.ROWS4_STRIPS):
         return mode
     if cout <= 128:
-        return 4 if (mode == 2 and 'halo3' in SKIP_FINE_PARTS) else mode
+        return M.ROWS2 if (mode == M.ROWS4 and 'halo3' in SKIP_FINE_PARTS) else mode
     if 'halo2' not in SKIP_FINE_PARTS:
         return mode
-    return 4 if mode == 2 else (5 if 'thin' in SKIP_FINE_PARTS else mode)
+    return M.ROWS2 if mode == M.ROWS4 else (M.ROWS2_STRIPS_THIN if 'thin' in SKIP_FINE_PARTS else mode)
+
+
+class SkipStep(NamedTuple):
+    """One launch of the work-list schedule."""
+    kind: str                          # 'stem' | 'conv'
+    pc: Optional[ops.PackedConv]       # (None: the stem)
+    pool: bool                         # MaxPool2d(2,2) fused into the epilogue
+    mac: bool                          # the MAC descriptor taken in the epilogue ...
+    store: bool                        # (False: the map itself is not written)
+    mac_off: int = 0                   # ... into descriptor columns mac_off .. mac_off + Cout
+
+
+class SkipSchedule(NamedTuple):
+    """`skip_plan`: the steps, one `ops.SkipLayer` per step, the op chain's pool bits."""
+    steps: list
+    layers: list
+    pool_mask: int
+
+    @property
+    def early(self):
+        """steps[:early] run in passes of <= FUSED_EMBED_MAX images, the rest once over all crops (`_embed_skip`): the stem and the
+        Cout <= 128 convs; every step when a wide-tile layer follows a 16 x 16-tile one (not the VGG16 shape)."""
+        early = 1 + sum(1 for st in self.steps[1:] if st.pc.cout <= 128 and not st.mac)
+        return len(self.steps) if any(st.pc.cout <= 128 for st in self.steps[early:]) else early
+
+
+def _bn_affine(bn):
+    """Eval-mode BatchNorm as y = x * scale + shift -> (scale, shift), on the module's device."""
+    scale = bn.weight * (bn.running_var + bn.eps).rsqrt()
+    return scale, bn.bias - bn.running_mean * scale
 
 
 def _passes(n, step, longest):
@@ -104,6 +136,10 @@ class MACVGGEngine:
     def __init__(self, model, device):
         self.plan = []
         mods = list(model.block1) + ['desc1'] + list(model.block2)
+
+        def bn_after(i):                                   # eval-mode BN folded into conv i -> (scale, shift) | (None, None)
+            return _bn_affine(mods[i + 1]) if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) else (None, None)
+
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -115,11 +151,7 @@ class MACVGGEngine:
                 else:
                     self.plan.append(('pool', None))
             elif isinstance(m, nn.Conv2d):
-                scale = shift = None
-                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d):
-                    bn = mods[i + 1]
-                    scale = bn.weight * (bn.running_var + bn.eps).rsqrt()
-                    shift = bn.bias - bn.running_mean * scale
+                scale, shift = bn_after(i)
                 self.plan.append(('conv', ops.PackedConv(m.weight, m.bias, 1, 1, scale=scale, shift=shift, device=device)))
             i += 1
         # conv1_1 + conv1_2 + pool1 fused into one persistent kernel when the plan starts with exactly that
@@ -130,70 +162,71 @@ class MACVGGEngine:
             for i, m in enumerate(mods):
                 if isinstance(m, nn.Conv2d) and len(packed) < 4:
                     w, b = m.weight.detach().float().cpu(), m.bias.detach().float().cpu()
-                    if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d):   # eval-mode BN folded in
-                        bn = mods[i + 1]
-                        sc = (bn.weight * (bn.running_var + bn.eps).rsqrt()).detach().float().cpu()
-                        w = w * sc[:, None, None, None]
-                        b = b * sc + (bn.bias.detach().float().cpu() - bn.running_mean.detach().float().cpu() * sc)
+                    scale, shift = bn_after(i)
+                    if scale is not None:
+                        sc = scale.detach().float().cpu()
+                        w, b = w * sc[:, None, None, None], b * sc + shift.detach().float().cpu()
                     packed += [w, b]
             self.stem = ops.PackedStem(*packed, device=device)
             self.plan = self.plan[2:]
         self.device = device
         self.embedding_size = model.embedding_size
-        self._skip_plans = {}      # input size -> the work-list schedule of `_embed_skip` (None: this plan has no such schedule)
-        self._mac_tables = {}      # id of a constant crop -> per MAC layer, the row / column suffix maxima of the constant crop's map
+        self._skip_plans = {}      # (input size, the switches `skip_plan` reads) -> SkipSchedule | None (this plan has no such schedule)
+        self._mac_tables = {}      # (constant crop, schedule) -> (that crop, per MAC layer the row / column suffix maxima of its map)
         self._const_crops = {}     # (mean, std, channels, size) -> the all-padding crop
 
     # ---- constant-padding tile skipping --------------------------------------------------------------------------------------
     def skip_plan(self, size):
-        """The work-list schedule for size x size inputs: (steps [(kind, PackedConv | None, pool, mac, store)], one `ops.skip_layer`
-        per step, pool_mask), or None when this engine's plan is not stem + 3x3 halo convolutions with the MAC descriptors fused
-        (then nothing is skipped).  Extent bookkeeping (include/cvpce_amd.h `cvpce_skip_layer`): the pass is a chain of ops on
-        the crop -- conv (+1) and pool (halve upwards) -- and every tensor is named by the number of ops before it."""
-        key = (size, SKIP_ROWS, SKIP_MAC, SKIP_STRIPS)
-        if key in self._skip_plans:
-            return self._skip_plans[key]
-        steps, layers, chain = None, [], []
-        if self.stem is not None and size % 16 == 0 and size <= 1024:
-            steps = [('stem', None, True, False)]
-            chain += [0, 0, 1]                               # conv1_1, conv1_2, pool1
-            h = size // 2
-            layers.append(ops.skip_layer(h, h, 8, 8, len(chain), size, size, 0, 1))
-            plan = self.plan + [('desc', None)]
-            i = 0
-            while steps is not None and i < len(plan):
-                kind, pc = plan[i]
-                if kind not in ('conv', 'conv_pool') or not (pc.cin_pad % 64 == 0 and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1)
-                                                             and pc.cout % 8 == 0 and pc.cout > 64 and pc.dtype == ops.BF16):
-                    steps = None
-                    break
-                mac = kind == 'conv' and i + 1 < len(plan) and plan[i + 1][0] == 'desc' and pc.cout > 128 and ops.USE_FUSED_MAC
-                after = plan[i + 2][0] if i + 2 < len(plan) else None
-                pool = kind == 'conv_pool' or (mac and after == 'pool' and h % 2 == 0)
-                store = not mac or after is not None
-                th, tw = (16, 32) if pc.cout <= 128 else (16, 16)
-                in_ops, oh = len(chain), h
-                chain.append(0)
-                if pool:
-                    chain.append(1)
-                    th, tw, oh = th // 2, tw // 2, h // 2
-                if not store:
-                    oh, th, tw = h, 16, 16
-                mode = 0 if (mac and not SKIP_MAC) else (1 if not SKIP_ROWS else (3 if (SKIP_STRIPS and pc.cout > 128) else 2))
-                layers.append(ops.skip_layer(oh, oh, th, tw, len(chain), h, h, in_ops, mode))
-                steps.append(('conv', pc, pool, mac, store))
-                i += (3 if pool else 2) if mac else 1
-                if not mac and i < len(plan) and plan[i][0] != 'conv' and plan[i][0] != 'conv_pool':
-                    steps = None                              # a stand-alone pool / descriptor: not this schedule
-                    break
-                h = oh
-                if h % 16 != 0 and i < len(plan):
-                    steps = None
-            if steps is not None and len(chain) > 32:
-                steps = None
-        pool_mask = sum(1 << i for i, p in enumerate(chain) if p)
-        self._skip_plans[key] = None if steps is None else (steps, layers, pool_mask)
+        """The work-list schedule for size x size inputs: SkipSchedule(steps [SkipStep], one `ops.skip_layer` per step, pool_mask),
+        or None when this engine's plan is not stem + 3x3 halo convolutions with the MAC descriptors fused (then nothing is
+        skipped).  Cached under every switch it reads."""
+        key = (size, SKIP_ROWS, SKIP_MAC, SKIP_STRIPS, ops.USE_FUSED_MAC)
+        if key not in self._skip_plans:
+            self._skip_plans[key] = self._make_skip_plan(size)
         return self._skip_plans[key]
+
+    def _make_skip_plan(self, size):
+        """Extent bookkeeping (include/cvpce_amd.h `cvpce_skip_layer`): the pass is a chain of ops on the crop -- conv (+1) and pool
+        (halve upwards) -- and every tensor is named by the number of ops before it."""
+        M = ops.SkipMode
+        if self.stem is None or size % 16 != 0 or size > 1024:
+            return None
+        chain = [0, 0, 1]                                    # conv1_1, conv1_2, pool1
+        h = size // 2
+        steps = [SkipStep('stem', None, True, False, True)]
+        layers = [ops.skip_layer(h, h, 8, 8, len(chain), size, size, 0, M.TILES)]
+        plan = self.plan + [('desc', None)]
+        i = mac_off = 0
+        while i < len(plan):
+            kind, pc = plan[i]
+            if kind not in ('conv', 'conv_pool') or not (pc.cin_pad % 64 == 0 and (pc.kh, pc.kw, pc.stride, pc.pad) == (3, 3, 1, 1)
+                                                         and pc.cout % 8 == 0 and pc.cout > 64 and pc.dtype == ops.BF16):
+                return None
+            mac = kind == 'conv' and i + 1 < len(plan) and plan[i + 1][0] == 'desc' and pc.cout > 128 and ops.USE_FUSED_MAC
+            after = plan[i + 2][0] if i + 2 < len(plan) else None
+            pool = kind == 'conv_pool' or (mac and after == 'pool' and h % 2 == 0)
+            store = not mac or after is not None
+            th, tw = (16, 32) if pc.cout <= 128 else (16, 16)
+            in_ops, oh = len(chain), h
+            chain.append(0)
+            if pool:
+                chain.append(1)
+                th, tw, oh = th // 2, tw // 2, h // 2
+            if not store:
+                oh, th, tw = h, 16, 16
+            mode = M.NONE if (mac and not SKIP_MAC) else (M.TILES if not SKIP_ROWS else (M.ROWS4_STRIPS if (SKIP_STRIPS and pc.cout > 128) else M.ROWS4))
+            layers.append(ops.skip_layer(oh, oh, th, tw, len(chain), h, h, in_ops, mode))
+            steps.append(SkipStep('conv', pc, pool, mac, store, mac_off))
+            mac_off += pc.cout if mac else 0
+            i += (3 if pool else 2) if mac else 1
+            if not mac and i < len(plan) and plan[i][0] not in ('conv', 'conv_pool'):
+                return None                                   # a stand-alone pool / descriptor: not this schedule
+            h = oh
+            if h % 16 != 0 and i < len(plan):
+                return None
+        if len(chain) > 32:
+            return None
+        return SkipSchedule(steps, layers, sum(1 << i for i, p in enumerate(chain) if p))
 
     def const_crop(self, mean, std, channels, size):
         """The all-padding crop in the layout the crop kernel writes: made BY the crop kernel from a zero-area box, so its
@@ -212,24 +245,22 @@ class MACVGGEngine:
         entry at the first row / column its list leaves out."""
         key = (const_in.data_ptr(), id(sched))
         if key in self._mac_tables:
-            return self._mac_tables[key]
-        steps = sched[0]
+            return self._mac_tables[key][1]
         t = ops.vgg_stem(const_in[None].contiguous(), self.stem)
         tables = {}
-        for li, (kind, pc, pool, mac, store) in enumerate(steps[1:], start=1):
-            if not mac:
-                t = ops.conv2d(t, pc, act=1, pool=pool)
+        for li, st in enumerate(sched.steps[1:], start=1):
+            if not st.mac:
+                t = ops.conv2d(t, st.pc, act=1, pool=st.pool)
                 continue
-            full = ops.conv2d(t, pc, act=1)                               # the map the MAC epilogue takes its maximum over
+            full = ops.conv2d(t, st.pc, act=1)                             # the map the MAC epilogue takes its maximum over
             m = full[0].to(torch.float32)                                 # (H, W, C), values >= 0
             zero = torch.zeros((1, m.shape[2]), dtype=torch.float32, device=m.device)
             rows = torch.cat((torch.cummax(m.amax(dim=1).flip(0), 0).values.flip(0), zero)).contiguous()
             cols = torch.cat((torch.cummax(m.amax(dim=0).flip(0), 0).values.flip(0), zero)).contiguous()
             tables[li] = (rows, cols)
-            if store:
-                t = ops.maxpool2d(full, 2, 2) if pool else full
-        self._mac_tables[key] = tables
-        self._keep_const = getattr(self, '_keep_const', []) + [const_in]  # (the key holds a data pointer: keep the tensor alive)
+            if st.store:
+                t = ops.maxpool2d(full, 2, 2) if st.pool else full
+        self._mac_tables[key] = (const_in, tables)                        # (the key holds a data pointer: the entry keeps the tensor alive)
         return tables
 
     def _embed_skip(self, x, ext, const_in, sched):
@@ -241,43 +272,29 @@ class MACVGGEngine:
           * LATE layers (conv3_1 on: <= 2 MB per crop) in ONE pass over all N + 1 images: half as many launches, each with twice the
             tiles per workgroup -- the uneven tail of a launch (workgroups run out of tiles a tile apart) costs half as much."""
         steps, layers, pool_mask = sched
-        N, S, nl = x.shape[0], x.shape[1], len(steps)
+        N, S, nl, early = x.shape[0], x.shape[1], len(steps), sched.early
         # the fine list modes (SKIP_FINE): layer 0 is the stem, whose mode stays
-        layers = [l if i == 0 else l[:-1] + [_fine_mode(l[-1], steps[i][1].cout)] for i, l in enumerate(layers)]
-        early = 1 + sum(1 for st in steps[1:] if st[1].cout <= 128 and not st[3])
-        if any(st[1].cout <= 128 for st in steps[early:]):
-            early = nl                                     # (not the VGG16 shape: wide-tile layers after halo2 ones -- everything in passes)
+        layers = [l if i == 0 else l._replace(skip=int(_fine_mode(l.mode, steps[i].pc.cout))) for i, l in enumerate(layers)]
         dev = x.device
-        mac_skips = any(st[3] and layers[i][-1] for i, st in enumerate(steps) if i)      # a MAC layer whose list leaves tiles / rows out
+        mac_skips = any(st.mac and l.mode != ops.SkipMode.NONE for st, l in zip(steps, layers))      # a MAC layer whose list leaves tiles / rows out
         tables = self.mac_tables(const_in, sched) if mac_skips else None
 
         def run(t, ext_, first, last, n_img, out_last=None):
             """steps[first:last] over n_img images (the constant crop last); the last of them writes into out_last if given."""
             sub = layers[first:last]
-            k = last - first
-            res = ops.embed_worklists(ext_, n_img, S, pool_mask, sub, (S // 16) ** 2 if first == 0 else max(1, (sub[0][5] // 16)) ** 2,
-                                      want_computed=mac_skips)
-            lists, counts = res[0], res[1]
-            has_thin = any(l[-1] == 5 for l in sub)          # then the thin lists / their counts follow the strip lists / counts
+            wl = ops.embed_worklists(ext_, n_img, S, pool_mask, sub, (S // 16) ** 2 if first == 0 else max(1, (sub[0].in_H // 16)) ** 2,
+                                     want_computed=mac_skips)
             if mac_skips:
-                o = sum(st[1].cout for st in steps[1:first] if st[3])
-                for j in range(k):
-                    if steps[first + j][3] if first + j else False:
-                        ops.mac_init(desc, o, tables[first + j][0], tables[first + j][1], res[2][j])
-                        o += steps[first + j][1].cout
-            off = sum(st[1].cout for st in steps[1:first] if st[3])
-            for j in range(k):
-                li = first + j
-                if li == 0:
-                    t = ops.vgg_stem_list(t, const_in, self.stem, lists[0], counts[0:1])
+                for j, st in enumerate(steps[first:last]):
+                    if st.mac:
+                        ops.mac_init(desc, st.mac_off, *tables[first + j], wl.computed_of(j))
+            for j, (st, l) in enumerate(zip(steps[first:last], sub)):
+                if st.kind == 'stem':
+                    t = ops.vgg_stem_list(t, const_in, self.stem, *wl.main(j))
                     continue
-                kind, pc, pool, mac, store = steps[li]
-                t = ops.conv2d_list(t, pc, lists[j], counts[j:j + 1], act=1, pool=pool, mac=desc if mac else None, mac_off=off, store=store,
-                                    units=counts[k + j:k + j + 1], out=out_last if (j == k - 1 and store) else None,
-                                    strips=(lists[k + j], counts[2 * k + j:2 * k + j + 1]) if layers[li][-1] in (3, 5) else None,
-                                    thin=(lists[2 * k + j], counts[3 * k + j:3 * k + j + 1]) if (has_thin and layers[li][-1] == 5) else None)
-                if mac:
-                    off += pc.cout
+                t = ops.conv2d_list(t, st.pc, *wl.main(j), act=1, pool=st.pool, mac=desc if st.mac else None, mac_off=st.mac_off, store=st.store,
+                                    units=wl.units(j), out=out_last if (j == len(sub) - 1 and st.store) else None,
+                                    strips=wl.strips(j, l.mode), thin=wl.thin(j, l.mode))
             return t
 
         desc = (torch.empty if mac_skips else torch.zeros)((N + 1, self.embedding_size), dtype=torch.float32, device=dev)
@@ -288,7 +305,7 @@ class MACVGGEngine:
                 run(x[s_:e_], ext[s_:e_], 0, nl, e_ - s_ + 1)
                 outs.append(desc[:e_ - s_])
             return torch.cat(outs)
-        eh, ec = layers[early - 1][0], steps[early - 1][1].cout if early > 1 else 64         # the last early layer's output: (eh, eh, ec) per image
+        eh, ec = layers[early - 1].H, steps[early - 1].pc.cout if early > 1 else 64         # the last early layer's output: (eh, eh, ec) per image
         big = torch.empty((N + 1, eh, eh, ec), dtype=torch.bfloat16, device=dev)
         for s_, e_ in _passes(N, FUSED_EMBED_BATCH, FUSED_EMBED_MAX - 1):
             if early == 1:                                  # (a plan whose first conv after the stem is already a late layer)
@@ -309,64 +326,53 @@ class MACVGGEngine:
         CU count so that the persistent kernels' tile counts stay whole multiples of their grid).
         ext (B,2) int32 + const_in (S,S,c): the crops' content extents (`ops.crop_extents`) and the all-padding crop
         (`const_crop`) -- tiles that lie in a crop's constant padding are then skipped (bit-identical results)."""
-        outs, outs_bf = [], []
         fused = batch is None and self.stem is not None and x.shape[1] * x.shape[2] <= INPUT_SIZE * INPUT_SIZE
         step = batch or (FUSED_EMBED_BATCH if fused else MAX_EMBED_BATCH)
-        plan = self.plan + [('desc', None)]            # the second descriptor: amax of the last map (classification.py:48-49)
         sched = self.skip_plan(x.shape[1]) if (SKIP_PADDING and ext is not None and const_in is not None and fused and x.shape[1] == x.shape[2]) else None
         if partial and sched is None:
             raise RuntimeError('embed_packed: crops that hold their content only (ops.crop_resize content_ext) need the work-list schedule')
-        if sched is not None and x.shape[0]:
+        if sched is not None:
             # (the late layers' tensors: 64 x 64 x 256 per crop -> at most LATE_EMBED_MAX crops per call under the 32-bit tensor limits)
-            for s, e in _passes(x.shape[0], LATE_EMBED_MAX, LATE_EMBED_MAX):
-                r = ops.l2_normalize(self._embed_skip(x[s:e], ext[s:e], const_in, sched).contiguous(), eps, want_bf16)
-                if want_bf16:
-                    outs.append(r[0]); outs_bf.append(r[1])
-                else:
-                    outs.append(r)
-            if want_bf16:
-                return torch.cat(outs), torch.cat(outs_bf)
-            return torch.cat(outs)
-        for s, e in _passes(x.shape[0], step, FUSED_EMBED_MAX if fused else step):
-            xb = x[s:e]
-            desc = torch.zeros((xb.shape[0], self.embedding_size), dtype=torch.float32, device=x.device)   # (zeros: the fused MAC epilogue takes atomic maxima of values >= 0)
-            off = 0
-            if self.stem is not None:
-                xb = ops.vgg_stem(xb, self.stem)
-            i = 0
-            while i < len(plan):
-                kind, pc = plan[i]
-                nxt = plan[i + 1][0] if i + 1 < len(plan) else None
-                if kind == 'conv' and nxt == 'desc' and ops.can_fuse_mac(xb, pc):
-                    # conv + ReLU with the MAC descriptor taken in its epilogue; the map itself is stored only if something
-                    # reads it: pooled when MaxPool2d(2,2) follows (conv4_3 -> pool4), not at all at the end (conv5_3)
-                    after = plan[i + 2][0] if i + 2 < len(plan) else None
-                    fuse_pool = after == 'pool' and xb.shape[1] % 2 == 0 and xb.shape[2] % 2 == 0
-                    xb = ops.conv2d_relu_mac(xb, pc, desc, off, store=after is not None, pool=fuse_pool)
-                    off += pc.cout
-                    i += 3 if fuse_pool else 2
-                    continue
-                if kind == 'conv':
-                    xb = ops.conv2d(xb, pc, act=1)
-                elif kind == 'conv_pool':
-                    xb = ops.conv2d(xb, pc, act=1, pool=True)
-                elif kind == 'pool':
-                    xb = ops.maxpool2d(xb, 2, 2)
-                else:
-                    ops.global_max_into(xb, desc, off)
-                    off += xb.shape[3]
-                i += 1
-            r = ops.l2_normalize(desc, eps, want_bf16)
-            if want_bf16:
-                outs.append(r[0]); outs_bf.append(r[1])
-            else:
-                outs.append(r)
+            descs = (self._embed_skip(x[s:e], ext[s:e], const_in, sched).contiguous() for s, e in _passes(x.shape[0], LATE_EMBED_MAX, LATE_EMBED_MAX))
+        else:
+            descs = (self._embed_plain(x[s:e]) for s, e in _passes(x.shape[0], step, FUSED_EMBED_MAX if fused else step))
+        outs = [ops.l2_normalize(desc, eps, want_bf16) for desc in descs]        # (each pass is normalised before the next one is launched)
         if not outs:
             e = torch.empty((0, self.embedding_size), dtype=torch.float32, device=x.device)
             return (e, e.to(torch.bfloat16)) if want_bf16 else e
-        if want_bf16:
-            return torch.cat(outs), torch.cat(outs_bf)
-        return torch.cat(outs)
+        return tuple(torch.cat(c) for c in zip(*outs)) if want_bf16 else torch.cat(outs)
+
+    def _embed_plain(self, xb):
+        """The plain schedule over one pass: xb (n,S,S,c) -> MAC descriptor (n,1024)."""
+        plan = self.plan + [('desc', None)]            # the second descriptor: amax of the last map (classification.py:48-49)
+        desc = torch.zeros((xb.shape[0], self.embedding_size), dtype=torch.float32, device=xb.device)   # (zeros: the fused MAC epilogue takes atomic maxima of values >= 0)
+        off = 0
+        if self.stem is not None:
+            xb = ops.vgg_stem(xb, self.stem)
+        i = 0
+        while i < len(plan):
+            kind, pc = plan[i]
+            nxt = plan[i + 1][0] if i + 1 < len(plan) else None
+            if kind == 'conv' and nxt == 'desc' and ops.can_fuse_mac(xb, pc):
+                # conv + ReLU with the MAC descriptor taken in its epilogue; the map itself is stored only if something
+                # reads it: pooled when MaxPool2d(2,2) follows (conv4_3 -> pool4), not at all at the end (conv5_3)
+                after = plan[i + 2][0] if i + 2 < len(plan) else None
+                fuse_pool = after == 'pool' and xb.shape[1] % 2 == 0 and xb.shape[2] % 2 == 0
+                xb = ops.conv2d_relu_mac(xb, pc, desc, off, store=after is not None, pool=fuse_pool)
+                off += pc.cout
+                i += 3 if fuse_pool else 2
+                continue
+            if kind == 'conv':
+                xb = ops.conv2d(xb, pc, act=1)
+            elif kind == 'conv_pool':
+                xb = ops.conv2d(xb, pc, act=1, pool=True)
+            elif kind == 'pool':
+                xb = ops.maxpool2d(xb, 2, 2)
+            else:
+                ops.global_max_into(xb, desc, off)
+                off += xb.shape[3]
+            i += 1
+        return desc
 
 
 class MACVGG(nn.Module):
@@ -491,10 +497,7 @@ class _ResNetSource(nn.Module):
 class MACResNetEngine:
     def __init__(self, model, device):
         def fold(conv, bn):
-            scale = shift = None
-            if isinstance(bn, nn.BatchNorm2d):
-                scale = bn.weight * (bn.running_var + bn.eps).rsqrt()
-                shift = bn.bias - bn.running_mean * scale
+            scale, shift = _bn_affine(bn) if isinstance(bn, nn.BatchNorm2d) else (None, None)
             return ops.PackedConv(conv.weight, conv.bias, conv.stride[0], conv.padding[0], scale=scale, shift=shift, device=device)
 
         self.blocks = []          # per descriptor block: list of ('stem', pc) | ('bottleneck', (c1, c2, c3, ds))

@@ -5,7 +5,9 @@ PyTorch-ROCm custom ops, CUDA/HIP dispatch key only) -> ctypes -> the C ABI of i
 kernels in libcvpce_hip.so.  torch is plumbing: device memory (tensors), the current HIP stream, the dispatcher.  There is
 no CPU kernel anywhere: CPU tensors are rejected loudly.
 """
+import enum
 import os as _os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -606,25 +608,93 @@ def pad_extents(images, pad=0.5):
     return ext
 
 
+class SkipMode(enum.IntEnum):
+    """`cvpce_skip_layer.skip` (include/cvpce_amd.h): what a layer's work lists leave out."""
+    NONE = 0                  # every tile is listed
+    TILES = 1                 # the tiles that are wholly constant are left out
+    ROWS4 = 2                 # ... and the listed tiles are cut at their last non-constant row, rounded up to 4 rows
+    ROWS4_STRIPS = 3          # ... and last-row tiles with only 4 useful rows go to the layer's strip list
+    ROWS2 = 4                 # as ROWS4, rows rounded up to 2
+    ROWS2_STRIPS_THIN = 5     # as ROWS4_STRIPS, rows rounded up to 2, and last-row tiles with only 2 useful rows go to its thin strip list
+
+    @property
+    def has_strips(self):
+        return self in (SkipMode.ROWS4_STRIPS, SkipMode.ROWS2_STRIPS_THIN)
+
+    @property
+    def has_thin(self):
+        return self is SkipMode.ROWS2_STRIPS_THIN
+
+
+class SkipLayer(NamedTuple):
+    """One `cvpce_skip_layer`, fields in the order of `_lib.SkipLayer._fields_` (plain ints: `embed_worklists` passes them on flat)."""
+    H: int
+    W: int
+    tile_h: int
+    tile_w: int
+    out_ops: int
+    in_H: int
+    in_W: int
+    in_ops: int
+    skip: int
+
+    @property
+    def mode(self):
+        return SkipMode(self.skip)
+
+
 def skip_layer(h, w, tile_h, tile_w, out_ops, in_h, in_w, in_ops, skip):
-    """One `cvpce_skip_layer` as the flat int list `embed_worklists` takes."""
-    return [int(v) for v in (h, w, tile_h, tile_w, out_ops, in_h, in_w, in_ops, skip)]
+    return SkipLayer(*(int(v) for v in (h, w, tile_h, tile_w, out_ops, in_h, in_w, in_ops, skip)))
+
+
+class WorkLists(NamedTuple):
+    """What `embed_worklists` fills for L layers, and the one place that knows how it is packed: `lists` (2 L | 3 L, stride) int64 holds
+    the main lists in rows j, the strip lists in rows L + j and -- the 3 L form, built when a layer has a thin list -- the thin strip lists
+    in rows 2 L + j; `counts` (3 L | 4 L,) int32 holds the tiles at j, the layers' MFMA work in sixteenths of a tile at L + j, the strip
+    entries at 2 L + j and the thin-strip entries at 3 L + j; `computed` (L, n_images, 2) int32 | None: conv rows computed / tile
+    columns listed per crop.  A list is handed to a launch as (its row, a one-element slice of `counts`)."""
+    lists: torch.Tensor
+    counts: torch.Tensor
+    computed: Optional[torch.Tensor]
+
+    @property
+    def n_layers(self):
+        return self.counts.shape[0] - self.lists.shape[0]
+
+    def _view(self, row_block, count_block, j):
+        L = self.n_layers
+        return self.lists[row_block * L + j], self.counts[count_block * L + j:count_block * L + j + 1]
+
+    def main(self, j):
+        return self._view(0, 0, j)
+
+    def strips(self, j, mode=None):
+        """layer j's strip list; None when `mode` (the layer's SkipMode, where the caller knows it) has none"""
+        return self._view(1, 2, j) if mode is None or mode.has_strips else None
+
+    def thin(self, j, mode=None):
+        """layer j's thin strip list; None when the tensors have the 2 L / 3 L form or `mode` has none"""
+        return self._view(2, 3, j) if self.lists.shape[0] == 3 * self.n_layers and (mode is None or mode.has_thin) else None
+
+    def units(self, j):
+        return self.counts[self.n_layers + j:self.n_layers + j + 1]
+
+    def computed_of(self, j):
+        return self.computed[j]
 
 
 def embed_worklists(ext0, n_images, size, pool_mask, layers, max_tiles, want_computed=False):
     """ext0 (n_images - 1, 2) int32 (the last image is the implied constant crop); pool_mask: the pass's op chain (bit i: op i is
-    a 2x2 pool, else a 3x3 conv); layers: list of `skip_layer` -> (lists (2 L, n_images * max_tiles) int64: the layers' lists, then
-    their strip lists; counts (3 L,) int32: tiles per layer, the layers' MFMA work in sixteenths of a tile, strip entries [, computed (L, n_images, 2) int32: conv rows computed /
-    tile columns listed per crop]), all on the device, no synchronisation.  With a layer of skip mode 5 the tensors carry the thin strip
-    lists as well: lists (3 L, ...), rows 2 L .. the thin lists; counts (4 L,), the last L the thin-strip entries."""
+    a 2x2 pool, else a 3x3 conv); layers: list of `skip_layer` -> the WorkLists of the L layers, `lists` with n_images * max_tiles
+    entries a row, `computed` only with want_computed; all on the device, no synchronisation."""
     _need_cuda(ext0)
     dev = ext0.device if ext0 is not None else torch.device('cuda', torch.cuda.current_device())
-    thin = any(l[-1] == 5 for l in layers)
-    lists = torch.empty(((3 if thin else 2) * len(layers), n_images * max_tiles), dtype=torch.int64, device=dev)   # rows L ..: the layers' strip lists
+    thin = any(l.mode.has_thin for l in layers)
+    lists = torch.empty(((3 if thin else 2) * len(layers), n_images * max_tiles), dtype=torch.int64, device=dev)
     counts = torch.empty(((4 if thin else 3) * len(layers),), dtype=torch.int32, device=dev)
     computed = torch.empty((len(layers), n_images, 2), dtype=torch.int32, device=dev) if want_computed else None
     T.embed_worklists(ext0, int(n_images), int(size), int(pool_mask), [v for l in layers for v in l], lists, counts, computed)
-    return (lists, counts, computed) if want_computed else (lists, counts)
+    return WorkLists(lists, counts, computed)
 
 
 def mac_init(desc, off, row_suffix_max, col_suffix_max, computed):

@@ -376,7 +376,8 @@ def test_list_and_strip_launches(cuda, refs):
     nl, max_tiles = len(layers), (S // 16) ** 2
     model = ec.worklist_model()
     e = torch.tensor(ec.WL_EXT, dtype=torch.int32)
-    lists, counts, computed = ops.embed_worklists(e.to(cuda), n, S, pool_mask, layers, max_tiles, want_computed=True)
+    wl = ops.embed_worklists(e.to(cuda), n, S, pool_mask, layers, max_tiles, want_computed=True)
+    lists, counts, computed = wl      # (the raw tensors are checked against the model by hand, the launches take `wl`'s views)
     L, cnt = lists.cpu(), counts.cpu().tolist()
     assert cnt == [len(m[0]) for m in model] + [m[2] for m in model] + [len(m[1]) for m in model]
     for l, (want, swant, _, _) in enumerate(model):
@@ -401,7 +402,7 @@ def test_list_and_strip_launches(cuda, refs):
     l1, l2 = c.layers
     ps = ops.PackedStem(l1.w.float(), l1.b.float(), l2.w.float(), l2.b.float(), device=cuda)
     with switches() as prof:
-        y0 = ops.vgg_stem_list(x_sent[:-1].contiguous().to(cuda), x_sent[-1].contiguous().to(cuda), ps, lists[0], counts[0:1])
+        y0 = ops.vgg_stem_list(x_sent[:-1].contiguous().to(cuda), x_sent[-1].contiguous().to(cuda), ps, *wl.main(0))
         assert prof.records[-1][0] == 'vgg_stem2_kernel'
     m0 = fp.listed_pixels(entries(0), n, 32, 32, 8, 8)
     assert bool(m0[3].all()) and 0 < int(m0[0].sum()) < 32 * 32
@@ -416,11 +417,12 @@ def test_list_and_strip_launches(cuda, refs):
         pc = packed(sc.layers[0], BF, cuda)
         sent = holed(to_nhwc(sc.x, BF), in_mask).to(cuda)
         ho = hin // 2 if pool else hin
-        strips = (lists[nl + li], counts[2 * nl + li:2 * nl + li + 1]) if cout > 128 else None
+        strips = wl.strips(li, layers[li].mode)
+        assert (strips is not None) == (cout > 128) and (strips is None or (strips[0].data_ptr(), strips[1].data_ptr()) == (lists[nl + li].data_ptr(), counts[2 * nl + li:].data_ptr()))
         m = fp.listed_pixels(entries(li), n, ho, ho, th, tw)
         with switches() as prof:
             if mac_off is None:
-                y = ops.conv2d_list(sent, pc, lists[li], counts[li:li + 1], act=1, pool=pool, strips=strips,
+                y = ops.conv2d_list(sent, pc, *wl.main(li), act=1, pool=pool, strips=strips,
                                     out=torch.full((n, ho, ho, cout), nan, dtype=BF, device=cuda))
             else:
                 const_map = ref[-1].permute(1, 2, 0).float()                                     # (H, W, C) >= 0: the constant crop's own map
@@ -428,8 +430,8 @@ def test_list_and_strip_launches(cuda, refs):
                 rows = torch.cat((torch.cummax(const_map.amax(dim=1).flip(0), 0).values.flip(0), zero)).to(cuda)
                 cols = torch.cat((torch.cummax(const_map.amax(dim=0).flip(0), 0).values.flip(0), zero)).to(cuda)
                 desc = torch.full((n, mac_off + cout + 24), -7.0, device=cuda)
-                ops.mac_init(desc, mac_off, rows, cols, computed[li].contiguous())
-                assert ops.conv2d_list(sent, pc, lists[li], counts[li:li + 1], act=1, mac=desc, mac_off=mac_off, store=False, strips=strips) is None
+                ops.mac_init(desc, mac_off, rows, cols, wl.computed_of(li).contiguous())
+                assert ops.conv2d_list(sent, pc, *wl.main(li), act=1, mac=desc, mac_off=mac_off, store=False, strips=strips) is None
             names = [r[0] for r in prof.records]
         assert names[0] == ('conv3x3_halo3_kernel' if cout <= 128 else 'conv3x3_halo2_kernel') and (strips is None or names[-1] == 'conv3x3_halo2_kernel[strips]'), names
         torch.cuda.synchronize()

@@ -38,7 +38,7 @@ def test_fine_worklists_match_python_model(cuda):
     enc = synthetic.synthetic_macvgg(seed=1).cuda()
     steps, layers, pool_mask = enc.engine().skip_plan(S)
     assert [l[-1] for l in layers] == [1] + [2] * 2 + [3] * 9        # `skip_plan` itself is unchanged
-    fine = [l[:-1] + [FINE.get(l[-1], l[-1])] for l in layers]
+    fine = [l._replace(skip=FINE.get(l[-1], l[-1])) for l in layers]
     g = torch.Generator().manual_seed(3)
     n = 131
     ext = torch.stack((torch.randint(1, S + 1, (n,), generator=g), torch.full((n,), S)), dim=1).to(torch.int32)
@@ -56,8 +56,8 @@ def test_fine_worklists_match_python_model(cuda):
     assert computed.cpu().tolist() == [m[4] for m in model]
     assert sum(len(m[1]) for m in model) > 0 and sum(len(m[2]) for m in model) > 0     # the random extents produce both strip classes
     # mode 4 alone keeps the shapes of modes 0 .. 3, and gives the same main lists where no tile goes to a strip list
-    only4 = [l[:-1] + [4 if l[-1] >= 2 else l[-1]] for l in layers]
-    l4, c4 = ops.embed_worklists(ext.cuda(), n + 1, S, pool_mask, only4, 256)
+    only4 = [l._replace(skip=4 if l[-1] >= 2 else l[-1]) for l in layers]
+    l4, c4, _ = ops.embed_worklists(ext.cuda(), n + 1, S, pool_mask, only4, 256)
     assert l4.shape[0] == 2 * nl and c4.numel() == 3 * nl
     m4 = fl.model(ext.tolist() + [[S, S]], S, pool_mask, only4)
     assert c4.cpu().tolist() == [len(m[0]) for m in m4] + [m[3] for m in m4] + [0] * nl
