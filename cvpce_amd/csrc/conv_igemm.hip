@@ -11,16 +11,20 @@
 // row is gathered straight from the NHWC tensor (one tap, 8 channels) into an
 // XOR-swizzled LDS tile (conflict-free ds_read_b128 fragments).
 //
-// Two kernels share the tiling, the fragment reads and the epilogue:
-//   conv_dma_kernel    the workhorse (Cin % 64 == 0, big M): 8 waves, 256x256
-//                      (or 4 waves, 128/64 x 256) output tile, K-step 64, operands
-//                      staged by LDS-DMA (`global_load_lds_dwordx4`, no VGPR round
-//                      trip, no ds_write); the XOR swizzle is applied to the per-lane
-//                      SOURCE address (the DMA writes LDS lane-linearly) and padding
-//                      halo / ragged rows read a 16-byte zero page.  Double buffered:
-//                      the DMA of K-step t+1 is in flight under the MFMAs of step t.
-//   conv_igemm_kernel  the generic fallback (any Cin % 8 == 0, small M, thin
-//                      channels): 4 waves, 128/64 x 128 tile, register-staged.
+// Three kernels share the GEMM view and the store path (conv_store4); conv2d_dispatch at the end of the file chooses:
+//   conv_dma16_kernel  the workhorse (Cin % 64 == 0, Cout >= 192, 128+ pixel tiles): 8 waves, 256x256 output tile,
+//                      K-step 32, a four-stage ring of LDS-DMA (`buffer_load ... lds`), v_mfma_f32_16x16x32.
+//                      One instance per storage type: <256,256,2,4,2,4>.
+//   conv_dma_kernel    K-step 64, operands staged by LDS-DMA (`global_load_lds_dwordx4`, no VGPR round trip, no
+//                      ds_write); the XOR swizzle is applied to the per-lane SOURCE address (the DMA writes LDS
+//                      lane-linearly) and padding halo / ragged rows read a 16-byte zero page.  Double buffered: the
+//                      DMA of K-step t+1 is in flight under the MFMAs of step t.  Instances: 4 waves, <128,128,2,2,2>
+//                      (64 < Cout <= 128) and <64,128,2,2,2> (32 < Cout <= 64) from 128 pixel tiles of 256 up; 8 waves,
+//                      <256,256,2,4,2> for the ring kernel's shapes that it does not cover -- an upsampled input
+//                      (in_up_shift) or more than 32 taps.  No model has such a layer.
+//   conv_igemm_kernel  the generic fallback (any Cin % 8 == 0, small M, thin channels, force_generic): 4 waves,
+//                      register-staged, tiles <128,128>, <64,128> with K-step 64 or 32 and <32,128> with K-step 64;
+//                      <128,128,64> also as the first launch of a split-K pair (conv_splitk_finish_kernel is the second).
 //
 // fuse_pool2: the M axis enumerates output pixels in 2x2-quad order so the four
 // pixels of a pooling window sit in four adjacent lanes; the epilogue takes the
@@ -34,8 +38,8 @@
 #include "common.h"
 #include "../../include/cvpce_amd.h"
 
-// compile-time timing experiments (never set in the shipped library): 1 no DMA in the K loop, 2 no barrier,
-// 4 no pixel DMA, 8 no MFMA.  Built by tools/ablate.sh into side libraries selected with CVPCE_LIB.
+// compile-time timing experiments on conv_igemm_kernel (never set in the shipped library): 1024 no global loads in the K loop,
+// 2048 no MFMA, 4096 no barrier, 8192 no LDS stores.  Built by tools/ablate.sh into side libraries selected with CVPCE_LIB.
 #ifndef CVPCE_DBG
 #define CVPCE_DBG 0
 #endif
@@ -86,8 +90,87 @@ __device__ __forceinline__ void decode_m(const ConvArgs& a, int m, int& img, int
     }
 }
 
-// Epilogue shared by both kernels: lane owns pixel (lane&31) of each 32-wide
-// pixel tile and channels 8g + 4h + {0..3} of each 32-channel tile.
+// The store path both accumulator layouts share: the residual's pixel for output pixel m, ...
+__device__ __forceinline__ size_t conv_res_pixel(const ConvArgs& a, int m, bool m_ok) {
+    size_t res_pix = 0;
+    if (a.res_mode == 1) {
+        res_pix = (size_t)m;
+    } else if (a.res_mode == 2 && m_ok) {
+        int img, oy, ox;
+        decode_m(a, m, img, oy, ox);
+        const int ry = (oy * a.Hr) / a.Ho, rx = (ox * a.Wr) / a.Wo;
+        res_pix = (size_t)(img * a.Hr + ry) * a.Wr + rx;
+    }
+    return res_pix;
+}
+
+// ... and channels co .. co + 3 of pixel m from their four sums: bias, residual, activation, fused pool, store (fp32, pooled or
+// 16-bit).  (The sums come by value: through a reference to the caller's array the compiler lays out every kernel's epilogue
+// differently, by value all but one as before the two epilogues shared it -- profiles/r18_igemm_cleanup.md.)
+template <typename E>
+__device__ __forceinline__ void conv_store4(const ConvArgs& a, const f32x4 acc4, int m, bool m_ok, size_t res_pix, int co, int lane) {
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = acc4[j];
+    if (a.out_f32) {
+        if (!m_ok || co >= a.Cout) return;
+        float* o = reinterpret_cast<float*>(a.out) + (size_t)m * a.Cout;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (co + j < a.Cout) {
+                float x = v[j];
+                if (a.bias) x += a.bias[co + j];
+                if (a.res_mode) x += E::widen(a.res[res_pix * a.Cout + co + j]);
+                if (a.relu == 1) x = fmaxf(x, 0.f);
+                else if (a.relu == 2) x = tanhf(x);
+                o[co + j] = x;
+            }
+        }
+    } else if (a.pool) {
+        // all 4 lanes of a quad share m_ok / co: shuffles stay convergent
+        if (a.bias && co < a.Cout) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] += b[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x = quad_max(v[j]);
+            if (a.relu == 1) x = fmaxf(x, 0.f);
+            v[j] = x;
+        }
+        if (m_ok && co < a.Cout && (lane & 3) == 0) {
+            bf16x4 o;
+#pragma unroll
+            for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
+            *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)(m >> 2) * a.Cout + co) = o;
+        }
+    } else {
+        if (!m_ok || co >= a.Cout) return;
+        // Cout % 4 == 0 is required for bf16 outputs (checked on the host)
+        if (a.bias) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] += b[j];
+        }
+        if (a.res_mode) {
+            const bf16x4 r = *reinterpret_cast<const bf16x4*>(a.res + res_pix * a.Cout + co);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] += E::widen(r[j]);
+        }
+        if (a.relu == 1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = relu_bits(v[j]);
+        }
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
+        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)m * a.Cout + co) = o;
+    }
+}
+
+// Epilogue of the 32x32x16 accumulator layout: lane owns pixel (lane&31) of each 32-wide pixel tile and channels
+// 8g + 4h + {0..3} of each 32-channel tile.
 template <typename E, int MT, int NT>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT], int c_base, int p_base, int lane) {
     const int lr = lane & 31, lh = lane >> 5;
@@ -95,84 +178,18 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
     for (int nt = 0; nt < NT; ++nt) {
         const int m = p_base + nt * 32 + lr;
         const bool m_ok = m < a.M;
-        size_t res_pix = 0;
-        if (a.res_mode == 1) {
-            res_pix = (size_t)m;
-        } else if (a.res_mode == 2 && m_ok) {
-            int img, oy, ox;
-            decode_m(a, m, img, oy, ox);
-            const int ry = (oy * a.Hr) / a.Ho, rx = (ox * a.Wr) / a.Wo;
-            res_pix = (size_t)(img * a.Hr + ry) * a.Wr + rx;
-        }
+        const size_t res_pix = conv_res_pixel(a, m, m_ok);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int co = c_base + mt * 32 + 8 * g + 4 * lh;
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = acc[mt][nt][4 * g + j];
-                if (a.out_f32) {
-                    if (!m_ok || co >= a.Cout) continue;
-                    float* o = reinterpret_cast<float*>(a.out) + (size_t)m * a.Cout;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (co + j < a.Cout) {
-                            float x = v[j];
-                            if (a.bias) x += a.bias[co + j];
-                            if (a.res_mode) x += E::widen(a.res[res_pix * a.Cout + co + j]);
-                            if (a.relu == 1) x = fmaxf(x, 0.f);
-                            else if (a.relu == 2) x = tanhf(x);
-                            o[co + j] = x;
-                        }
-                    }
-                } else if (a.pool) {
-                    // all 4 lanes of a quad share m_ok / co: shuffles stay convergent
-                    if (a.bias && co < a.Cout) {
-                        const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += b[j];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float x = quad_max(v[j]);
-                        if (a.relu == 1) x = fmaxf(x, 0.f);
-                        v[j] = x;
-                    }
-                    if (m_ok && co < a.Cout && (lane & 3) == 0) {
-                        bf16x4 o;
-#pragma unroll
-                        for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)(m >> 2) * a.Cout + co) = o;
-                    }
-                } else {
-                    if (!m_ok || co >= a.Cout) continue;
-                    // Cout % 4 == 0 is required for bf16 outputs (checked on the host)
-                    if (a.bias) {
-                        const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += b[j];
-                    }
-                    if (a.res_mode) {
-                        const bf16x4 r = *reinterpret_cast<const bf16x4*>(a.res + res_pix * a.Cout + co);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += E::widen(r[j]);
-                    }
-                    if (a.relu == 1) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = relu_bits(v[j]);
-                    }
-                    bf16x4 o;
-#pragma unroll
-                    for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
-                    *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)m * a.Cout + co) = o;
-                }
+                conv_store4<E>(a, f32x4{acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]}, m, m_ok, res_pix, c_base + mt * 32 + 8 * g + 4 * lh, lane);
             }
         }
     }
 }
 
-// Epilogue for the 16x16x32 accumulator layout: lane owns pixel (lane&15) of each 16-pixel block and channels
+// Epilogue of the 16x16x32 accumulator layout: lane owns pixel (lane&15) of each 16-pixel block and channels
 // 4*(lane>>4) + {0..3} of each 16-channel block.
 template <typename E, int MT, int NT>
 __device__ __forceinline__ void conv_epilogue16(const ConvArgs& a, f32x4 (&acc)[MT][NT], int c_base, int p_base, int lane) {
@@ -181,74 +198,10 @@ __device__ __forceinline__ void conv_epilogue16(const ConvArgs& a, f32x4 (&acc)[
     for (int nt = 0; nt < NT; ++nt) {
         const int m = p_base + nt * 16 + lp;
         const bool m_ok = m < a.M;
-        size_t res_pix = 0;
-        if (a.res_mode == 1) {
-            res_pix = (size_t)m;
-        } else if (a.res_mode == 2 && m_ok) {
-            int img, oy, ox;
-            decode_m(a, m, img, oy, ox);
-            const int ry = (oy * a.Hr) / a.Ho, rx = (ox * a.Wr) / a.Wo;
-            res_pix = (size_t)(img * a.Hr + ry) * a.Wr + rx;
-        }
+        const size_t res_pix = conv_res_pixel(a, m, m_ok);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int co = c_base + mt * 16 + 4 * lq;
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = acc[mt][nt][j];
-            if (a.out_f32) {
-                if (!m_ok || co >= a.Cout) continue;
-                float* o = reinterpret_cast<float*>(a.out) + (size_t)m * a.Cout;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (co + j < a.Cout) {
-                        float x = v[j];
-                        if (a.bias) x += a.bias[co + j];
-                        if (a.res_mode) x += E::widen(a.res[res_pix * a.Cout + co + j]);
-                        if (a.relu == 1) x = fmaxf(x, 0.f);
-                        else if (a.relu == 2) x = tanhf(x);
-                        o[co + j] = x;
-                    }
-                }
-            } else if (a.pool) {
-                if (a.bias && co < a.Cout) {
-                    const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] += b[j];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x = quad_max(v[j]);
-                    if (a.relu == 1) x = fmaxf(x, 0.f);
-                    v[j] = x;
-                }
-                if (m_ok && co < a.Cout && (lane & 3) == 0) {
-                    bf16x4 o;
-#pragma unroll
-                    for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
-                    *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)(m >> 2) * a.Cout + co) = o;
-                }
-            } else {
-                if (!m_ok || co >= a.Cout) continue;
-                if (a.bias) {
-                    const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + co);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] += b[j];
-                }
-                if (a.res_mode) {
-                    const bf16x4 r = *reinterpret_cast<const bf16x4*>(a.res + res_pix * a.Cout + co);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] += E::widen(r[j]);
-                }
-                if (a.relu == 1) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = relu_bits(v[j]);
-                }
-                bf16x4 o;
-#pragma unroll
-                for (int j = 0; j < 1; ++j) o = E::pack4(f32x4{v[0], v[1], v[2], v[3]});
-                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.out) + (size_t)m * a.Cout + co) = o;
-            }
+            conv_store4<E>(a, acc[mt][nt], m, m_ok, res_pix, c_base + mt * 16 + 4 * lq, lane);
         }
     }
 }
@@ -433,218 +386,22 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma_kernel(ConvArgs a
 }
 
 // ===========================================================================
-// LDS-DMA kernel, 4-stage ring: K-step 32, three K-steps of DMA in flight
+// LDS-DMA ring kernel: K-step 32, four stages, v_mfma_f32_16x16x32
 // ===========================================================================
-// Issued -> landed latency of an LDS-DMA piece under load is ~1 us (about one 64-deep K-step of
-// MFMA time), so a 2-buffer scheme exposes it every step.  Here the ring holds four 32-deep
-// K-steps (4 x 32 KiB at 256x256): stage t+3 is issued while stage t computes, the wave waits with
-// a COUNTED vmcnt (never 0 in steady state) and a raw s_barrier (a __syncthreads() would drain
-// vmcnt to 0).  K order: (64-channel chunk, kh, kw, 32-channel half, channel).
-template <typename E, int TC, int TP, int WC, int WP, int MINW, int NS>
-__global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma4_kernel(ConvArgs a) {
-    constexpr int BK = 32;
-    static_assert(NS == 3 || NS == 4, "ring depth");
-    constexpr int NW = WC * WP;
-    constexpr int WJ = TC / (16 * NW);     // weight DMA pieces per wave per K-step (16 rows of 64 B each)
-    constexpr int PJ = TP / (16 * NW);
-    constexpr int NP = WJ + PJ;
-    constexpr int MT = TC / WC / 32;
-    constexpr int NT = TP / WP / 32;
-    static_assert(WJ >= 1 && PJ >= 1, "tile/wave geometry");
-
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* Ws = reinterpret_cast<bf16_t*>(smem);          // [NS][TC][BK]
-    bf16_t* Ps = Ws + NS * TC * BK;                        // [NS][TP][BK]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wc = wid / WP, wp = wid % WP;
-    const int swz = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_c = swz % a.tiles_c, tile_p = swz / a.tiles_c;
-
-    // piece j of wave w fills rows j*16*NW + w*16 .. +15 (row = lane>>2, physical chunk = lane&3);
-    // swizzle f(row) = (row>>2)&3 = (lane>>4)&3 is the same for every piece of a lane
-    const int lrow = wid * 16 + (lane >> 2);
-    const int lchunk = (lane & 3) ^ ((lane >> 4) & 3);
-
-    // Per-lane, K-invariant part of every pixel-piece address, computed ONCE: byte offset of (image, oy*stride,
-    // ox*stride, lane's 8-channel slice) and a bit mask of the taps that fall inside the image.  The tap / channel
-    // walk of the K loop is wave-uniform (SALU); each DMA piece then costs one v_add + one v_cndmask of address math.
-    // (Ablation, VGG conv4_2: with the per-piece index recomputation the DMA stage cost 0.31 ms of a 1.37 ms launch.)
-    unsigned poff[PJ], pmask[PJ];
-#pragma unroll
-    for (int j = 0; j < PJ; ++j) {
-        const int m = tile_p * TP + j * 16 * NW + lrow;
-        poff[j] = 0u;
-        pmask[j] = 0u;
-        if (m < a.M) {
-            int img, oy, ox;
-            decode_m(a, m, img, oy, ox);
-            const int y0 = oy * a.stride, x0 = ox * a.stride;
-            poff[j] = (unsigned)((((size_t)(img * a.H + y0) * a.W + x0) * a.Cin + lchunk * 8) * 2);
-            for (int t = 0; t < a.KH * a.KW; ++t) {
-                const int iy = y0 - a.pad + t / a.KW, ix = x0 - a.pad + t % a.KW;
-                if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) pmask[j] |= 1u << t;
-            }
-        }
-    }
-    // wave-uniform K walk: (64-channel chunk, kh, kw, 32-channel half)
-    int kh = 0, kw = 0, half = 0, cbase = 0, tapi = 0;
-    int tap_off = ((0 - a.pad) * a.W + (0 - a.pad)) * a.Cin * 2;     // byte shift of tap (kh,kw), may be negative
-
-    // LDS-DMA through BUFFER instructions (`buffer_load_dwordx4 ... offen lds`), not `global_load_lds`: the latter is
-    // FLAT-encoded, and hipcc then treats every later LDS wait as lgkmcnt(0) (flat ops may return out of order), which
-    // serialises the fragment prefetch.  A buffer descriptor also gives the zero fill for free: an out-of-range
-    // offset (padding halo, ragged rows, K padding) returns 0 -- no zero page, no select on a 64-bit pointer.
-    const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.wgt, 0, a.wgt_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srd_p = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    unsigned woff[WJ];
-#pragma unroll
-    for (int j = 0; j < WJ; ++j)
-        woff[j] = (unsigned)(((size_t)(tile_c * TC + lrow + j * 16 * NW) * a.K_pad + lchunk * 8) * 2);
-#define CVPCE_DMA4_STAGE(KT, BUF)                                                                              \
-    {                                                                                                          \
-        const int kbyte = (KT) * (BK * 2);                                                                     \
-        _Pragma("unroll") for (int j = 0; j < WJ; ++j)                                                         \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w,                                                    \
-                (lds_void*)(Ws + (BUF) * TC * BK + (j * 16 * NW + wid * 16) * BK), 16, (int)woff[j], kbyte, 0, 0); \
-        const int uni = tap_off + (cbase + 32 * half) * 2;                                                     \
-        const bool ch_ok = cbase < a.Cin;                                                                      \
-        _Pragma("unroll") for (int j = 0; j < PJ; ++j) {                                                       \
-            const bool ok = ch_ok && ((pmask[j] >> tapi) & 1u);                                                \
-            if (!(CVPCE_DBG & 4)) __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p,                              \
-                (lds_void*)(Ps + (BUF) * TP * BK + (j * 16 * NW + wid * 16) * BK), 16,                         \
-                (int)(ok ? poff[j] + (unsigned)uni : 0xFFFFFFF0u), 0, 0, 0);                                   \
-        }                                                                                                      \
-        half ^= 1;                                                                                             \
-        if (half == 0) {                                                                                       \
-            ++tapi;                                                                                            \
-            tap_off += a.Cin * 2;                                                                              \
-            if (++kw == a.KW) {                                                                                \
-                kw = 0;                                                                                        \
-                tap_off += (a.W - a.KW) * a.Cin * 2;                                                           \
-                if (++kh == a.KH) {                                                                            \
-                    kh = 0; tapi = 0; cbase += 64;                                                             \
-                    tap_off = ((0 - a.pad) * a.W + (0 - a.pad)) * a.Cin * 2;                                   \
-                }                                                                                              \
-            }                                                                                                  \
-        }                                                                                                      \
-    }
-
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int nk = a.K_pad / BK;
-    // Software pipeline over 16-deep fragment groups (two per stage).  The ds_reads of group g+1 are issued
-    // BEFORE the MFMAs of group g and the stage hand-off (counted vmcnt + barrier + next DMA issue) sits between the
-    // two MFMA groups of a stage, so the matrix pipe keeps draining 8 queued MFMAs while the wave waits, syncs and
-    // issues DMA.  (Ablation on VGG conv4_2: fragment reads + barrier with neither DMA nor MFMA took 0.72 ms of a
-    // 1.43 ms launch when they were serialised with the MFMAs.)
-    //   stage s lives in ring slot s & 3; when MFMA(kt, group 1) is issued, stage kt+1 must be visible (its group-0
-    //   fragments are being fetched) and stages kt+2, kt+3 are in flight.
-    CVPCE_DMA4_STAGE(0, 0)
-    if (nk > 1) CVPCE_DMA4_STAGE(1, 1)
-    if (NS == 4 && nk > 2) CVPCE_DMA4_STAGE(2, 2)
-    const int lr = lane & 31, lh = lane >> 5;
-    int wrow[MT], prow[NT];       // byte-free row bases and swizzle terms of this lane's fragments
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) wrow[mt] = wc * (TC / WC) + mt * 32 + lr;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) prow[nt] = wp * (TP / WP) + nt * 32 + lr;
-    bf16x8 af[2][MT], bfr[2][NT];
-    // Fragment reads are hand-issued (`ds_read_b128` in inline asm) and hand-counted: hipcc's waitcnt pass falls back to
-    // lgkmcnt(0) for LDS reads that are pending across the loop back-edge or sit next to LDS-DMA, which would make
-    // every MFMA group wait for the group that was only just prefetched.  Inline asm hides the reads from that pass;
-    // `s_waitcnt lgkmcnt(N)` + sched_barrier below are the only LDS waits in the loop (cdna_hip_programming.md 5.4 r18).
-    const unsigned lds_w0 = (unsigned)(size_t)(lds_char*)Ws, lds_p0 = (unsigned)(size_t)(lds_char*)Ps;
-    unsigned woffb[MT], poffb[NT], wsw[MT], psw[NT];      // row byte offsets and swizzle terms of this lane's fragments
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) { woffb[mt] = wrow[mt] * (BK * 2); wsw[mt] = (wrow[mt] >> 2) & 3; }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { poffb[nt] = prow[nt] * (BK * 2); psw[nt] = (prow[nt] >> 2) & 3; }
-#define CVPCE_FRAGS(SLOT, STAGE, KK)                                                                           \
-    {                                                                                                          \
-        const unsigned wb_ = lds_w0 + ((STAGE) % NS) * (TC * BK * 2), pb_ = lds_p0 + ((STAGE) % NS) * (TP * BK * 2); \
-        const unsigned chunk = (KK) * 2 + lh;                                                                  \
-        if (!(CVPCE_DBG & 16) || (STAGE) == 0) {                                                               \
-        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                      \
-            asm volatile("ds_read_b128 %0, %1" : "=v"(af[SLOT][mt]) : "v"(wb_ + woffb[mt] + ((chunk ^ wsw[mt]) << 4))); \
-        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                      \
-            asm volatile("ds_read_b128 %0, %1" : "=v"(bfr[SLOT][nt]) : "v"(pb_ + poffb[nt] + ((chunk ^ psw[nt]) << 4))); \
-        }                                                                                                      \
-    }
-#define CVPCE_MFMAS(SLOT)                                                                                      \
-    {                                                                                                          \
-        __builtin_amdgcn_s_setprio(1);                                                                         \
-        if ((CVPCE_DBG & 32)) {                                                                                \
-        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                      \
-            _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                \
-                f32x4* q4 = reinterpret_cast<f32x4*>(&acc[mt][nt]);                                            \
-                q4[2 * (SLOT)] = E::mfma16(af[SLOT][mt], bfr[SLOT][nt], q4[2 * (SLOT)]); \
-                q4[2 * (SLOT) + 1] = E::mfma16(af[SLOT][mt], bfr[SLOT][nt], q4[2 * (SLOT) + 1]); \
-            }                                                                                                  \
-        } else if (!(CVPCE_DBG & 8)) {                                                                         \
-        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                      \
-            _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                  \
-                acc[mt][nt] = E::mfma32(af[SLOT][mt], bfr[SLOT][nt], acc[mt][nt]); \
-        }                                                                                                      \
-        __builtin_amdgcn_s_setprio(0);                                                                         \
-    }
-    // stage 0 becomes visible; fetch its first fragment group
-    if (NS == 4 && nk > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-    else if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    CVPCE_FRAGS(0, 0, 0)
-    for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // group 0 (issued one MFMA group ago) has landed
-        __builtin_amdgcn_sched_barrier(0);
-        CVPCE_FRAGS(1, kt, 1)                       // group 1 of this stage, in flight under MFMA group 0
-        __builtin_amdgcn_sched_barrier(0);
-        CVPCE_MFMAS(0)
-        __builtin_amdgcn_sched_barrier(0);
-        // hand-off: stage kt+1 must have landed for every wave; slot (kt+NS-1)%NS == (kt-1)%NS is free for the next DMA.
-        // Stages kt+2 .. kt+NS-2 (NS-3 of them) may stay in flight across the wait.
-        if (kt + 1 < nk) {
-            const int ahead = nk - 2 - kt;
-            if (NS == 4 && ahead >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(CVPCE_DBG & 2)) __builtin_amdgcn_s_barrier();
-            if (kt + NS - 1 < nk && !(CVPCE_DBG & 1)) CVPCE_DMA4_STAGE(kt + NS - 1, (kt + NS - 1) % NS)
-            CVPCE_FRAGS(0, kt + 1, 0)               // group 0 of the next stage, in flight under MFMA group 1
-            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(MT + NT) : "memory");   // group 1 landed; the MT+NT newer reads stay in flight
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        CVPCE_MFMAS(1)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef CVPCE_FRAGS
-#undef CVPCE_MFMAS
-#undef CVPCE_DMA4_STAGE
-    conv_epilogue<E, MT, NT>(a, acc, tile_c * TC + wc * (TC / WC), tile_p * TP + wp * (TP / WP), lane);
-}
-
-// ===========================================================================
-// LDS-DMA kernel, 4-stage ring, v_mfma_f32_16x16x32_bf16 variant
-// ===========================================================================
-// Same staging / ring / hand-off as conv_dma4_kernel, but the products run on the 16x16x32 MFMA shape: at equal
-// cycles per FLOP the chip holds a higher clock on it under load (measured here: MFMA-only stream of VGG conv4_2
-// 0.99 -> 0.89 ms, whole kernel +7 %; cf. MI355X_MICROARCH.md DVFS item 7).  A lane's fragment is row (lane&15),
-// 16-byte K-chunk (lane>>4) of a 16-row block, so one ds_read_b128 covers a whole 16x32 operand block; the XOR term
-// T[(row>>2)&3], T = {0,2,3,1}, keeps those reads conflict-free.  Accumulators: col = lane&15 (pixel),
-// row = 4*(lane>>4)+reg (cout).
-// Issued -> landed latency of an LDS-DMA piece under load is ~1 us (about one 64-deep K-step of
-// MFMA time), so a 2-buffer scheme exposes it every step.  Here the ring holds four 32-deep
-// K-steps (4 x 32 KiB at 256x256): stage t+3 is issued while stage t computes, the wave waits with
-// a COUNTED vmcnt (never 0 in steady state) and a raw s_barrier (a __syncthreads() would drain
-// vmcnt to 0).  K order: (64-channel chunk, kh, kw, 32-channel half, channel).
+// The ring.  Issued -> landed latency of an LDS-DMA piece under load is ~1 us (about one 64-deep K-step of MFMA
+// time), so the 2-buffer scheme of conv_dma_kernel exposes it every step.  Here the ring holds four 32-deep K-steps
+// (4 x 32 KiB at 256x256): stage t+3 is issued while stage t computes, the wave waits with a COUNTED vmcnt (never 0
+// in steady state) and a raw s_barrier (a __syncthreads() would drain vmcnt to 0).
+// K order: (64-channel chunk, kh, kw, 32-channel half, channel) -- the chunk-major order of the packed weights, each
+// 64-deep step of it cut in two; the taps of one chunk are consecutive stages, so their overlapping pixel reads hit the
+// XCD's L2.
+// The products run on the 16x16x32 MFMA shape: at equal cycles per FLOP the chip holds a higher clock on it under
+// load than on 32x32x16 (measured here: MFMA-only stream of VGG conv4_2 0.99 -> 0.89 ms, whole kernel +7 %; cf.
+// MI355X_MICROARCH.md DVFS item 7).  A lane's fragment is row (lane&15), 16-byte K-chunk (lane>>4) of a 16-row block,
+// so one ds_read_b128 covers a whole 16x32 operand block; the XOR term T[(row>>2)&3], T = {0,2,3,1}, keeps those
+// reads conflict-free.  Accumulators: col = lane&15 (pixel), row = 4*(lane>>4)+reg (cout).
+// Not covered (conv2d_dispatch sends them to conv_dma_kernel<256,256>): an upsampled input (the tap mask and the pixel
+// offset below are computed on the stored map) and more than 32 taps (the mask is one 32-bit word).
 template <typename E, int TC, int TP, int WC, int WP, int MINW, int NS>
 __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs a) {
     constexpr int BK = 32;
@@ -708,7 +465,7 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs
 #pragma unroll
     for (int j = 0; j < WJ; ++j)
         woff[j] = (unsigned)(((size_t)(tile_c * TC + lrow + j * 16 * NW) * a.K_pad + lchunk * 8) * 2);
-#define CVPCE_DMA4_STAGE(KT, BUF)                                                                              \
+#define CVPCE_RING_STAGE(KT, BUF)                                                                              \
     {                                                                                                          \
         const int kbyte = (KT) * (BK * 2);                                                                     \
         _Pragma("unroll") for (int j = 0; j < WJ; ++j)                                                         \
@@ -718,7 +475,7 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs
         const bool ch_ok = cbase < a.Cin;                                                                      \
         _Pragma("unroll") for (int j = 0; j < PJ; ++j) {                                                       \
             const bool ok = ch_ok && ((pmask[j] >> tapi) & 1u);                                                \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p,                              \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_p,                                                    \
                 (lds_void*)(Ps + (BUF) * TP * BK + (j * 16 * NW + wid * 16) * BK), 16,                         \
                 (int)(ok ? poff[j] + (unsigned)uni : 0xFFFFFFF0u), 0, 0, 0);                                   \
         }                                                                                                      \
@@ -753,12 +510,16 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs
     // 1.43 ms launch when they were serialised with the MFMAs.)
     //   stage s lives in ring slot s & 3; when MFMA(kt, group 1) is issued, stage kt+1 must be visible (its group-0
     //   fragments are being fetched) and stages kt+2, kt+3 are in flight.
-    CVPCE_DMA4_STAGE(0, 0)
-    if (nk > 1) CVPCE_DMA4_STAGE(1, 1)
-    if (NS == 4 && nk > 2) CVPCE_DMA4_STAGE(2, 2)
+    CVPCE_RING_STAGE(0, 0)
+    if (nk > 1) CVPCE_RING_STAGE(1, 1)
+    if (NS == 4 && nk > 2) CVPCE_RING_STAGE(2, 2)
     // Fragment pipeline.  Group 0 = cout blocks 0..MT/2-1 + ALL pixel blocks (MT/2 + NT reads), group 1 = cout blocks
     // MT/2..MT-1 (MT/2 reads).  Pixel fragments are double buffered across stages (group 1 of stage t still multiplies
     // stage t's pixels while group 0 of stage t+1 is being fetched).
+    // The reads are hand-issued (`ds_read_b128` in inline asm) and hand-counted: hipcc's waitcnt pass falls back to lgkmcnt(0)
+    // for LDS reads that are pending across the loop back-edge or sit next to LDS-DMA, which would make every MFMA group
+    // wait for the group that was only just prefetched.  Inline asm hides the reads from that pass; the `s_waitcnt
+    // lgkmcnt(N)` + sched_barrier of the stage body are the only LDS waits in the loop.
     constexpr int MH = MT / 2;
     const unsigned lds_w0 = (unsigned)(size_t)(lds_char*)Ws, lds_p0 = (unsigned)(size_t)(lds_char*)Ps;
     const unsigned lrow16 = lane & 15;
@@ -807,7 +568,7 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs
             if (NS == 4 && ahead >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");               \
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                              \
             __builtin_amdgcn_s_barrier();                                                                      \
-            if ((KT) + NS - 1 < nk) CVPCE_DMA4_STAGE((KT) + NS - 1, ((KT) + NS - 1) % NS)                      \
+            if ((KT) + NS - 1 < nk) CVPCE_RING_STAGE((KT) + NS - 1, ((KT) + NS - 1) % NS)                      \
             CVPCE_READ_A((KT) + 1, 0)                           /* group 0 of the next stage */                \
             CVPCE_READ_B((KT) + 1, (SET) ^ 1)                                                                  \
             asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(MH + NT) : "memory");   /* group 1 landed */            \
@@ -828,7 +589,7 @@ __global__ __launch_bounds__(WC * WP * 64, MINW) void conv_dma16_kernel(ConvArgs
 #undef CVPCE_READ_A
 #undef CVPCE_READ_B
 #undef CVPCE_MFMAS
-#undef CVPCE_DMA4_STAGE
+#undef CVPCE_RING_STAGE
     conv_epilogue16<E, MT, NT>(a, acc, tile_c * TC + wc * (TC / WC), tile_p * TP + wp * (TP / WP), lane);
 }
 
@@ -1014,14 +775,21 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
     conv_epilogue<E, MT, NT>(a, acc, tile_c * TC + wc * (TC / WC), tile_p * TP + wp * (TP / WP), lane);
 }
 
-template <typename E, int TC, int TP, int BK, int WC, int WP>
-static int launch_conv(const ConvArgs& a0, hipStream_t stream) {
+// dynamic LDS of a kernel instance: `stages` buffers of a TC x BK weight tile and a TP x BK pixel tile
+constexpr size_t conv_lds(int stages, int tc, int tp, int bk) { return (size_t)stages * (tc + tp) * bk * sizeof(bf16_t); }
+
+// One launch of `Kernel` on TC x TP output tiles, `per_tile` workgroups of THREADS threads each: the tile counts, the dynamic-LDS
+// attribute (one flag per template instance and device) for the instances that need more than the 64 KiB a kernel may take
+// without it -- no other launch pays its hipGetDevice --, the launch, its check.
+template <auto Kernel, int TC, int TP, int THREADS, size_t LDS>
+static int launch_conv(const ConvArgs& a0, hipStream_t stream, int per_tile = 1) {
     ConvArgs a = a0;
     a.tiles_p = (a.M + TP - 1) / TP;
     a.tiles_c = (a.Cout + TC - 1) / TC;
-    size_t smem = (size_t)2 * (TC + TP) * BK * sizeof(bf16_t);
-    dim3 grid(a.tiles_p * a.tiles_c);
-    hipLaunchKernelGGL((conv_igemm_kernel<E, TC, TP, BK, WC, WP>), grid, dim3(256), smem, stream, a);
+    if constexpr (LDS > 64 * 1024) {
+        if (!cvpce_smem_attr_done<Kernel>((const void*)Kernel, (int)LDS)) return CVPCE_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)(a.tiles_p * a.tiles_c * per_tile)), dim3(THREADS), LDS, stream, a);
     return cvpce_check_launch();
 }
 
@@ -1079,60 +847,12 @@ static int launch_conv_split(const ConvArgs& a0, int ksplit, void* workspace, si
     if (!workspace || workspace_bytes < need || ((size_t)workspace & 15)) return CVPCE_ERR_ARG;
     a.ksplit = ksplit;
     a.ws = (float*)workspace;
-    const size_t smem = (size_t)2 * (128 + 128) * 64 * sizeof(bf16_t);
-    hipLaunchKernelGGL((conv_igemm_kernel<E, 128, 128, 64, 2, 2, true>), dim3((unsigned)(ntile * ksplit)), dim3(256), smem, stream, a);
-    const int rc = cvpce_check_launch();
+    const int rc = launch_conv<conv_igemm_kernel<E, 128, 128, 64, 2, 2, true>, 128, 128, 256, conv_lds(2, 128, 128, 64)>(a, stream, ksplit);
     if (rc != CVPCE_OK) return rc;
     if (ksplit == 4) hipLaunchKernelGGL((conv_splitk_finish_kernel<E, 4>), dim3((unsigned)ntile * 4), dim3(256), 0, stream, a);
     else if (ksplit == 2) hipLaunchKernelGGL((conv_splitk_finish_kernel<E, 2>), dim3((unsigned)ntile * 4), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((conv_splitk_finish_kernel<E, 0>), dim3((unsigned)ntile * 4), dim3(256), 0, stream, a);
     return cvpce_check_launch();
-}
-
-template <typename E, int TC, int TP, int WC, int WP, int MINW>
-static int launch_conv_dma(const ConvArgs& a0, hipStream_t stream) {
-    ConvArgs a = a0;
-    a.tiles_p = (a.M + TP - 1) / TP;
-    a.tiles_c = (a.Cout + TC - 1) / TC;
-    const size_t smem = (size_t)2 * (TC + TP) * 64 * sizeof(bf16_t);
-    if (!cvpce_smem_attr_done<conv_dma_kernel<E, TC, TP, WC, WP, MINW>>((const void*)conv_dma_kernel<E, TC, TP, WC, WP, MINW>, (int)smem))
-        return CVPCE_ERR_LAUNCH;     // (one flag per template instance and device)
-    dim3 grid(a.tiles_p * a.tiles_c);
-    hipLaunchKernelGGL((conv_dma_kernel<E, TC, TP, WC, WP, MINW>), grid, dim3(WC * WP * 64), smem, stream, a);
-    return cvpce_check_launch();
-}
-
-template <typename E, int TC, int TP, int WC, int WP, int MINW, int NS>
-static int launch_conv_dma4(const ConvArgs& a0, hipStream_t stream) {
-    ConvArgs a = a0;
-    a.tiles_p = (a.M + TP - 1) / TP;
-    a.tiles_c = (a.Cout + TC - 1) / TC;
-    const size_t smem = (size_t)NS * (TC + TP) * 32 * sizeof(bf16_t);
-    if (!cvpce_smem_attr_done<conv_dma4_kernel<E, TC, TP, WC, WP, MINW, NS>>((const void*)conv_dma4_kernel<E, TC, TP, WC, WP, MINW, NS>, (int)smem))
-        return CVPCE_ERR_LAUNCH;
-    dim3 grid(a.tiles_p * a.tiles_c);
-    hipLaunchKernelGGL((conv_dma4_kernel<E, TC, TP, WC, WP, MINW, NS>), grid, dim3(WC * WP * 64), smem, stream, a);
-    return cvpce_check_launch();
-}
-
-template <typename E, int TC, int TP, int WC, int WP, int MINW, int NS>
-static int launch_conv_dma16(const ConvArgs& a0, hipStream_t stream) {
-    ConvArgs a = a0;
-    a.tiles_p = (a.M + TP - 1) / TP;
-    a.tiles_c = (a.Cout + TC - 1) / TC;
-    const size_t smem = (size_t)NS * (TC + TP) * 32 * sizeof(bf16_t);
-    if (!cvpce_smem_attr_done<conv_dma16_kernel<E, TC, TP, WC, WP, MINW, NS>>((const void*)conv_dma16_kernel<E, TC, TP, WC, WP, MINW, NS>, (int)smem))
-        return CVPCE_ERR_LAUNCH;
-    dim3 grid(a.tiles_p * a.tiles_c);
-    hipLaunchKernelGGL((conv_dma16_kernel<E, TC, TP, WC, WP, MINW, NS>), grid, dim3(WC * WP * 64), smem, stream, a);
-    return cvpce_check_launch();
-}
-
-#include <stdlib.h>
-// dev A/B switch (environment, read once): CVPCE_NO_TC32=1 sends thin outputs through the 64-cout tile as before round 3
-static bool use_tc32() {
-    static const bool on = !(getenv("CVPCE_NO_TC32") && getenv("CVPCE_NO_TC32")[0] == '1');
-    return on;
 }
 
 template <typename E>
@@ -1143,6 +863,7 @@ static int conv2d_dispatch(const void* in, const void* wgt, const float* bias, c
                            int fuse_pool2, int force_generic, void* stream, int ksplit = 0, void* workspace = nullptr,
                            size_t workspace_bytes = 0) {
     if (N <= 0) return CVPCE_OK;
+    if (force_generic != 0 && force_generic != 1) return CVPCE_ERR_ARG;
     if (!in || !wgt || !out) return CVPCE_ERR_ARG;
     if (Cin % 8 != 0 || K_pad % 32 != 0 || (Cin % 64 == 0 && K_pad % 64 != 0) || Cout_pad % 256 != 0 || Cout_pad < Cout)
         return CVPCE_ERR_ARG;
@@ -1172,26 +893,31 @@ static int conv2d_dispatch(const void* in, const void* wgt, const float* bias, c
         if (ksplit < 2 || ksplit > 16 || !bk64 || Cout <= 64 || fuse_pool2 || ksplit > K_pad / 64) return CVPCE_ERR_ARG;
         return launch_conv_split<E>(a, ksplit, workspace, workspace_bytes, s);
     }
-    // LDS-DMA workhorse: K-step 64 within one tap, and enough pixel tiles to fill 256 CUs.
-    //   Cout >= 192: 8 waves, 256x256 tile, 128 KiB LDS, 1 workgroup / CU (2 waves / SIMD)
+    // LDS-DMA workhorses: K-step 64 (32 in the ring) within one tap, and enough pixel tiles to fill 256 CUs.
+    //   Cout >= 192: 8 waves, 256x256 tile, 128 KiB LDS, 1 workgroup / CU (2 waves / SIMD); the ring kernel, or the 2-buffer
+    //                kernel for what the ring does not cover (an upsampled input, a tap mask of more than 32 bits)
     //   Cout <= 128: 4 waves, 128x128 or 64x128 tile, 64 / 48 KiB LDS, 2 workgroups / CU
     const long long tiles256 = ((long long)a.M + 255) / 256;
-    if (bk64 && force_generic != 1) {
+    if (bk64 && !force_generic) {
         if (Cout >= 192 && tiles256 * ((Cout + 255) / 256) >= 128)
-            return (force_generic == 2 || in_up_shift || KH * KW > 32) ? launch_conv_dma<E, 256, 256, 2, 4, 2>(a, s)
-                   : (force_generic == 3)                                ? launch_conv_dma4<E, 256, 256, 2, 4, 2, 4>(a, s)
-                                                                        : launch_conv_dma16<E, 256, 256, 2, 4, 2, 4>(a, s);
-        if (Cout > 64 && Cout <= 128 && tiles256 >= 128) return launch_conv_dma<E, 128, 128, 2, 2, 2>(a, s);
-        if (Cout > 32 && Cout <= 64 && tiles256 >= 128) return launch_conv_dma<E, 64, 128, 2, 2, 2>(a, s);
+            return (in_up_shift || KH * KW > 32)
+                       ? launch_conv<conv_dma_kernel<E, 256, 256, 2, 4, 2>, 256, 256, 512, conv_lds(2, 256, 256, 64)>(a, s)
+                       : launch_conv<conv_dma16_kernel<E, 256, 256, 2, 4, 2, 4>, 256, 256, 512, conv_lds(4, 256, 256, 32)>(a, s);
+        if (Cout > 64 && Cout <= 128 && tiles256 >= 128)
+            return launch_conv<conv_dma_kernel<E, 128, 128, 2, 2, 2>, 128, 128, 256, conv_lds(2, 128, 128, 64)>(a, s);
+        if (Cout > 32 && Cout <= 64 && tiles256 >= 128)
+            return launch_conv<conv_dma_kernel<E, 64, 128, 2, 2, 2>, 64, 128, 256, conv_lds(2, 64, 128, 64)>(a, s);
     }
     if (Cout > 64) {
-        return bk64 ? launch_conv<E, 128, 128, 64, 2, 2>(a, s) : launch_conv<E, 128, 128, 32, 2, 2>(a, s);
-    } else if (Cout <= 32 && bk64 && use_tc32()) {
+        return bk64 ? launch_conv<conv_igemm_kernel<E, 128, 128, 64, 2, 2>, 128, 128, 256, conv_lds(2, 128, 128, 64)>(a, s)
+                    : launch_conv<conv_igemm_kernel<E, 128, 128, 32, 2, 2>, 128, 128, 256, conv_lds(2, 128, 128, 32)>(a, s);
+    } else if (Cout <= 32 && bk64) {
         // thin outputs on wide inputs (cls_logits 256 -> 9, the Gaussian subnet's 64 -> 32): a 32-cout tile halves the MFMA work spent
         // on cout padding (with K-step 32 a 32-row weight tile is less than one staging pass of the 256 threads: not instantiated)
-        return launch_conv<E, 32, 128, 64, 1, 4>(a, s);
+        return launch_conv<conv_igemm_kernel<E, 32, 128, 64, 1, 4>, 32, 128, 256, conv_lds(2, 32, 128, 64)>(a, s);
     } else {
-        return bk64 ? launch_conv<E, 64, 128, 64, 2, 2>(a, s) : launch_conv<E, 64, 128, 32, 2, 2>(a, s);
+        return bk64 ? launch_conv<conv_igemm_kernel<E, 64, 128, 64, 2, 2>, 64, 128, 256, conv_lds(2, 64, 128, 64)>(a, s)
+                    : launch_conv<conv_igemm_kernel<E, 64, 128, 32, 2, 2>, 64, 128, 256, conv_lds(2, 64, 128, 32)>(a, s);
     }
 }
 

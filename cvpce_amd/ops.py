@@ -40,7 +40,7 @@ def _need_cuda(*ts):
 # ---------------------------------------------------------------------------
 # switches: read as module globals at call time (tests and tools assign to them), most of them A/B switches with an environment variable
 # ---------------------------------------------------------------------------
-FORCE_GENERIC_CONV = False   # A/B switch: route every conv through the register-staged fallback kernel
+FORCE_GENERIC_CONV = False   # A/B switch (a boolean): route every conv through the register-staged fallback kernel
 USE_HALO_3X3 = True          # A/B switch: 3x3 s1 layers with Cin % 64 == 0 through the halo-patch kernel
 HALO_RAGGED = bool(int(_os.environ.get('CVPCE_HALO_RAGGED', '0')))          # test switch: also send small maps and maps that 16x16 tiles do not cover exactly through the halo kernel
 USE_HALO_THIN_OUT = _os.environ.get('CVPCE_HALO_THIN_OUT', '1') != '0'   # A/B switch: the head's output convs through the thin-output form of the wide halo kernel
@@ -119,14 +119,16 @@ class PackedConv:
         return ((h + 2 * self.pad - self.kh) // self.stride + 1, (w + 2 * self.pad - self.kw) // self.stride + 1)
 
 
-def igemm_tile(pc, m):
-    """The kernel `cvpce_conv2d_nhwc_*` runs layer `pc` with on m = N Ho Wo output pixels -> (kernel, its template arguments): THE mirror of
-    conv2d_dispatch in csrc/conv_igemm.hip (tile TC x TP, K-step BK).  FORCE_GENERIC_CONV 2 and 3 (A/B variants of the 256 x 256 kernel)
-    count as 1 here."""
+def igemm_tile(pc, m, in_up_shift=0):
+    """The kernel `cvpce_conv2d_nhwc_*` runs layer `pc` with on m = N Ho Wo output pixels (of an input upsampled by in_up_shift) ->
+    (kernel, its template arguments): THE mirror of conv2d_dispatch in csrc/conv_igemm.hip (tile TC x TP, K-step BK)."""
     bk64 = pc.cin_pad % 64 == 0
     tiles256 = (m + 255) // 256
     if bk64 and not FORCE_GENERIC_CONV:
         if pc.cout >= 192 and tiles256 * ((pc.cout + 255) // 256) >= 128:
+            # the ring kernel keeps a tap mask of 32 bits per pixel and does not upsample: those layers take the 2-buffer kernel
+            if in_up_shift or pc.kh * pc.kw > 32:
+                return 'conv_dma_kernel', (256, 256, 2, 4, 2)
             return 'conv_dma16_kernel', (256, 256, 2, 4, 2, 4)
         if 64 < pc.cout <= 128 and tiles256 >= 128:
             return 'conv_dma_kernel', (128, 128, 2, 2, 2)
@@ -173,8 +175,8 @@ class ConvProfile:
         return out
 
     @staticmethod
-    def variant(pc, m):
-        kernel, args = igemm_tile(pc, m)
+    def variant(pc, m, in_up_shift=0):
+        kernel, args = igemm_tile(pc, m, in_up_shift)
         return f"{kernel}<{','.join(map(str, args))}>"
 
     def summary(self):
@@ -293,7 +295,7 @@ def conv_route(pc, n, h, w, act, out_f32, has_residual, in_up_shift, pool):
     # small maps with a long K (layer4's 3x3 convs on 25 x 25 maps, the stride-2 3x3s that open layer3 / layer4, P5 / P6 / P7): the
     # register-staged kernel with K split over `ks` workgroups per output tile (csrc/conv_igemm.hip SPLIT), the 128-cout tile only
     if not pool:
-        kernel, tile = igemm_tile(pc, n * ho * wo)
+        kernel, tile = igemm_tile(pc, n * ho * wo, in_up_shift)
         if kernel == 'conv_igemm_kernel' and tile[0] == 128:
             ks = splitk_factor(pc, ho, wo)
             if ks:
@@ -348,7 +350,7 @@ def conv2d(x, pc, act=0, out_f32=False, residual=None, res_mode=0, in_up_shift=0
                         int(act), int(out_f32), int(in_up_shift), int(res_mode), ks, _splitk_workspace(pc, n, ho, wo, ks, x.device))
     else:
         T.conv2d_nhwc(x, pc.weight, pc.bias, residual, out, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, ho, wo, pc.k_pad, pc.cout_pad,
-                      int(act), int(out_f32), int(in_up_shift), int(res_mode), int(pool), int(FORCE_GENERIC_CONV))   # FORCE_GENERIC_CONV: False/True or 2, 3 = A/B variants
+                      int(act), int(out_f32), int(in_up_shift), int(res_mode), int(pool), int(bool(FORCE_GENERIC_CONV)))
     if t is not None:
         t.stop()
         flops = 2.0 * n * ho * wo * pc.cout * pc.kh * pc.kw * pc.cin    # algorithmic FLOPs: real (unpadded) channels, 2 FLOP per MAC
@@ -366,7 +368,7 @@ def conv2d(x, pc, act=0, out_f32=False, residual=None, res_mode=0, in_up_shift=0
             nbytes = n * ho * wo * cin * x.element_size() + _nbytes(out, residual, pc.weight)
             t.file('conv1x1_kernel', flops, nbytes, f'conv1x1 {ho}x{wo} {shape} s{pc.stride}' + (' +res' if residual is not None else ''), hbm=True)
         else:
-            variant = ConvProfile.variant(pc, n * ho * wo)
+            variant = ConvProfile.variant(pc, n * ho * wo, in_up_shift)
             t.file(variant, flops, nbytes, f"{variant.split('<')[0]} {ho}x{wo} {shape} k{pc.kh} s{pc.stride}" + (' f32 out' if out_f32 else '')
                    + (f' split-K {ks}' if ks else ''))
     return out

@@ -65,7 +65,8 @@ extern "C" {
  *   out_f32       : NHWC fp32 output (head logits / box regressions / gaussians)
  *   fuse_pool2    : the following nn.MaxPool2d(2,2) is taken in the epilogue; `out` is
  *                   [N][Ho/2][Wo/2][Cout] (VGG16 `features` conv+ReLU+pool triples)
- *   force_generic : 1 = always use the register-staged fallback kernel (A/B tests) */
+ *   force_generic : 1 = always use the register-staged fallback kernel (A/B tests); 0 = the library chooses; other values
+ *                   are refused */
 int cvpce_conv2d_nhwc_bf16(const void* in, const void* wgt, const float* bias, const void* res, void* out,
                            int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                            int Ho, int Wo, int K_pad, int Cout_pad, int act, int out_f32, int in_up_shift,

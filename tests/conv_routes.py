@@ -27,7 +27,7 @@ MAPS = [(1, 16, 16), (2, 25, 25), (1, 50, 52), (1, 100, 100), (4, 200, 200)]    
 DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16}
 # every switch the GPU tests flip, with its other value(s)
 SWITCHES = [('USE_HALO_3X3', False), ('USE_CONV1X1', False), ('USE_THIN_3X3', False), ('USE_HALO_THIN_OUT', False), ('CONV_SPLITK', False),
-            ('HALO_RAGGED', True), ('CONV1X1_ANY_SHAPE', True), ('FORCE_GENERIC_CONV', True), ('FORCE_GENERIC_CONV', 2), ('FORCE_GENERIC_CONV', 3)]
+            ('HALO_RAGGED', True), ('CONV1X1_ANY_SHAPE', True), ('FORCE_GENERIC_CONV', True)]
 
 OPS_CONV2D = {'conv2d_nhwc', 'conv2d_splitk', 'conv1x1_nhwc', 'conv3x3_halo', 'conv3x3_halo_thin_out', 'conv3x3_thin'}
 RECORD_NAMES_CONV2D = {'conv_igemm_kernel<128,128,64,2,2>', 'conv_igemm_kernel<64,128,32,2,2>', 'conv_igemm_kernel<64,128,64,2,2>',

@@ -282,6 +282,7 @@ DMA = {   # the LDS-DMA ring kernels need their whole batch (128 pixel tiles of 
     'dma128': (2, 64, 128, 128, 128, 3, 1, 1, {}),
     'dma256': (2, 64, 128, 128, 256, 3, 1, 1, {}),
     'dma_ragged': (1, 64, 181, 182, 192, 3, 1, 1, {}),
+    'dma_in_up': (1, 64, 91, 90, 192, 3, 1, 1, {'in_up': 1}),      # 182 x 180 output: 128 pixel tiles, the last ragged; conv_dma_kernel<256,256>
     'dma_res_up': (2, 64, 128, 128, 256, 1, 1, 0, {'res': 'up', 'act': 0}),
     'pool_dma64': (2, 64, 128, 128, 64, 3, 1, 1, {'pool': True}),
 }

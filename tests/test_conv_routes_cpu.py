@@ -43,3 +43,23 @@ def test_table_covers_every_route(table):
     assert {records[0][0] for _, records, _, _ in base} == RECORD_NAMES_CONV2D
     assert {records[0][0] for _, records, _, _ in conv2d} == RECORD_NAMES_CONV2D | {'conv3x3_halo2_kernel[detector]'}
     assert any(calls[0][0] == 'conv2d_splitk' and calls[0][-1] == 4 for calls, _, _, _ in base)
+
+
+@pytest.mark.parametrize('entry', ['cvpce_conv2d_nhwc_bf16', 'cvpce_conv2d_nhwc_f16'])
+def test_force_generic_is_zero_or_one(entry):
+    """`force_generic` selects no kernel variants any more: the entry points refuse every value but 0 and 1, behind the N <= 0 return
+    that comes before every check.  Dummy pointers and the return-code convention of tests/halo_host_cases.py (0: N <= 0; 1: refused;
+    2: accepted, failed at the launch for want of a device), so only where no GPU is visible."""
+    from halo_host_cases import P, gpu_visible
+    if gpu_visible():
+        pytest.skip('a GPU is visible: an accepted case would launch a kernel on dummy pointers')
+    from cvpce_amd._lib import lib
+
+    def call(n, force_generic):
+        # in, wgt, bias, res, out, N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo, K_pad, Cout_pad, act, out_f32, in_up_shift,
+        # res_mode, Hr, Wr, fuse_pool2, force_generic, stream: a 64 -> 64 3x3 layer on 16 x 16 maps
+        return int(getattr(lib, entry)(P, P, P, 0, P, n, 16, 16, 64, 64, 3, 3, 1, 1, 16, 16, 576, 256, 1, 0, 0, 0, 0, 0, 0, force_generic, 0))
+
+    assert [call(2, fg) for fg in (2, 3, -1)] == [1, 1, 1]
+    assert call(0, 2) == 0
+    assert [call(2, fg) for fg in (0, 1)] == [2, 2]              # the same call is refused for nothing else

@@ -139,10 +139,14 @@ def test_igemm_generic(cuda, refs, cid):
 
 @pytest.mark.parametrize('cid', ec.ids('dma'))
 def test_lds_dma_ring(cuda, refs, cid):
-    """the LDS-DMA ring kernels (256 x 256, 128 x 128 and 64 x 128 tiles); the whole batch runs (they need 128 pixel tiles), the last image is compared"""
+    """the LDS-DMA ring kernels (256 x 256, 128 x 128 and 64 x 128 tiles); the whole batch runs (they need 128 pixel tiles), the last image is compared.
+    dma_in_up: the 2-buffer 256 x 256 kernel, which takes the ring kernel's shapes on an upsampled input (its padding test runs on
+    upsampled coordinates) -- no model has such a layer, so this is the only launch of that instance"""
     c, ref = refs(cid)
     y, route, rec, _ = launch_conv(cuda, c, USE_HALO_3X3=False, USE_CONV1X1=False)
     assert route == 'igemm' and rec.startswith('conv_dma'), (route, rec)
+    if c.name == 'dma_in_up':
+        assert rec == 'conv_dma_kernel<256,256,2,4,2>', rec
     same(widen(y, c.keep), ref, cid)
 
 

@@ -392,7 +392,7 @@ def _conv2d_case(cuda, dt, name, n, cin, h, w, cout, k, stride, pad, o, splitk=0
             run()
         return
     if o.get('variant'):
-        assert ops.ConvProfile.variant(pc, n * ho * wo) == o['variant']
+        assert ops.ConvProfile.variant(pc, n * ho * wo, in_up) == o['variant']
     got = fp.check(run, [xin, rin] + wa, [out] + ([ws] if ws else []), written=[None] + ([fp.SCRATCH] if ws else []))
     ref = conv_ref(x, cin, wgt, bias, dt, stride, pad, act=act, res=res, pool=pool, in_up=in_up)
     assert rel_err(nchw(got[0]), ref) < (TOL32 if f32 else TOL16)
@@ -408,6 +408,8 @@ def test_conv2d_nhwc_generic(cuda, case, dt):
 
 DMA_CASES = [  # M = 13 * 41 * 61 = 127 * 256 + 1: the smallest M that selects each LDS-DMA tile form, ragged in Cout
     ('dma256', 13, 64, 41, 61, 192, 3, 1, 1, {'variant': 'conv_dma16_kernel<256,256,2,4,2,4>'}),
+    # the same form on an upsampled input goes to the 2-buffer kernel; an upsampled map is even, M = 13 * 42 * 62 = 132 * 256 + 60
+    ('dma256_in_up', 13, 64, 21, 31, 192, 3, 1, 1, {'in_up': 1, 'variant': 'conv_dma_kernel<256,256,2,4,2>'}),
     ('dma128', 13, 64, 41, 61, 96, 3, 1, 1, {'variant': 'conv_dma_kernel<128,128,2,2,2>'}),
     ('dma64', 13, 64, 41, 61, 40, 3, 1, 1, {'variant': 'conv_dma_kernel<64,128,2,2,2>'}),
 ]
@@ -418,13 +420,19 @@ DMA_CASES = [  # M = 13 * 41 * 61 = 127 * 256 + 1: the smallest M that selects e
 def test_conv2d_nhwc_lds_dma(cuda, case, dt):
     """cvpce_conv2d_nhwc_* on the LDS-DMA kernels: the dispatch takes them from 128 pixel tiles of 256 up, so M = 32 513 pixels -- 127
     full tiles and a last one that holds a single pixel, with image boundaries inside the tiles -- is the smallest M for each form;
-    one M below it `variant` names a register-staged kernel.  Which kernel ran is read from ops.ConvProfile.variant, the Python
+    one M below it `variant` names a register-staged kernel (dma256_in_up: the 2-buffer 256 x 256 kernel on an upsampled input, at
+    M = 33 852, 133 tiles with a ragged last one).  Which kernel ran is read from ops.ConvProfile.variant, the Python
     mirror of the dispatch in csrc/conv_igemm.hip (conv2d_dispatch): the library does not report the kernel it launched, so this
     confirms the case against the mirror, and the mirror is held to the C++ only by reading the two side by side."""
     from cvpce_amd import ops
     name, n, cin, h, w, cout = case[:6]
     pc = ops.PackedConv(torch.zeros(cout, cin, 3, 3), None, 1, 1, device=cuda, dtype=dt)
-    assert n * h * w == 127 * 256 + 1 and 'conv_igemm_kernel' in ops.ConvProfile.variant(pc, n * h * w - 1)
+    in_up = case[9].get('in_up', 0)
+    if in_up:
+        assert n * (2 * h) * (2 * w) == 132 * 256 + 60          # (upsampled maps are even: no batch of them has 127 * 256 + 1 pixels)
+    else:
+        assert n * h * w == 127 * 256 + 1
+    assert 'conv_igemm_kernel' in ops.ConvProfile.variant(pc, 127 * 256, in_up)
     _conv2d_case(cuda, dt, *case)
 
 

@@ -30,7 +30,7 @@ LAYERS = {
 ap = argparse.ArgumentParser()
 ap.add_argument('--layers', default=','.join(LAYERS))
 ap.add_argument('--iters', type=int, default=10)
-ap.add_argument('--generic', type=int, default=0)
+ap.add_argument('--generic', action='store_true', help='every layer through the register-staged fallback kernel')
 ap.add_argument('--dbg', type=int, default=0)
 ap.add_argument('--no-halo', action='store_true')
 ap.add_argument('--relu-input', action='store_true', help='post-ReLU-like input (half zeros, non-negative) instead of N(0,1): the data regime of the real pipeline (matters: the MFMA kernels are power-limited)')
