@@ -214,9 +214,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
         // lane id recomputed here (2 VALU ops, once per patch) instead of living in a VGPR across the K loop; the volatile
         // asm also keeps the per-piece constants below from being hoisted out of the chunk loop (18+ VGPRs)
         const int ln = halo_lane_id();
+        // a cut tile (LIST without strips, rows < 16) reads patch rows 0 .. rows + 1 and nothing behind them (G2_CUT_PAIR), so a piece
+        // whose first pixel lies behind those rows is not fetched: its LDS keeps an earlier tile's data, which nobody reads.  `rows`
+        // is that of the tile being FETCHED.  The test is wave-uniform (a piece belongs to one wave).  The hand-off's vmcnt(6) needs
+        // no change: it counts what may still be in flight, and with fewer pieces issued the six youngest are still the weight loads
+        int fetched = G2_NPIX;
+        if constexpr (LIST && SH == 0) fetched = (wl_rows((unsigned)ext[0]) + 2) * G2_P;
 #pragma unroll
         for (int i = 0; i < NPP; ++i) {
-            if (i < npp) {
+            if (i < npp && (!(LIST && SH == 0) || (wc + NW * i) * 8 < fetched)) {
                 const int j = wc + NW * i;
                 const int pp = j * 8 + (ln >> 3);
                 const int py = pp / G2_P, px = pp - py * G2_P;
@@ -371,40 +377,49 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
     }
     // LIST launches: a tile computes only its first `rows_` output rows, `rows_` any EVEN number 2 .. 16 -- the rest lies in the crop's
     // constant region and is never read by anyone.  Output row r needs patch rows r .. r + 2, so a step streams patch rows
-    // 0 .. rows_ + 1 and stops: one uniform branch per row pair (every G2_RP is a scheduling region of its own, so a branch between two
-    // of them splits nothing).  The two reads the step has prefetched beyond, patch rows rows_ + 2 and rows_ + 3, are stale: the cut
-    // step waits for them (G2_STALE_LANDED) before it hands over, so whatever slot they sit in -- relative to 2 T, slots 2, 3 for
-    // rows_ = 0 (mod 4), the slots the next step's rows 0, 1 go to; slots 0, 1 for rows_ = 2 (mod 4), the slots of its rows 2, 3 -- is
-    // free when the next read into it is issued.  The next step's rows 0, 1 go to slots 2, 3: for rows_ = 2 (mod 4) the slots of
-    // patch rows rows_, rows_ + 1, the last two consumed; their MFMAs were issued before the reads that overwrite them, as everywhere
-    // in the ring.  The waits count as in a full step: when G2_ROW(TN, 0) waits for lgkmcnt(2), rows 0, 1, 2 are in flight.
-    // Accumulator rows rows_, rows_ + 1 collect partial sums nobody stores.  A THIN strip pass (SH == 2) streams patch rows 0 .. 15
-    // and never reads rows 16, 17: rows_ = 14 throughout, no stale read.  BEFORE: what precedes the step's hand-over to the next one
-    // (the chunk hand-off in the last step).
+    // 0 .. rows_ + 1 and stops: uniform branches per row pair (every G2_RP is a scheduling region of its own, so a branch between two
+    // of them splits nothing) -- one for the whole pair, one for the cut pair, two `if` side by side: written as if / else the
+    // accumulators meet in a diamond per pair and the allocator spills (256 VGPRs + 60 .. 104 bytes of scratch against 226 .. 230 and
+    // none), and rows_ is re-read opaquely once per step so that the 14 conditions are compared where they are used instead of being
+    // kept in SGPR pairs across the steps (which spilled those to VGPR lanes).  The hints put the full pairs in the fall-through path:
+    // out of line they cost the layers without a cut tile 1.5 - 3 % (profiles/r19_cut_rows.md).  A CUT tile (rows_ < 16, no strips) ends EXACTLY: the pair of patch rows rows_, rows_ + 1 is its last,
+    // and that pair runs as G2_CUT_PAIR -- no prefetch behind it (patch rows rows_ + 2, rows_ + 3 are never read, and issue_patch does
+    // not fetch them), and only the taps whose output row lies below rows_: kh = 1, 2 of patch row rows_, kh = 2 of patch row
+    // rows_ + 1.  6 rows_ MFMAs per step and wave, none into a row the epilogue does not store; every stored row still collects its
+    // kh = 0, 1, 2 in that order.  With nothing prefetched behind them the two rows wait for what is really in flight: lgkmcnt(1),
+    // then lgkmcnt(0) (as the thin strips do for their rows 14, 15).  The next step's rows 0, 1 go to ring slots 2, 3 relative to
+    // 2 T: for rows_ = 2 (mod 4) the slots of patch rows rows_, rows_ + 1, the last two consumed; their MFMAs were issued before
+    // the reads that overwrite them, as everywhere in the ring.  The waits then count as in a full step: when G2_ROW(TN, 0) waits
+    // for lgkmcnt(2), rows 0, 1, 2 are in flight.  Every read a step issues is consumed by a G2_ROW or a G2_CUT_ROW of that step: no
+    // destination register is dead while its data is in flight.  A THIN strip pass (SH == 2) streams patch rows 0 .. 15 and never reads
+    // rows 16, 17: rows_ = 14 throughout.  BEFORE: what precedes the step's hand-over to the next one (the chunk hand-off in the
+    // last step).
 #define G2_MORE(R) (!LIST || SH == 4 || (SH == 2 ? (R) < 14 : rows_ > (R)))
-    // the stale reads' destination registers are dead to the compiler the moment they are issued: it hands them to the next value it
-    // computes (seen: an LDS address of G2_SET_E three instructions behind a short strip row), and the late data would land on that.
-    // So a cut step waits until they have landed before anything else is computed -- they were issued two MFMA groups ago
-#define G2_STALE_LANDED()                                                                                      \
+    // patch row P of a cut tile's last pair, taps KH0 .. 2, with LEFT reads still in flight behind it
+#define G2_CUT_ROW(T, P, KH0, LEFT)                                                                            \
     {                                                                                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bfr[((P) + 2 * (T)) & 3]) : "n"(LEFT));                    \
+        if constexpr ((KH0) <= 1) G2_ROW_KH(T, P, 1)                                                           \
+        G2_ROW_KH(T, P, 2)                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
     }
+#define G2_CUT_PAIR(T, P) G2_CUT_ROW(T, P, 1, 1) G2_CUT_ROW(T, (P) + 1, 2, 0)
+    // patch rows P, P + 1 (P even, 2 .. 14)
+#define G2_PAIR(T, P)                                                                                          \
+    if constexpr (LIST && SH == 0) {                                                                           \
+        if (__builtin_expect(rows_ > (P), 1)) { G2_RP(T, P) G2_RP(T, (P) + 1) }                                \
+        if (__builtin_expect(rows_ == (P), 0)) { G2_CUT_PAIR(T, P) }                                           \
+    } else if (G2_MORE((P) - 2)) { G2_RP(T, P) G2_RP(T, (P) + 1) }
 #define G2_ROWS_AND_TAIL(T, TN, BUFB_NEXT, BEFORE)                                                             \
-    G2_RP(T, 0) G2_RP(T, 1) G2_RP(T, 2) G2_RP(T, 3)                                                            \
-    if (G2_MORE(2)) { G2_RP(T, 4) G2_RP(T, 5) }                                                                \
-    if (G2_MORE(4)) { G2_RP(T, 6) G2_RP(T, 7) }                                                                \
-    if (G2_MORE(6)) { G2_RP(T, 8) G2_RP(T, 9) }                                                                \
-    if (G2_MORE(8)) { G2_RP(T, 10) G2_RP(T, 11) }                                                              \
-    if (G2_MORE(10)) { G2_RP(T, 12) G2_RP(T, 13) }                                                             \
-    if (G2_MORE(12)) { G2_RP(T, 14) G2_RP(T, 15) }                                                             \
+    if constexpr (LIST && SH == 0) asm volatile("" : "+s"(rows_));                                             \
+    G2_RP(T, 0) G2_RP(T, 1)                                                                                    \
+    G2_PAIR(T, 2) G2_PAIR(T, 4) G2_PAIR(T, 6) G2_PAIR(T, 8) G2_PAIR(T, 10) G2_PAIR(T, 12) G2_PAIR(T, 14)       \
     if (G2_MORE(14)) {                                                                                         \
         BEFORE                                                                                                 \
         G2_SET_E(TN, BUFB_NEXT)                                                                                \
         G2_READ(TN, 0) G2_ROW(T, 16)                                                                           \
         G2_READ(TN, 1) G2_ROW(T, 17)                                                                           \
     } else {                                                                                                   \
-        G2_STALE_LANDED()                                                                                      \
         BEFORE                                                                                                 \
         G2_SET_E(TN, BUFB_NEXT)                                                                                \
         G2_READ(TN, 0)                                                                                         \
@@ -596,8 +611,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void conv3x3_halo2_kernel
 #undef G2_STEP
 #undef G2_HANDOFF
 #undef G2_ROWS_AND_TAIL
+#undef G2_PAIR
+#undef G2_CUT_PAIR
+#undef G2_CUT_ROW
 #undef G2_MORE
-#undef G2_STALE_LANDED
 #undef G2_RP
 #undef G2_ROW
 #undef G2_ROW_KH

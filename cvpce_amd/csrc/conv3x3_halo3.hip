@@ -143,9 +143,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
         // lane id recomputed here (2 VALU ops, once per patch) instead of living in a VGPR across the K loop; the volatile
         // asm also keeps the per-piece constants below from being hoisted out of the chunk loop (18+ VGPRs)
         const int ln = halo_lane_id();
+        // a cut tile (LIST, rows < 16) reads patch rows 0 .. rows + 1 only, so a piece whose first pixel lies behind them is not fetched
+        // and its LDS keeps an earlier tile's data, which nobody reads; `rows` is that of the tile being fetched, the test is
+        // wave-uniform, and the hand-off's vmcnt(6) holds with fewer pieces in flight (see issue_patch in conv3x3_halo2.hip)
+        int fetched = G3_NPIX;
+        if constexpr (LIST) fetched = (wl_rows((unsigned)ext) + 2) * G3_PW;
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
-            if (i < npp) {
+            if (i < npp && (!LIST || (wid + 8 * i) * 16 < fetched)) {
                 const int j = wid + 8 * i;
                 const int pp = j * 16 + (ln >> 2);
                 const int py = pp / G3_PW, px = pp - py * G3_PW;
@@ -260,26 +265,36 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
         { G3_TIC() if (!(CVPCE_DBG & 64)) __builtin_amdgcn_s_barrier(); G3_TOC(2) }     /* (64: timing-only ablation, no hand-off wait / barrier) */ \
         issue_next_patch();                                                                                    \
     }
-    // LIST launches compute only the first `rows_` (even, 2 .. 16) output rows of a tile, a branch per row pair: see G2_ROWS_AND_TAIL in
-    // conv3x3_halo2.hip (the same ring, the same argument for rows_ = 0 and = 2 mod 4)
+    // LIST launches compute only the first `rows_` (even, 2 .. 16) output rows of a tile, two branches per row pair, and a cut tile
+    // (rows_ < 16) ends exactly: its last pair, patch rows rows_, rows_ + 1, prefetches nothing behind it, issues only the taps whose
+    // output row lies below rows_ (kh = 1, 2, then kh = 2) and waits for what is really in flight, lgkmcnt(1) then lgkmcnt(0).  See
+    // G2_ROWS_AND_TAIL in conv3x3_halo2.hip (the same ring, the same argument for rows_ = 0 and = 2 mod 4)
 #define G3_MORE(R) (!LIST || rows_ > (R))
+    // patch row P of a cut tile's last pair, taps KH0 .. 2, with LEFT reads still in flight behind it
+#define G3_CUT_ROW(T, P, KH0, LEFT)                                                                            \
+    {                                                                                                          \
+        if constexpr (!(CVPCE_DBG & 32)) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(bfr[((P) + 2 * (T)) & 3]) : "n"(LEFT)); \
+        _Pragma("unroll") for (int kh_ = (KH0); kh_ < 3; ++kh_)                                                \
+            _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                \
+                acc[mt_][(P) - kh_] = E::mfma16(af[(T) & 1][kh_][mt_], bfr[((P) + 2 * (T)) & 3], acc[mt_][(P) - kh_]); \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
+    }
+    // patch rows P, P + 1 (P even, 2 .. 14)
+#define G3_PAIR(T, P)                                                                                          \
+    if constexpr (LIST) {                                                                                      \
+        if (__builtin_expect(rows_ > (P), 1)) { G3_RP(T, P) G3_RP(T, (P) + 1) }                                \
+        if (__builtin_expect(rows_ == (P), 0)) { G3_CUT_ROW(T, P, 1, 1) G3_CUT_ROW(T, (P) + 1, 2, 0) } \
+    } else { G3_RP(T, P) G3_RP(T, (P) + 1) }
 #define G3_ROWS_AND_TAIL(T, TN, BUFB_NEXT, BEFORE)                                                             \
-    G3_RP(T, 0) G3_RP(T, 1) G3_RP(T, 2) G3_RP(T, 3)                                                            \
-    if (G3_MORE(2)) { G3_RP(T, 4) G3_RP(T, 5) }                                                                \
-    if (G3_MORE(4)) { G3_RP(T, 6) G3_RP(T, 7) }                                                                \
-    if (G3_MORE(6)) { G3_RP(T, 8) G3_RP(T, 9) }                                                                \
-    if (G3_MORE(8)) { G3_RP(T, 10) G3_RP(T, 11) }                                                              \
-    if (G3_MORE(10)) { G3_RP(T, 12) G3_RP(T, 13) }                                                             \
-    if (G3_MORE(12)) { G3_RP(T, 14) G3_RP(T, 15) }                                                             \
+    if constexpr (LIST) asm volatile("" : "+s"(rows_));                                                        \
+    G3_RP(T, 0) G3_RP(T, 1)                                                                                    \
+    G3_PAIR(T, 2) G3_PAIR(T, 4) G3_PAIR(T, 6) G3_PAIR(T, 8) G3_PAIR(T, 10) G3_PAIR(T, 12) G3_PAIR(T, 14)       \
     if (G3_MORE(14)) {                                                                                         \
         BEFORE                                                                                                 \
         G3_SET_E(TN, BUFB_NEXT)                                                                                \
         G3_READ(TN, 0) G3_ROW(T, 16)                                                                           \
         G3_READ(TN, 1) G3_ROW(T, 17)                                                                           \
     } else {                                                                                                   \
-        /* the stale reads have landed before anything else is computed: see G2_STALE_LANDED */                \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
         BEFORE                                                                                                 \
         G3_SET_E(TN, BUFB_NEXT)                                                                                \
         G3_READ(TN, 0)                                                                                         \
@@ -449,6 +464,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo3_kernel(Halo3Args a) {
 #undef G3_STEP
 #undef G3_HANDOFF
 #undef G3_ROWS_AND_TAIL
+#undef G3_PAIR
+#undef G3_CUT_ROW
 #undef G3_MORE
 #undef G3_RP
 #undef G3_ROW

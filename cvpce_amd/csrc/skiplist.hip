@@ -105,8 +105,10 @@ __global__ __launch_bounds__(1024) void embed_worklists_kernel(WorklistArgs a) {
             a.computed[((long long)blockIdx.x * a.n + n) * 2] = ny > 0 ? (ny - 1) * 16 + last_rows : 0;
             a.computed[((long long)blockIdx.x * a.n + n) * 2 + 1] = nx;
         }
-        // MFMA work of this crop's tiles in sixteenths of a tile: full tiles 16, a tile cut at `rows` rows + 1 (it streams patch rows
-        // 0 .. rows + 1), a strip 4 (three strips share one pass of 72 MFMAs per step against a full tile's 96), a thin strip 2 (four share 48)
+        // MFMA work of this crop's tiles in sixteenths of a tile: full tiles 16, a tile cut at `rows` is BOOKED as rows + 1, a strip 4
+        // (three strips share one pass of 72 MFMAs per step against a full tile's 96), a thin strip 2 (four share 48).  The halo
+        // kernels' cut tiles now end exactly (6 rows MFMAs per step: the taps of patch rows rows, rows + 1 into rows nobody stores are
+        // not issued), so the figure OVERSTATES a cut tile by one sixteenth; it is kept because the list tests pin it
         if (ny > 0) atomicAdd(&s_units, nx * (16 * (ny - 1) + (strips ? 4 : (thin ? 2 : (last_rows < 16 ? last_rows + 1 : 16)))));
         s_geo[tid] = ((unsigned)ny << 16) | ((unsigned)nx << 8) | (unsigned)last_rows;
         s_ext[tid] = wl_pack_ext((unsigned)eiy, (unsigned)eix);

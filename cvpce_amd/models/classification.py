@@ -59,6 +59,7 @@ SKIP_STRIPS = _os.environ.get('CVPCE_SKIP_STRIPS', '1') != '0'
 # the 16 x 16-tile kernel, the thin strip lists (which need the latter).  Each part is on by default only if it won its own same-call
 # A/B (profiles/r16_fine_lists.md, 1 600 bench-shaped crops): even rows + thin strips in the 16 x 16-tile kernel -0.82 ms of 24.5, every
 # run; even rows alone, in either kernel, inside the 0.2 ms spread -- so the wide-tile kernel's layers keep the 4-row cut.
+# Measured again with the exact tail of the cut tiles (profiles/r19_cut_rows.md): `halo3` -0.08 ms in the median, not in every round -- still off.
 SKIP_FINE = _os.environ.get('CVPCE_SKIP_FINE', '1') != '0'
 SKIP_FINE_PARTS = tuple(p for p in _os.environ.get('CVPCE_SKIP_FINE_PARTS', 'halo2,thin').split(',') if p)
 

@@ -287,7 +287,8 @@ typedef struct {
  * strip list (its last-row tiles with rows == 2, for cvpce_conv3x3_halo_strips2 of include/cvpce_amd_lists.h; empty for the other modes) and
  * counts[3 * n_layers + l] its entries.  Without such a layer the shapes, and every value, are those of modes 0 .. 3.
  * counts has 3 * n_layers entries: counts[n_layers + l] = the MFMA work layer l performs, in sixteenths of a full tile (a tile cut
- * at `rows` < 16 streams rows + 1 of its 16 row groups, a strip counts 4, a thin strip 2) -- what `roofline` counts as executed FLOPs;
+ * at `rows` < 16 is booked as rows + 1 sixteenths -- one more than its MFMAs since the kernels end a cut tile exactly --, a strip counts
+ * 4, a thin strip 2) -- what `roofline` counts as executed FLOPs;
  * counts[2 * n_layers + l] = entries of layer l's strip list.
  * computed (optional, [n_layers][n_images][2]): per layer and crop, (conv-output rows computed, tile columns listed) -- the region
  * cvpce_mac_init has to cover from the constant crop. */
