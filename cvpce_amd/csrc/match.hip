@@ -1,20 +1,18 @@
 // K11: cosine-distance matrix detections x gallery as ONE MFMA GEMM with a
 // fused per-query top-k epilogue -- the (Q,G) matrix is never written to HBM.
-// Replaces /root/reference/cvpce/models/classification.py:87-95
-// (`distance` = 1 - cosine_similarity, `nearest_neighbors` = argsort[:, :k] of
-// a materialised (Q,G,D) x2 gather).
+// Replaces `distance` (1 - cosine_similarity) and `nearest_neighbors` (argsort[:, :k] of a
+// materialised (Q,G,D) x2 gather) of the reference's module cvpce.models.classification.
 //
 //   dist[q][g] = 1 - <Q[q], G[g]> / (max(|Q[q]|,eps) * max(|G[g]|,eps))
 //
 // Layout: Q [Qn][D], G [Gn][D] row-major (K contiguous for both operands),
 // bf16 storage, fp32 accumulate (v_mfma_f32_32x32x16_bf16); or fp32 storage
 // on the exact-f32 matrix pipe (v_mfma_f32_32x32x2_f32) for index-exact parity.
-// Tile 128 gallery rows x 128 | 64 queries (chosen per launch by whole rounds of the chip), K-step 64, swizzled LDS, register
-// staged double buffer (same pipeline as conv_igemm).  Epilogue: the tile's
-// distances go to LDS as [g][q] (conflict-free both ways), every query finds
-// its k smallest (distance, index) pairs lexicographically (ties -> lowest
-// index), partials [Q][tiles_g][k] are merged by a second tiny kernel.  k > 16 (up to the gallery size): the
-// distances go to a block in the workspace instead, followed by an exact per-query select and sort (match_select_kernel).
+// Two GEMM cores, chosen per launch by match_plan: match_kernel (tile 128 gallery rows x 128 | 64 queries, K-step 64, swizzled LDS,
+// register staged double buffer, same pipeline as conv_igemm; bf16 and f32) and match_big_kernel (bf16 only: 128 MG gallery rows x
+// 64 NQ queries, both operands by LDS-DMA).  Both find every query's k smallest (distance, index) pairs of the tile lexicographically
+// (ties -> lowest index); the partials [Q][tiles_g][k] are merged by a second tiny kernel.  k > 16 (up to the gallery size): match_kernel
+// writes its distances to a block in the workspace instead, followed by an exact per-query select and sort (match_select_kernel).
 #include "common.h"
 #include "../../include/cvpce_amd.h"
 #include <math.h>
@@ -34,6 +32,30 @@ struct MatchArgs {
     long long* out_idx; float* out_dist;  // large k: the results [Qn][k]
     float* dist; int ldd;                 // large k: the distance block [Qn][ldd] (match_kernel<F32, TQ, true>)
 };
+
+// Dynamic LDS of match_kernel<F32, TQ, STORE>, byte offsets.  K loop: two buffers of 128 gallery rows at 0, two of TQ query rows at `q`.
+// The epilogue reuses the staging (the last K-step ended on a barrier): the tile's distances as f32 at 0, one gallery row `ldg` floats and
+// one query `ldq` floats apart -- selecting: [g][q] (conflict-free both ways); STORE: [q][g], rows padded to 129 floats (the fragment
+// writes of a lane half hit 32 different banks) -- then, selecting only, the scan's candidates cd [256] f32 and cix [256] int, then the
+// tile's 128 gallery norms.  `bytes` is what a launch asks for: the staging (f32: 128 KiB, 64-query tiles: 48 KiB) or, for the bf16
+// 128-query tiles, the larger epilogue image.
+struct MatchLds { int q, staging, ldg, ldq, cd, cix, gn, epilogue, bytes; };
+constexpr MatchLds match_lds(bool f32, int tq, bool store) {
+    const int rowb = MT_BK * (f32 ? 4 : 2), staging = 2 * (MT_TG + tq) * rowb;
+    const int ldg = store ? 1 : tq, ldq = store ? MT_TG + 1 : 1;
+    const int cd = (store ? tq * (MT_TG + 1) : MT_TG * tq) * 4, cix = cd + 256 * 4;
+    const int gn = store ? cd : cix + 256 * 4, epilogue = gn + MT_TG * 4;
+    return {2 * MT_TG * rowb, staging, ldg, ldq, cd, cix, gn, epilogue, (f32 || tq == 64) ? staging : epilogue};
+}
+// Dynamic LDS of match_big_kernel<NQ, MG>: two K-stages of (128 MG gallery + 64 NQ query) rows of 128 bytes.  Epilogue, over the staging: 1 / |g| of
+// the tile's rows (1 KiB), the candidates cd, cix [4][TQ] of the four gallery waves, the round's winner wd, wix [TQ].
+#define MB_ROWB 128                        // bytes of one row of a K-stage (64 bf16)
+struct MatchBigLds { int stage, cd, cix, wd, wix, epilogue, bytes; };
+constexpr MatchBigLds match_big_lds(int nq, int mg) {
+    const int tq = 64 * nq, stage = (128 * mg + tq) * MB_ROWB;
+    const int cd = 1024, cix = cd + 4 * tq * 4, wd = cix + 4 * tq * 4, wix = wd + tq * 4;
+    return {stage, cd, cix, wd, wix, wix + tq * 4, 2 * stage};
+}
 
 // (distance, row) as ONE unsigned 64-bit key whose integer order is the lexicographic order: the float's bits made monotone
 // (negative: all bits flipped, non-negative: sign bit set) above the row index
@@ -95,6 +117,63 @@ __device__ __forceinline__ float match_norm_term(float norm) { return F32 ? norm
 
 // lexicographic (d, i) < (e, j)
 __device__ __forceinline__ bool lex_lt(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
+__device__ __forceinline__ void lex_min(float d, int i, float& bd, int& bi) { if (lex_lt(d, i, bd, bi)) { bd = d; bi = i; } }
+// one step of a selection round: (d, i) becomes the best so far (bd, bi) if it lies after the previous pick (pd, pi) and before the best
+__device__ __forceinline__ void match_take(float d, int i, float pd, int pi, float& bd, int& bi) { if (lex_lt(pd, pi, d, i)) lex_min(d, i, bd, bi); }
+
+// XCD-aware tile order of both GEMM kernels.  Workgroups are dealt to the 8 XCDs round-robin, each with its own 4-MiB L2; with gallery tiles
+// fastest over blockIdx every XCD touches EVERY gallery tile (20 MB at 10 000 x 1 024) and the operands stream from beyond L2
+// (9.5 TB/s measured at 1 600 queries: 43 FLOP per byte of a 128 x 64 tile = the 400 TFLOP/s the kernel was stuck at).
+// Here XCD x gets a contiguous range of the logical order (xcd_remap), and that order is gallery-class major: class c =
+// the gallery tiles c, c + 8, ... with all their query tiles -- an eighth of the gallery (2.5 MB) stays resident in the
+// XCD's L2 while the query tiles sweep past it.
+__device__ __forceinline__ void match_tile_of_block(int tiles_g, int tiles_q, int& tile_g, int& tile_q) {
+    int l = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    int cls = 0, ng = (tiles_g + 7) >> 3;
+    while (cls < 7 && l >= ng * tiles_q) {       // at most 7 steps, scalar
+        l -= ng * tiles_q;
+        ++cls;
+        ng = (tiles_g - cls + 7) >> 3;
+    }
+    tile_q = l / ng;
+    tile_g = cls + 8 * (l - tile_q * ng);
+}
+
+// Distance epilogue of match_kernel: the tile's gallery norms to s_gn (one coalesced load instead of 64 scattered ones per lane), then
+// every accumulator as a distance to T[gl * LDG + ql * LDQ] (gl, ql: row and query within the tile).  Rows past the gallery are +inf,
+// and so is a NaN distance (non-finite embedding): it sorts last and still yields a valid index.  Ends on the barrier.
+template <bool F32, int TQ, int LDG, int LDQ>
+__device__ __forceinline__ void match_tile_distances(const MatchArgs& a, int tile_g, int tile_q, const f32x16 (&acc)[2][TQ / 64],
+                                                     float* __restrict__ T, float* __restrict__ s_gn) {
+    constexpr int NT = TQ / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wc = wid >> 1, wp = wid & 1, lr = lane & 31, lh = lane >> 5;
+    if (tid < MT_TG) {
+        const int gg = tile_g * MT_TG + tid;
+        s_gn[tid] = match_norm_term<F32>((gg < a.Gn) ? a.gn[gg] : 1.f);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int ql = wp * 32 * NT + nt * 32 + lr;
+        const int qg = tile_q * TQ + ql;
+        const float qn = match_norm_term<F32>((qg < a.Qn) ? a.qn[qg] : 1.f);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int gl = wc * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int gg = tile_g * MT_TG + gl;
+                float d = INFINITY;
+                if (gg < a.Gn) {
+                    d = match_distance<F32>(acc[mt][nt][r], qn, s_gn[gl]);
+                    if (!(d == d)) d = INFINITY;
+                }
+                T[gl * LDG + ql * LDQ] = d;
+            }
+    }
+    __syncthreads();
+}
 
 // TQ = queries per tile: 128 (waves 2 x 2, 64 gallery rows x 64 queries each) or 64 (64 x 32 each; 48 KiB of LDS, three
 // workgroups per CU).  Which one a launch takes is a question of tile COUNT, not of kernel quality: 1 600 x 10 000 gives
@@ -112,30 +191,16 @@ __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs 
     constexpr int PASS = MT_TG / RPP;                // 4 / 8
     constexpr int PASSQ = TQ / RPP;                  // query rows per thread
     constexpr int RPB = (256 / ROWB) > 0 ? (256 / ROWB) : 1;   // rows per 256-B bank row: 2 / 1
+    constexpr MatchLds L = match_lds(F32, TQ, STORE);
+    static_assert(L.staging <= L.bytes && L.epilogue <= L.bytes, "the launch's LDS holds the staging and the epilogue image");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* Gs = smem;                                  // [2][128 rows][ROWB]
-    unsigned char* Qs = smem + 2 * MT_TG * ROWB;
+    unsigned char* Qs = smem + L.q;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wc = wid >> 1, wp = wid & 1;
-    // XCD-aware tile order.  Workgroups are dealt to the 8 XCDs round-robin, each with its own 4-MiB L2; with gallery tiles
-    // fastest over blockIdx every XCD touches EVERY gallery tile (20 MB at 10 000 x 1 024) and the operands stream from beyond L2
-    // (9.5 TB/s measured at 1 600 queries: 43 FLOP per byte of a 128 x 64 tile = the 400 TFLOP/s the kernel was stuck at).
-    // Here XCD x gets a contiguous range of the logical order (xcd_remap), and that order is gallery-class major: class c =
-    // the gallery tiles c, c + 8, ... with all their query tiles -- an eighth of the gallery (2.5 MB) stays resident in the
-    // XCD's L2 while the query tiles sweep past it.
     int tile_g, tile_q;
-    {
-        int l = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-        int cls = 0, ng = (a.tiles_g + 7) >> 3;
-        while (cls < 7 && l >= ng * a.tiles_q) {       // at most 7 steps, scalar
-            l -= ng * a.tiles_q;
-            ++cls;
-            ng = (a.tiles_g - cls + 7) >> 3;
-        }
-        tile_q = l / ng;
-        tile_g = cls + 8 * (l - tile_q * ng);
-    }
+    match_tile_of_block(a.tiles_g, a.tiles_q, tile_g, tile_q);
     const int c = tid % CPR, r0 = tid / CPR;
 
     const unsigned char* gbase = (const unsigned char*)a.g;
@@ -267,75 +332,19 @@ __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs 
         if constexpr (NS > 2) { if (kt + 1 < nk) k_step(kt + 1, std::integral_constant<int, 2 % NS>{}); }
     }
 
+    // ---- epilogue: the tile's distances to LDS (match_tile_distances), then to the distance block (STORE) or per-query top-k ----
+    float* T = reinterpret_cast<float*>(smem);
+    match_tile_distances<F32, TQ, L.ldg, L.ldq>(a, tile_g, tile_q, acc, T, reinterpret_cast<float*>(smem + L.gn));
     if constexpr (STORE) {
-        // ---- epilogue of the large-k path: distances -> LDS [q][g] (rows padded to 129 floats: the fragment writes of a lane
-        // half hit 32 different banks), then every query's 128 distances to its row of the block, coalesced along g.  The
-        // distance expression, the NaN rule and the rows past the gallery (+inf) are those of the selecting epilogue below.
-        constexpr int LD = MT_TG + 1;
-        float* Ts = reinterpret_cast<float*>(smem);                    // TQ x 129 f32 = 66 | 33 KiB (the staging is free: the
-        float* s_gn = reinterpret_cast<float*>(smem + TQ * LD * 4);    // last K-step ended on a barrier)
-        if (tid < MT_TG) {
-            const int gg = tile_g * MT_TG + tid;
-            s_gn[tid] = match_norm_term<F32>((gg < a.Gn) ? a.gn[gg] : 1.f);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int ql = wp * 32 * NT + nt * 32 + lr;
-            const int qg = tile_q * TQ + ql;
-            const float qn = match_norm_term<F32>((qg < a.Qn) ? a.qn[qg] : 1.f);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int gl = wc * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int gg = tile_g * MT_TG + gl;
-                    float d = INFINITY;
-                    if (gg < a.Gn) {
-                        d = match_distance<F32>(acc[mt][nt][r], qn, s_gn[gl]);
-                        if (!(d == d)) d = INFINITY;
-                    }
-                    Ts[ql * LD + gl] = d;
-                }
-        }
-        __syncthreads();
+        // every query's 128 distances to its row of the block, coalesced along g
         const int qv = min(TQ, a.Qn - tile_q * TQ);                   // query rows of this tile inside the block
         float* out = a.dist + (size_t)tile_q * TQ * a.ldd + (size_t)tile_g * MT_TG;
-        for (int i = tid; i < qv * MT_TG; i += 256) out[(size_t)(i >> 7) * a.ldd + (i & 127)] = Ts[(i >> 7) * LD + (i & 127)];
+        for (int i = tid; i < qv * MT_TG; i += 256) out[(size_t)(i >> 7) * a.ldd + (i & 127)] = T[(i >> 7) * L.ldq + (i & 127)];
         return;
     }
-
-    // ---- epilogue: distances -> LDS [g][q], then per-query top-k -------------
     constexpr int NH = 256 / TQ;                                      // threads per query in the scan: 2 | 4 parts of the 128 gallery rows
-    float* Tl = reinterpret_cast<float*>(smem);                       // 128 x TQ f32 = 64 | 32 KiB
-    float* cd = reinterpret_cast<float*>(smem + MT_TG * TQ * 4);      // [NH][TQ]
-    int* cix = reinterpret_cast<int*>(smem + MT_TG * TQ * 4 + 256 * 4);
-    float* s_gn = reinterpret_cast<float*>(smem + MT_TG * TQ * 4 + 2 * 256 * 4);      // the tile's 128 gallery norms (one coalesced load
-    if (tid < MT_TG) {                                                                 // instead of 64 scattered ones per lane)
-        const int gg = tile_g * MT_TG + tid;
-        s_gn[tid] = match_norm_term<F32>((gg < a.Gn) ? a.gn[gg] : 1.f);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int ql = wp * 32 * NT + nt * 32 + lr;
-        const int qg = tile_q * TQ + ql;
-        const float qn = match_norm_term<F32>((qg < a.Qn) ? a.qn[qg] : 1.f);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gl = wc * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const int gg = tile_g * MT_TG + gl;
-                float d = INFINITY;
-                if (gg < a.Gn) {
-                    d = match_distance<F32>(acc[mt][nt][r], qn, s_gn[gl]);
-                    if (!(d == d)) d = INFINITY;   // a NaN distance (non-finite embedding) sorts last and still yields a valid index
-                }
-                Tl[gl * TQ + ql] = d;
-            }
-    }
-    __syncthreads();
+    float* cd = reinterpret_cast<float*>(smem + L.cd);                // [NH][TQ]
+    int* cix = reinterpret_cast<int*>(smem + L.cix);
     const int ql = tid & (TQ - 1), part = tid / TQ;
     const int qg = tile_q * TQ + ql;
     float pd = -INFINITY;
@@ -346,22 +355,16 @@ __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs 
         for (int g0 = part * (MT_TG / NH); g0 < (part + 1) * (MT_TG / NH); g0 += 8) {
             float dv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) dv[u] = Tl[(g0 + u) * TQ + ql];             // 8 LDS reads in flight
+            for (int u = 0; u < 8; ++u) dv[u] = T[(g0 + u) * TQ + ql];              // 8 LDS reads in flight
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int gi = tile_g * MT_TG + g0 + u;
-                if (lex_lt(pd, pi, dv[u], gi) && lex_lt(dv[u], gi, bd, bi)) { bd = dv[u]; bi = gi; }
-            }
+            for (int u = 0; u < 8; ++u) match_take(dv[u], tile_g * MT_TG + g0 + u, pd, pi, bd, bi);
         }
         cd[part * TQ + ql] = bd;
         cix[part * TQ + ql] = bi;
         __syncthreads();
 #pragma unroll
-        for (int p = 1; p < NH; ++p) {                   // every part learns the tile's minimum: it bounds its next round
-            const float od = cd[((part + p) & (NH - 1)) * TQ + ql];
-            const int oi = cix[((part + p) & (NH - 1)) * TQ + ql];
-            if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
-        }
+        for (int p = 1; p < NH; ++p)                     // every part learns the tile's minimum: it bounds its next round
+            lex_min(cd[((part + p) & (NH - 1)) * TQ + ql], cix[((part + p) & (NH - 1)) * TQ + ql], bd, bi);
         pd = bd; pi = bi;
         if (part == 0 && qg < a.Qn) {
             const size_t o = ((size_t)qg * a.tiles_g + tile_g) * a.k + r;
@@ -392,10 +395,6 @@ __global__ __launch_bounds__(256, TQ == 64 ? 3 : 2) void match_kernel(MatchArgs 
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void lds_void_m;
 typedef __attribute__((address_space(3))) char lds_char_m;
-#define MB_ROWB 128                        // bytes of one row of a K-stage (64 bf16)
-#ifndef MB_ABL
-#define MB_ABL 0
-#endif
 
 // MG = gallery fragments (32 rows) per wave: the tile is TG = 128 MG gallery rows (MG = 2: the throughput form; MG = 1: twice the workgroups
 // for launches that would otherwise leave most CUs without a tile -- a few hundred queries, where the time is the per-CU operand intake)
@@ -404,24 +403,16 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
     constexpr int TQ = 64 * NQ;
     constexpr int TG = 128 * MG;
     constexpr int GP = 2 * MG;                          // gallery DMA pieces per wave and stage (TG / 8 rows per piece / 8 waves)
-    constexpr int STAGE = (TG + TQ) * MB_ROWB;      // gallery rows, then query rows
+    constexpr MatchBigLds L = match_big_lds(NQ, MG);
+    constexpr int STAGE = L.stage;                      // gallery rows, then query rows
+    static_assert(TG * 4 <= L.cd && L.epilogue <= L.bytes, "the epilogue's regions lie within the staging");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = wid >> 1, wq = wid & 1;
     const int lr = lane & 31, lh = lane >> 5;
     int tile_g, tile_q;
-    {   // XCD-aware order, as in match_kernel: an eighth of the gallery tiles per XCD, all their query tiles
-        int l = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-        int cls = 0, ng = (a.tiles_g + 7) >> 3;
-        while (cls < 7 && l >= ng * a.tiles_q) {
-            l -= ng * a.tiles_q;
-            ++cls;
-            ng = (a.tiles_g - cls + 7) >> 3;
-        }
-        tile_q = l / ng;
-        tile_g = cls + 8 * (l - tile_q * ng);
-    }
+    match_tile_of_block(a.tiles_g, a.tiles_q, tile_g, tile_q);
     const unsigned rowbytes = (unsigned)a.D * 2u;
     const __amdgpu_buffer_rsrc_t srd_g = __builtin_amdgcn_make_buffer_rsrc((void*)a.g, 0, (unsigned)((size_t)a.Gn * rowbytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_q = __builtin_amdgcn_make_buffer_rsrc((void*)a.q, 0, (unsigned)((size_t)a.Qn * rowbytes), 0x00020000);
@@ -545,12 +536,8 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
         const int nb = (kt + 1) & 1;
         // stage kt has landed for this wave (its only loads in flight), and -- behind the barrier -- for every wave; every wave has
         // also finished its fragment reads of stage kt - 1 (lgkmcnt(0) above), whose buffer the next DMA overwrites
-#if !(MB_ABL & 1)           /* timing-only ablations (tools/dev/build_variant.sh match.hip abl -DMB_ABL=..): 1 no wait for the stage's DMA, 2 no barrier */
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#if !(MB_ABL & 2)
         __builtin_amdgcn_s_barrier();
-#endif
         __builtin_amdgcn_sched_barrier(0);
         MB_READ(0, 0, soff)
         __builtin_amdgcn_sched_barrier(0);
@@ -585,10 +572,10 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
     // ---- epilogue: per-query k smallest (distance, row) of this tile's 256 gallery rows --------------------------------------------
     __builtin_amdgcn_s_barrier();                                   // every wave is past its last fragment read: the staging LDS is free
     float* s_rg = reinterpret_cast<float*>(smem);                   // [256] 1 / |g| (NaN for rows past the gallery: never selected)
-    float* cd = reinterpret_cast<float*>(smem + 1024);              // [4][TQ] candidates of the four gallery waves
-    int* cix = reinterpret_cast<int*>(smem + 1024 + 4 * TQ * 4);
-    float* wd = reinterpret_cast<float*>(smem + 1024 + 8 * TQ * 4); // [TQ] the round's winner (k > 1: bounds the next round)
-    int* wix = reinterpret_cast<int*>(smem + 1024 + 9 * TQ * 4);
+    float* cd = reinterpret_cast<float*>(smem + L.cd);              // [4][TQ] candidates of the four gallery waves
+    int* cix = reinterpret_cast<int*>(smem + L.cix);
+    float* wd = reinterpret_cast<float*>(smem + L.wd);              // [TQ] the round's winner (k > 1: bounds the next round)
+    int* wix = reinterpret_cast<int*>(smem + L.wix);
     if (tid < TG) {
         const int gg = tile_g * TG + tid;
         s_rg[tid] = (gg < a.Gn) ? match_norm_term<false>(a.gn[gg]) : __builtin_nanf("");
@@ -650,8 +637,8 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
                     for (int nq = 0; nq < NQ; ++nq) {
                         float d = match_distance<false>(acc[mg][nq][4 * r4 + e4], qnv[nq], gn4[e4]);
                         d = (d == d) ? d : INFINITY;
-                        // branch-free (bitwise, not short-circuit): after the previous pick AND before the best so far.  gi ascends along the
-                        // scan, so "before the best" is d < best alone
+                        // match_take's rule, branch-free (bitwise, not short-circuit): after the previous pick AND before the best so far.  gi
+                        // ascends along the scan, so "before the best" is d < best alone
                         const bool after = (d > pd[nq]) | ((d == pd[nq]) & (gi > pi[nq]));
                         // (equal distances keep the lower row = the earlier one of this ascending scan; an all-infinite query -- non-finite
                         // embedding -- must still pick its first admissible row: `bi` untouched means nothing was taken yet)
@@ -665,9 +652,7 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
 #pragma unroll
         for (int nq = 0; nq < NQ; ++nq) {
             // the other half of the wave holds the other 32 gallery rows of the same query
-            const float od = __shfl_xor(bd[nq], 32);
-            const int oi = __shfl_xor(bi[nq], 32);
-            if (lex_lt(od, oi, bd[nq], bi[nq])) { bd[nq] = od; bi[nq] = oi; }
+            lex_min(__shfl_xor(bd[nq], 32), __shfl_xor(bi[nq], 32), bd[nq], bi[nq]);
             if (lh == 0) {
                 cd[wg * TQ + 32 * NQ * wq + 32 * nq + lr] = bd[nq];
                 cix[wg * TQ + 32 * NQ * wq + 32 * nq + lr] = bi[nq];
@@ -678,11 +663,7 @@ __global__ __launch_bounds__(512, 1) void match_big_kernel(MatchArgs a) {
             float bd = cd[tid];
             int bi = cix[tid];
 #pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const float od = cd[w * TQ + tid];
-                const int oi = cix[w * TQ + tid];
-                if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
-            }
+            for (int w = 1; w < 4; ++w) lex_min(cd[w * TQ + tid], cix[w * TQ + tid], bd, bi);
             wd[tid] = bd;
             wix[tid] = bi;
             const int qg = tile_q * TQ + tid;
@@ -728,19 +709,10 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const float* __restric
         float bd = INFINITY;
         int bi = 0x7FFFFFFF;
 #pragma unroll
-        for (int e = 0; e < PER; ++e)
-            if (lex_lt(pd, pi, dv[e], iv[e]) && lex_lt(dv[e], iv[e], bd, bi)) { bd = dv[e]; bi = iv[e]; }
-        for (int j = PER * 64 + lane; j < n; j += 64) {            // (n > 512: the tail straight from memory)
-            const float dj = d[j];
-            const int ij = ix[j];
-            if (lex_lt(pd, pi, dj, ij) && lex_lt(dj, ij, bd, bi)) { bd = dj; bi = ij; }
-        }
+        for (int e = 0; e < PER; ++e) match_take(dv[e], iv[e], pd, pi, bd, bi);
+        for (int j = PER * 64 + lane; j < n; j += 64) match_take(d[j], ix[j], pd, pi, bd, bi);   // (n > 512: the tail straight from memory)
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float od = __shfl_xor(bd, off);
-            const int oi = __shfl_xor(bi, off);
-            if (lex_lt(od, oi, bd, bi)) { bd = od; bi = oi; }
-        }
+        for (int off = 32; off > 0; off >>= 1) lex_min(__shfl_xor(bd, off), __shfl_xor(bi, off), bd, bi);
         if (lane == 0) {
             out_idx[(size_t)q * k + r] = (long long)bi;
             if (out_dist) out_dist[(size_t)q * k + r] = bd;
@@ -989,75 +961,161 @@ __global__ __launch_bounds__(256) void match_merge_runs_kernel(const unsigned lo
     }
 }
 
-// which bf16 core a launch takes: 0 = by the cost model below, 1 = always the 128-row kernel, 2 = always the 256-row LDS-DMA kernel;
-// g_match_nq = 2..5 pins the 256-row kernel's query-tile width (0 = by the model).  Test / measurement switch: results never depend on it.
-static int g_match_core = []() { const char* e = getenv("CVPCE_MATCH_CORE"); return !e ? 0 : (e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : 0)); }();
-static int g_match_mg = []() { const char* e = getenv("CVPCE_MATCH_MG"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2) ? v : 0; }();
-static int g_match_nq = []() { const char* e = getenv("CVPCE_MATCH_NQ"); const int v = e ? atoi(e) : 0; return (v >= 2 && v <= 5) ? v : 0; }();
+// Test / measurement switches of the bf16 path: read once from the environment, core / nq / mg overwritten by cvpce_match_set_core.  Results
+// never depend on them.  core (CVPCE_MATCH_CORE = small | big): 0 = by the cost model of match_plan, 1 = always the 128-row kernel, 2 = always
+// the LDS-DMA kernel; nq = 2..5 (CVPCE_MATCH_NQ) and mg = 1 | 2 (CVPCE_MATCH_MG) pin that kernel's tile, tq = 64 | 128 (CVPCE_MATCH_TQ) the
+// 128-row kernel's query tile; 0 = by the model.
+struct MatchForced { int core, nq, mg, tq; };
+static MatchForced g_match_forced = []() {
+    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
+    const char* c = getenv("CVPCE_MATCH_CORE");
+    const int nq = num("CVPCE_MATCH_NQ"), mg = num("CVPCE_MATCH_MG"), tq = num("CVPCE_MATCH_TQ");
+    return MatchForced{!c ? 0 : (c[0] == 's' ? 1 : (c[0] == 'b' ? 2 : 0)), (nq >= 2 && nq <= 5) ? nq : 0, (mg == 1 || mg == 2) ? mg : 0,
+                       (tq == 64 || tq == 128) ? tq : 0};
+}();
 extern "C" int cvpce_match_set_core(int core, int nq, int mg) {
     if (core < 0 || core > 2 || !(nq == 0 || (nq >= 2 && nq <= 5)) || mg < 0 || mg > 2 || (mg == 1 && nq == 5)) return CVPCE_ERR_ARG;
-    g_match_core = core;
-    g_match_nq = nq;
-    g_match_mg = mg;
+    g_match_forced = MatchForced{core, nq, mg, g_match_forced.tq};
     return CVPCE_OK;
 }
 
-extern "C" size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k) {
-    if (k > MATCH_KMAX) return (Qn > 0 && Gn > 0 ? match_large_k_plan(Qn, Gn, k).bytes : 0) + 512;
-    const size_t tiles_g = (Gn + MT_TG - 1) / MT_TG;
-    return (size_t)Qn * tiles_g * k * 8 + 512;
-}
-
-// query tile of the 128-row bf16 kernel: 64-query tiles cost ~0.6 of a 128-query tile and run three to a CU instead of two; the
-// cheaper schedule in whole rounds of the chip wins (CVPCE_MATCH_TQ = 64 | 128 forces one: dev A/B)
-static int match_small_tq(int tiles_g, int Qn) {
-    static const int forced = []() { const char* e = getenv("CVPCE_MATCH_TQ"); return e ? atoi(e) : 0; }();
+// Every launch decision of cvpce_match_topk, made on the host without a HIP call (cvpce_match_plan reports it).
+enum { MATCH_PATH_SMALL = 0, MATCH_PATH_BIG = 1, MATCH_PATH_LARGE_K = 2 };
+struct MatchPlan {
+    int rc;                                 // CVPCE_ERR_ARG: the arguments are rejected (only `workspace` is filled in)
+    int path;                               // fused top-k on the 128-row core | on the LDS-DMA core | the large-k search
+    int tq;                                 // SMALL, LARGE_K: queries per tile of match_kernel
+    int nq, mg;                             // BIG: match_big_kernel's tile, 64 nq queries x 128 mg gallery rows
+    int tiles_g, tiles_q, lds, threads;     // the GEMM launch (LARGE_K: of a chunk of lk.qc queries)
+    size_t part_i;                          // fused paths: byte offset of the partial indices in the workspace
+    size_t workspace;                       // bytes cvpce_match_topk needs
+    MatchLargeK lk;                         // LARGE_K
+};
+static MatchPlan match_plan(int Qn, int Gn, int D, int k, int is_f32, const MatchForced& f) {
+    MatchPlan p = {};
+    p.rc = CVPCE_ERR_ARG;
+    const bool large = k > MATCH_KMAX;
+    // the workspace depends on (Qn, Gn, k) alone: filled in whatever becomes of the other arguments (cvpce_match_workspace_bytes)
+    const int tiles128 = (Gn + MT_TG - 1) / MT_TG;
+    if (large && Qn > 0 && Gn > 0) p.lk = match_large_k_plan(Qn, Gn, k);
+    p.part_i = ((size_t)Qn * tiles128 * k * 4 + 255) / 256 * 256;          // (laid out for the 128-row tiling: enough for either core)
+    p.workspace = (large ? p.lk.bytes : (size_t)Qn * tiles128 * k * 8) + 512;
+    if (D <= 0 || D % MT_BK != 0 || k < 1 || Gn < k) return p;
+    if (Qn <= 0) { p.rc = CVPCE_OK; return p; }                            // nothing to launch
+    // 32-bit buffer offsets: rows rounded up to whole tiles of tg x tq stay below 2^32 bytes
+    auto fits = [&](int tg, int tq) {
+        const unsigned long long es = is_f32 ? 4 : 2;
+        return ((unsigned long long)Gn + tg) * D * es < (1ull << 32) && ((unsigned long long)Qn + tq) * D * es < (1ull << 32);
+    };
+    if (!fits(MT_TG, MT_TQ)) return p;
+    const int qn = large ? p.lk.qc : Qn;                                   // queries of one GEMM launch
     const long long cus = g_cvpce_persistent_wgs;
-    const long long t128 = (long long)tiles_g * ((Qn + 127) / 128), t64 = (long long)tiles_g * ((Qn + 63) / 64);
-    const double c128 = (double)((t128 + 2 * cus - 1) / (2 * cus)) * 1.0, c64 = (double)((t64 + 3 * cus - 1) / (3 * cus)) * 0.6;
-    return forced == 64 || forced == 128 ? forced : (c64 < c128 ? 64 : 128);
+    const long long t128 = (long long)tiles128 * ((qn + 127) / 128), t64 = (long long)tiles128 * ((qn + 63) / 64);
+    const long long r128 = (t128 + 2 * cus - 1) / (2 * cus), r64 = (t64 + 3 * cus - 1) / (3 * cus);
+    // query tile of the 128-row bf16 kernel: 64-query tiles cost ~0.6 of a 128-query tile and run three to a CU instead of two; the
+    // cheaper schedule in whole rounds of the chip wins
+    p.path = large ? MATCH_PATH_LARGE_K : MATCH_PATH_SMALL;
+    p.tq = is_f32 ? MT_TQ : (f.tq ? f.tq : ((double)r64 * 0.6 < (double)r128 * 1.0 ? 64 : 128));
+    // Which bf16 core and tile: the LDS-DMA kernel (match_big_kernel, 128 MG gallery rows x 64 NQ queries per workgroup) or the 128-row
+    // register-staged one, by estimated time.  Model (microseconds; least-squares fit to tools/dev/bench_match.py on MI355X, 63 launches of
+    // 200 ... 3 200 queries x 1 000 ... 10 000 rows x 512 | 1 024, rms error 8 %, picks the fastest variant or one within 1 % of it on all nine
+    // shapes):  launch = fixed + rounds x (D / 512) x round, where a round's cost grows with the share u of the CUs that hold a tile in it
+    // (L2 intake and clocks):
+    //   LDS-DMA kernel:   fixed 3.9 + 0.48 NQ,  round (0.74 + 1.97 NQ) x (MG = 1 ? 0.575 : 1) x (1 + 0.75 u)
+    //   128-row kernel:   fixed 10.4,           round 5.4 x (1 + 0.75 u) (64-query tiles, three per CU) | 9.0 x (1 + 0.75 u) (128-query, two per CU)
+    // Every bf16 kernel forms identical distances, so the choice changes no result (MatchForced pins one: tests and A/B measurements).
+    if (!is_f32 && !large) {
+        const double dk = (double)D / 512.0;
+        const double e128 = 10.4 + (double)r128 * dk * 9.0 * (1.0 + 0.75 * (double)t128 / (double)(r128 * 2 * cus));
+        const double e64 = 10.4 + (double)r64 * dk * 5.4 * (1.0 + 0.75 * (double)t64 / (double)(r64 * 3 * cus));
+        const double best = e64 < e128 ? e64 : e128;
+        double best_big = 1e30;
+        int big_nq = 0, big_mg = 2;
+        for (int mg = 1; mg <= 2; ++mg)
+            for (int nq = 2; nq <= 5; ++nq) {
+                if ((f.nq && nq != f.nq) || (f.mg && mg != f.mg) || (mg == 1 && nq == 5)) continue;
+                const long long t = (long long)((Gn + 128 * mg - 1) / (128 * mg)) * ((Qn + 64 * nq - 1) / (64 * nq)), rounds = (t + cus - 1) / cus;
+                const double u = (double)t / (double)(rounds * cus);
+                const double e = 3.9 + 0.48 * nq + (double)rounds * dk * (0.74 + 1.97 * nq) * (mg == 1 ? 0.575 : 1.0) * (1.0 + 0.75 * u);
+                if (e < best_big) { best_big = e; big_nq = nq; big_mg = mg; }
+            }
+        // (a handful of queries against a small gallery is launch latency either way: the 128-row kernel keeps those)
+        const bool keep_small = f.core == 1 || (f.core == 0 && (!(best_big < best) || (long long)Qn * Gn < 64 * 1024));
+        if (big_nq && !keep_small) { p.path = MATCH_PATH_BIG; p.tq = 0; p.nq = big_nq; p.mg = big_mg; }
+    }
+    const bool big = p.path == MATCH_PATH_BIG;
+    const int tile_g = big ? 128 * p.mg : MT_TG, tile_q = big ? 64 * p.nq : p.tq;
+    if (big && !fits(tile_g, tile_q)) return p;
+    p.tiles_g = (Gn + tile_g - 1) / tile_g;
+    p.tiles_q = (qn + tile_q - 1) / tile_q;
+    p.lds = big ? match_big_lds(p.nq, p.mg).bytes : match_lds(is_f32, p.tq, large).bytes;
+    p.threads = big ? 512 : 256;
+    p.rc = CVPCE_OK;
+    return p;
 }
 
-// The large-k search (see match_select_kernel): per chunk of p.qc queries, distance block -> select -> sort [-> merge passes], all on
+extern "C" size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k) { return match_plan(Qn, Gn, MT_BK, k, 0, g_match_forced).workspace; }
+
+extern "C" int cvpce_match_plan(int Qn, int Gn, int D, int k, int is_f32, long long* out) {
+    if (!out) return CVPCE_ERR_ARG;
+    const MatchPlan p = match_plan(Qn, Gn, D, k, is_f32, g_match_forced);
+    const long long v[CVPCE_MATCH_PLAN_FIELDS] = {p.path, p.tq, p.nq, p.mg, p.tiles_g, p.tiles_q, p.lds, p.threads, p.lk.qc, (long long)p.lk.gpad,
+                                                  (long long)p.lk.bytes, (long long)p.workspace};
+    for (int i = 0; i < CVPCE_MATCH_PLAN_FIELDS; ++i) out[i] = v[i];
+    return p.rc;
+}
+
+// One GEMM launch of the plan: the shared-memory attribute of the instance it launches, then the launch.
+template <auto Kernel>
+static bool match_launch(const MatchPlan& p, const MatchArgs& a, hipStream_t s) {
+    if (!cvpce_smem_attr_done<Kernel>((const void*)Kernel, p.lds)) return false;
+    hipLaunchKernelGGL(Kernel, dim3(p.tiles_g * p.tiles_q), dim3(p.threads), p.lds, s, a);
+    return true;
+}
+template <bool STORE>
+static bool match_launch_small(const MatchPlan& p, int is_f32, const MatchArgs& a, hipStream_t s) {
+    if (is_f32) return match_launch<match_kernel<true, 128, STORE>>(p, a, s);
+    return p.tq == 128 ? match_launch<match_kernel<false, 128, STORE>>(p, a, s) : match_launch<match_kernel<false, 64, STORE>>(p, a, s);
+}
+static bool match_launch_big(const MatchPlan& p, const MatchArgs& a, hipStream_t s) {
+    switch (p.nq * 4 + p.mg) {
+#define MB_LAUNCH(NQ_, MG_) case NQ_ * 4 + MG_: return match_launch<match_big_kernel<NQ_, MG_>>(p, a, s);
+        MB_LAUNCH(2, 2) MB_LAUNCH(3, 2) MB_LAUNCH(4, 2) MB_LAUNCH(5, 2) MB_LAUNCH(2, 1) MB_LAUNCH(3, 1) MB_LAUNCH(4, 1)
+#undef MB_LAUNCH
+    }
+    return false;
+}
+
+// The large-k search (see match_select_kernel): per chunk of p.lk.qc queries, distance block -> select -> sort [-> merge passes], all on
 // the caller's stream.  The distances come from match_kernel (the 128-row core; its bf16 instances form the same distances as the
 // LDS-DMA core), so a query's first 16 results equal those of the fused path bit for bit.
-static int match_large_k(MatchArgs a, int is_f32, void* workspace, hipStream_t s) {
+static int match_large_k(MatchArgs a, const MatchPlan& p, int is_f32, void* workspace, hipStream_t s) {
     const int Qn = a.Qn, Gn = a.Gn, k = a.k;
-    const MatchLargeK p = match_large_k_plan(Qn, Gn, k);
-    const int lds_store_f32 = 2 * 2 * 128 * 256, lds_store_128 = 128 * (MT_TG + 1) * 4 + 512, lds_store_64 = 2 * (128 + 64) * 128;
     const bool staged = Gn <= MATCH_SEL_STAGE;
     const int lds_sel = (MATCH_SEL_BINS + 64 + (staged ? Gn : 0)) * 4;
-    if (!cvpce_smem_attr_done<match_kernel<true, 128, true>>((const void*)match_kernel<true, 128, true>, lds_store_f32) ||
-        !cvpce_smem_attr_done<match_kernel<false, 128, true>>((const void*)match_kernel<false, 128, true>, lds_store_128) ||
-        !cvpce_smem_attr_done<match_kernel<false, 64, true>>((const void*)match_kernel<false, 64, true>, lds_store_64) ||
-        !cvpce_smem_attr_done<match_select_kernel<true>>((const void*)match_select_kernel<true>, (MATCH_SEL_BINS + 64 + MATCH_SEL_STAGE) * 4) ||
+    if (!cvpce_smem_attr_done<match_select_kernel<true>>((const void*)match_select_kernel<true>, (MATCH_SEL_BINS + 64 + MATCH_SEL_STAGE) * 4) ||
         !cvpce_smem_attr_done<match_sort_kernel>((const void*)match_sort_kernel, MATCH_SORT_RUN * 8))
         return CVPCE_ERR_LAUNCH;
     float* dist = (float*)workspace;
-    unsigned long long* surv = (unsigned long long*)((char*)workspace + p.dist_bytes);
-    unsigned long long* tmp = (unsigned long long*)((char*)workspace + p.dist_bytes + p.surv_bytes);
+    unsigned long long* surv = (unsigned long long*)((char*)workspace + p.lk.dist_bytes);
+    unsigned long long* tmp = (unsigned long long*)((char*)workspace + p.lk.dist_bytes + p.lk.surv_bytes);
     const int runs = (k + MATCH_SORT_RUN - 1) / MATCH_SORT_RUN;
     int P = 64;
     while (P < k && P < MATCH_SORT_RUN) P <<= 1;
     const int sort_threads = P / 2 < 64 ? 64 : (P / 2 > 1024 ? 1024 : P / 2);
     const size_t es = is_f32 ? 4 : 2;
-    a.tiles_g = (Gn + MT_TG - 1) / MT_TG;
     a.dist = dist;
-    a.ldd = (int)p.gpad;
-    for (int c0 = 0; c0 < Qn; c0 += p.qc) {
-        const int qc = min(p.qc, Qn - c0);
+    a.ldd = (int)p.lk.gpad;
+    for (int c0 = 0; c0 < Qn; c0 += p.lk.qc) {
+        const int qc = min(p.lk.qc, Qn - c0);
+        const MatchPlan cp = match_plan(qc, Gn, a.D, k, is_f32, g_match_forced);    // (a shorter last chunk may take the other query tile)
         MatchArgs c = a;
         c.q = (const char*)a.q + (size_t)c0 * a.D * es;
         c.qn = a.qn + c0;
-        c.Qn = qc;
+        c.Qn = qc; c.tiles_g = cp.tiles_g; c.tiles_q = cp.tiles_q;
         long long* oi = a.out_idx + (size_t)c0 * k;
         float* od = a.out_dist ? a.out_dist + (size_t)c0 * k : nullptr;
-        const int tq = is_f32 ? MT_TQ : match_small_tq(c.tiles_g, qc);
-        c.tiles_q = (qc + tq - 1) / tq;
-        const dim3 grid(c.tiles_g * c.tiles_q);
-        if (is_f32) hipLaunchKernelGGL((match_kernel<true, 128, true>), grid, dim3(256), lds_store_f32, s, c);
-        else if (tq == 128) hipLaunchKernelGGL((match_kernel<false, 128, true>), grid, dim3(256), lds_store_128, s, c);
-        else hipLaunchKernelGGL((match_kernel<false, 64, true>), grid, dim3(256), lds_store_64, s, c);
+        if (!match_launch_small<true>(cp, is_f32, c, s)) return CVPCE_ERR_LAUNCH;
         if (staged) hipLaunchKernelGGL(match_select_kernel<true>, dim3(qc), dim3(MATCH_SEL_THREADS), lds_sel, s, (const float*)dist, a.ldd, Gn, k, surv);
         else hipLaunchKernelGGL(match_select_kernel<false>, dim3(qc), dim3(MATCH_SEL_THREADS), lds_sel, s, (const float*)dist, a.ldd, Gn, k, surv);
         hipLaunchKernelGGL(match_sort_kernel, dim3(qc, runs), dim3(sort_threads), (size_t)P * 8, s, surv, k, P, oi, od);
@@ -1078,90 +1136,20 @@ extern "C" int cvpce_match_topk(const void* queries, const void* gallery, const 
                                 int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
                                 long long* out_idx, float* out_dist, void* stream) {
     if (!queries || !gallery || !q_norms || !g_norms || !workspace || !out_idx) return CVPCE_ERR_ARG;
-    if (D <= 0 || D % MT_BK != 0 || k < 1 || Gn < k) return CVPCE_ERR_ARG;
+    const MatchPlan p = match_plan(Qn, Gn, D, k, is_f32, g_match_forced);
+    if (p.rc != CVPCE_OK) return p.rc;
     if (Qn <= 0) return CVPCE_OK;
-    if (workspace_bytes < cvpce_match_workspace_bytes(Qn, Gn, k)) return CVPCE_ERR_ARG;
-    {   // 32-bit buffer offsets (rows rounded up to whole tiles stay below 2^32)
-        const unsigned long long es = is_f32 ? 4 : 2;
-        if (((unsigned long long)Gn + MT_TG) * D * es >= (1ull << 32) || ((unsigned long long)Qn + MT_TQ) * D * es >= (1ull << 32)) return CVPCE_ERR_ARG;
-    }
-    MatchArgs a;
+    if (workspace_bytes < p.workspace) return CVPCE_ERR_ARG;
+    MatchArgs a = {};
     a.q = queries; a.g = gallery; a.qn = q_norms; a.gn = g_norms; a.Qn = Qn; a.Gn = Gn; a.D = D; a.k = k;
     a.out_idx = out_idx; a.out_dist = out_dist;
-    a.dist = nullptr; a.ldd = 0;
-    if (k > MATCH_KMAX) return match_large_k(a, is_f32, workspace, (hipStream_t)stream);
-    a.tiles_g = (Gn + MT_TG - 1) / MT_TG;
-    const int tq = is_f32 ? MT_TQ : match_small_tq(a.tiles_g, Qn);
-    // Which bf16 core and tile: the LDS-DMA kernel (match_big_kernel, 128 MG gallery rows x 64 NQ queries per workgroup) or the 128-row
-    // register-staged one, by estimated time.  Model (microseconds; least-squares fit to tools/dev/bench_match.py on MI355X, 63 launches of
-    // 200 ... 3 200 queries x 1 000 ... 10 000 rows x 512 | 1 024, rms error 8 %, picks the fastest variant or one within 1 % of it on all nine
-    // shapes):  launch = fixed + rounds x (D / 512) x round, where a round's cost grows with the share u of the CUs that hold a tile in it
-    // (L2 intake and clocks):
-    //   LDS-DMA kernel:   fixed 3.9 + 0.48 NQ,  round (0.74 + 1.97 NQ) x (MG = 1 ? 0.575 : 1) x (1 + 0.75 u)
-    //   128-row kernel:   fixed 10.4,           round 5.4 x (1 + 0.75 u) (64-query tiles, three per CU) | 9.0 x (1 + 0.75 u) (128-query, two per CU)
-    // Every bf16 kernel forms identical distances, so the choice changes no result (cvpce_match_set_core / CVPCE_MATCH_CORE = small | big,
-    // CVPCE_MATCH_NQ = 2..5, CVPCE_MATCH_MG = 1 | 2 force one: tests and A/B measurements).
-    int big_nq = 0, big_mg = 2;
-    if (!is_f32) {
-        const int core = g_match_core, forced_nq = g_match_nq;
-        const long long cus = g_cvpce_persistent_wgs;
-        const double dk = (double)D / 512.0;
-        const long long t128 = (long long)a.tiles_g * ((Qn + 127) / 128), t64 = (long long)a.tiles_g * ((Qn + 63) / 64);
-        const long long r128 = (t128 + 2 * cus - 1) / (2 * cus), r64 = (t64 + 3 * cus - 1) / (3 * cus);
-        const double e128 = 10.4 + (double)r128 * dk * 9.0 * (1.0 + 0.75 * (double)t128 / (double)(r128 * 2 * cus));
-        const double e64 = 10.4 + (double)r64 * dk * 5.4 * (1.0 + 0.75 * (double)t64 / (double)(r64 * 3 * cus));
-        const double best = e64 < e128 ? e64 : e128;
-        double best_big = 1e30;
-        for (int mg = 1; mg <= 2; ++mg)
-            for (int nq = 2; nq <= 5; ++nq) {
-                if ((forced_nq && nq != forced_nq) || (g_match_mg && mg != g_match_mg) || (mg == 1 && nq == 5)) continue;
-                const long long t = (long long)((Gn + 128 * mg - 1) / (128 * mg)) * ((Qn + 64 * nq - 1) / (64 * nq)), rounds = (t + cus - 1) / cus;
-                const double u = (double)t / (double)(rounds * cus);
-                const double e = 3.9 + 0.48 * nq + (double)rounds * dk * (0.74 + 1.97 * nq) * (mg == 1 ? 0.575 : 1.0) * (1.0 + 0.75 * u);
-                if (e < best_big) { best_big = e; big_nq = nq; big_mg = mg; }
-            }
-        // (a handful of queries against a small gallery is launch latency either way: the 128-row kernel keeps those)
-        if (core == 1 || (core == 0 && (!(best_big < best) || (long long)Qn * Gn < 64 * 1024))) big_nq = 0;
-    }
-    a.part_d = (float*)workspace;
-    a.part_i = (int*)((char*)workspace + ((size_t)Qn * a.tiles_g * k * 4 + 255) / 256 * 256);    // (laid out for the 128-row tiling: enough for either)
+    a.tiles_g = p.tiles_g; a.tiles_q = p.tiles_q;
     hipStream_t s = (hipStream_t)stream;
-    if (big_nq) {
-        const int tg = 128 * big_mg;
-        a.tiles_g = (Gn + tg - 1) / tg;
-        a.tiles_q = (Qn + 64 * big_nq - 1) / (64 * big_nq);
-        if ((unsigned long long)((unsigned long long)Qn + 64 * big_nq) * D * 2 >= (1ull << 32) || ((unsigned long long)Gn + tg) * D * 2 >= (1ull << 32)) return CVPCE_ERR_ARG;
-        const dim3 gridb(a.tiles_g * a.tiles_q);
-        const size_t smemb = (size_t)2 * (tg + 64 * big_nq) * MB_ROWB;
-#define MB_LAUNCH(NQ_, MG_)                                                                                                    \
-        case NQ_ * 4 + MG_:                                                                                                    \
-            if (!cvpce_smem_attr_done<match_big_kernel<NQ_, MG_>>((const void*)match_big_kernel<NQ_, MG_>, 2 * (128 * MG_ + 64 * NQ_) * MB_ROWB)) return CVPCE_ERR_LAUNCH; \
-            hipLaunchKernelGGL((match_big_kernel<NQ_, MG_>), gridb, dim3(512), smemb, s, a);                                   \
-            break;
-        switch (big_nq * 4 + big_mg) {
-            MB_LAUNCH(2, 2) MB_LAUNCH(3, 2) MB_LAUNCH(4, 2) MB_LAUNCH(5, 2) MB_LAUNCH(2, 1) MB_LAUNCH(3, 1) MB_LAUNCH(4, 1)
-            default: return CVPCE_ERR_ARG;
-        }
-#undef MB_LAUNCH
-    } else {
-    a.tiles_q = (Qn + tq - 1) / tq;
-    dim3 grid(a.tiles_g * a.tiles_q);
-    if (!cvpce_smem_attr_done<match_kernel<true, 128>>((const void*)match_kernel<true, 128>, 2 * 2 * 128 * 256) ||
-        !cvpce_smem_attr_done<match_kernel<false, 128>>((const void*)match_kernel<false, 128>, 128 * 128 * 4 + 2048 + 512) ||
-        !cvpce_smem_attr_done<match_kernel<false, 64>>((const void*)match_kernel<false, 64>, 2 * (128 + 64) * 128))
-        return CVPCE_ERR_LAUNCH;
-    if (is_f32) {
-        size_t smem = (size_t)2 * 2 * 128 * 256;    // 128 KiB staging (>= 66 KiB epilogue image)
-        hipLaunchKernelGGL((match_kernel<true, 128>), grid, dim3(256), smem, s, a);
-    } else if (tq == 128) {
-        size_t smem = (size_t)128 * 128 * 4 + 2048 + 512;  // epilogue image (+ candidates, + the tile's gallery norms) dominates (staging needs 64 KiB)
-        hipLaunchKernelGGL((match_kernel<false, 128>), grid, dim3(256), smem, s, a);
-    } else {
-        size_t smem = (size_t)2 * (128 + 64) * 128;        // 48 KiB of staging dominates (epilogue image 32 KiB + 2.5 KiB)
-        hipLaunchKernelGGL((match_kernel<false, 64>), grid, dim3(256), smem, s, a);
-    }
-    }
-    hipLaunchKernelGGL(match_merge_kernel, dim3((Qn + 3) / 4), dim3(256), 0, s, a.part_d, a.part_i, Qn, a.tiles_g * k,
-                       k, out_idx, out_dist);
+    if (p.path == MATCH_PATH_LARGE_K) return match_large_k(a, p, is_f32, workspace, s);
+    a.part_d = (float*)workspace;
+    a.part_i = (int*)((char*)workspace + p.part_i);
+    if (!(p.path == MATCH_PATH_BIG ? match_launch_big(p, a, s) : match_launch_small<false>(p, is_f32, a, s))) return CVPCE_ERR_LAUNCH;
+    hipLaunchKernelGGL(match_merge_kernel, dim3((Qn + 3) / 4), dim3(256), 0, s, a.part_d, a.part_i, Qn, a.tiles_g * k, k, out_idx, out_dist);
     return cvpce_check_launch();
 }
+

@@ -339,6 +339,14 @@ int cvpce_detect_postprocess(const float* const* logits, const float* const* reg
  * its k = 16 result bit for bit.  No host synchronisation, no device allocation: everything runs on `stream`. */
 int cvpce_row_norms(const void* x, float* out, int rows, int D, int is_f32, float eps, void* stream);
 size_t cvpce_match_workspace_bytes(int Qn, int Gn, int k);
+/* Host only, like the workspace query: the launch cvpce_match_topk would make for these arguments, under the switches of
+ * cvpce_match_set_core.  Returns what cvpce_match_topk would return for them (CVPCE_ERR_ARG: rejected) and fills
+ * out[CVPCE_MATCH_PLAN_FIELDS] = { path (0 fused top-k on the 128-row kernel, 1 fused on the LDS-DMA kernel, 2 large k),
+ * tq (paths 0, 2: queries per tile), nq, mg (path 1: tile of 64 nq queries x 128 mg gallery rows), tiles_g, tiles_q, LDS bytes and
+ * threads per workgroup of the GEMM launch, large k: queries per chunk, row stride of the distance block, bytes of a chunk's blocks,
+ * workspace bytes }. */
+#define CVPCE_MATCH_PLAN_FIELDS 12
+int cvpce_match_plan(int Qn, int Gn, int D, int k, int is_f32, long long* out);
 int cvpce_match_topk(const void* queries, const void* gallery, const float* q_norms, const float* g_norms,
                      int Qn, int Gn, int D, int k, int is_f32, void* workspace, size_t workspace_bytes,
                      long long* out_idx, float* out_dist, void* stream);

@@ -547,9 +547,26 @@ def test_match_reference_kat_and_golden(cuda, golden_dir):
         assert (d.gather(1, got) - d.gather(1, case['indices'])).abs().max() < 1e-5
 
 
+# The bf16 128-query instances of the 128-row core run only where whole rounds of the chip favour them: 79 x 6 = 474 tiles are one round
+# of 512 slots, against two rounds of 64-query tiles.  Tests of this shape pin that core and assert through the plan that they ran it.
+TQ128_SHAPE = (768, 10000, 64)
+
+
+def _pin_128_query_tiles(qn, gn, d, k, dtype=torch.bfloat16):
+    """pins the 128-row core (the caller resets it) and asserts that the launch of these arguments takes its 128-query tiles"""
+    import ctypes
+    from cvpce_amd import ops
+    from cvpce_amd._lib import lib
+    assert ops.match_set_core(1, 0, 0) == 0
+    out = (ctypes.c_longlong * 12)()
+    assert lib.cvpce_match_plan(qn, gn, d, k, int(dtype == torch.float32), out) == 0
+    assert (out[0], out[1]) == (2 if k > 16 else 0, 128)          # path: fused on the 128-row core | large k; tq
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('qn,gn,d,k', [(200, 1000, 1024, 1), (37, 3200, 1024, 4), (130, 129, 512, 3), (5, 10000, 512, 1),
-                                        (200, 10000, 512, 1), (1600, 10000, 1024, 1)])   # the last two: BASELINE configs[3] (distance-GEMM stress)
+                                        (200, 10000, 512, 1), (1600, 10000, 1024, 1),    # these two: BASELINE configs[3] (distance-GEMM stress)
+                                        TQ128_SHAPE + (4,)])
 def test_match_parity(cuda, dtype, qn, gn, d, k):
     from cvpce_amd import ops
     from oracle import match as omatch
@@ -557,7 +574,12 @@ def test_match_parity(cuda, dtype, qn, gn, d, k):
     G = F.normalize(torch.rand(gn, d, generator=g), dim=1)     # non-negative like MAC descriptors
     Q = F.normalize(torch.rand(qn, d, generator=g), dim=1)
     Gd, Qd = G.to(dtype), Q.to(dtype)
-    idx, dist = ops.match_topk(Qd.to(cuda), Gd.to(cuda), k, return_distance=True)
+    try:
+        if (qn, gn, d) == TQ128_SHAPE:
+            _pin_128_query_tiles(qn, gn, d, k, dtype)
+        idx, dist = ops.match_topk(Qd.to(cuda), Gd.to(cuda), k, return_distance=True)
+    finally:
+        ops.match_set_core(0, 0, 0)
     ref_d = omatch.cosine_distance_matrix(Gd.float(), Qd.float())    # oracle on the same (rounded) operands
     ref_idx = torch.sort(ref_d, dim=-1, stable=True).indices[:, :k]
     srt = ref_d.sort(dim=-1).values[:, :k + 1]
@@ -567,7 +589,7 @@ def test_match_parity(cuda, dtype, qn, gn, d, k):
     torch.testing.assert_close(dist.cpu(), ref_d.gather(1, idx.cpu()), rtol=0, atol=2e-6)
 
 
-@pytest.mark.parametrize('qn,gn,d', [(200, 10000, 512), (1600, 10000, 1024), (333, 1357, 256), (5, 40, 64)])
+@pytest.mark.parametrize('qn,gn,d', [(200, 10000, 512), (1600, 10000, 1024), (333, 1357, 256), (5, 40, 64), TQ128_SHAPE])
 def test_match_cores_and_tiles_give_identical_results(cuda, qn, gn, d):
     """The bf16 search has two cores (the 128-row register-staged kernel; the LDS-DMA kernel of round 5 with tiles of 128 MG gallery rows x
     64 NQ queries).  Which one a launch takes is a cost model's choice, so every variant must return the SAME indices and the SAME
@@ -587,6 +609,8 @@ def test_match_cores_and_tiles_give_identical_results(cuda, qn, gn, d):
     try:
         for core, nq, mg in variants:
             assert ops.match_set_core(core, nq, mg) == 0
+            if core == 1 and (qn, gn, d) == TQ128_SHAPE:
+                _pin_128_query_tiles(qn, gn, d, 4), _pin_128_query_tiles(qn, gn, d, 1)
             got = [ops.match_topk(Qd, Gd, 4, return_distance=True), ops.match_topk(Qd, Gd, 1, return_distance=True),
                    ops.match_topk(Qd, Gd, 1, return_distance=True)]
             torch.cuda.synchronize()

@@ -53,6 +53,31 @@ def test_large_k_prefix_equals_fused_top16(cuda, dtype, qn, gn, d):
         assert int(idx.min()) >= 0 and int(idx.max()) < gn
 
 
+def test_large_k_prefix_on_128_query_tiles(cuda):
+    """768 x 10 000: whole rounds of the chip favour the 128-row core's 128-query tiles (474 tiles in one round of 512 slots), bf16
+    instances no other shape of this file reaches.  With that core pinned: k = 17 (the storing instance) against k = 16 (the selecting one)."""
+    import ctypes
+    from cvpce_amd import ops
+    from cvpce_amd._lib import lib
+    qn, gn, d = 768, 10000, 64
+    Q, G = _operands(qn, gn, d, qn * 7 + gn, specials=True)
+    Qd, Gd = Q.to(torch.bfloat16).to(cuda), G.to(torch.bfloat16).to(cuda)
+    try:
+        assert ops.match_set_core(1, 0, 0) == 0
+        for k, path in ((16, 0), (17, 2)):
+            out = (ctypes.c_longlong * 12)()
+            assert lib.cvpce_match_plan(qn, gn, d, k, 0, out) == 0
+            assert (out[0], out[1]) == (path, 128)              # path, queries per tile
+        i16, d16 = ops.match_topk(Qd, Gd, 16, return_distance=True)
+        i17, d17 = ops.match_topk(Qd, Gd, 17, return_distance=True)
+    finally:
+        ops.match_set_core(0, 0, 0)
+    assert i17[:, :16].equal(i16) and _bits(d17[:, :16]).equal(_bits(d16))
+    assert i17[1].cpu().equal(torch.arange(17)) and bool(torch.isinf(d17[1]).all())      # the NaN query
+    assert int(i17.min()) >= 0 and int(i17.max()) < gn
+    assert bool((d17[:, 16] >= d17[:, 15]).all())
+
+
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('qn,gn,d', [(200, 10000, 512), (1600, 10000, 1024)])
 def test_large_k_oracle_parity(cuda, dtype, qn, gn, d):
