@@ -68,6 +68,7 @@ SIGNATURES = {
     'cvpce_conv3x3_halo_list': (c_int, [_vp, _vp, _fp, _vp, _fp, c_int, c_int] + [c_int] * 9 + [_vp, _ip, _vp]),
     'cvpce_conv3x3_halo_strips': (c_int, [_vp, _vp, _fp, _vp, _fp, c_int, c_int] + [c_int] * 9 + [_vp, _ip, _vp]),
     'cvpce_detect_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'cvpce_detect_plan': (c_int, [POINTER(c_int), POINTER(c_int)] + [c_int] * 6 + [POINTER(c_longlong)]),
     'cvpce_detect_postprocess': (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int), POINTER(c_int),
                                          POINTER(c_int), POINTER(c_int), _fp, _ip, _fp,
                                          c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_float,

@@ -1,18 +1,19 @@
 // RetinaNet post-processing on the GPU, torchvision 0.9
 // semantics (Appendix A: postprocess_detections, BoxCoder.decode_single,
 // clip_boxes_to_image, batched_nms/nms, transform.postprocess), reached from
-// /root/reference/cvpce/models/proposals.py:176-181 via RetinaNet.forward and
-// consumed at /root/reference/cvpce/production.py:13-15.
+// the reference's cvpce/models/proposals.py:176-181 via RetinaNet.forward and
+// consumed at its cvpce/production.py:13-15.
 //
 //   decode_select  one 1024-thread workgroup per 8192-logit CHUNK of a (level, image): score threshold (exact, see
 //                score_passes), exact top-k of the chunk by radix select on (logit key, ~index) held in registers; the
-//                chunk's survivors (<= topk, unsorted) go to a scratch run.  P3 of an 800 x 800 image is 11 chunks on 11 CUs
-//                where one workgroup used to walk all 90 000 logits.
+//                chunk's survivors (<= topk, unsorted) go to a scratch run of CAP entries.  P3 of an 800 x 800 image is 11
+//                chunks on 11 CUs where one workgroup used to walk all 90 000 logits.
 //   decode_merge   one workgroup per (level, image): the same selection over the level's runs (a chunk's top-k holds every
-//                member of the level's top-k that lies in the chunk), LDS bitonic sort of the <= 1024 survivors, anchor
-//                synthesis + box decode + clip.
+//                member of the level's top-k that lies in the chunk), bitonic sort of the survivors (CAP 1024: one key per
+//                thread in registers; CAP 4096: in LDS), anchor synthesis + box decode + clip.
 //   decode_topk  the one-kernel form of the two above (one workgroup per (level, image), logits beyond 56 per thread
-//                streamed per pass): kept for levels of more than 32 chunks and for workspaces without room for the runs.
+//                streamed per pass): kept for levels of more chunks than one merge workgroup holds (32 at CAP 1024, 8 at
+//                CAP 4096) and for images with more chunks than the workspace has runs (12 per level).
 //   nms_sort     one workgroup per image: the levels' sorted candidate lists are merged by RANK (every candidate finds, by
 //                binary search in LDS, how many candidates of the other levels precede it) -> sorted by (logit desc,
 //                level asc, rank asc), i.e. the order of the concatenated candidate list under a stable sort.
@@ -41,13 +42,33 @@
 #pragma clang fp contract(off)
 
 #define MAX_LEVELS 8
-#define SORT_CAP 8192            // candidates per image at CAP 1024 (8 levels x 1024)
-#define TOPK_CAP_WIDE 4096       // largest topk (CAP of the wide instantiations)
-#define SORT_CAP_WIDE 20480      // candidates per image at CAP 4096 (5 levels x 4096)
+#define DECODE_CHUNK 8192          // logits per decode_select workgroup (8 per thread, in registers)
+#define DECODE_MAX_RUNS 32         // 1024-entry runs one decode_merge workgroup holds in registers (one entry per thread and run)
+#define DECODE_RUNS_PER_LEVEL 12   // workspace room: N * L * 12 runs (800^2: 17 per image; 1333^2: 43)
 
+// Everything that depends on the capacity: the candidates per image the NMS kernels hold, the CAP-entry runs one decode_merge
+// workgroup holds (the same 32 keys per thread at either capacity) and the length of a level's segment of nms_sort's LDS keys.
 template <int CAP> struct Cap;
-template <> struct Cap<1024> { static constexpr int sort = SORT_CAP; };
-template <> struct Cap<TOPK_CAP_WIDE> { static constexpr int sort = SORT_CAP_WIDE; };
+template <> struct Cap<1024> {
+    static constexpr int sort = 8192;                                       // 8 levels x 1024
+    static constexpr int merge_runs = DECODE_MAX_RUNS;
+    static constexpr __host__ __device__ int seg(int) { return 1024; }      // L * 1024 keys: <= 32 KiB
+};
+template <> struct Cap<4096> {
+    static constexpr int sort = 20480;                                      // 5 levels x 4096
+    static constexpr int merge_runs = DECODE_MAX_RUNS * 1024 / 4096;
+    static constexpr __host__ __device__ int seg(int topk) { return topk; } // L * topk <= 20 480 keys: <= 80 KiB
+};
+
+// the levels' candidate lists: written by the decode kernels, read by nms_sort
+struct Candidates {
+    float* boxes;                      // [N][L*topk][4]
+    float* scores;                     // [N][L*topk]
+    float* logits;                     // [N][L*topk]
+    int* labels;                       // [N][L*topk]
+    int* count;                        // [N][L]
+    int L, N, topk;
+};
 
 struct DecodeArgs {
     const float* logits[MAX_LEVELS];   // [N][gh*gw*A*K]
@@ -55,13 +76,9 @@ struct DecodeArgs {
     int gh[MAX_LEVELS], gw[MAX_LEVELS], sh[MAX_LEVELS], sw[MAX_LEVELS];
     const float* base_anchors;         // [L][A][4]
     const int* image_hw;               // [N][2] resized (unpadded) sizes
-    int L, N, A, K, topk;
+    int A, K;
     float score_thresh, xform_clip;
-    float* cand_boxes;                 // [N][L*topk][4]
-    float* cand_scores;                // [N][L*topk]
-    float* cand_logits;                // [N][L*topk]
-    int* cand_labels;                  // [N][L*topk]
-    int* cand_count;                   // [N][L]
+    Candidates c;
     // chunked form (decode_select_kernel + decode_merge_kernel)
     int chunk_first[MAX_LEVELS + 1];   // first chunk of each level in an image's chunk list; [L] = chunks per image
     unsigned long long* runs;          // [N][chunks per image][CAP] (logit key << 32 | ~index in level), unsorted, 0 = empty
@@ -74,12 +91,33 @@ __device__ __forceinline__ unsigned ordered_key(float f) {
 }
 __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.f / (1.f + expf(-x)); }
 
+struct LevelView { int n; const float* lg; const float* rg; };   // one (level, image): its n = gh*gw*A*K logits and its regressions
+__device__ __forceinline__ LevelView level_view(const DecodeArgs& a, int level, int img) {
+    const int cells = a.gh[level] * a.gw[level] * a.A, n = cells * a.K;
+    return {n, a.logits[level] + (size_t)img * n, a.regs[level] + (size_t)img * (size_t)cells * 4};
+}
+
+// wave-aggregated histogram update: the lanes that share the first active lane's bin are counted by ONE LDS atomic (on the
+// leading digits nearly every key of a level falls into the same two or three bins, and 64 lanes hitting one bin
+// serialise), the others add individually
+__device__ __forceinline__ void wave_hist_add(int* hist, bool pred, unsigned bin, int lane) {
+    const unsigned long long act = __ballot(pred);
+    if (act) {
+        const int leader = __ffsll((long long)act) - 1;
+        const unsigned lb = (unsigned)__builtin_amdgcn_readlane((int)bin, leader);
+        const bool same = pred && bin == lb;
+        const unsigned long long sm = __ballot(same);
+        if (lane == leader) atomicAdd(&hist[lb], __popcll(sm));
+        if (pred && !same) atomicAdd(&hist[bin], 1);
+    }
+}
+
 // candidate t (rank t of its level) from its composite: anchor synthesis, box decode and clip (BoxCoder.decode_single,
 // clip_boxes_to_image), written to slot level * topk + t of the image's candidate list
 __device__ __forceinline__ void decode_candidate(const DecodeArgs& a, int level, int img, int t, unsigned long long comp,
                                                  const float* lg, const float* rg) {
     const int gw = a.gw[level];
-    const int slot = a.L * a.topk;
+    const int slot = a.c.L * a.c.topk;
     const int idx = (int)(0xFFFFFFFFu - (unsigned)(comp & 0xFFFFFFFFull));
     const float l = lg[idx];
     const int aidx = idx / a.K, label = idx - aidx * a.K;
@@ -98,11 +136,11 @@ __device__ __forceinline__ void decode_candidate(const DecodeArgs& a, int level,
     const float ih = (float)a.image_hw[img * 2 + 0], iw = (float)a.image_hw[img * 2 + 1];
     x1 = fminf(fmaxf(x1, 0.f), iw); x2 = fminf(fmaxf(x2, 0.f), iw);
     y1 = fminf(fmaxf(y1, 0.f), ih); y2 = fminf(fmaxf(y2, 0.f), ih);
-    const size_t o = (size_t)img * slot + (size_t)level * a.topk + t;
-    *reinterpret_cast<float4*>(a.cand_boxes + o * 4) = make_float4(x1, y1, x2, y2);
-    a.cand_scores[o] = sigmoidf_ref(l);
-    a.cand_logits[o] = l;
-    a.cand_labels[o] = label;
+    const size_t o = (size_t)img * slot + (size_t)level * a.c.topk + t;
+    *reinterpret_cast<float4*>(a.c.boxes + o * 4) = make_float4(x1, y1, x2, y2);
+    a.c.scores[o] = sigmoidf_ref(l);
+    a.c.logits[o] = l;
+    a.c.labels[o] = label;
 }
 
 // descending bitonic sort of n (power of two) 64-bit keys in LDS by `nthreads` threads
@@ -148,6 +186,31 @@ __device__ __forceinline__ void bitonic_sort1024_desc(unsigned long long* s, int
     __syncthreads();
 }
 
+// the common tail of decode_topk and decode_merge: the level's k survivors in sel[0 .. k) (the rest of sel[CAP] zero) are sorted
+// (REG_SORT: by the register network, CAP 1024 only), counted and decoded into the level's candidate list
+template <int CAP, bool REG_SORT>
+__device__ __forceinline__ void finish_level(const DecodeArgs& a, int level, int img, int k, unsigned long long* sel, int tid) {
+    static_assert(!REG_SORT || CAP == 1024, "the register network sorts exactly 1024 keys");
+    if constexpr (REG_SORT) bitonic_sort1024_desc(sel, tid);
+    else bitonic_sort_desc(sel, CAP, tid, 1024);
+    const LevelView v = level_view(a, level, img);
+    if (tid == 0) a.c.count[img * a.c.L + level] = k;
+    for (int t = tid; t < k; t += 1024) decode_candidate(a, level, img, t, sel[t], v.lg, v.rg);
+}
+
+// one pass over the streamed logits [nreg, n) of decode_topk: UNROLL independent loads per thread in flight, then f(logit, index)
+// on each (indices past n arrive as -inf: sigmoid(-inf) = 0)
+template <int UNROLL, class F>
+__device__ __forceinline__ void stream_logits(const float* lg, int nreg, int n, int tid, F f) {
+    for (int base = nreg; base < n; base += UNROLL * 1024) {
+        float v[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) { const int i = base + u * 1024 + tid; v[u] = i < n ? lg[i] : -INFINITY; }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) f(v[u], base + u * 1024 + tid);
+    }
+}
+
 template <int CAP>
 __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
     __shared__ unsigned long long sel[CAP];
@@ -156,10 +219,9 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
     __shared__ int s_cnt, s_prefix, s_need, s_nsel, s_eqbase, s_eqtotal;
 
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
-    const int gh = a.gh[level], gw = a.gw[level];
-    const int n = gh * gw * a.A * a.K;
-    const float* lg = a.logits[level] + (size_t)img * n;
-    const float* rg = a.regs[level] + (size_t)img * (size_t)(gh * gw * a.A) * 4;
+    const LevelView lv = level_view(a, level, img);
+    const int n = lv.n;
+    const float* lg = lv.lg;
 
     if (tid == 0) { s_cnt = 0; s_nsel = 0; s_eqbase = 0; s_eqtotal = 0; }
     for (int i = tid; i < CAP; i += 1024) sel[i] = 0ull;
@@ -173,20 +235,6 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
     const int lane = tid & 63;
     const int nreg = n < R * 1024 ? n : R * 1024;       // logits [0, nreg) live in registers, [nreg, n) are streamed
     unsigned keys[R];
-    // wave-aggregated histogram update: the lanes that share the first active lane's bin are counted by ONE LDS atomic (on the
-    // leading digits nearly every key of a level falls into the same two or three bins, and 64 lanes hitting one bin
-    // serialise), the others add individually
-    auto hist_add = [&](bool pred, unsigned bin) {
-        const unsigned long long act = __ballot(pred);
-        if (act) {
-            const int leader = __ffsll((long long)act) - 1;
-            const unsigned lb = (unsigned)__builtin_amdgcn_readlane((int)bin, leader);
-            const bool same = pred && bin == lb;
-            const unsigned long long sm = __ballot(same);
-            if (lane == leader) atomicAdd(&hist[lb], __popcll(sm));
-            if (pred && !same) atomicAdd(&hist[bin], 1);
-        }
-    };
     auto take = [&](unsigned key, int i) {
         const int pos = atomicAdd(&s_nsel, 1);
         if (pos < CAP) sel[pos] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
@@ -201,19 +249,13 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
         keys[u] = ok ? ordered_key(l) : 0u;                     // ordered_key is 0 only for one NaN pattern, never a candidate
         local += ok ? 1 : 0;
     }
-    for (int base = nreg; base < n; base += UNROLL * 1024) {
-        float v[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) { const int i = base + u * 1024 + tid; v[u] = i < n ? lg[i] : -INFINITY; }
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) local += (sigmoidf_ref(v[u]) > a.score_thresh) ? 1 : 0;   // sigmoid(-inf) = 0
-    }
+    stream_logits<UNROLL>(lg, nreg, n, tid, [&](float l, int) { local += (sigmoidf_ref(l) > a.score_thresh) ? 1 : 0; });
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);
     if (lane == 0) atomicAdd(&s_cnt, local);
     __syncthreads();
     const int cnt = s_cnt;
-    const int k = cnt < a.topk ? cnt : a.topk;
+    const int k = cnt < a.c.topk ? cnt : a.c.topk;
 
     unsigned T = 0;       // key of the k-th largest candidate
     int need_eq = 0;      // how many candidates with key == T are taken (lowest index first)
@@ -226,18 +268,12 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
 #pragma unroll
             for (int u = 0; u < R; ++u) {
                 const unsigned key = keys[u];
-                hist_add(key != 0u && (key & mask) == prefix, (key >> shift) & 255u);
+                wave_hist_add(hist, key != 0u && (key & mask) == prefix, (key >> shift) & 255u, lane);
             }
-            for (int base = nreg; base < n; base += UNROLL * 1024) {
-                float v[UNROLL];
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) { const int i = base + u * 1024 + tid; v[u] = i < n ? lg[i] : -INFINITY; }
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) {
-                    const unsigned key = ordered_key(v[u]);
-                    hist_add((sigmoidf_ref(v[u]) > a.score_thresh) && ((key & mask) == prefix), (key >> shift) & 255u);
-                }
-            }
+            stream_logits<UNROLL>(lg, nreg, n, tid, [&](float l, int) {
+                const unsigned key = ordered_key(l);
+                wave_hist_add(hist, (sigmoidf_ref(l) > a.score_thresh) && ((key & mask) == prefix), (key >> shift) & 255u, lane);
+            });
             __syncthreads();
             if (tid == 0) {
                 int cum = 0, b = 255;
@@ -266,16 +302,11 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
             const unsigned key = keys[u];
             if (key != 0u && (cnt <= k || key >= T)) take(key, u * 1024 + tid);
         }
-        for (int base = nreg; base < n; base += UNROLL * 1024) {
-            float v[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) { const int i = base + u * 1024 + tid; v[u] = i < n ? lg[i] : -INFINITY; }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                const unsigned key = ordered_key(v[u]);
-                if ((sigmoidf_ref(v[u]) > a.score_thresh) && (cnt <= k || key >= T)) take(key, base + u * 1024 + tid);
-            }
-        }
+        // (cnt, k and T by value: captured by reference the kernel compiles to 127 VGPRs and 44 bytes of scratch instead of 122 and 0)
+        stream_logits<UNROLL>(lg, nreg, n, tid, [&, cnt, k, T](float l, int i) {
+            const unsigned key = ordered_key(l);
+            if ((sigmoidf_ref(l) > a.score_thresh) && (cnt <= k || key >= T)) take(key, i);
+        });
     } else {
         // more candidates tie at the key T than fit: take the first need_eq of them in index order (ordered compaction)
         for (int base = 0; base < n; base += 1024) {
@@ -308,10 +339,7 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
         }
     }
     __syncthreads();
-    bitonic_sort_desc(sel, CAP, tid, 1024);
-
-    if (tid == 0) a.cand_count[img * a.L + level] = k;
-    for (int t = tid; t < k; t += 1024) decode_candidate(a, level, img, t, sel[t], lg, rg);
+    finish_level<CAP, false>(a, level, img, k, sel, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -322,10 +350,6 @@ __global__ __launch_bounds__(1024) void decode_topk_kernel(DecodeArgs a) {
 __device__ __forceinline__ bool score_passes(float l, float thresh, float t_lo, float t_hi) {
     return l > t_hi || (l >= t_lo && sigmoidf_ref(l) > thresh);      // NaN: false, as sigmoid(NaN) > thresh is
 }
-
-#define DECODE_CHUNK 8192          // logits per decode_select workgroup (8 per thread, in registers)
-#define DECODE_MAX_RUNS 32         // 1024-entry runs one decode_merge workgroup holds in registers (one entry per thread and run)
-#define DECODE_RUNS_PER_LEVEL 12   // workspace room: N * L * 12 runs (800^2: 17 per image; 1333^2: 43)
 
 template <int CAP>
 struct SelectShared {
@@ -366,19 +390,7 @@ __device__ __forceinline__ int select_topk_regs(const unsigned long long (&comp)
             for (int u = 0; u < R; ++u) {
                 if (u < nslots) {
                     const unsigned long long c = comp[u];
-                    const bool pred = c != 0ull && (c & mask) == prefix;
-                    const unsigned bin = (unsigned)(c >> shift) & 255u;
-                    // wave-aggregated: the lanes sharing the first active lane's bin cost ONE LDS atomic (on the leading byte
-                    // nearly all keys of a level fall into two or three bins), the others add individually
-                    const unsigned long long act = __ballot(pred);
-                    if (act) {
-                        const int leader = __ffsll((long long)act) - 1;
-                        const unsigned lb = (unsigned)__builtin_amdgcn_readlane((int)bin, leader);
-                        const bool same = pred && bin == lb;
-                        const unsigned long long sm = __ballot(same);
-                        if (lane == leader) atomicAdd(&sh.hist[lb], __popcll(sm));
-                        if (pred && !same) atomicAdd(&sh.hist[bin], 1);
-                    }
+                    wave_hist_add(sh.hist, c != 0ull && (c & mask) == prefix, (unsigned)(c >> shift) & 255u, lane);
                 }
             }
             __syncthreads();
@@ -441,11 +453,11 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeArgs a) {
     __shared__ SelectShared<CAP> sh;
     const int chunk = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     int level = 0;
-    while (level + 1 < a.L && chunk >= a.chunk_first[level + 1]) ++level;
-    const int n = a.gh[level] * a.gw[level] * a.A * a.K;
+    while (level + 1 < a.c.L && chunk >= a.chunk_first[level + 1]) ++level;
+    const LevelView lv = level_view(a, level, img);
+    const float* lg = lv.lg;
     const int c0 = (chunk - a.chunk_first[level]) * DECODE_CHUNK;
-    const int c1 = c0 + DECODE_CHUNK < n ? c0 + DECODE_CHUNK : n;
-    const float* lg = a.logits[level] + (size_t)img * n;
+    const int c1 = c0 + DECODE_CHUNK < lv.n ? c0 + DECODE_CHUNK : lv.n;
     constexpr int R = DECODE_CHUNK / 1024;
     unsigned long long comp[R];
 #pragma unroll
@@ -456,44 +468,34 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeArgs a) {
         // ordered_key is 0 only for one NaN pattern, never a candidate
         comp[u] = ok ? (((unsigned long long)ordered_key(l) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
     }
-    const int k = select_topk_regs<R, CAP>(comp, R, a.topk, sh, tid);
-    (void)k;
+    select_topk_regs<R, CAP>(comp, R, a.c.topk, sh, tid);
     // the whole CAP-entry run is written (zeros past the chunk's survivors): the merge kernel loads its runs without waiting
     // for their counts
-    for (int i = tid; i < CAP; i += 1024) a.runs[((size_t)img * a.chunk_first[a.L] + chunk) * CAP + i] = sh.sel[i];
+    for (int i = tid; i < CAP; i += 1024) a.runs[((size_t)img * a.chunk_first[a.c.L] + chunk) * CAP + i] = sh.sel[i];
 }
 
 template <int CAP>
 __global__ __launch_bounds__(1024) void decode_merge_kernel(DecodeArgs a) {
     __shared__ SelectShared<CAP> sh;
     const int level = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
-    const int gh = a.gh[level], gw = a.gw[level];
-    const int n = gh * gw * a.A * a.K;
-    const float* lg = a.logits[level] + (size_t)img * n;
-    const float* rg = a.regs[level] + (size_t)img * (size_t)(gh * gw * a.A) * 4;
-    // the level's runs are contiguous: nch * CAP entries, CAP / 1024 slots per run (nch <= DECODE_MAX_RUNS * 1024 / CAP, host)
+    // the level's runs are contiguous: nch * CAP entries, CAP / 1024 slots per run (nch <= Cap<CAP>::merge_runs, host)
     const int nch = a.chunk_first[level + 1] - a.chunk_first[level];
     const int nslots = nch * (CAP / 1024);
-    const unsigned long long* run = a.runs + ((size_t)img * a.chunk_first[a.L] + a.chunk_first[level]) * CAP;
+    const unsigned long long* run = a.runs + ((size_t)img * a.chunk_first[a.c.L] + a.chunk_first[level]) * CAP;
     unsigned long long comp[DECODE_MAX_RUNS];
 #pragma unroll
     for (int u = 0; u < DECODE_MAX_RUNS; ++u) {
         comp[u] = 0ull;
         if (u < nslots) comp[u] = run[(size_t)u * 1024 + tid];    // (independent loads, all in flight together)
     }
-    const int k = select_topk_regs<DECODE_MAX_RUNS, CAP>(comp, nslots, a.topk, sh, tid);
-    if constexpr (CAP == 1024) bitonic_sort1024_desc(sh.sel, tid);
-    else bitonic_sort_desc(sh.sel, CAP, tid, 1024);
-
-    if (tid == 0) a.cand_count[img * a.L + level] = k;
-    for (int t = tid; t < k; t += 1024) decode_candidate(a, level, img, t, sh.sel[t], lg, rg);
+    const int k = select_topk_regs<DECODE_MAX_RUNS, CAP>(comp, nslots, a.c.topk, sh, tid);
+    finish_level<CAP, CAP == 1024>(a, level, img, k, sh.sel, tid);
 }
 
 // ---------------------------------------------------------------------------
 struct NmsArgs {
-    const float* cand_boxes; const float* cand_scores; const float* cand_logits; const int* cand_labels;
-    const int* cand_count;
-    int L, N, topk, Tmax, words;       // Tmax = roundup(L*topk, 64); words = Tmax/64
+    Candidates c;
+    int Tmax, words;                   // Tmax = roundup(L*topk, 64); words = Tmax/64
     float nms_thresh, conf_thresh;
     int max_keep;                      // detections_per_img
     const float* ratios;               // [N][2] (ratio_h, ratio_w) = orig / resized
@@ -510,20 +512,21 @@ struct NmsArgs {
 
 template <int CAP>
 __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
-    // L segments of `seg` logit keys: 1024 at CAP 1024 (<= 32 KiB), topk at CAP 4096 (L * topk <= 20 480: <= 80 KiB)
+    // L segments of Cap<CAP>::seg(topk) logit keys
     extern __shared__ __attribute__((aligned(16))) unsigned keys[];
-    const int seg = CAP == 1024 ? 1024 : a.topk;
+    const int L = a.c.L, topk = a.c.topk;
+    const int seg = Cap<CAP>::seg(topk);
     __shared__ int offs[MAX_LEVELS + 1];
     __shared__ float s_max[16];
     const int img = blockIdx.x, tid = threadIdx.x;
-    const int slot = a.L * a.topk;
+    const int slot = L * topk;
     if (tid == 0) {
         int t = 0;
-        for (int l = 0; l < a.L; ++l) { offs[l] = t; t += a.cand_count[img * a.L + l]; }
-        offs[a.L] = t;
+        for (int l = 0; l < L; ++l) { offs[l] = t; t += a.c.count[img * L + l]; }
+        offs[L] = t;
     }
     __syncthreads();
-    const int T = offs[a.L];
+    const int T = offs[L];
     // Each level's candidates arrive sorted (decode: logit descending, then lower anchor index): the keys of level l are laid
     // into the segment l of LDS and every candidate computes its RANK in the merged order -- its rank in its own
     // level plus, by binary search, the number of candidates of every other level that precede it -- and is copied straight to
@@ -531,13 +534,13 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
     // level first, then the lower rank, which is the order of the concatenated candidate list -- so a candidate of level l
     // counts the keys >= its own in the levels below l and the keys > its own in the levels above.
     float mx = -INFINITY;
-    for (int i = tid; i < a.L * seg; i += 1024) {
+    for (int i = tid; i < L * seg; i += 1024) {
         unsigned kv = 0u;
         const int l = i / seg, r = i - l * seg;
         if (r < offs[l + 1] - offs[l]) {
-            const int src = l * a.topk + r;
-            kv = ordered_key(a.cand_logits[(size_t)img * slot + src]);
-            const float4 b = *reinterpret_cast<const float4*>(a.cand_boxes + ((size_t)img * slot + src) * 4);
+            const int src = l * topk + r;
+            kv = ordered_key(a.c.logits[(size_t)img * slot + src]);
+            const float4 b = *reinterpret_cast<const float4*>(a.c.boxes + ((size_t)img * slot + src) * 4);
             mx = fmaxf(mx, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
         }
         keys[i] = kv;
@@ -549,11 +552,11 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
     mx = s_max[0];
     for (int w = 1; w < 16; ++w) mx = fmaxf(mx, s_max[w]);
     if (tid == 0) a.s_total[img] = T;
-    for (int l = 0; l < a.L; ++l)                                    // (the level is uniform per iteration)
+    for (int l = 0; l < L; ++l)                                      // (the level is uniform per iteration)
     for (int r = tid; r < offs[l + 1] - offs[l]; r += 1024) {
         const unsigned kv = keys[l * seg + r];
         int rank = r;
-        for (int m = 0; m < a.L; ++m) {
+        for (int m = 0; m < L; ++m) {
             if (m == l) continue;
             const unsigned* keys_m = keys + m * seg;
             const unsigned bound = m < l ? kv - 1u : kv;             // count keys > bound (kv >= 1: ordered_key of a candidate)
@@ -564,14 +567,22 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(NmsArgs a) {
             }
             rank += lo;
         }
-        const size_t src = (size_t)img * slot + l * a.topk + r;
+        const size_t src = (size_t)img * slot + l * topk + r;
         const size_t dst = (size_t)img * a.Tmax + rank;
-        *reinterpret_cast<float4*>(a.s_boxes + dst * 4) = *reinterpret_cast<const float4*>(a.cand_boxes + src * 4);
-        a.s_scores[dst] = a.cand_scores[src];
-        const int lab = a.cand_labels[src];
+        *reinterpret_cast<float4*>(a.s_boxes + dst * 4) = *reinterpret_cast<const float4*>(a.c.boxes + src * 4);
+        a.s_scores[dst] = a.c.scores[src];
+        const int lab = a.c.labels[src];
         a.s_labels[dst] = lab;
         a.s_off[dst] = (float)lab * (mx + 1.f);   // batched_nms class offset (0 for num_classes == 1)
     }
+}
+
+// sorted box j of an image, shifted by its class offset (batched_nms)
+__device__ __forceinline__ float4 load_offset_box(const NmsArgs& a, int img, int j) {
+    float4 b = *reinterpret_cast<const float4*>(a.s_boxes + ((size_t)img * a.Tmax + j) * 4);
+    const float o = a.s_off[(size_t)img * a.Tmax + j];
+    b.x += o; b.y += o; b.z += o; b.w += o;
+    return b;
 }
 
 __global__ __launch_bounds__(64) void nms_mask_kernel(NmsArgs a) {
@@ -584,23 +595,14 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(NmsArgs a) {
     const int t = threadIdx.x;
     {
         const int j = cb * 64 + t;
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (j < T) {
-            b = *reinterpret_cast<const float4*>(a.s_boxes + ((size_t)img * a.Tmax + j) * 4);
-            const float o = a.s_off[(size_t)img * a.Tmax + j];
-            b.x += o; b.y += o; b.z += o; b.w += o;
-        }
+        const float4 b = j < T ? load_offset_box(a, img, j) : make_float4(0.f, 0.f, 0.f, 0.f);
         cbox[t] = b;
         carea[t] = (b.z - b.x) * (b.w - b.y);
     }
     __syncthreads();
     const int i = rb * 64 + t;
     if (i >= T) return;
-    float4 bi = *reinterpret_cast<const float4*>(a.s_boxes + ((size_t)img * a.Tmax + i) * 4);
-    {
-        const float o = a.s_off[(size_t)img * a.Tmax + i];
-        bi.x += o; bi.y += o; bi.z += o; bi.w += o;
-    }
+    const float4 bi = load_offset_box(a, img, i);
     const float area_i = (bi.z - bi.x) * (bi.w - bi.y);
     const float thr = a.nms_thresh;
     // iou = inter / uni > thr, as the oracle evaluates it -- but the division runs only where rounding could decide: p = fl(thr *
@@ -773,60 +775,143 @@ __global__ __launch_bounds__(1024) void nms_scan_kernel(NmsArgs a) {
     if (tid == 0) { a.out_count[img] = nout; a.out_conf_count[img] = s_conf; }
 }
 
-// per-level top-k capacity of the kernels the host selects for `topk` (0: beyond every instantiation)
-static int topk_capacity(int topk) { return topk <= 1024 ? 1024 : topk <= TOPK_CAP_WIDE ? TOPK_CAP_WIDE : 0; }
+// ---------------------------------------------------------------------------
+// Host side: the workspace layout and every launch decision are made once, without a HIP call (cvpce_detect_plan reports them).
 
-extern "C" size_t cvpce_detect_workspace_bytes(int N, int L, int topk) {
-    const size_t slot = (size_t)L * topk;
-    const size_t Tmax = (slot + 63) / 64 * 64, words = Tmax / 64;
-    const size_t cap = topk_capacity(topk) ? topk_capacity(topk) : 1024;
-    size_t b = 0;
-    b += (size_t)N * slot * (4 + 1 + 1 + 1) * 4;      // cand boxes/scores/logits/labels
-    b += (size_t)N * L * 4;                            // cand_count
-    b += (size_t)N * Tmax * (4 + 1 + 1 + 1) * 4;       // sorted boxes/scores/labels/off
-    b += (size_t)N * 4;                                // s_total
-    b += (size_t)N * Tmax * words * 8;                 // mask
-    b += (size_t)N * L * DECODE_RUNS_PER_LEVEL * cap * 8;   // chunk runs (CAP entries each)
-    b += (size_t)N * 4;                                // done flags of the two-phase NMS
-    return b + 16 * 256;   // every sub-allocation is rounded up to 256 B
+// per-level top-k capacity of the kernels the host selects for `topk` (beyond every instantiation: 1024, whose plan rejects it)
+static int topk_capacity(int topk) { return topk > 1024 && topk <= 4096 ? 4096 : 1024; }
+
+// The workspace's sub-allocations in carve order, each starting on a multiple of 256 bytes (the mask first: 64-bit words).
+enum { WS_MASK, WS_CAND_BOXES, WS_CAND_SCORES, WS_CAND_LOGITS, WS_CAND_LABELS, WS_CAND_COUNT, WS_S_BOXES, WS_S_SCORES, WS_S_LABELS,
+       WS_S_OFF, WS_S_TOTAL, WS_RUNS, WS_DONE, WS_PARTS };
+constexpr size_t WS_ROUNDING = 16 * 256;       // what the workspace query adds to the unrounded sum for the carve's rounding
+static_assert(WS_PARTS * 255 < WS_ROUNDING, "the rounded carve must fit in the bytes cvpce_detect_workspace_bytes reports");
+struct DetectWorkspace {
+    size_t off[WS_PARTS];
+    size_t bytes;                      // cvpce_detect_workspace_bytes: the unrounded sum + WS_ROUNDING (>= the end of the carve)
+};
+static DetectWorkspace detect_workspace(int N, int L, int topk, int cap) {
+    const size_t n = (size_t)N, slot = (size_t)L * topk, Tmax = (slot + 63) / 64 * 64, words = Tmax / 64;
+    const size_t size[WS_PARTS] = {
+        n * Tmax * words * 8,                                      // mask
+        n * slot * 16, n * slot * 4, n * slot * 4, n * slot * 4,   // cand boxes, scores, logits, labels
+        n * L * 4,                                                 // cand_count
+        n * Tmax * 16, n * Tmax * 4, n * Tmax * 4, n * Tmax * 4,   // sorted boxes, scores, labels, class offsets
+        n * 4,                                                     // s_total
+        n * L * DECODE_RUNS_PER_LEVEL * cap * 8,                   // chunk runs (CAP entries each)
+        n * 4,                                                     // done flags of the two-phase NMS
+    };
+    DetectWorkspace w = {};
+    size_t at = 0;
+    for (int i = 0; i < WS_PARTS; ++i) {
+        w.off[i] = at;
+        at += (size[i] + 255) / 256 * 256;
+        w.bytes += size[i];
+    }
+    w.bytes += WS_ROUNDING;
+    return w;
 }
 
-// the five launches of one post-processing call at capacity CAP
+extern "C" size_t cvpce_detect_workspace_bytes(int N, int L, int topk) { return detect_workspace(N, L, topk, topk_capacity(topk)).bytes; }
+
+enum { DECODE_CHUNKED = 0, DECODE_ONE_MERGE = 1, DECODE_ONE_ROOM = 2, DECODE_ONE_SWITCH = 3 };
+struct DetectPlan {
+    int rc;                            // CVPCE_ERR_ARG: the arguments are rejected
+    int cap;
+    // decode_select + decode_merge, or why decode_topk instead: a level has more chunks than one merge workgroup holds | the
+    // image's chunks exceed the workspace's runs | CVPCE_DECODE_ONE_KERNEL is set
+    int decode;
+    int chunks, chunk_first[MAX_LEVELS + 1];   // per image; first chunk of each level
+    int Tmax, words;                   // roundup(L * topk, 64) candidates per image; 64-bit words of a mask row
+    int sort_lds;                      // dynamic LDS bytes of nms_sort
+    int limit;                         // candidates of NMS phase 1; 0: one phase over all of them
+    int launches;
+    DetectWorkspace ws;
+};
+
 template <int CAP>
-static int launch_postprocess(const DecodeArgs& d, NmsArgs n, bool chunked, int chunks, size_t limit, hipStream_t s) {
-    const int L = d.L, N = d.N;
-    if (chunked && !getenv("CVPCE_DECODE_ONE_KERNEL")) {
-        hipLaunchKernelGGL(decode_select_kernel<CAP>, dim3(chunks, N), dim3(1024), 0, s, d);
+static DetectPlan detect_plan_at(const int* gh, const int* gw, int L, int N, int A, int K, int topk, int detections_per_img) {
+    using C = Cap<CAP>;
+    DetectPlan p = {};
+    p.rc = CVPCE_ERR_ARG;
+    p.cap = CAP;
+    if (L < 1 || L > MAX_LEVELS || A < 1 || K < 1 || topk < 1 || topk > CAP || detections_per_img < 1) return p;
+    if (L * topk > C::sort || detections_per_img > C::sort) return p;
+    p.ws = detect_workspace(N, L, topk, CAP);
+    if (N <= 0) { p.rc = CVPCE_OK; return p; }                    // nothing to launch
+    p.Tmax = (L * topk + 63) / 64 * 64;
+    p.words = p.Tmax / 64;
+    p.sort_lds = L * C::seg(topk) * 4;
+    for (int l = 0; l < L; ++l) {
+        if (gh[l] < 1 || gw[l] < 1) return p;
+        const long long n = (long long)gh[l] * gw[l] * A * K;
+        const long long nch = (n + DECODE_CHUNK - 1) / DECODE_CHUNK;
+        if (n > 0x7FFFFFFFll) return p;
+        if (nch > C::merge_runs) p.decode = DECODE_ONE_MERGE;
+        p.chunk_first[l] = p.chunks;
+        p.chunks += (int)(nch < C::merge_runs ? nch : C::merge_runs);
+    }
+    p.chunk_first[L] = p.chunks;
+    if (p.decode == DECODE_CHUNKED && p.chunks > L * DECODE_RUNS_PER_LEVEL) p.decode = DECODE_ONE_ROOM;
+    if (p.decode == DECODE_CHUNKED && getenv("CVPCE_DECODE_ONE_KERNEL")) p.decode = DECODE_ONE_SWITCH;
+    // phase 1 on the first 8 x detections_per_img candidates (>= 1024), phase 2 on all of them for the images that need it
+    int limit = detections_per_img * 8;
+    limit = ((limit < 1024 ? 1024 : limit) + 63) / 64 * 64;
+    p.limit = (limit >= p.Tmax || getenv("CVPCE_NMS_ONE_PHASE")) ? 0 : limit;
+    p.launches = (p.decode == DECODE_CHUNKED ? 2 : 1) + 1 + (p.limit ? 4 : 2);
+    p.rc = CVPCE_OK;
+    return p;
+}
+
+// topk <= 1024: at most 8192 candidates per image (CAP 1024); topk <= 4096: at most 20 480 (CAP 4096)
+static DetectPlan detect_plan(const int* gh, const int* gw, int L, int N, int A, int K, int topk, int detections_per_img) {
+    return topk_capacity(topk) == 1024 ? detect_plan_at<1024>(gh, gw, L, N, A, K, topk, detections_per_img)
+                                       : detect_plan_at<4096>(gh, gw, L, N, A, K, topk, detections_per_img);
+}
+
+extern "C" int cvpce_detect_plan(const int* gh, const int* gw, int L, int N, int A, int K, int topk, int detections_per_img,
+                                 long long* out) {
+    if (!gh || !gw || !out) return CVPCE_ERR_ARG;
+    const DetectPlan p = detect_plan(gh, gw, L, N, A, K, topk, detections_per_img);
+    int i = 0;
+    for (long long v : {p.cap, p.decode == DECODE_CHUNKED ? 1 : 0, p.decode, p.chunks}) out[i++] = v;
+    for (int l = 0; l <= MAX_LEVELS; ++l) out[i++] = p.chunk_first[l];
+    for (long long v : {p.Tmax, p.words, p.sort_lds, p.limit, p.launches}) out[i++] = v;
+    out[i++] = (long long)p.ws.bytes;
+    for (int w = 0; w < WS_PARTS; ++w) out[i++] = (long long)p.ws.off[w];
+    static_assert(4 + MAX_LEVELS + 1 + 5 + 1 + WS_PARTS == CVPCE_DETECT_PLAN_FIELDS, "the field list of include/cvpce_amd.h");
+    return p.rc;
+}
+
+// the four to seven launches of one post-processing call at capacity CAP
+template <int CAP>
+static int launch_postprocess(const DetectPlan& p, const DecodeArgs& d, NmsArgs n, hipStream_t s) {
+    const int L = d.c.L, N = d.c.N;
+    if (p.decode == DECODE_CHUNKED) {
+        hipLaunchKernelGGL(decode_select_kernel<CAP>, dim3(p.chunks, N), dim3(1024), 0, s, d);
         hipLaunchKernelGGL(decode_merge_kernel<CAP>, dim3(L, N), dim3(1024), 0, s, d);
     } else {
         hipLaunchKernelGGL(decode_topk_kernel<CAP>, dim3(L, N), dim3(1024), 0, s, d);
     }
-    const size_t sort_lds = (size_t)L * (CAP == 1024 ? 1024 : d.topk) * 4;
-    if (sort_lds > 64 * 1024) {
-        // above 64 KiB of dynamic LDS the kernel's limit is raised once per process (gfx950: 160 KiB per CU); the first call of a
-        // geometry runs eagerly, so this never happens inside a graph capture
-        static bool raised = false;
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_sort_kernel<CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    SORT_CAP_WIDE * 4) != hipSuccess)
-                return CVPCE_ERR_LAUNCH;
-            raised = true;
-        }
+    // above 64 KiB of dynamic LDS the kernel's limit is raised (gfx950: 160 KiB per CU); the first call of a geometry runs eagerly,
+    // so this never happens inside a graph capture.  CAP 1024 holds L * 1024 keys, 32 KiB at the most.
+    if constexpr (Cap<CAP>::sort * 4 > 64 * 1024) {
+        if (p.sort_lds > 64 * 1024 &&
+            !cvpce_smem_attr_done<nms_sort_kernel<CAP>>((const void*)nms_sort_kernel<CAP>, Cap<CAP>::sort * 4))
+            return CVPCE_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(nms_sort_kernel<CAP>, dim3(N), dim3(1024), sort_lds, s, n);
-    const size_t Tmax = (size_t)n.Tmax, words = (size_t)n.words;
-    if (limit >= Tmax || getenv("CVPCE_NMS_ONE_PHASE")) {
-        n.limit = (int)Tmax; n.phase = 0;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
+    hipLaunchKernelGGL(nms_sort_kernel<CAP>, dim3(N), dim3(1024), p.sort_lds, s, n);
+    auto mask_scan = [&](int limit, int phase) {
+        const unsigned w = (unsigned)(limit / 64);
+        n.limit = limit; n.phase = phase;
+        hipLaunchKernelGGL(nms_mask_kernel, dim3(w, w, N), dim3(64), 0, s, n);
         hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
+    };
+    if (!p.limit) {
+        mask_scan(p.Tmax, 0);
     } else {
-        const unsigned w1 = (unsigned)(limit / 64);
-        n.limit = (int)limit; n.phase = 1;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3(w1, w1, N), dim3(64), 0, s, n);
-        hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
-        n.limit = (int)Tmax; n.phase = 2;
-        hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)words, (unsigned)words, N), dim3(64), 0, s, n);
-        hipLaunchKernelGGL(nms_scan_kernel<CAP>, dim3(N), dim3(1024), 0, s, n);
+        mask_scan(p.limit, 1);
+        mask_scan(p.Tmax, 2);
     }
     return cvpce_check_launch();
 }
@@ -841,79 +926,38 @@ extern "C" int cvpce_detect_postprocess(const float* const* logits, const float*
     if (!logits || !regs || !gh || !gw || !stride_h || !stride_w || !base_anchors || !image_hw || !ratios ||
         !workspace || !out_boxes || !out_scores || !out_labels || !out_count || !out_conf_count)
         return CVPCE_ERR_ARG;
-    // topk <= 1024: at most 8192 candidates per image (CAP 1024); topk <= 4096: at most 20 480 (CAP 4096)
-    const int cap = topk_capacity(topk);
-    if (L < 1 || L > MAX_LEVELS || A < 1 || K < 1 || topk < 1 || cap == 0 || detections_per_img < 1)
-        return CVPCE_ERR_ARG;
-    const size_t sort_cap = cap == 1024 ? SORT_CAP : SORT_CAP_WIDE;
-    if ((size_t)L * topk > sort_cap || (size_t)detections_per_img > sort_cap) return CVPCE_ERR_ARG;
-    if (N <= 0) return CVPCE_OK;
-    if (workspace_bytes < cvpce_detect_workspace_bytes(N, L, topk)) return CVPCE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t slot = (size_t)L * topk;
-    const size_t Tmax = (slot + 63) / 64 * 64, words = Tmax / 64;
-    char* p = (char*)workspace;
-    auto take = [&](size_t bytes) { char* q = p; p += (bytes + 255) / 256 * 256; return (void*)q; };
-    // mask first: keeps 8-byte alignment trivially
-    unsigned long long* mask = (unsigned long long*)take((size_t)N * Tmax * words * 8);
-    float* cand_boxes = (float*)take((size_t)N * slot * 16);
-    float* cand_scores = (float*)take((size_t)N * slot * 4);
-    float* cand_logits = (float*)take((size_t)N * slot * 4);
-    int* cand_labels = (int*)take((size_t)N * slot * 4);
-    int* cand_count = (int*)take((size_t)N * L * 4);
-    float* s_boxes = (float*)take((size_t)N * Tmax * 16);
-    float* s_scores = (float*)take((size_t)N * Tmax * 4);
-    int* s_labels = (int*)take((size_t)N * Tmax * 4);
-    float* s_off = (float*)take((size_t)N * Tmax * 4);
-    int* s_total = (int*)take((size_t)N * 4);
-    const size_t max_runs = (size_t)L * DECODE_RUNS_PER_LEVEL;          // per image
-    unsigned long long* runs = (unsigned long long*)take((size_t)N * max_runs * cap * 8);
-    int* done = (int*)take((size_t)N * 4);
-    if ((size_t)(p - (char*)workspace) > workspace_bytes) return CVPCE_ERR_ARG;
+    const DetectPlan p = detect_plan(gh, gw, L, N, A, K, topk, detections_per_img);
+    if (p.rc != CVPCE_OK || N <= 0) return p.rc;
+    if (workspace_bytes < p.ws.bytes) return CVPCE_ERR_ARG;
+    auto part = [&](int i) { return (void*)((char*)workspace + p.ws.off[i]); };
 
-    DecodeArgs d;
+    DecodeArgs d = {};
     for (int l = 0; l < L; ++l) {
-        if (!logits[l] || !regs[l] || gh[l] < 1 || gw[l] < 1) return CVPCE_ERR_ARG;
+        if (!logits[l] || !regs[l]) return CVPCE_ERR_ARG;
         d.logits[l] = logits[l]; d.regs[l] = regs[l];
         d.gh[l] = gh[l]; d.gw[l] = gw[l]; d.sh[l] = stride_h[l]; d.sw[l] = stride_w[l];
     }
-    d.base_anchors = base_anchors; d.image_hw = image_hw; d.L = L; d.N = N; d.A = A; d.K = K; d.topk = topk;
+    d.base_anchors = base_anchors; d.image_hw = image_hw; d.A = A; d.K = K;
     d.score_thresh = score_thresh; d.xform_clip = xform_clip;
-    d.cand_boxes = cand_boxes; d.cand_scores = cand_scores; d.cand_logits = cand_logits; d.cand_labels = cand_labels;
-    d.cand_count = cand_count;
-    // chunked form unless a level is too large for one merge workgroup (DECODE_MAX_RUNS runs of 1024, 8 runs of 4096) or the
-    // image's chunks exceed the workspace's runs
-    const int max_merge = DECODE_MAX_RUNS * 1024 / cap;
-    bool chunked = true;
-    int chunks = 0;
-    for (int l = 0; l < L; ++l) {
-        const long long n = (long long)gh[l] * gw[l] * A * K;
-        const long long nch = (n + DECODE_CHUNK - 1) / DECODE_CHUNK;
-        if (n > 0x7FFFFFFFll) return CVPCE_ERR_ARG;
-        if (nch > max_merge) chunked = false;
-        d.chunk_first[l] = chunks;
-        chunks += (int)(nch < max_merge ? nch : max_merge);
-    }
-    d.chunk_first[L] = chunks;
-    if ((size_t)chunks > max_runs) chunked = false;
-    d.runs = runs;
+    d.c = Candidates{(float*)part(WS_CAND_BOXES), (float*)part(WS_CAND_SCORES), (float*)part(WS_CAND_LOGITS),
+                     (int*)part(WS_CAND_LABELS), (int*)part(WS_CAND_COUNT), L, N, topk};
+    for (int l = 0; l <= L; ++l) d.chunk_first[l] = p.chunk_first[l];
+    d.runs = (unsigned long long*)part(WS_RUNS);
     d.t_lo = -INFINITY; d.t_hi = INFINITY;                             // (outside this band of thresholds: always the sigmoid)
     if (score_thresh >= 1e-6f && score_thresh <= 0.99f) {
         const double t = log((double)score_thresh / (1.0 - (double)score_thresh)), m = 1e-3 * (1.0 + fabs(t));
         d.t_lo = (float)(t - m); d.t_hi = (float)(t + m);
     }
 
-    NmsArgs n;
-    n.cand_boxes = cand_boxes; n.cand_scores = cand_scores; n.cand_logits = cand_logits; n.cand_labels = cand_labels;
-    n.cand_count = cand_count; n.L = L; n.N = N; n.topk = topk; n.Tmax = (int)Tmax; n.words = (int)words;
+    NmsArgs n = {};
+    n.c = d.c; n.Tmax = p.Tmax; n.words = p.words;
     n.nms_thresh = nms_thresh; n.conf_thresh = conf_thresh; n.max_keep = detections_per_img; n.ratios = ratios;
-    n.s_boxes = s_boxes; n.s_scores = s_scores; n.s_labels = s_labels; n.s_off = s_off; n.s_total = s_total;
-    n.mask = mask; n.out_boxes = out_boxes; n.out_scores = out_scores; n.out_labels = out_labels;
+    n.s_boxes = (float*)part(WS_S_BOXES); n.s_scores = (float*)part(WS_S_SCORES); n.s_labels = (int*)part(WS_S_LABELS);
+    n.s_off = (float*)part(WS_S_OFF); n.s_total = (int*)part(WS_S_TOTAL);
+    n.mask = (unsigned long long*)part(WS_MASK); n.out_boxes = out_boxes; n.out_scores = out_scores; n.out_labels = out_labels;
     n.out_count = out_count; n.out_conf_count = out_conf_count;
-    n.done = done;
-    // phase 1 on the first 8 x detections_per_img candidates (>= 1024), phase 2 on all of them for the images that need it
-    size_t limit = (size_t)detections_per_img * 8;
-    limit = ((limit < 1024 ? 1024 : limit) + 63) / 64 * 64;
-    if (cap == 1024) return launch_postprocess<1024>(d, n, chunked, chunks, limit, s);
-    return launch_postprocess<TOPK_CAP_WIDE>(d, n, chunked, chunks, limit, s);
+    n.done = (int*)part(WS_DONE);
+    hipStream_t s = (hipStream_t)stream;
+    return p.cap == 1024 ? launch_postprocess<1024>(p, d, n, s) : launch_postprocess<4096>(p, d, n, s);
 }
+

@@ -319,9 +319,22 @@ int cvpce_conv3x3_halo_list(const void* in, const void* wgt, const float* bias, 
  * base_anchors f32 [L][A][4]; image_hw int [N][2] resized sizes; ratios f32 [N][2] (orig/resized h,w).
  * Outputs: boxes [N][dpi][4] (original pixels), scores [N][dpi], labels i64 [N][dpi], count [N],
  * conf_count [N] = #scores > conf_thresh.  The workspace (cvpce_detect_workspace_bytes: candidates, sorted candidates,
- * the IoU bit matrix, N * L * 12 chunk runs of 8 KiB for the chunked top-k) is scratch: nothing is kept across calls.
+ * the IoU bit matrix, N * L * 12 chunk runs for the chunked top-k, of 8 KiB for topk <= 1024 and 32 KiB above) is scratch:
+ * nothing is kept across calls.
  * Ordering: by fp32 logit (a monotone refinement of the score order), then the lower index (csrc/detect.hip). */
 size_t cvpce_detect_workspace_bytes(int N, int L, int topk);
+/* Host only, like the workspace query: the launches cvpce_detect_postprocess would make for these integers (with a workspace of
+ * cvpce_detect_workspace_bytes and valid pointers), under the environment switches CVPCE_DECODE_ONE_KERNEL and
+ * CVPCE_NMS_ONE_PHASE as they stand at the call.  Returns what cvpce_detect_postprocess would return for them (CVPCE_ERR_ARG:
+ * rejected) and fills out[CVPCE_DETECT_PLAN_FIELDS] = { capacity (1024 | 4096), chunked (1: decode_select + decode_merge, 0: the
+ * one-kernel decode), why not chunked (0 chunked, 1 a level has more chunks than one merge workgroup holds, 2 the image's chunks
+ * exceed the workspace's runs, 3 the switch), chunks per image, chunk_first[0 .. 8] (first chunk of each level, [L] = chunks; 0
+ * beyond), Tmax (candidates per image rounded up to 64), words (Tmax / 64), dynamic LDS bytes of nms_sort, candidates of NMS phase
+ * 1 (0: NMS runs in one phase), launches, workspace bytes, byte offset of each of the 13 sub-allocations in carve order (mask,
+ * candidate boxes, scores, logits, labels, counts, sorted boxes, scores, labels, class offsets, totals, chunk runs, done flags) }. */
+#define CVPCE_DETECT_PLAN_FIELDS 32
+int cvpce_detect_plan(const int* gh, const int* gw, int L, int N, int A, int K, int topk, int detections_per_img,
+                      long long* out);
 int cvpce_detect_postprocess(const float* const* logits, const float* const* regs, const int* gh, const int* gw,
                              const int* stride_h, const int* stride_w, const float* base_anchors,
                              const int* image_hw, const float* ratios, int L, int N, int A, int K, int topk,

@@ -50,8 +50,15 @@ def test_postprocess_parity_at_the_wide_capacity(cuda, geom, topk, dpi, k, seed,
     from cvpce_amd import ops
     from cvpce_amd.models import proposals as P
     from oracle import gln as og
+    import detect_plan as dp
     padded, grids, resized, original = geom
     n = 2
+    rc, plan = dp.query(grids, n, 9, k, topk, dpi)
+    assert rc == 0 and plan['cap'] == 4096
+    if (geom, topk, k) == (SMALL, 1500, 1):      # chunked decode at the wide capacity, P3 of 46 080 logits in 6 chunks
+        assert (plan['chunked'], plan['chunk_first1']) == (1, 6)
+    if (geom, topk, k) == (SMALL, 4096, 2):      # P3 of 92 160 logits: 12 chunks, one merge workgroup holds 8 runs of 4096
+        assert (plan['chunked'], plan['why'], plan['chunk_first1']) == (0, dp.MERGE_LIMIT, 8)
     cls, reg = _random_head_outputs(n, grids, 9, k, seed, bias=bias, quantum=quantum)
     anchors = og.grid_anchors(padded, grids)
     strides = [(padded[0] // gh, padded[1] // gw) for gh, gw in grids]

@@ -244,9 +244,12 @@ def test_detect_postprocess_parity(cuda, dpi, seed, bias, k, quantum, monkeypatc
     from cvpce_amd import ops
     from cvpce_amd.models import proposals as P
     from oracle import gln as og
+    import detect_plan as dp
     n = 2
     padded = (800, 832)
     grids = [(100, 104), (50, 52), (25, 26), (13, 13), (7, 7)]
+    rc, plan = dp.query(grids, n, 9, k, og.TOPK_CANDIDATES, dpi)
+    assert rc == 0 and (plan['chunked'], plan['why']) == ((0, dp.MERGE_LIMIT) if k == 3 else (1, dp.CHUNKED))
     cls, reg = _random_head_outputs(n, grids, 9, k, seed, bias=bias, quantum=quantum)
     resized = [(800, 810), (790, 832)]
     original = [(2048, 2073), (1000, 1053)]
@@ -279,6 +282,35 @@ def test_detect_postprocess_parity(cuda, dpi, seed, bias, k, quantum, monkeypatc
         ratios.to(cuda), 9, k, og.TOPK_CANDIDATES, og.SCORE_THRESH, og.NMS_THRESH, og.BBOX_XFORM_CLIP, dpi, 0.5)
     for x, y in zip(one, (boxes, scores, labels, count, conf)):
         assert torch.equal(x, y)
+
+
+def test_detect_postprocess_without_room_for_the_runs(cuda, monkeypatch):
+    """One level of 110 x 110 x 9 = 108 900 logits is 14 chunks: one merge workgroup would hold them (32), the workspace's 12 runs per
+    level do not, so the call takes the one-kernel decode without the switch (asserted through the plan) -- and equals the oracle."""
+    from cvpce_amd import ops
+    from cvpce_amd.models import proposals as P
+    from oracle import gln as og
+    import detect_plan as dp
+    monkeypatch.delenv('CVPCE_DECODE_ONE_KERNEL', raising=False)
+    dpi, padded, grids, resized, original = 300, (880, 880), [(110, 110)], (880, 870), (1760, 1751)
+    rc, plan = dp.query(grids, 1, 9, 1, og.TOPK_CANDIDATES, dpi)
+    assert rc == 0 and (plan['chunks'], plan['chunked'], plan['why']) == (14, 0, dp.WORKSPACE_ROOM)
+    cls, reg = _random_head_outputs(1, grids, 9, 1, 11, quantum=0.25)
+    ratios = (torch.tensor(original, dtype=torch.float32) / torch.tensor(resized, dtype=torch.float32)).view(1, 2)
+    boxes, scores, labels, count, conf = ops.detect_postprocess(
+        [cls[0].to(cuda)], [reg[0].to(cuda)], grids, [(8, 8)], P._base_anchors()[:1].contiguous().to(cuda),
+        torch.tensor([resized], dtype=torch.int32).to(cuda), ratios.to(cuda), 9, 1, og.TOPK_CANDIDATES, og.SCORE_THRESH, og.NMS_THRESH,
+        og.BBOX_XFORM_CLIP, dpi, 0.5)
+    torch.cuda.synchronize()
+    b, s, l = og.postprocess_image([cls[0][0].view(-1, 1)], [reg[0][0]], og.grid_anchors(padded, grids), resized, dpi)
+    b = og.resize_boxes(b, resized, original)
+    c = int(count[0])
+    assert c == len(b) and c > 0, (c, len(b))
+    torch.testing.assert_close(scores[0, :c].cpu(), s, rtol=0, atol=1e-6)
+    torch.testing.assert_close(boxes[0, :c].cpu(), b, rtol=1e-5, atol=2e-3)
+    assert torch.equal(labels[0, :c].cpu(), l)
+    assert int(conf[0]) == int((s > 0.5).sum())
+    assert (scores[0, :c - 1] >= scores[0, 1:c]).all()
 
 
 def test_detect_score_threshold_band(cuda, monkeypatch):
