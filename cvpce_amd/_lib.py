@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h, the
-8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and the
-thin-strip launch of include/cvpce_amd_lists.h).
+8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
+include/cvpce_amd_homography.h and the thin-strip launch of include/cvpce_amd_lists.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -111,12 +111,20 @@ PLANOGRAM_SIGNATURES = {
     'cvpce_planogram_match': (c_int, [_ip] * 11 + [c_int] * 6 + [c_longlong, _vp, c_size_t, _ip, _ip, _vp]),
 }
 
+# include/cvpce_amd_homography.h: the comparator's tail (homography, projection, claim).  A table of its own, like the header.
+HOMOGRAPHY_SIGNATURES = {
+    'cvpce_homography_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'cvpce_homography_ransac': (c_int, [_fp, _ip, _fp, _ip, _ip, _ip, _ip, _vp] + [c_int] * 5 + [ctypes.c_uint, c_int, _vp, c_size_t, _vp]),
+    'cvpce_homography_finish': (c_int, [_fp, _ip, _ip, _fp, _ip, _ip, _ip, _ip, _ip, _vp] + [c_int] * 7 + [ctypes.c_uint, c_int, _vp, c_size_t,
+                                        _ip, _vp, _ip, _ip, _ip, _ip, _ip, _fp, _vp]),
+}
+
 # include/cvpce_amd_lists.h: the thin-strip companion of the work-list launches.  A table of its own, like the header.
 LISTS_SIGNATURES = {
     'cvpce_conv3x3_halo_strips2': SIGNATURES['cvpce_conv3x3_halo_strips'],
 }
 
-for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, LISTS_SIGNATURES):
+for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -82,7 +82,9 @@ class _DeviceMetricsCommand(click.Command):
     def format_options(self, ctx, formatter):
         super().format_options(ctx, formatter)
         with formatter.section('Options beyond the reference\'s'):
-            formatter.write_dl([(self.LABEL, self.HELP)])
+            formatter.write_dl([(self.LABEL, self.HELP)] + list(self.MORE))
+
+    MORE = ()                                    # further (label, help) rows of a subclass with a second switch
 
 
 def _device_metrics_switch():
@@ -100,6 +102,37 @@ class _DeviceGraphsCommand(_DeviceMetricsCommand):
 
 def _device_graphs_switch():
     return bool(click.get_current_context().meta.get(_DeviceGraphsCommand.KEY, False))
+
+
+class _DeviceTailCommand(_DeviceGraphsCommand):
+    """--device-graphs as above, and --device-tail / --no-device-tail (default: off) beside it, arranged the same way."""
+    TAIL_SWITCH = {'--device-tail': True, '--no-device-tail': False}
+    TAIL_HELP = ('Also run the homography, the projection and the per-label claim on the GPU (cvpce_amd.planograms_device.finalize_batch; '
+                 'the documented tail rule).  Needs --device-graphs: without it the command stops with an error.  [default: off]')
+    TAIL_KEY = 'cvpce_amd.device_tail'
+    TAIL_LABEL = '--device-tail / --no-device-tail'
+
+    def parse_args(self, ctx, args):
+        rest = []
+        ctx.meta[self.TAIL_KEY] = False
+        for i, a in enumerate(args):
+            if a == '--':
+                rest += args[i:]
+                break
+            if a in self.TAIL_SWITCH:
+                ctx.meta[self.TAIL_KEY] = self.TAIL_SWITCH[a]
+            else:
+                rest.append(a)
+        graphs = [self.SWITCH[a] for a in (rest[:rest.index('--')] if '--' in rest else rest) if a in self.SWITCH]
+        if ctx.meta[self.TAIL_KEY] and not (graphs and graphs[-1]) and not ctx.resilient_parsing:
+            raise click.UsageError('--device-tail needs --device-graphs', ctx)          # (it implies nothing on its own)
+        return super().parse_args(ctx, rest)
+
+    MORE = ((TAIL_LABEL, TAIL_HELP),)
+
+
+def _device_tail_switch():
+    return bool(click.get_current_context().meta.get(_DeviceTailCommand.TAIL_KEY, False))
 
 
 @click.group()
@@ -279,7 +312,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command(cls=_DeviceGraphsCommand)
+@cli.command(cls=_DeviceTailCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -306,7 +339,8 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     proposal_generator.requires_grad_(False)
     generator = production.ProposalGenerator(proposal_generator)
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
-    evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch()))
+    evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
+                                                                                              device_tail=_device_tail_switch()))
     total_a = total_e = 0.0
     # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
     # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,

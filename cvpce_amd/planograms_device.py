@@ -3,6 +3,10 @@
 
   build_graphs       8-direction nearest-neighbour graphs of a batch of box sets: one launch (csrc/planogram.hip)
   common_subgraphs   hypothesis-seeded common subgraph of a batch of (expected, actual) graph pairs: one launch, one copy back
+  match_on_device    the same launch without the copy back: the matchings stay on the device for `finalize_batch`
+  finalize_batch     RANSAC homography, refit, projection and per-label claim of a batch (csrc/homography.hip): two launches, one
+                     copy back -- the opt-in counterpart of `planograms.finalize_via_ransac` (the tail rule of DESIGN.md 4b)
+  finalize_result    a record of `finalize_batch` as the tuple `finalize_via_ransac` returns
   to_networkx        a device graph as the DiGraph the host functions expect (node order 0..n-1, adjacency in stamp order)
   prepare            caches a planogram's device graph in its dict, as `expected['graph']` caches the host graph
 
@@ -24,11 +28,13 @@ from collections import Counter
 import networkx as nx
 import torch
 
-from . import torch_ops_planogram  # noqa: F401  (registers torch.ops.cvpce_amd.planogram_*)
+from . import torch_ops_homography, torch_ops_planogram  # noqa: F401  (register torch.ops.cvpce_amd.planogram_* / homography_*)
 from .planograms import CARDINALS
 from .torch_ops_planogram import MAX_NODES
 
 CACHE_KEY = 'device_graph'
+RANSAC_HYPOTHESES = 2048          # per image, all evaluated (the host's adaptive loop stops at 2000 at the latest)
+STATUS = ('ok', 'none', 'invalid')
 
 
 class Graph:
@@ -150,8 +156,8 @@ def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
         raise ValueError('one actual graph per expected graph')
     if not expected:
         return []
-    args, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction)
-    torch.ops.cvpce_amd.planogram_match(*args)
+    matching = match_on_device(expected, actual, min_score, stop_at_fraction)
+    out, out_off = matching.out, matching.rows
     host = torch.empty(out.shape, dtype=torch.int32).pin_memory()
     host.copy_(out, non_blocking=True)
     torch.cuda.current_stream(out.device).synchronize()
@@ -164,6 +170,105 @@ def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
             grown.add((host[o + 2 * k], host[o + 2 * k + 1]))
         res.append(grown)
     return res
+
+
+class DeviceMatching:
+    """The matchings of a batch as the match kernel left them on the device: `pairs` [rows][2], `count` [P], `out_off` [P+1] (int32,
+    views of `out` = pairs then counts), the label-id tables `label1` / `label2` with their offsets `off1` / `off2`, and on the host
+    the node counts `n1` / `n2` and the row offsets `rows`."""
+    __slots__ = ('pairs', 'count', 'out_off', 'out', 'label1', 'off1', 'label2', 'off2', 'n1', 'n2', 'rows')
+
+
+def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
+    """The launch of `common_subgraphs` alone -> `DeviceMatching`; nothing is copied back and nothing is waited for."""
+    if len(expected) != len(actual) or not expected:
+        raise ValueError('one actual graph per expected graph, at least one pair')
+    args, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction)
+    torch.ops.cvpce_amd.planogram_match(*args)
+    m = DeviceMatching()
+    m.label1, m.off1, m.label2, m.off2, m.out_off, m.pairs, m.count = args[2], args[3], args[6], args[7], args[10], args[15], args[16]
+    m.out, m.rows, m.n1, m.n2 = out, out_off, [len(g) for g in expected], [len(g) for g in actual]
+    return m
+
+
+def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses):
+    """Everything the two tail launches need, uploaded -> (arguments of homography_ransac, of homography_finish, the output blob,
+    its layout).  Every output lies in ONE allocation -- positions (f32), H (f64), then the int32 fields status, winner, winner count,
+    final count, matching size, matched_expected, matched_actual -- so that one copy brings it back."""
+    b = len(matching.n1)
+    if not (b == len(expected_boxes) == len(actual_boxes) == len(reproj_thresholds)) or not b:
+        raise ValueError('one entry per image, at least one image')
+    if not 1 <= hypotheses <= torch_ops_homography.MAX_HYPOTHESES:
+        raise ValueError(f'between 1 and {torch_ops_homography.MAX_HYPOTHESES} hypotheses, got {hypotheses}')
+    device = matching.pairs.device
+    n1, n2 = matching.n1, matching.n2
+    for boxes, n in zip(list(expected_boxes) + list(actual_boxes), n1 + n2):
+        if boxes.dim() != 2 or boxes.shape[0] != n or boxes.shape[1] != 4:
+            raise ValueError('the boxes of the graphs that were matched, (n, 4) each')
+    sum1, sum2 = sum(n1), sum(n2)
+    host = torch.cat([bx.detach().to(device='cpu', dtype=torch.float32) for bx in list(expected_boxes) + list(actual_boxes)]).contiguous()
+    boxes = _upload(host, device)
+    params = _upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
+    workspace = torch.empty(max(torch_ops_homography.workspace_bytes(b, hypotheses), 8) // 4, dtype=torch.int32, device=device)
+    at_h, at_i = 16 * sum1, 16 * sum1 + 72 * b
+    blob = torch.empty(at_i + 4 * (5 * b + sum1 + sum2), dtype=torch.uint8, device=device)
+    pos, hmat, i32 = blob[:at_h].view(torch.float32).view(sum1, 4), blob[at_h:at_i].view(torch.float64), blob[at_i:].view(torch.int32)
+    status, winner, wcount, fcount = (i32[k * b:(k + 1) * b] for k in range(4))
+    me, ma = i32[5 * b:5 * b + sum1], i32[5 * b + sum1:]
+    max_pairs = max(1, max(min(a, c) for a, c in zip(n1, n2)))
+    common = (matching.pairs, matching.count, matching.out_off, params)
+    ransac = (boxes[:sum1], matching.off1, boxes[sum1:], matching.off2, *common, max_pairs, seed, hypotheses, workspace)
+    finish = (boxes[:sum1], matching.label1, matching.off1, boxes[sum1:], matching.label2, matching.off2, *common, max(n1), max(n2), max_pairs,
+              seed, hypotheses, workspace, status, hmat, winner, wcount, fcount, me, ma, pos)
+    return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b])
+
+
+def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold=0.5, seed=0,
+                   hypotheses=RANSAC_HYPOTHESES):
+    """`planograms.finalize_via_ransac` for every image of a batch under the tail rule: two launches on the matchings
+    as they lie on the device (`match_on_device`) and ONE pinned copy back.  expected / actual: the lists of `Graph` the matching was
+    made from; expected_boxes / actual_boxes: their (n, 4) boxes; reproj_thresholds: one per image, in pixels.
+    -> one record per image: {'status': 'ok' | 'none' | 'invalid', 'matched_expected', 'matched_actual' (bool), 'expected_positions'
+    (float32 (n1, 4)), 'homography' (3 x 3 float64, None unless ok), 'inliers' (of the refit), 'points', 'matching' (its size),
+    'winner', 'winner_inliers'}."""
+    if not len(expected) == len(actual) == len(matching.n1) or [len(g) for g in expected] != matching.n1 or [len(g) for g in actual] != matching.n2:
+        raise ValueError('the graphs the matching was made from')
+    ransac, finish, blob, (at_h, at_i, size) = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses)
+    torch.ops.cvpce_amd.homography_ransac(*ransac)
+    torch.ops.cvpce_amd.homography_finish(*finish)
+    size.copy_(matching.count)                                     # (the matching's size travels in the same copy)
+    b, n1, n2 = len(expected), matching.n1, matching.n2
+    sum1 = sum(n1)
+    back = torch.empty(blob.shape, dtype=torch.uint8).pin_memory()
+    back.copy_(blob, non_blocking=True)
+    torch.cuda.current_stream(blob.device).synchronize()
+    pos, hmat, i32 = back[:at_h].view(torch.float32).view(sum1, 4), back[at_h:at_i].view(torch.float64).view(b, 3, 3), back[at_i:].view(torch.int32)
+    head = i32[:5 * b].view(5, b).tolist()
+    me, ma = i32[5 * b:5 * b + sum1] != 0, i32[5 * b + sum1:] != 0
+    off1, off2 = _offsets(n1), _offsets(n2)
+    records = []
+    for p in range(b):
+        ok = head[0][p] == torch_ops_homography.OK
+        m = head[4][p]
+        records.append({'status': STATUS[head[0][p]], 'matched_expected': me[off1[p]:off1[p + 1]].clone(), 'matched_actual': ma[off2[p]:off2[p + 1]].clone(),
+                        'expected_positions': pos[off1[p]:off1[p + 1]].clone(), 'homography': hmat[p].clone() if ok else None,
+                        'inliers': head[3][p], 'points': 5 if m == 1 else 3 * m, 'matching': m, 'winner': head[1][p], 'winner_inliers': head[2][p]})
+    return records
+
+
+def finalize_result(record, expected_labels, return_matched_actual=False, report_accuracy=False, return_expected_positions=False):
+    """A record of `finalize_batch` as the tuple `planograms.finalize_via_ransac` returns for the same flags (all None without a
+    homography).  An 'invalid' record -- a matching that is not one of its graphs -- is an error."""
+    if record['status'] == 'invalid':
+        raise RuntimeError('finalize_batch: the matching does not belong to the graphs')
+    if report_accuracy:
+        print(f"Homography accuracy: {record['inliers'] / max(record['points'], 1)}")
+    if record['status'] != 'ok':
+        return (None,) * 5 if return_matched_actual else (None,) * 4          # (the host's own lengths)
+    matched_expected, positions = record['matched_expected'], record['expected_positions']
+    missing_expected = torch.where(~matched_expected)[0]
+    out = (matched_expected,) + ((record['matched_actual'],) if return_matched_actual else ()) + ((positions,) if return_expected_positions else ())
+    return out + (missing_expected, positions[missing_expected], [expected_labels[i] for i in missing_expected.tolist()])
 
 
 def to_networkx(graph):

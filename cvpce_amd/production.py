@@ -237,12 +237,18 @@ class PlanogramComparator:
     """production.py:76-116: graph matching -> RANSAC homography -> per-label IoU matching -> optional re-classification
     of the expected-but-undetected positions (a second trip through the crop / embed / match kernels)."""
 
-    def __init__(self, graph_threshold=0.5, device_graphs=False):
+    def __init__(self, graph_threshold=0.5, device_graphs=False, device_tail=False):
         """device_graphs (opt-in): the neighbour graphs and the common subgraph come from the kernels of `planograms_device` (its
         documented rule at equal distances); the homography and everything after it stay the host's.  `host_routed`
-        counts the images that took the host path with the switch on (a graph of more than 1024 nodes)."""
+        counts the images that took the host path with the switch on (a graph of more than 1024 nodes).
+        device_tail (opt-in, needs device_graphs): the homography, the projection and the per-label claim run on the device too
+        (`planograms_device.finalize_batch`, the tail rule of DESIGN.md 4b): a window's graphs, matchings and tails are launched back
+        to back and one copy brings back what the verdict needs; the re-classification stays where it is."""
+        if device_tail and not device_graphs:
+            raise ValueError('device_tail needs device_graphs: the tail kernels read the matching where the match kernel left it')
         self.graph_threshold = graph_threshold
         self.device_graphs = device_graphs
+        self.device_tail = device_tail
         self.host_routed = 0
 
     def compare(self, expected, actual, image=None, classifier=None):
@@ -261,8 +267,9 @@ class PlanogramComparator:
 
     def compare_batch(self, expecteds, actuals, images=None, classifier=None):
         """[compare(e, a, img, classifier) for ...] with the graph stages of the whole batch in two launches (all graphs, all matchings)
-        and one copy back; the host tail (homography, per-label claim, re-classification) runs per image.  With `device_graphs` off it
-        is the plain loop."""
+        and one copy back; the host tail (homography, per-label claim, re-classification) runs per image -- with `device_tail` the
+        homography and the claim are two more launches of the window and only the re-classification stays per image.  With
+        `device_graphs` off it is the plain loop."""
         images = [None] * len(expecteds) if images is None else images
         if not self.device_graphs:
             return [self._compare_host(e, a, img, classifier) for e, a, img in zip(expecteds, actuals, images)]
@@ -282,21 +289,35 @@ class PlanogramComparator:
             built = pd.build_graphs([(g['boxes'], g['labels']) for g in build], self.graph_threshold)
             fresh = iter(built[:len(build) - len(todo)])
             ge = [have[i] if have[i] is not None else next(fresh) for i in todo]
-            matchings = pd.common_subgraphs(ge, built[len(build) - len(todo):])
+            ga = built[len(build) - len(todo):]
+            if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
+                records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [expecteds[i]['boxes'] for i in todo],
+                                            [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo])
+                for i, rec in zip(todo, records):
+                    tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
+                    results[i] = self._finish(rec['matching'], expecteds[i], actuals[i], images[i], classifier, tail)
+                return results
+            matchings = pd.common_subgraphs(ge, ga)
             for i, matching in zip(todo, matchings):
                 results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
         return results
 
-    def _finish(self, matching, expected, actual, image, classifier):
+    @staticmethod
+    def _reproj_threshold(image):
+        return 10 if image is None else min(datautils.image_hw(image)) * 0.01
+
+    def _finish(self, matching, expected, actual, image, classifier, tail=None):
+        """matching: the common subgraph, or its size where `tail` -- `finalize_via_ransac`'s tuple, computed elsewhere -- comes along."""
         from . import planograms
-        reproj_threshold = 10 if image is None else min(datautils.image_hw(image)) * 0.01
-        if not len(matching):
+        size = matching if isinstance(matching, int) else len(matching)
+        if not size:
             return 0
-        found, missing_indices, missing_positions, missing_labels = planograms.finalize_via_ransac(
-            matching, expected['boxes'], actual['boxes'], expected['labels'], actual['labels'],
-            reproj_threshold=reproj_threshold)
+        if tail is None:
+            tail = planograms.finalize_via_ransac(matching, expected['boxes'], actual['boxes'], expected['labels'], actual['labels'],
+                                                  reproj_threshold=self._reproj_threshold(image))
+        found, missing_indices, missing_positions, missing_labels = tail
         if found is None:                       # no homography (production.py:98-99)
-            return len(matching) / len(expected['boxes'])
+            return size / len(expected['boxes'])
         if classifier is not None and image is not None and len(missing_positions):
             h, w = datautils.image_hw(image)
             pos = missing_positions.clone()

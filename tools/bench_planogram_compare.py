@@ -7,12 +7,16 @@ Scenes: gridded planograms of 24 (4 x 6) and 200 (8 x 25) boxes (synthetic.plano
   device_graphs   the one launch that builds the 16 graphs of a batch, HIP events, median of --launches
   device_match    the one launch that matches the 8 pairs, HIP events
   device_e2e      PlanogramComparator(device_graphs=True).compare_batch without its host tail: uploads, both launches, the copy back
-  host_tail       finalize_via_ransac on the device matching (what stays on the host)
+  host_tail       finalize_via_ransac on the device matching (what stays on the host without `device_tail`)
+  device_tail_launches   the two launches of planograms_device.finalize_batch (RANSAC scoring, then winner / refit / projection / claim)
+                  on the 8 matchings as they lie on the device, HIP events
+  device_e2e_tail PlanogramComparator(device_graphs=True, device_tail=True).compare_batch: uploads, the four launches, the one copy
+                  back and the verdict, wall clock.  Its yardstick in the same run is host_tail + device_e2e
   evaluate_iter   images/s of PlanogramEvaluator.evaluate_iter with the real comparator, switch off and on, in this one call: the
                   detector / embedder / matcher run on synthetic shelf images as in bench.py and the comparator is handed the scene's
-                  detections (the synthetic detector's own boxes are noise)
+                  detections (the synthetic detector's own boxes are noise); `tail`: both switches on
 
-    python tools/bench_planogram_compare.py [--batch 8] [--launches 30] [--markdown profiles/r14_planogram_graphs.md]
+    python tools/bench_planogram_compare.py [--batch 8] [--launches 30] [--markdown profiles/r23_planogram_tail.md]
 """
 import argparse
 import json
@@ -100,8 +104,22 @@ def time_device(pairs, launches):
         if m:
             planograms.finalize_via_ransac(m, e['boxes'], a['boxes'], e['labels'], a['labels'], reproj_threshold=10)
     tail = time.perf_counter() - t0
+    on_device = pd.match_on_device(graphs[:n], graphs[n:])
+    ransac, finish, _, _ = pd._prepare_tail(on_device, [e['boxes'] for e, _ in pairs], [a['boxes'] for _, a in pairs], [10] * n, 0.5, 0,
+                                            pd.RANSAC_HYPOTHESES)
+    t_ms = events(lambda: (torch.ops.cvpce_amd.homography_ransac(*ransac), torch.ops.cvpce_amd.homography_finish(*finish)), launches)
+    cmp = production.PlanogramComparator(device_graphs=True, device_tail=True)
+    e2e_tail, verdicts = [], None
+    for r in range(6):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        verdicts = cmp.compare_batch([e for e, _ in pairs], [a for _, a in pairs])
+        if r:
+            e2e_tail.append(time.perf_counter() - t0)
+    host_verdicts = production.PlanogramComparator(device_graphs=True).compare_batch([e for e, _ in pairs], [a for _, a in pairs])
     return {'device_graphs_launch': g_ms / n, 'device_match_launch': m_ms / n, 'device_e2e': 1e3 * statistics.median(e2e) / n,
-            'host_tail': 1e3 * tail / n}, matchings
+            'host_tail': 1e3 * tail / n, 'device_tail_launches': t_ms / n, 'device_e2e_tail': 1e3 * statistics.median(e2e_tail) / n,
+            'same_verdict_tail': sum(float(a) == float(b) for a, b in zip(verdicts, host_verdicts))}, matchings
 
 
 class PlantedEvaluator(production.PlanogramEvaluator):
@@ -143,7 +161,8 @@ def main():
                                 match_dtype=torch.bfloat16)
     pg = production.ProposalGenerator(det, device=dev, confidence_threshold=0.5)
     evaluators = {'off': PlantedEvaluator(pg, clf, production.PlanogramComparator()),
-                  'on': PlantedEvaluator(pg, clf, production.PlanogramComparator(device_graphs=True))}
+                  'on': PlantedEvaluator(pg, clf, production.PlanogramComparator(device_graphs=True)),
+                  'tail': PlantedEvaluator(pg, clf, production.PlanogramComparator(device_graphs=True, device_tail=True))}
     images = [synthetic.shelf_image(300 + k, 1024, 1024).to(dev) for k in range(args.batch)]
     rows = []
     for name, (r, c) in (('24 boxes (4 x 6)', (4, 6)), ('200 boxes (8 x 25)', (8, 25))):
@@ -153,25 +172,31 @@ def main():
         it = time_evaluate_iter(pairs, images, evaluators)
         row = {'scene': name, 'batch': args.batch, **host, **device,
                'host_graph_stages': host['host_build_graph_x2'] + host['host_common_subgraph'],
-               'evaluate_iter_off_img_s': it['off'][0], 'evaluate_iter_on_img_s': it['on'][0],
+               'evaluate_iter_off_img_s': it['off'][0], 'evaluate_iter_on_img_s': it['on'][0], 'evaluate_iter_tail_img_s': it['tail'][0],
+               'same_verdict_iter_tail': sum(a == b for a, b in zip(it['on'][1], it['tail'][1])),
                'same_matching_size': sum(len(a) == len(b) for a, b in zip(host_m, dev_m)),
                'same_verdict': sum(a == b for a, b in zip(it['off'][1], it['on'][1]))}
         row['speedup_graph_stages'] = row['host_graph_stages'] / row['device_e2e']
+        row['tail_yardstick'] = row['host_tail'] + row['device_e2e']
         rows.append(row)
         print(json.dumps(row), flush=True)
     if args.markdown:
         cols = ['host_build_graph_x2', 'host_common_subgraph', 'host_ransac_tail', 'device_graphs_launch', 'device_match_launch', 'device_e2e',
-                'host_tail', 'evaluate_iter_off_img_s', 'evaluate_iter_on_img_s']
+                'host_tail', 'device_tail_launches', 'device_e2e_tail', 'evaluate_iter_off_img_s', 'evaluate_iter_on_img_s', 'evaluate_iter_tail_img_s']
         with open(args.markdown, 'w') as f:
-            f.write('# Planogram comparator: graph stages on the device against the host path\n\n'
+            f.write('# Planogram comparator: graph stages and tail on the device against the host path\n\n'
                     f'`python tools/bench_planogram_compare.py --batch {args.batch} --launches {args.launches}`, one process, MI355X; ms per image '
-                    'unless the column says images/s.  Host columns: the parent commit\'s path (the switch off).  Grids are full of exact ties, '
+                    'unless the column says images/s.  Host columns: the path with every switch off.  Grids are full of exact ties, '
                     'so the device graphs follow the device rule (DESIGN.md 4b) there: `same verdict` counts the images of the batch whose '
-                    'verdict is the host\'s all the same.\n\n')
-            f.write('| scene | ' + ' | '.join(cols) + ' | graph stages host / device | same verdict |\n|---|' + '---|' * (len(cols) + 2) + '\n')
+                    'verdict is the host\'s all the same.  `device_e2e_tail` (graphs, matching and tail on the device, one copy back) is to be '
+                    'read against `host_tail + device_e2e` of the same run; `tail verdicts` counts the images whose verdict with the device '
+                    'tail equals the verdict with the device graphs and the host tail (compare_batch / evaluate_iter).\n\n')
+            f.write('| scene | ' + ' | '.join(cols) + ' | graph stages host / device | same verdict | host_tail + device_e2e | tail verdicts |\n|---|'
+                    + '---|' * (len(cols) + 4) + '\n')
             for row in rows:
                 f.write(f"| {row['scene']} | " + ' | '.join(f'{row[c]:.4g}' for c in cols) +
-                        f" | {row['speedup_graph_stages']:.1f}x | {row['same_verdict']}/{row['batch']} |\n")
+                        f" | {row['speedup_graph_stages']:.1f}x | {row['same_verdict']}/{row['batch']} | {row['tail_yardstick']:.4g} | "
+                        f"{row['same_verdict_tail']}/{row['batch']} / {row['same_verdict_iter_tail']}/{row['batch']} |\n")
     return 0
 
 
