@@ -246,7 +246,7 @@ def dihe_eval(img_dir, test_imgs, annotations, model, resnet_layers, batch_norm,
         encoder = classification.macresnet_encoder(pretrained=False, desc_layers=list(resnet_layers)).cuda()
     encoder.load_state_dict(torch.load(enc_weights, map_location='cpu')[EMBEDDER_STATE_DICT_KEY])
     encoder.eval().requires_grad_(False)
-    sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True)
+    sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8')
     only_list = skip_list = None
     if only == 'test':
         skip_list = GP_TEST_VALIDATION_SET_SIZE
@@ -270,8 +270,8 @@ def prebuild_index(img_dir, datatype, out_dir, dihe_state):
 
     Passes all the images in the training set through the encoder and saves the resulting embedding vectors
     (classifier_index.pkl, usable with --load-classifier-index)."""
-    sampleset = (datautils.GroceryProductsDataset(img_dir, include_annotations=True) if datatype == 'gp'
-                 else datautils.InternalTrainSet(img_dir[0], include_annotations=True))
+    sampleset = (datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8') if datatype == 'gp'
+                 else datautils.InternalTrainSet(img_dir[0], include_annotations=True, image_format='uint8'))
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, verbose=True)
     classifier.save_index(os.path.join(out_dir, 'classifier_index.pkl'))
 
@@ -293,7 +293,7 @@ def prebuild_index(img_dir, datatype, out_dir, dihe_state):
 def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco, load_classifier_index, gln_state, dihe_state):
     """Evaluate product detection performance."""
     dataloader_workers = _reader_threads()
-    sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True)
+    sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8')
     testset = datautils.GroceryProductsTestSet(test_imgs, annotations, retinanet_annotations=True, image_format='uint8')
     thresholds = _coco_or(iou_threshold, coco)
     proposal_generator = proposals_eval.load_gln(gln_state, False, detections_per_img=200)
@@ -331,10 +331,10 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     dataloader_workers = _reader_threads()
     if datatype == 'gp':
         planoset = datautils.PlanogramTestSet(test_imgs, test_annotations, planograms, image_format='uint8')
-        sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True)
+        sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8')
     else:
         planoset = datautils.InternalPlanoSet(planograms, image_format='uint8')
-        sampleset = datautils.InternalTrainSet(img_dir[0], include_annotations=True)
+        sampleset = datautils.InternalTrainSet(img_dir[0], include_annotations=True, image_format='uint8')
     proposal_generator = proposals_eval.load_gln(gln_state, False)
     proposal_generator.requires_grad_(False)
     generator = production.ProposalGenerator(proposal_generator)

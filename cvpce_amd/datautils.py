@@ -294,15 +294,22 @@ class GroceryProductsDataset:
     (<root>/<category>/.../<name>.<ext>), skipping hierarchies that match `skip`; annotation = 'Category/.../name'.
     Items: (image, image, categories[, annotation]) with the image resized so that its longer side is 256, scaled to
     [-1,1] and padded right / bottom with 0 to 256x256 (`tensorize`, :397-415).  Directory entries are visited in sorted
-    order (the reference takes os.scandir order).  Random crops and masks are training-time and not rebuilt."""
+    order (the reference takes os.scandir order).  Random crops and masks are training-time and not rebuilt.
+    image_format='uint8': the image of an item is the resized (h,w,3) uint8 image itself -- a gallery byte image, which
+    stands for the float item `gallery_float` makes of it; nothing after PIL's resize runs on the host."""
 
     IGNORED_FILES = ('.DS_Store', 'index.txt', 'TrainingClassesIndex.mat', 'classes.csv', 'Thumbs.db')
 
     def __init__(self, image_roots, skip=(r'^Background.*$', r'^.*/[Oo]riginals?$'), only=None, random_crop=False,
                  resize=True, test_can_load=False, include_annotations=False, include_masks=False, index_from_file=False,
-                 **_unused):
+                 image_format='float', **_unused):
         if include_masks:
             raise NotImplementedError('training-time masks are out of scope (DESIGN.md 6)')
+        if image_format not in IMAGE_FORMATS:
+            raise ValueError(f'image_format must be one of {IMAGE_FORMATS}, got {image_format!r}')
+        if image_format == 'uint8' and not resize:
+            raise ValueError("image_format='uint8' needs resize=True: a gallery byte image is at most 256 x 256 (unresized items cannot be batched in either form)")
+        self.image_format = image_format
         if isinstance(image_roots, str):
             image_roots = (image_roots,)
         skip_re = _re.compile('|'.join(f'({s})' for s in skip))
@@ -366,13 +373,30 @@ class GroceryProductsDataset:
     def index_for_ann(self, ann):
         return next((i for i, a in enumerate(self.annotations) if a == ann), None)
 
-    def tensorize(self, img, tanh=False):
+    @staticmethod
+    def _resized(img):
+        """The PIL image resized so that its longer side is 256 (the step both item forms share)."""
         from PIL import Image
+        S = CLASSIFICATION_IMAGE_SIZE
+        h, w = (S, round(S * img.width / img.height)) if img.height > img.width else (round(S * img.height / img.width), S)
+        return img.resize((w, h), Image.BILINEAR), h, w
+
+    def byteize(self, img):
+        """The uint8 item of an RGB PIL image: the resized image's own bytes, (h,w,3)."""
+        return pil_to_uint8(self._resized(img)[0])[:, :, :3].contiguous()
+
+    def _item(self, img, i):
+        t = self.byteize(img) if self.image_format == 'uint8' else self.tensorize(img, True)
+        if self.include_annotations:
+            return t, t, self.categories[i], self.annotations[i]
+        return t, t, self.categories[i]
+
+    def tensorize(self, img, tanh=False):
         if not self.resize:
             return pil_to_tensor(img)
         S = CLASSIFICATION_IMAGE_SIZE
-        h, w = (S, round(S * img.width / img.height)) if img.height > img.width else (round(S * img.height / img.width), S)
-        t = pil_to_tensor(img.resize((w, h), Image.BILINEAR))[:3]
+        img, h, w = self._resized(img)
+        t = pil_to_tensor(img)[:3]
         if tanh:
             t = t * 2 - 1
         out = torch.full((t.shape[0], S, S), 0.0 if tanh else 0.5)
@@ -386,18 +410,32 @@ class GroceryProductsDataset:
         img = _open_image(self.paths[i])
         if img.mode != 'RGB':
             img = img.convert('RGB')
-        t = self.tensorize(img, True)
-        if self.include_annotations:
-            return t, t, self.categories[i], self.annotations[i]
-        return t, t, self.categories[i]
+        return self._item(img, i)
+
+
+def gallery_float(u8, size=CLASSIFICATION_IMAGE_SIZE):
+    """The float image a gallery byte image stands for: (h,w,3) uint8, 1 <= h, w <= size -> (3,size,size) float32, the
+    content `uint8_table[b] * 2 - 1` (torch float32 arithmetic on the host, the very values `tensorize(img, tanh=True)` computes),
+    everything at y >= h or x >= w 0.0.  The host definition: tests, documents and the GALLERY_U8-off route of `Classifier.build_index`
+    use it, the product path's kernel looks the same values up in a table."""
+    from .ops import uint8_table
+    if not (torch.is_tensor(u8) and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[2] == 3):
+        raise TypeError(f'a gallery byte image is a (h,w,3) uint8 tensor, got {type(u8).__name__} {tuple(getattr(u8, "shape", ()))}')
+    h, w = int(u8.shape[0]), int(u8.shape[1])
+    if not (1 <= h <= size and 1 <= w <= size):
+        raise ValueError(f'a gallery byte image is at most {size} x {size} and not empty, got {h} x {w}')
+    idx = u8.cpu().permute(2, 0, 1).to(torch.int64)
+    out = torch.full((3, size, size), 0.0)
+    out[:, :h, :w] = uint8_table()[idx] * 2 - 1
+    return out
 
 
 class InternalTrainSet(GroceryProductsDataset):
     """datautils.py:453-482: product renders with an alpha channel; the annotation is the numeric product code at the
     end of the path, transparent pixels become white."""
 
-    def __init__(self, root, skip=(r'^Unknown.*$',), resize=True, include_annotations=False, **_unused):
-        super().__init__([root], skip=skip, resize=resize, include_annotations=include_annotations)
+    def __init__(self, root, skip=(r'^Unknown.*$',), resize=True, include_annotations=False, image_format='float', **_unused):
+        super().__init__([root], skip=skip, resize=resize, include_annotations=include_annotations, image_format=image_format)
         code_re = _re.compile(r'^(.+/)*(\d+)')
         self.annotations = [code_re.match(a).group(2) for a in self.annotations]
 
@@ -415,6 +453,12 @@ class InternalTrainSet(GroceryProductsDataset):
     def __getitem__(self, i):
         from PIL import Image
         img = _open_image(self.paths[i]).convert('RGBA')
+        if self.image_format == 'uint8':
+            # transparent -> white on the bytes: the float code below goes through the same bytes ((b / 255 * 255).round() == b)
+            a = pil_to_uint8(img).numpy()
+            rgb = a[:, :, :3].copy()
+            rgb[a[:, :, 3] == 0] = 255
+            return self._item(Image.fromarray(rgb, 'RGB'), i)
         white = Image.new('RGBA', img.size, (255, 255, 255, 255))
         a = pil_to_tensor(img)
         rgb = a[:3].clone()

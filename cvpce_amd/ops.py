@@ -15,6 +15,7 @@ from ._lib import lib
 from .torch_ops import T
 from . import torch_ops_input  # noqa: F401  (registers torch.ops.cvpce_amd.*_u8, the byte-reading input kernels)
 from . import torch_ops_lists  # noqa: F401  (registers torch.ops.cvpce_amd.conv3x3_halo_strips2, the thin-strip launch)
+from . import torch_ops_gallery  # noqa: F401  (registers torch.ops.cvpce_amd.gallery_pack_u8, the gallery side's byte kernel)
 
 BF16 = torch.bfloat16
 F16 = torch.float16
@@ -1025,6 +1026,56 @@ def pack_embed_input(images, to_tanh, mean, std):
     out = torch.empty((b, s, s, 8), dtype=BF16, device=images.device)
     T.pack_embed_input(images, out, int(to_tanh), [float(v) for v in mean], [float(v) for v in std])
     return out
+
+
+# ---------------------------------------------------------------------------
+# gallery side: 8-bit product images (csrc/gallery.hip; include/cvpce_amd_gallery.h)
+# A gallery byte image is a contiguous (h,w,3) uint8 tensor, 1 <= h, w <= S, that stands for the (3,S,S) float image
+# `datautils.gallery_float` makes of it: content `uint8_table[b] * 2 - 1`, everything at y >= h or x >= w 0.0.
+# ---------------------------------------------------------------------------
+_GALLERY_TABLES = {}
+GALLERY_MAX_IMAGES = 65535   # images per launch (include/cvpce_amd_gallery.h CVPCE_GALLERY_MAX_IMAGES)
+
+
+def gallery_table(device, mean, std):
+    """(3,257) bf16 on `device`: per channel the embedder-input value of the 256 codes and, last, of the padding (0.0 in tanh range).
+    Made BY `pack_embed_input` (to_tanh off) from the 257 float values the float gallery path would hand it, so the byte kernel's pixels
+    have that path's bits by construction, whatever mean / std are.  Cached per (device, mean, std)."""
+    key = (str(torch.device(device)), tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    t = _GALLERY_TABLES.get(key)
+    if t is None:
+        vals = torch.cat((uint8_table() * 2 - 1, torch.zeros(1)))                     # (257,) float32, the host's arithmetic
+        packed = pack_embed_input(vals.view(257, 1, 1, 1).expand(257, 3, 1, 1).contiguous().to(device), False, mean, std)
+        t = _GALLERY_TABLES[key] = packed[:, 0, 0, :3].t().contiguous()
+    return t
+
+
+def gallery_pack_u8(data, geom, n, size, channels, mean, std, content_only=False, out=None, ext=None):
+    """n gallery byte images -> (out (n,size,size,channels) bf16, ext (n,2) int32 = (h, w)): the embedder's input pixels and the
+    content extents, one launch (per GALLERY_MAX_IMAGES images / 2^31 bytes of size x size x 3 images).
+    data: flat uint8 device buffer, the images back to back; geom (>= n,3) int32 device: byte offset, h, w per image.
+    channels 4 | 8: the pixel widths `crop_resize` modes 2 / 1 write.  content_only: the padding is left unwritten (only the work-list
+    embedder may be given such crops: `embed_packed(..., partial=True)`)."""
+    _need_cuda(data, geom)
+    n, size, channels = int(n), int(size), int(channels)
+    if out is None:
+        out = torch.empty((n, size, size, channels), dtype=BF16, device=data.device)
+    if ext is None:
+        ext = torch.empty((n, 2), dtype=torch.int32, device=data.device)
+    table = gallery_table(data.device, mean, std)
+    per_launch = max(1, min(GALLERY_MAX_IMAGES, ((1 << 31) - 1) // (size * size * 3)))
+    for start in range(0, n, per_launch):
+        nb = min(per_launch, n - start)
+        t = _start()
+        T.gallery_pack_u8(data, geom[start:start + nb], table, out[start:start + nb], int(bool(content_only)), ext[start:start + nb])
+        if t is not None:
+            t.stop()
+            # algorithmic bytes: every image byte once + the pixels written (all of them, or the content only)
+            g = geom[start:start + nb, 1:].to(torch.long).clamp(0, size)
+            area = int((g[:, 0] * g[:, 1]).sum())
+            pixels = area if content_only else nb * size * size
+            t.file('gallery_pack_u8_kernel', None, area * 3 + pixels * channels * out.element_size(), hbm=True)
+    return out, ext
 
 
 # ---------------------------------------------------------------------------

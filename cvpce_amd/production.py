@@ -23,6 +23,35 @@ from .models.classification import TANH_MEAN, TANH_STD
 ENGINE_BATCH = 1024
 INDEX_BATCH = 64      # build_index: gallery images per pass (the host side -- reading and staging f32 images -- dominates there)
 PINNED_STAGING = True  # build_index: persistent pinned double buffer instead of torch.stack + pin_memory per pass
+# build_index: gallery byte images (uint8 (h,w,3) items) are uploaded as bytes and packed by csrc/gallery.hip; off (an A/B
+# switch), they become float items on the host (`datautils.gallery_float`) and take the float path.  Same embeddings, bit for bit.
+GALLERY_U8 = os.environ.get('CVPCE_GALLERY_U8', '1') != '0'
+
+
+def is_gallery_bytes(img):
+    """Whether a gallery item's image is a gallery byte image: a uint8 (h,w,3) tensor."""
+    return torch.is_tensor(img) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
+
+
+def pack_gallery_bytes(images, buf, geom, size=datautils.CLASSIFICATION_IMAGE_SIZE):
+    """The host side of a byte pass: copies every image's bytes ONCE, back to back with no alignment between images, into the flat
+    uint8 buffer `buf` and writes (byte offset, h, w) per image into geom (>= len(images),3) int32 -> the bytes used.
+    images: uint8 (h,w,3) tensors with 1 <= h, w <= size (anything else: ValueError, before anything is copied)."""
+    for img in images:
+        if not is_gallery_bytes(img) or not (1 <= img.shape[0] <= size and 1 <= img.shape[1] <= size):
+            raise ValueError(f'a gallery byte image is a uint8 (h,w,3) tensor with 1 <= h, w <= {size}, got {img.dtype} {tuple(img.shape)}')
+    total = sum(img.numel() for img in images)
+    if total > buf.numel() or len(images) > geom.shape[0]:
+        raise ValueError(f'{len(images)} images of {total} bytes do not fit the staging buffers ({buf.numel()} bytes, {geom.shape[0]} rows)')
+    off, rows = 0, []
+    for img in images:
+        k = img.numel()
+        buf[off:off + k].copy_(img.reshape(-1))
+        rows.append((off, int(img.shape[0]), int(img.shape[1])))
+        off += k
+    if rows:
+        geom[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int32))
+    return off
 
 
 def _nondegenerate(boxes):
@@ -152,15 +181,52 @@ class Classifier:
                 yield pending.popleft().result()
 
     def build_index(self, sample_set, verbose=False):
-        """production.py:36-48.  Gallery images are already in [-1,1] (datautils.py:446): no scale_to_tanh."""
+        """production.py:36-48.  Gallery images are already in [-1,1] (datautils.py:446): no scale_to_tanh.
+        An item's image is either that float (3,256,256) tensor or a gallery byte image, uint8 (h,w,3) (a reader with
+        image_format='uint8'): byte images are staged, uploaded and packed as bytes (`flush_bytes`), with the same
+        embeddings bit for bit; a sample set may mix the two forms."""
         chunks, annotations, imgs = [], [], []
         step = max(self.batch_size, INDEX_BATCH)
         staging = []          # two pinned host buffers (step, C, H, W) + the event after which each may be refilled
+        staging_u8 = []       # byte passes: two [pinned bytes (step * S * S * 3,), pinned geom (step, 3) int32, event]
+        S = datautils.CLASSIFICATION_IMAGE_SIZE
+        use_bytes = GALLERY_U8 and hasattr(self.encoder, 'engine')      # (any other encoder object: float items, as before)
+
+        def flush_bytes():
+            """A pass over gallery byte images: one copy of each image's bytes into pinned memory, two non-blocking uploads (the
+            bytes and their geometry), one launch that makes the embedder's input pixels and the content extents; with the work-list
+            schedule the constant padding is neither written nor computed on."""
+            eng = self.encoder.engine()
+            n = len(imgs)
+            if not staging_u8:
+                staging_u8[:] = [[torch.empty(step * S * S * 3, dtype=torch.uint8).pin_memory(),
+                                  torch.empty((step, 3), dtype=torch.int32).pin_memory(), None] for _ in range(2)]
+            staging_u8.append(staging_u8.pop(0))
+            buf, geom, ev = staging_u8[0]
+            if ev is not None:
+                ev.synchronize()
+            used = pack_gallery_bytes(imgs, buf, geom, S)
+            data = buf[:used].to(device=eng.device, non_blocking=True)
+            geom_dev = geom[:n].to(device=eng.device, non_blocking=True)
+            staging_u8[0][2] = torch.cuda.Event()
+            staging_u8[0][2].record()
+            mean, std = getattr(self.encoder, 'input_mean', TANH_MEAN), getattr(self.encoder, 'input_std', TANH_STD)
+            channels = 4 if getattr(eng, 'stem', None) is not None else 8       # (as BatchedPipeline._crops: the fused stem reads 8-byte pixels)
+            if hasattr(eng, 'skip_plan') and eng.will_skip(S):
+                packed, ext = ops.gallery_pack_u8(data, geom_dev, n, S, channels, mean, std, content_only=True)
+                emb = eng.embed_packed(packed, ext=ext, const_in=eng.const_crop(mean, std, channels, S), partial=True)
+            else:
+                packed, _ = ops.gallery_pack_u8(data, geom_dev, n, S, channels, mean, std, content_only=False)
+                emb = eng.embed_packed(packed)
+            chunks.append(emb.detach().to(device=self.emb_device))
+            imgs.clear()
 
         def flush():
             if not imgs:
                 return
             first = imgs[0]
+            if is_gallery_bytes(first):
+                return flush_bytes()
             if first.is_cuda or not torch.cuda.is_available() or not PINNED_STAGING:
                 batch = torch.stack(imgs).to(device=self.device)
             else:
@@ -180,7 +246,12 @@ class Classifier:
             imgs.clear()
 
         for i, item in enumerate(self._gallery_items(sample_set)):
-            imgs.append(item[0])
+            img = item[0]
+            if is_gallery_bytes(img) and not use_bytes:
+                img = datautils.gallery_float(img, S)
+            if imgs and is_gallery_bytes(img) != is_gallery_bytes(imgs[0]):
+                flush()                                        # a change of form ends the pass: order is kept, mixed sets work
+            imgs.append(img)
             annotations.append(item[-1])
             if verbose and (i + 1) % self.batch_size == 0 and (i // self.batch_size) % 100 == 0:
                 print(i // self.batch_size)
