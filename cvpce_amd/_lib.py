@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h, the
 8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
-include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h and the gallery kernel of
-include/cvpce_amd_gallery.h).
+include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
+include/cvpce_amd_gallery.h and the comparator's re-classification kernels of include/cvpce_amd_reclass.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -130,7 +130,14 @@ GALLERY_SIGNATURES = {
     'cvpce_gallery_pack_u8': (c_int, [_vp, _ip, _vp, _vp, c_int, c_int, c_int, c_int, _ip, _vp]),
 }
 
-for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES):
+# include/cvpce_amd_reclass.h: the two ends of the comparator's re-classification.  A table of its own, like the header.
+RECLASS_SIGNATURES = {
+    'cvpce_reclass_plan': (c_int, [_ip, _ip, _fp, _ip, _ip] + [c_int] * 3 + [_fp, _ip, _ip, _vp]),
+    'cvpce_reclass_verdict': (c_int, [_ip, _ip, _ip, _vp, _ip, _ip, _ip, _ip, _ip] + [c_int] * 6 + [_ip, _ip, _vp]),
+}
+
+for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
+               RECLASS_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

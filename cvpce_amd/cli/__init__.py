@@ -135,6 +135,38 @@ def _device_tail_switch():
     return bool(click.get_current_context().meta.get(_DeviceTailCommand.TAIL_KEY, False))
 
 
+class _DeviceReclassCommand(_DeviceTailCommand):
+    """The two switches above, and --device-reclass / --no-device-reclass (default: off) beside them, arranged the same way."""
+    RECLASS_SWITCH = {'--device-reclass': True, '--no-device-reclass': False}
+    RECLASS_HELP = ('Also re-classify a window\'s expected-but-undetected positions in one GPU pass instead of image by image through the '
+                    'host (cvpce_amd.planograms_device.reclassify_batch; the documented re-classification rule).  Needs --device-tail: '
+                    'without it the command stops with an error.  [default: off]')
+    RECLASS_KEY = 'cvpce_amd.device_reclass'
+    RECLASS_LABEL = '--device-reclass / --no-device-reclass'
+
+    def parse_args(self, ctx, args):
+        rest = []
+        ctx.meta[self.RECLASS_KEY] = False
+        for i, a in enumerate(args):
+            if a == '--':
+                rest += args[i:]
+                break
+            if a in self.RECLASS_SWITCH:
+                ctx.meta[self.RECLASS_KEY] = self.RECLASS_SWITCH[a]
+            else:
+                rest.append(a)
+        tails = [self.TAIL_SWITCH[a] for a in (rest[:rest.index('--')] if '--' in rest else rest) if a in self.TAIL_SWITCH]
+        if ctx.meta[self.RECLASS_KEY] and not (tails and tails[-1]) and not ctx.resilient_parsing:
+            raise click.UsageError('--device-reclass needs --device-tail', ctx)        # (it implies nothing on its own)
+        return super().parse_args(ctx, rest)
+
+    MORE = _DeviceTailCommand.MORE + ((RECLASS_LABEL, RECLASS_HELP),)
+
+
+def _device_reclass_switch():
+    return bool(click.get_current_context().meta.get(_DeviceReclassCommand.RECLASS_KEY, False))
+
+
 @click.group()
 def cli():
     """Computer vision based planogram compliance evaluation -- MI355X inference / evaluation commands."""
@@ -312,7 +344,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command(cls=_DeviceTailCommand)
+@cli.command(cls=_DeviceReclassCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -340,7 +372,8 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     generator = production.ProposalGenerator(proposal_generator)
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
     evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
-                                                                                              device_tail=_device_tail_switch()))
+                                                                                              device_tail=_device_tail_switch(),
+                                                                                              device_reclass=_device_reclass_switch()))
     total_a = total_e = 0.0
     # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
     # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,

@@ -6,6 +6,8 @@
   match_on_device    the same launch without the copy back: the matchings stay on the device for `finalize_batch`
   finalize_batch     RANSAC homography, refit, projection and per-label claim of a batch (csrc/homography.hip): two launches, one
                      copy back -- the opt-in counterpart of `planograms.finalize_via_ransac` (the tail rule of DESIGN.md 4b)
+  reclassify_batch   the re-classification of a window's expected-but-undetected positions (csrc/reclass.hip at both ends of one crop /
+                     embed / match pass): one more wait -- the opt-in counterpart of the per-image loop of `PlanogramComparator._finish`
   finalize_result    a record of `finalize_batch` as the tuple `finalize_via_ransac` returns
   to_networkx        a device graph as the DiGraph the host functions expect (node order 0..n-1, adjacency in stamp order)
   prepare            caches a planogram's device graph in its dict, as `expected['graph']` caches the host graph
@@ -223,25 +225,99 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
     return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b])
 
 
+class ReclassPlan:
+    """What `reclass_plan` left on the device for a window, and the tail outputs the verdict kernel reads beside it: `boxes`
+    [B][cap][4] f32, `expected_index` [B][cap] and `count` [B] int32 (slots at and beyond an image's count are unwritten), the views
+    `status`, `matched_expected` and `off1` of the tail's tensors, and on the host `counts` (a list, brought back in the tail's own
+    synchronisation), the box counts `n1` and `cap` = max n1."""
+    __slots__ = ('boxes', 'expected_index', 'count', 'status', 'matched_expected', 'off1', 'counts', 'n1', 'cap')
+
+
+def _launch_plan(matching, finish, image_table):
+    """`reclass_plan` behind `homography_finish` on the same stream, and its counts on their way to pinned memory -> (ReclassPlan
+    without `counts`, the pinned tensor the counts land in once the stream has been waited for)."""
+    from . import torch_ops_reclass  # noqa: F401  (registers torch.ops.cvpce_amd.reclass_*)
+    b = len(matching.n1)
+    if len(image_table) != b:
+        raise ValueError('one (h, w, enabled) row per image')
+    status, me, pos = finish[16], finish[21], finish[23]
+    device = status.device
+    plan = ReclassPlan()
+    plan.n1, plan.cap = list(matching.n1), max(matching.n1)
+    plan.status, plan.matched_expected, plan.off1 = status, me, matching.off1
+    table = _upload(torch.tensor([[int(h), int(w), int(bool(on))] for h, w, on in image_table], dtype=torch.int32), device)
+    plan.boxes = torch.empty((b, plan.cap, 4), dtype=torch.float32, device=device)
+    slots = torch.empty(b * plan.cap + b, dtype=torch.int32, device=device)
+    plan.expected_index, plan.count = slots[:b * plan.cap].view(b, plan.cap), slots[b * plan.cap:]
+    torch.ops.cvpce_amd.reclass_plan(status, me, pos, matching.off1, table, plan.boxes, plan.expected_index, plan.count)
+    host = torch.empty(b, dtype=torch.int32).pin_memory()
+    host.copy_(plan.count, non_blocking=True)
+    return plan, host
+
+
+def reclassify_batch(plan, images, classifier, expected_label_ids):
+    """The window's second trip through the crop / embed / match kernels in one pass (the re-classification rule of DESIGN.md 4b):
+    every image's planned positions are cropped straight to the embedder's bf16 input (`production.roi_crops`: boxes and counts are
+    read on the device), compacted with the host's counts, embedded by ONE schedule and matched by ONE distance GEMM;
+    `reclass_verdict` compares label ids and one pinned copy brings back the per-image found counts -- the only wait of this pass.
+    plan: the `ReclassPlan` of `finalize_batch(..., reclass=...)` with at least one position; images: the window's images (either
+    form; read only where the image's count is > 0); expected_label_ids: one list of ids per image (`Classifier.expected_label_ids`).
+    -> list of found counts, -1 for an image without a homography."""
+    from . import ops, production
+    b, cap, counts = len(plan.n1), plan.cap, plan.counts
+    device = plan.count.device
+    total, sum1 = sum(counts), sum(plan.n1)
+    if not total or len(images) != b or [len(ids) for ids in expected_label_ids] != plan.n1:
+        raise ValueError('a plan with positions, one image and one id vector per image of the plan')
+    crops, ext, const_in, partial = production.roi_crops(
+        classifier.encoder, device, [ops.input_image(img, device) if c else None for img, c in zip(images, counts)], plan.boxes, plan.count)
+    # one upload for the small tables: every slot's row in the compacted crops (-1 beyond the count), the compaction itself, the ids
+    rows, sel, at = [], [], 0
+    for i, c in enumerate(counts):
+        rows += list(range(at, at + c)) + [-1] * (cap - c)
+        sel += range(i * cap, i * cap + c)
+        at += c
+    small = _upload(torch.tensor(rows + sel + [v for ids in expected_label_ids for v in ids], dtype=torch.int32), device)
+    slot_row, sel, ids = small[:b * cap].view(b, cap), small[b * cap:b * cap + total], small[b * cap + total:]
+    if total != b * cap:                        # (the embedder only runs over the valid crops, as BatchedPipeline._select has it)
+        crops = crops.index_select(0, sel)
+        ext = ext.index_select(0, sel) if ext is not None else None
+    eng = classifier.encoder.engine()
+    emb = eng.embed_packed(crops, ext=ext, const_in=const_in, partial=partial) if ext is not None else eng.embed_packed(crops)
+    indices = classifier.match(emb).contiguous()
+    out = torch.empty(sum1 + b, dtype=torch.int32, device=device)
+    torch.ops.cvpce_amd.reclass_verdict(plan.expected_index, plan.count, slot_row, indices, classifier.gallery_label_id, ids,
+                                        plan.matched_expected, plan.off1, plan.status, out[:sum1], out[sum1:])
+    host = torch.empty(b, dtype=torch.int32).pin_memory()
+    host.copy_(out[sum1:], non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    return host.tolist()
+
+
 def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold=0.5, seed=0,
-                   hypotheses=RANSAC_HYPOTHESES):
+                   hypotheses=RANSAC_HYPOTHESES, reclass=None):
     """`planograms.finalize_via_ransac` for every image of a batch under the tail rule: two launches on the matchings
     as they lie on the device (`match_on_device`) and ONE pinned copy back.  expected / actual: the lists of `Graph` the matching was
     made from; expected_boxes / actual_boxes: their (n, 4) boxes; reproj_thresholds: one per image, in pixels.
     -> one record per image: {'status': 'ok' | 'none' | 'invalid', 'matched_expected', 'matched_actual' (bool), 'expected_positions'
     (float32 (n1, 4)), 'homography' (3 x 3 float64, None unless ok), 'inliers' (of the refit), 'points', 'matching' (its size),
-    'winner', 'winner_inliers'}."""
+    'winner', 'winner_inliers'}.
+    reclass (optional): one (image height, image width, enabled) per image -- `reclass_plan` is launched behind the tail and its counts
+    come back in the same synchronisation -> (records, `ReclassPlan`) for `reclassify_batch`."""
     if not len(expected) == len(actual) == len(matching.n1) or [len(g) for g in expected] != matching.n1 or [len(g) for g in actual] != matching.n2:
         raise ValueError('the graphs the matching was made from')
     ransac, finish, blob, (at_h, at_i, size) = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses)
     torch.ops.cvpce_amd.homography_ransac(*ransac)
     torch.ops.cvpce_amd.homography_finish(*finish)
+    plan, plan_counts = _launch_plan(matching, finish, reclass) if reclass is not None else (None, None)
     size.copy_(matching.count)                                     # (the matching's size travels in the same copy)
     b, n1, n2 = len(expected), matching.n1, matching.n2
     sum1 = sum(n1)
     back = torch.empty(blob.shape, dtype=torch.uint8).pin_memory()
     back.copy_(blob, non_blocking=True)
     torch.cuda.current_stream(blob.device).synchronize()
+    if plan is not None:
+        plan.counts = plan_counts.tolist()
     pos, hmat, i32 = back[:at_h].view(torch.float32).view(sum1, 4), back[at_h:at_i].view(torch.float64).view(b, 3, 3), back[at_i:].view(torch.int32)
     head = i32[:5 * b].view(5, b).tolist()
     me, ma = i32[5 * b:5 * b + sum1] != 0, i32[5 * b + sum1:] != 0
@@ -253,7 +329,7 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
         records.append({'status': STATUS[head[0][p]], 'matched_expected': me[off1[p]:off1[p + 1]].clone(), 'matched_actual': ma[off2[p]:off2[p + 1]].clone(),
                         'expected_positions': pos[off1[p]:off1[p + 1]].clone(), 'homography': hmat[p].clone() if ok else None,
                         'inliers': head[3][p], 'points': 5 if m == 1 else 3 * m, 'matching': m, 'winner': head[1][p], 'winner_inliers': head[2][p]})
-    return records
+    return records if plan is None else (records, plan)
 
 
 def finalize_result(record, expected_labels, return_matched_actual=False, report_accuracy=False, return_expected_positions=False):

@@ -8,6 +8,7 @@ Differences from the reference, all on the device-boundary side:
   * degenerate (zero-area after `.to(long)`) boxes make the reference raise inside
     `resize_for_classification`; here they are dropped (documented divergence).
 """
+import itertools
 import os
 
 import torch
@@ -26,6 +27,7 @@ PINNED_STAGING = True  # build_index: persistent pinned double buffer instead of
 # build_index: gallery byte images (uint8 (h,w,3) items) are uploaded as bytes and packed by csrc/gallery.hip; off (an A/B
 # switch), they become float items on the host (`datautils.gallery_float`) and take the float path.  Same embeddings, bit for bit.
 GALLERY_U8 = os.environ.get('CVPCE_GALLERY_U8', '1') != '0'
+_INDEX_GENERATIONS = itertools.count(1)         # Classifier.index_generation: a new number at every refresh of a classifier's index
 
 
 def is_gallery_bytes(img):
@@ -155,6 +157,32 @@ class Classifier:
         g = ops.pad_features(self.embedding.to(device=self.device, dtype=self.match_dtype))
         self._gallery = g
         self._gallery_norms = ops.row_norms(g)
+        self._refresh_label_ids()
+
+    def _refresh_label_ids(self):
+        """The label-id space the comparator's device re-classification compares in: `label_ids` maps an annotation to an id >= 0 (equal
+        annotations, equal id), `gallery_label_id` [G] int32 on the device holds every gallery row's id, and `index_generation` counts
+        the refreshes, so that an id vector cached elsewhere (`expected_label_ids`) is known to be stale.  An unhashable annotation
+        leaves no id space (`label_ids` None): such a classifier's windows are re-classified per image, as before."""
+        self.index_generation = next(_INDEX_GENERATIONS)        # (one counter for all classifiers: no two indices share a number)
+        ids = {}
+        try:
+            rows = [ids.setdefault(a, len(ids)) for a in self.annotations]
+        except TypeError:
+            self.label_ids, self.gallery_label_id = None, None
+            return
+        self.label_ids = ids
+        self.gallery_label_id = torch.tensor(rows, dtype=torch.int32).to(self.device)
+
+    def expected_label_ids(self, labels):
+        """labels (a planogram's expected labels) -> their ids as a list, -1 for a label no gallery item has; None where there is no
+        id space or a label is unhashable."""
+        if self.label_ids is None:
+            return None
+        try:
+            return [self.label_ids.get(l, -1) for l in labels]
+        except TypeError:
+            return None
 
     def set_index(self, embedding, annotations):
         self.embedding, self.annotations = embedding, annotations
@@ -308,19 +336,28 @@ class PlanogramComparator:
     """production.py:76-116: graph matching -> RANSAC homography -> per-label IoU matching -> optional re-classification
     of the expected-but-undetected positions (a second trip through the crop / embed / match kernels)."""
 
-    def __init__(self, graph_threshold=0.5, device_graphs=False, device_tail=False):
+    def __init__(self, graph_threshold=0.5, device_graphs=False, device_tail=False, device_reclass=False):
         """device_graphs (opt-in): the neighbour graphs and the common subgraph come from the kernels of `planograms_device` (its
         documented rule at equal distances); the homography and everything after it stay the host's.  `host_routed`
         counts the images that took the host path with the switch on (a graph of more than 1024 nodes).
         device_tail (opt-in, needs device_graphs): the homography, the projection and the per-label claim run on the device too
         (`planograms_device.finalize_batch`, the tail rule of DESIGN.md 4b): a window's graphs, matchings and tails are launched back
-        to back and one copy brings back what the verdict needs; the re-classification stays where it is."""
+        to back and one copy brings back what the verdict needs; the re-classification runs per image through the host.
+        device_reclass (opt-in, needs device_tail): the re-classification of a window's expected-but-undetected positions is one
+        device pass too (`planograms_device.reclassify_batch`, the re-classification rule of DESIGN.md 4b): the positions are
+        planned behind the tail, cropped to bf16 embedder input, embedded by one schedule, matched by one GEMM and compared as label
+        ids; a window costs two waits.  `reclass_host_routed` counts the windows that took the per-image re-classification with the
+        switch on (an annotation or an expected label that cannot be hashed into the id space)."""
         if device_tail and not device_graphs:
             raise ValueError('device_tail needs device_graphs: the tail kernels read the matching where the match kernel left it')
+        if device_reclass and not device_tail:
+            raise ValueError('device_reclass needs device_tail: the plan kernel reads the positions where the tail kernel left them')
         self.graph_threshold = graph_threshold
         self.device_graphs = device_graphs
         self.device_tail = device_tail
+        self.device_reclass = device_reclass
         self.host_routed = 0
+        self.reclass_host_routed = 0
 
     def compare(self, expected, actual, image=None, classifier=None):
         if self.device_graphs:
@@ -339,8 +376,9 @@ class PlanogramComparator:
     def compare_batch(self, expecteds, actuals, images=None, classifier=None):
         """[compare(e, a, img, classifier) for ...] with the graph stages of the whole batch in two launches (all graphs, all matchings)
         and one copy back; the host tail (homography, per-label claim, re-classification) runs per image -- with `device_tail` the
-        homography and the claim are two more launches of the window and only the re-classification stays per image.  With
-        `device_graphs` off it is the plain loop."""
+        homography and the claim are two more launches of the window and only the re-classification stays per image; with
+        `device_reclass` that is one pass of the window as well (`_reclassified`: two waits, whatever the number of images with
+        positions to classify).  With `device_graphs` off it is the plain loop."""
         images = [None] * len(expecteds) if images is None else images
         if not self.device_graphs:
             return [self._compare_host(e, a, img, classifier) for e, a, img in zip(expecteds, actuals, images)]
@@ -362,6 +400,9 @@ class PlanogramComparator:
             ge = [have[i] if have[i] is not None else next(fresh) for i in todo]
             ga = built[len(build) - len(todo):]
             if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
+                ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
+                if ids is not None:
+                    return self._reclassified(results, todo, ge, ga, ids, expecteds, actuals, images, classifier)
                 records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [expecteds[i]['boxes'] for i in todo],
                                             [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo])
                 for i, rec in zip(todo, records):
@@ -371,6 +412,52 @@ class PlanogramComparator:
             matchings = pd.common_subgraphs(ge, ga)
             for i, matching in zip(todo, matchings):
                 results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
+        return results
+
+    LABEL_IDS_KEY = 'reclass_label_ids'           # a planogram dict's cached id vector, beside planograms_device.CACHE_KEY
+
+    def _window_label_ids(self, planograms, classifier):
+        """The expected labels of a window as ids of the classifier's id space, one list per planogram -- cached in the planogram's
+        dict with the classifier's index generation, so a `set_index` invalidates it.  No classifier: nothing will be classified, no
+        ids are needed ([None, ...]).  -> None where a label or an annotation cannot be hashed: the window is re-classified per
+        image (`reclass_host_routed`)."""
+        if classifier is None:
+            return [None] * len(planograms)
+        generation = getattr(classifier, 'index_generation', None)
+        out = []
+        for plano in planograms:
+            cached = plano.get(self.LABEL_IDS_KEY) if isinstance(plano, dict) else None
+            if cached is not None and generation is not None and cached[0] == generation and len(cached[1]) == len(plano['labels']):
+                ids = cached[1]
+            else:
+                ids = classifier.expected_label_ids(plano['labels']) if generation is not None else None
+                if ids is None:
+                    self.reclass_host_routed += 1
+                    return None
+                if isinstance(plano, dict):
+                    plano[self.LABEL_IDS_KEY] = (generation, ids)
+            out.append(ids)
+        return out
+
+    def _reclassified(self, results, todo, ge, ga, ids, expecteds, actuals, images, classifier):
+        """The `device_reclass` window: graphs -> match -> tail -> plan back to back and the first wait; where the plan holds
+        positions, crops -> embedder -> match -> verdict and the second wait (`planograms_device.reclassify_batch`).  The verdict
+        of an image with a homography is found_count / n1 -- the value and dtype of `_finish`'s found.sum() / len(found); every
+        other image, and a window without positions, ends in `_finish` as with `device_tail` alone."""
+        from . import planograms_device as pd
+        table = []
+        for i in todo:
+            on = classifier is not None and images[i] is not None
+            table.append(datautils.image_hw(images[i]) + (1,) if on else (0, 0, 0))
+        records, plan = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [expecteds[i]['boxes'] for i in todo],
+                                          [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], reclass=table)
+        found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, ids) if sum(plan.counts) else None
+        for p, (i, rec) in enumerate(zip(todo, records)):
+            if found is not None and rec['status'] == 'ok':
+                results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
+            else:
+                tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
+                results[i] = self._finish(rec['matching'], expecteds[i], actuals[i], images[i], classifier, tail)
         return results
 
     @staticmethod
@@ -509,6 +596,39 @@ class PlanogramEvaluator:
 CROP_CONTENT_ONLY = os.environ.get('CVPCE_CROP_CONTENT', '1') != '0'   # A/B switch: the crop kernel leaves the constant padding unwritten for the work-list embedder
 
 
+def roi_crops(encoder, device, images, boxes, count, content_only=True):
+    """The embedder's input for the first count[i] of the boxes[i] of every image, launched WITHOUT knowing the counts on the host --
+    what `BatchedPipeline._crops` does for the detector's confident boxes and `planograms_device.reclassify_batch` for a window's
+    positions to re-classify.  images: device images (either form); an entry may be None: nothing is launched for it and its slots
+    stay unwritten (the caller knows its count to be 0).  boxes (n,per,4) f32 and count (n,) int32 on `device`.
+    -> (crops (n * per,S,S,4|8) bf16, their content extents | None, the encoder's all-padding crop | None, partial), as `_crops`
+    documents them."""
+    emb_eng = encoder.engine()
+    n, dpi = boxes.shape[0], boxes.shape[1]
+    size = datautils.CLASSIFICATION_IMAGE_SIZE
+    # the fused VGG stem reads 4- or 8-channel pixels: 8-byte pixels halve what the crop kernel writes and the stem re-reads
+    narrow = getattr(emb_eng, 'stem', None) is not None
+    mean, std = getattr(encoder, 'input_mean', TANH_MEAN), getattr(encoder, 'input_std', TANH_STD)
+    crops = torch.empty((n * dpi, size, size, 4 if narrow else 8), dtype=torch.bfloat16, device=device)
+    # content extents of the crops (the part of a crop beyond them is the pad constant of datautils.py:232-239: the embedder
+    # skips the tiles that lie in it) -- only for an encoder whose engine has the work-list schedule
+    skip = hasattr(emb_eng, 'skip_plan') and emb_eng.skip_plan(size) is not None
+    ext = torch.empty((n * dpi, 2), dtype=torch.int32, device=device) if skip else None
+    hw = [None if img is None else datautils.image_hw(img) for img in images]    # (either form)
+    same_size = all(s is not None and s == hw[0] for s in hw)
+    partial = bool(content_only and skip and CROP_CONTENT_ONLY and emb_eng.will_skip(size))
+    if skip and same_size:                   # (images of one size: the extents of the whole batch in one launch)
+        ops.crop_extents(boxes.reshape(n * dpi, 4), count, hw[0][0], hw[0][1], size, out=ext, per_image=dpi)
+    for i, img in enumerate(images):
+        if img is None:
+            continue
+        if skip and not same_size:
+            ops.crop_extents(boxes[i], count[i:i + 1], hw[i][0], hw[i][1], size, out=ext[i * dpi:(i + 1) * dpi])
+        ops.crop_resize(img, boxes[i], size, mode=2 if narrow else 1, mean=mean, std=std, count=count[i:i + 1],
+                        out=crops[i * dpi:(i + 1) * dpi], content_ext=ext[i * dpi:(i + 1) * dpi] if partial else None)
+    return crops, ext, (emb_eng.const_crop(mean, std, crops.shape[3], size) if skip else None), partial
+
+
 class BatchedPipeline:
     """detect -> RoI crop -> embed -> match for a batch of shelf images, device-resident end to end.
 
@@ -531,30 +651,7 @@ class BatchedPipeline:
         padding beyond the extents is never read by that schedule (it reads the constant crop instead), so it is not produced either;
         `embed_packed(..., partial=True)` refuses to run any other schedule on such crops."""
         boxes, scores, labels, count, conf_count, gauss = det_out
-        eng = self.detector.engine()
-        emb_eng = self.classifier.encoder.engine()
-        dpi = self.detector.detections_per_img
-        size = datautils.CLASSIFICATION_IMAGE_SIZE
-        n = len(images)
-        # the fused VGG stem reads 4- or 8-channel pixels: 8-byte pixels halve what the crop kernel writes and the stem re-reads
-        narrow = getattr(emb_eng, 'stem', None) is not None
-        mean, std = getattr(self.classifier.encoder, 'input_mean', TANH_MEAN), getattr(self.classifier.encoder, 'input_std', TANH_STD)
-        crops = torch.empty((n * dpi, size, size, 4 if narrow else 8), dtype=torch.bfloat16, device=eng.device)
-        # content extents of the crops (the part of a crop beyond them is the pad constant of datautils.py:232-239: the embedder
-        # skips the tiles that lie in it) -- only for an encoder whose engine has the work-list schedule
-        skip = hasattr(emb_eng, 'skip_plan') and emb_eng.skip_plan(size) is not None
-        ext = torch.empty((n * dpi, 2), dtype=torch.int32, device=eng.device) if skip else None
-        hw = [datautils.image_hw(img) for img in images]    # (either form)
-        same_size = all(s == hw[0] for s in hw)
-        partial = bool(content_only and skip and CROP_CONTENT_ONLY and emb_eng.will_skip(size))
-        if skip and same_size:                   # (images of one size: the extents of the whole batch in one launch)
-            ops.crop_extents(boxes.reshape(n * dpi, 4), conf_count, hw[0][0], hw[0][1], size, out=ext, per_image=dpi)
-        for i, img in enumerate(images):
-            if skip and not same_size:
-                ops.crop_extents(boxes[i], conf_count[i:i + 1], hw[i][0], hw[i][1], size, out=ext[i * dpi:(i + 1) * dpi])
-            ops.crop_resize(img, boxes[i], size, mode=2 if narrow else 1, mean=mean, std=std, count=conf_count[i:i + 1],
-                            out=crops[i * dpi:(i + 1) * dpi], content_ext=ext[i * dpi:(i + 1) * dpi] if partial else None)
-        return crops, ext, (emb_eng.const_crop(mean, std, crops.shape[3], size) if skip else None), partial
+        return roi_crops(self.classifier.encoder, self.detector.engine().device, images, boxes, conf_count, content_only)
 
     def _select(self, crops, counts, ext=None):
         """The embedder only runs over the valid crops (compaction = a gather of row indices; their extents go along)."""

@@ -15,8 +15,14 @@ Scenes: gridded planograms of 24 (4 x 6) and 200 (8 x 25) boxes (synthetic.plano
   evaluate_iter   images/s of PlanogramEvaluator.evaluate_iter with the real comparator, switch off and on, in this one call: the
                   detector / embedder / matcher run on synthetic shelf images as in bench.py and the comparator is handed the scene's
                   detections (the synthetic detector's own boxes are noise); `tail`: both switches on
+  reclass leg     (--reclass-markdown) the re-classification stage with a stated miss rate: every 9th planted detection is withheld from
+                  the comparator and every 11th expected label is replaced by one no gallery item has, the gallery carries the planograms'
+                  own labels and the shelf images are large enough to hold the projected positions.  compare_batch ms per image and
+                  evaluate_iter images/s with `device_tail` alone and with `device_reclass` as well, in this one process, and what a
+                  window costs in launches and waits on either path
 
     python tools/bench_planogram_compare.py [--batch 8] [--launches 30] [--markdown profiles/r23_planogram_tail.md]
+                                            [--reclass-markdown profiles/r25_reclass.md]
 """
 import argparse
 import json
@@ -26,6 +32,7 @@ import sys
 import time
 
 import torch
+from torch.utils._python_dispatch import TorchDispatchMode
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -148,11 +155,159 @@ def time_evaluate_iter(pairs, images, evaluators):
     return res
 
 
+def miss_scenes(rows, cols, batch):
+    """`scenes` with a stated miss rate: every 9th planted detection is withheld from the comparator, every 11th expected label is
+    replaced by a label no gallery item has -> pairs, and (h, w) of a shelf image that holds every detection."""
+    out, far = [], torch.zeros(2)
+    for e, a in scenes(rows, cols, batch):
+        keep = [i for i in range(len(a['labels'])) if i % 9 != 4]
+        labels = [('not_in_the_gallery' if i % 11 == 5 else l) for i, l in enumerate(e['labels'])]
+        far = torch.maximum(far, a['boxes'][:, 2:].amax(dim=0))
+        out.append(({'boxes': e['boxes'], 'labels': labels}, {'boxes': a['boxes'][keep].contiguous(), 'labels': [a['labels'][i] for i in keep]}))
+    w, h = (max(1024, -(-int(v + 8) // 64) * 64) for v in far.tolist())
+    return out, (h, w)
+
+
+class WindowCounter(TorchDispatchMode):
+    """What one window costs: `kernels` = calls of the project's own ops (one launch each), `torch_device_ops` = every other operator
+    that touches a device tensor (copies, gathers, fills: at most a launch each), `waits` = the points at which the host waits for the
+    device (stream / event synchronize, a blocking device-to-host copy, a scalar read off a device tensor)."""
+
+    def __init__(self):
+        super().__init__()
+        self.kernels = self.torch_device_ops = self.waits = 0
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        tensors = [t for t in list(args) + list(kwargs.values()) if torch.is_tensor(t)]
+        for a in args:
+            if isinstance(a, (list, tuple)):
+                tensors += [t for t in a if torch.is_tensor(t)]
+        on_device = any(t.is_cuda for t in tensors)
+        name = func.name() if hasattr(func, 'name') else str(func)
+        if name.startswith('cvpce_amd::'):
+            self.kernels += 1
+        elif on_device:
+            self.torch_device_ops += 1
+        out = func(*args, **kwargs)
+        if on_device and name.startswith('aten::_local_scalar_dense'):
+            self.waits += 1
+        elif on_device and torch.is_tensor(out) and not out.is_cuda and not kwargs.get('non_blocking', False) \
+                and name.startswith(('aten::_to_copy', 'aten::copy_')) and not (name.startswith('aten::copy_') and len(args) > 2 and args[2]):
+            self.waits += 1
+        return out
+
+    def __enter__(self):
+        self._saved = (torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize, torch.cuda.synchronize)
+        counter = self
+
+        def wrap(fn):
+            def counted(*a, **kw):
+                counter.waits += 1
+                return fn(*a, **kw)
+            return counted
+        torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize, torch.cuda.synchronize = (wrap(f) for f in self._saved)
+        return super().__enter__()
+
+    def __exit__(self, *exc):
+        torch.cuda.Stream.synchronize, torch.cuda.Event.synchronize, torch.cuda.synchronize = self._saved
+        return super().__exit__(*exc)
+
+
+def time_reclass(name, rows, cols, batch, det, enc, dev):
+    """The leg with a stated miss rate -> one row: `device_tail` alone against `device_reclass` as well, same process, same inputs."""
+    pairs, (h, w) = miss_scenes(rows, cols, batch)
+    gallery = synthetic.TensorGallery(synthetic.gallery_images(64, seed=100), [synthetic.PLANOGRAM_LABELS[i % len(synthetic.PLANOGRAM_LABELS)] for i in range(64)])
+    clf = production.Classifier(enc, gallery, device=dev, emb_device=dev, batch_size=32, match_dtype=torch.bfloat16)
+    pg = production.ProposalGenerator(det, device=dev, confidence_threshold=0.5)
+    images = [synthetic.shelf_image(400 + k, h, w).to(dev) for k in range(batch)]
+    es, acts = [e for e, _ in pairs], [a for _, a in pairs]
+    cmps = {'tail': production.PlanogramComparator(device_graphs=True, device_tail=True),
+            'reclass': production.PlanogramComparator(device_graphs=True, device_tail=True, device_reclass=True)}
+    row = {'scene': name, 'batch': batch, 'image': f'{h} x {w}', 'expected_boxes': sum(len(e['labels']) for e in es) / batch}
+    # what the stage has to do on this input: positions classified, recovered, not recovered (from the `device_tail` path itself)
+    crops = []
+    inner = clf.classify
+    clf.classify = lambda imgs, *a, **kw: (crops.append(len(imgs)), inner(imgs, *a, **kw))[1]
+    with_clf = cmps['tail'].compare_batch(es, acts, images, clf)
+    del clf.classify
+    without = cmps['tail'].compare_batch(es, acts, images, None)
+    recovered = sum(round((float(a) - float(b)) * len(e['labels'])) for a, b, e in zip(with_clf, without, es))
+    row.update(images_with_positions=len(crops), positions=sum(crops) / batch, recovered=recovered / batch, not_recovered=(sum(crops) - recovered) / batch,
+               unmatched=sum(round((1 - float(b)) * len(e['labels'])) for b, e in zip(without, es)) / batch)
+    verdicts, times = {}, {key: [] for key in cmps}
+    for r in range(REPEATS + 2):                            # (the two paths alternate window by window; the first two rounds warm up)
+        for key, cmp in cmps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            verdicts[key] = cmp.compare_batch(es, acts, images, clf)
+            torch.cuda.synchronize()
+            if r > 1:
+                times[key].append(time.perf_counter() - t0)
+    for key, cmp in cmps.items():
+        row[f'compare_batch_{key}'] = 1e3 * statistics.median(times[key]) / batch
+        row[f'compare_batch_{key}_min_max'] = [1e3 * min(times[key]) / batch, 1e3 * max(times[key]) / batch]
+        with WindowCounter() as c:
+            cmp.compare_batch(es, acts, images, clf)
+        row.update({f'kernels_{key}': c.kernels, f'torch_ops_{key}': c.torch_device_ops, f'waits_{key}': c.waits})
+    row['same_verdict'] = sum(float(a) == float(b) and type(a) is type(b) for a, b in zip(verdicts['tail'], verdicts['reclass']))
+    evaluators = {key: PlantedEvaluator(pg, clf, cmp) for key, cmp in cmps.items()}
+    rates, vals = {key: [] for key in cmps}, {}
+    for r in range(REPEATS + 1):                            # (alternating again; round 0 warms up)
+        for key, ev in evaluators.items():
+            ev.planted, ev._at = [(a['boxes'], a['labels']) for a in acts], 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vals[key] = [float(v) for v in ev.evaluate_iter(zip(images, es), lookahead=batch)]
+            dt = time.perf_counter() - t0
+            if r:
+                rates[key].append(batch / dt)
+    for key in cmps:
+        row[f'evaluate_iter_{key}'] = statistics.median(rates[key])
+        row[f'evaluate_iter_{key}_min_max'] = [min(rates[key]), max(rates[key])]
+    row['same_verdict_iter'] = sum(a == b for a, b in zip(vals['tail'], vals['reclass']))
+    return row
+
+
+REPEATS = 15                # timed windows per path and figure of the re-classification leg
+RECLASS_COLS = ('image', 'expected_boxes', 'unmatched', 'positions', 'recovered', 'not_recovered', 'compare_batch_tail', 'compare_batch_reclass',
+                'evaluate_iter_tail', 'evaluate_iter_reclass', 'kernels_tail', 'kernels_reclass', 'torch_ops_tail', 'torch_ops_reclass',
+                'waits_tail', 'waits_reclass')
+
+
+def write_reclass(path, rows, args):
+    def fmt(row, c):
+        v = row[c]
+        if isinstance(v, str):
+            return v
+        lo_hi = row.get(c + '_min_max')
+        return f'{v:.4g}' + (f' ({lo_hi[0]:.4g} - {lo_hi[1]:.4g})' if lo_hi else '')
+    with open(path, 'w') as f:
+        f.write('# Planogram comparator: the re-classification in one device pass against the per-image pass\n\n'
+                f'`python tools/bench_planogram_compare.py --batch {args.batch} --launches {args.launches} --reclass-markdown ...`, one process, MI355X.  '
+                'Every 9th planted detection is withheld from the comparator and every 11th expected label is replaced by a label no gallery item '
+                'has; the gallery of 64 carries the planograms\' 12 labels; the shelf images hold every projected position.  `unmatched`: expected '
+                'boxes per image the per-label claim leaves; `positions`: how many of them are valid and classified again; `recovered` / '
+                '`not_recovered`: what the re-classification makes of them (synthetic noise images: a position is recovered when the nearest '
+                'gallery item happens to carry its label).  `compare_batch_*`: ms per image, wall clock around a window that ends in a synchronise; '
+                '`evaluate_iter_*`: images/s of `PlanogramEvaluator.evaluate_iter` with the window as lookahead (detector, crops, embedder and '
+                f'matcher included); both as median (min - max) of {REPEATS} windows per path, the two paths alternating window by window.  `tail`: `device_graphs` + `device_tail` (the '
+                'yardstick: the re-classification per image through the host); `reclass`: `device_reclass` as well.  Per window of '
+                f'{args.batch} images: `kernels` = launches of the project\'s own kernels, `torch_ops` = other torch operators on device tensors '
+                '(copies, gathers), `waits` = points at which the host waits for the device.\n\n')
+        f.write('| scene | ' + ' | '.join(RECLASS_COLS) + ' | same verdict (compare_batch / evaluate_iter) |\n|---|' + '---|' * (len(RECLASS_COLS) + 1) + '\n')
+        for row in rows:
+            f.write(f"| {row['scene']} | " + ' | '.join(fmt(row, c) for c in RECLASS_COLS) +
+                    f" | {row['same_verdict']}/{row['batch']} / {row['same_verdict_iter']}/{row['batch']} |\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--launches', type=int, default=30)
     ap.add_argument('--markdown', help='also write the table to this file')
+    ap.add_argument('--reclass-markdown', help='run the re-classification leg and write its table to this file')
+    ap.add_argument('--reclass-only', action='store_true', help='skip everything but the re-classification leg')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     det = synthetic.synthetic_gln(seed=0, detections_per_img=200).to(dev)
@@ -165,7 +320,14 @@ def main():
                   'tail': PlantedEvaluator(pg, clf, production.PlanogramComparator(device_graphs=True, device_tail=True))}
     images = [synthetic.shelf_image(300 + k, 1024, 1024).to(dev) for k in range(args.batch)]
     rows = []
-    for name, (r, c) in (('24 boxes (4 x 6)', (4, 6)), ('200 boxes (8 x 25)', (8, 25))):
+    grids = (('24 boxes (4 x 6)', (4, 6)), ('200 boxes (8 x 25)', (8, 25)))
+    if args.reclass_markdown:
+        reclass_rows = []
+        for name, (r, c) in grids:
+            reclass_rows.append(time_reclass(name, r, c, args.batch, det, enc, dev))
+            print(json.dumps(reclass_rows[-1]), flush=True)
+        write_reclass(args.reclass_markdown, reclass_rows, args)
+    for name, (r, c) in (() if args.reclass_only else grids):
         pairs = scenes(r, c, args.batch)
         host, host_m = time_host(pairs)
         device, dev_m = time_device(pairs, args.launches)
