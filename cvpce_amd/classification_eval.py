@@ -1,6 +1,8 @@
 """Embed+match top-k accuracy harness -- counterpart of /root/reference/cvpce/classification_eval.py:6-56.
 `testset` yields `(image (3,H,W) f32 in [0,1] or (H,W,3) uint8, list of target annotations, boxes (T,4) integer xyxy)`; with
-num_workers > 0 it is read through `feeding.ImageFeeder` (the gallery reader pool of the `Classifier` has the same size)."""
+num_workers > 0 it is read through `feeding.ImageFeeder` (the gallery reader pool of the `Classifier` has the same size).
+`device_eval=True` (opt-in): `window` images at a time go through `device_classification.ClassificationTally` -- one crop / embed /
+match pass per window, the comparison on the device, one wait at the end; the same counts."""
 import torch
 
 from . import feeding, ops, production, datautils
@@ -16,8 +18,10 @@ def clip_boxes_to_image(boxes, size):
 
 
 @torch.no_grad()
-def eval_dihe(encoder, sampleset, testset, batch_size, num_workers=0, k=(1,), verbose=False):
+def eval_dihe(encoder, sampleset, testset, batch_size, num_workers=0, k=(1,), verbose=False, device_eval=False, window=8):
     classifier = production.Classifier(encoder, sampleset, batch_size=batch_size, num_workers=num_workers, k=max(k))
+    if device_eval:
+        return _eval_dihe_windows(classifier, testset, num_workers, k, verbose, window)
     total, correct = 0, {knn: 0 for knn in k}
     missed, confusion, per_ann = {}, {}, {}
     for i, (img, target_anns, boxes) in enumerate(feeding.feed(testset, num_workers, classifier.device)):
@@ -42,3 +46,28 @@ def eval_dihe(encoder, sampleset, testset, batch_size, num_workers=0, k=(1,), ve
         worst = sorted(((v / per_ann[a], v, a) for a, v in missed.items()), reverse=True)[:10]
         print('Most missed: ' + ', '.join(f'{a} ({n}, {p * 100} %)' for p, n, a in worst))
     return accuracy
+
+
+def _eval_dihe_windows(classifier, testset, num_workers, k, verbose, window):
+    """`eval_dihe` with `device_eval`: the test set is read as above, every `window` images make one `ClassificationTally.update`,
+    and the report is the reference's in full (classification_eval.py:50-55)."""
+    from . import device_classification
+    tally = device_classification.ClassificationTally(classifier, k)
+    pending = []
+
+    def flush():
+        if pending:
+            tally.update(*zip(*pending))
+            pending.clear()
+
+    for i, (img, target_anns, boxes) in enumerate(feeding.feed(testset, num_workers, classifier.device)):
+        if verbose and i % 10 == 0:
+            print(f'{i}...')
+        pending.append((ops.input_image(img, classifier.device), boxes, target_anns))
+        if len(pending) >= max(1, window):
+            flush()
+    flush()
+    result = tally.compute()
+    if verbose:
+        print('\n'.join(device_classification.report(result)))
+    return result['accuracy']

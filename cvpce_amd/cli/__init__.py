@@ -11,7 +11,10 @@ form, decoded that many at a time ahead of the kernels and uploaded from pinned 
 thread; the printed metrics are the same to the last digit, the inputs being the same bits).  The two whole-pipeline commands
 have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
 One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
-(default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`).
+(default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `eval-planograms` takes
+--device-graphs, --device-tail and --device-reclass (default off; `_DeviceReclassCommand`), and `dihe eval` takes --device-eval /
+--no-device-eval (default off: EVAL_WINDOW images at a time are cropped, embedded and matched in one pass and compared on the GPU;
+`_DeviceEvalCommand`).
 
     python -m cvpce_amd.cli --help
 """
@@ -167,6 +170,19 @@ def _device_reclass_switch():
     return bool(click.get_current_context().meta.get(_DeviceReclassCommand.RECLASS_KEY, False))
 
 
+class _DeviceEvalCommand(_DeviceMetricsCommand):
+    """The same arrangement for --device-eval / --no-device-eval (default: off) of `dihe eval`."""
+    SWITCH = {'--device-eval': True, '--no-device-eval': False}
+    HELP = ('Crop, embed and match a window of test images in one GPU pass and compare label ids there instead of image by image '
+            'through the host (cvpce_amd.device_classification; the same counts).  [default: off]')
+    KEY = 'cvpce_amd.device_eval'
+    LABEL = '--device-eval / --no-device-eval'
+
+
+def _device_eval_switch():
+    return bool(click.get_current_context().meta.get(_DeviceEvalCommand.KEY, False))
+
+
 @click.group()
 def cli():
     """Computer vision based planogram compliance evaluation -- MI355X inference / evaluation commands."""
@@ -252,7 +268,7 @@ def dihe():
     """Product classification (DIHE embedder)."""
 
 
-@dihe.command(name='eval')
+@dihe.command(name='eval', cls=_DeviceEvalCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to GP training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to GP test image root')
@@ -285,7 +301,8 @@ def dihe_eval(img_dir, test_imgs, annotations, model, resnet_layers, batch_norm,
     elif only == 'val':
         only_list = GP_TEST_VALIDATION_SET_SIZE
     testset = datautils.GroceryProductsTestSet(test_imgs, annotations, only=only_list, skip=skip_list, image_format='uint8')
-    accuracy = classification_eval.eval_dihe(encoder, sampleset, testset, batch_size, dataloader_workers, k=knn, verbose=True)
+    accuracy = classification_eval.eval_dihe(encoder, sampleset, testset, batch_size, dataloader_workers, k=knn, verbose=True,
+                                             device_eval=_device_eval_switch(), window=EVAL_WINDOW)
     print(f'--> accuracy {accuracy}')
 
 
