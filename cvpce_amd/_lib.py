@@ -1,8 +1,8 @@
 """ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h, the
 8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
 include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
-include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h and the classification
-harness's kernel of include/cvpce_amd_classeval.h).
+include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
+harness's kernel of include/cvpce_amd_classeval.h and the detections kernels of include/cvpce_amd_actuals.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -142,8 +142,14 @@ CLASSEVAL_SIGNATURES = {
     'cvpce_classeval_rank': (c_int, [_vp, _ip, _ip] + [c_int] * 3 + [_ip, _vp]),
 }
 
+# include/cvpce_amd_actuals.h: a window's detections as the comparator's actual side.  A table of its own, like the header.
+ACTUALS_SIGNATURES = {
+    'cvpce_actuals_count': (c_int, [_fp, _ip, c_int, c_int, _ip, _vp]),
+    'cvpce_actuals_pack': (c_int, [_fp, _ip, _vp, c_int, _ip, c_int, _ip, c_float, c_int, c_int, c_int, _fp, _ip, _ip, _fp, _ip, _vp]),
+}
+
 for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES):
+               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

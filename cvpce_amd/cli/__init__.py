@@ -12,7 +12,7 @@ thread; the printed metrics are the same to the last digit, the inputs being the
 have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
 One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
 (default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `eval-planograms` takes
---device-graphs, --device-tail and --device-reclass (default off; `_DeviceReclassCommand`), and `dihe eval` takes --device-eval /
+--device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`), and `dihe eval` takes --device-eval /
 --no-device-eval (default off: EVAL_WINDOW images at a time are cropped, embedded and matched in one pass and compared on the GPU;
 `_DeviceEvalCommand`).
 
@@ -168,6 +168,38 @@ class _DeviceReclassCommand(_DeviceTailCommand):
 
 def _device_reclass_switch():
     return bool(click.get_current_context().meta.get(_DeviceReclassCommand.RECLASS_KEY, False))
+
+
+class _DeviceDetectionsCommand(_DeviceReclassCommand):
+    """The three switches above, and --device-detections / --no-device-detections (default: off) beside them, arranged the same way."""
+    DETECTIONS_SWITCH = {'--device-detections': True, '--no-device-detections': False}
+    DETECTIONS_HELP = ('Also keep a window\'s detections on the GPU from the matcher to the comparator instead of copying them to the host '
+                       '(cvpce_amd.planograms_device.DeviceActuals; the documented detections rule).  Needs --device-tail: without it the '
+                       'command stops with an error.  [default: off]')
+    DETECTIONS_KEY = 'cvpce_amd.device_detections'
+    DETECTIONS_LABEL = '--device-detections / --no-device-detections'
+
+    def parse_args(self, ctx, args):
+        rest = []
+        ctx.meta[self.DETECTIONS_KEY] = False
+        for i, a in enumerate(args):
+            if a == '--':
+                rest += args[i:]
+                break
+            if a in self.DETECTIONS_SWITCH:
+                ctx.meta[self.DETECTIONS_KEY] = self.DETECTIONS_SWITCH[a]
+            else:
+                rest.append(a)
+        tails = [self.TAIL_SWITCH[a] for a in (rest[:rest.index('--')] if '--' in rest else rest) if a in self.TAIL_SWITCH]
+        if ctx.meta[self.DETECTIONS_KEY] and not (tails and tails[-1]) and not ctx.resilient_parsing:
+            raise click.UsageError('--device-detections needs --device-tail', ctx)        # (it implies nothing on its own)
+        return super().parse_args(ctx, rest)
+
+    MORE = _DeviceReclassCommand.MORE + ((DETECTIONS_LABEL, DETECTIONS_HELP),)
+
+
+def _device_detections_switch():
+    return bool(click.get_current_context().meta.get(_DeviceDetectionsCommand.DETECTIONS_KEY, False))
 
 
 class _DeviceEvalCommand(_DeviceMetricsCommand):
@@ -361,7 +393,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command(cls=_DeviceReclassCommand)
+@cli.command(cls=_DeviceDetectionsCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -390,7 +422,8 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
     evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
                                                                                               device_tail=_device_tail_switch(),
-                                                                                              device_reclass=_device_reclass_switch()))
+                                                                                              device_reclass=_device_reclass_switch()),
+                                              device_detections=_device_detections_switch())
     total_a = total_e = 0.0
     # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
     # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,

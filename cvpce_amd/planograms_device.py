@@ -11,6 +11,9 @@
   finalize_result    a record of `finalize_batch` as the tuple `finalize_via_ransac` returns
   to_networkx        a device graph as the DiGraph the host functions expect (node order 0..n-1, adjacency in stamp order)
   prepare            caches a planogram's device graph in its dict, as `expected['graph']` caches the host graph
+  DeviceActuals      a window's detections as `BatchedPipeline.run(actuals=True)` left them on the device (csrc/actuals.hip): the actual
+                     side of `build_graphs`, `match_on_device` and `finalize_batch` without a copy to the host (the detections rule of
+                     DESIGN.md 4b)
 
 A graph is three [n][8] tables -- per node and direction slot (planograms.CARDINALS) the neighbour, the edge weight and an insertion
 stamp -- plus the labels.  networkx's adjacency order is edge insertion order and decides the order in which the common subgraph
@@ -35,6 +38,8 @@ from .planograms import CARDINALS
 from .torch_ops_planogram import MAX_NODES
 
 CACHE_KEY = 'device_graph'
+BOXES_KEY = 'device_boxes'        # a planogram dict's boxes on the device (`expected_boxes_on_device`)
+IDS_KEY = 'device_label_ids'      # a planogram dict's expected labels in the classifier's id space (`expected_label_ids`)
 RANSAC_HYPOTHESES = 2048          # per image, all evaluated (the host's adaptive loop stops at 2000 at the latest)
 STATUS = ('ok', 'none', 'invalid')
 
@@ -49,6 +54,51 @@ class Graph:
 
     def __len__(self):
         return len(self.labels)
+
+
+class DeviceActuals:
+    """The detections of a window where `actuals_pack` left them.  On the device: `boxes` [sum2][4] f32 -- every image's kept
+    (non-degenerate, confident) boxes back to back in slot order --, `row` and `label` [sum2] int32 (each box's nearest gallery row and
+    that row's id in the classifier's id space), `thresh` [B] f32 (`graph_threshold` of each image's kept boxes; unwritten for an
+    image that keeps nothing), `status` [B] int32 (0, or what `actuals_pack` found wrong) and `off2` [B+1] int32, the row offsets.
+    On the host: `n2`, the list of the images' box counts, and `thresh_size`, the fraction the thresholds were computed with."""
+    __slots__ = ('boxes', 'row', 'label', 'thresh', 'status', 'off2', 'n2', 'thresh_size')
+
+    def __init__(self, boxes, row, label, thresh, status, off2, n2, thresh_size):
+        self.boxes, self.row, self.label, self.thresh, self.status, self.off2 = boxes, row, label, thresh, status, off2
+        self.n2, self.thresh_size = list(n2), thresh_size
+
+    def __len__(self):
+        return len(self.n2)
+
+    def to_host(self, i, annotations):
+        """-> (boxes (n, 4) on the host, the n label strings) of image i: what `detect_and_classify_batch` hands to the comparator.
+        (Two blocking copies: for an image that takes the host path.)"""
+        o = sum(self.n2[:i])
+        rows = self.row[o:o + self.n2[i]].cpu().tolist()
+        return self.boxes[o:o + self.n2[i]].cpu(), [annotations[r] for r in rows]
+
+    def select(self, images):
+        """-> the pack of the images `images` (ascending indices), gathered on the device; all of them: the pack itself"""
+        images = list(images)
+        if images == list(range(len(self.n2))):
+            return self
+        off = _offsets(self.n2)
+        return self.concat([DeviceActuals(self.boxes[off[i]:off[i + 1]], self.row[off[i]:off[i + 1]], self.label[off[i]:off[i + 1]],
+                                          self.thresh[i:i + 1], self.status[i:i + 1], None, [self.n2[i]], self.thresh_size) for i in images])
+
+    @staticmethod
+    def concat(packs):
+        """The packs of several size groups (or images) as one, joined on the device; only the new offsets are uploaded."""
+        packs = list(packs)
+        if len(packs) == 1 and packs[0].off2 is not None:
+            return packs[0]
+        if not packs or any(p.thresh_size != packs[0].thresh_size for p in packs):
+            raise ValueError('at least one pack, all made with one thresh_size')
+        n2 = [n for p in packs for n in p.n2]
+        cat = lambda name: torch.cat([getattr(p, name) for p in packs])
+        off2 = _upload(torch.tensor(_offsets(n2), dtype=torch.int32), packs[0].boxes.device)
+        return DeviceActuals(cat('boxes'), cat('row'), cat('label'), cat('thresh'), cat('status'), off2, n2, packs[0].thresh_size)
 
 
 def graph_threshold(boxes, thresh_size):
@@ -70,7 +120,10 @@ def _offsets(lengths):
 
 def build_graphs(items, thresh_size=0.5, device=None):
     """items: list of (boxes (n,4) xyxy, labels list of n) -> list of `Graph` on the device, built by one launch.  1 <= n <= MAX_NODES.
-    Device work only: nothing is copied back."""
+    Device work only: nothing is copied back.  items may be a `DeviceActuals` instead: its boxes, offsets and thresholds are read
+    where they lie, nothing is uploaded, and the graphs' `labels` are placeholders (the ids are `DeviceActuals.label`)."""
+    if isinstance(items, DeviceActuals):
+        return _build_actual_graphs(items, thresh_size)
     if not items:
         return []
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else device
@@ -94,6 +147,21 @@ def build_graphs(items, thresh_size=0.5, device=None):
     return [Graph(labels, nbr[o:o + n], weight[o:o + n], stamp[o:o + n], parent + (o,)) for (_, labels), o, n in zip(items, off, sizes)]
 
 
+def _build_actual_graphs(actuals, thresh_size):
+    sizes = actuals.n2
+    if actuals.thresh_size != thresh_size:
+        raise ValueError(f'the detections carry thresholds for thresh_size {actuals.thresh_size}, not {thresh_size}')
+    if not sizes or not 1 <= min(sizes) or max(sizes) > MAX_NODES:
+        raise ValueError(f'a device graph has between 1 and {MAX_NODES} nodes, got {sizes}')
+    device, total = actuals.boxes.device, sum(sizes)
+    nbr = torch.empty((total, 8), dtype=torch.int32, device=device)
+    weight = torch.empty((total, 8), dtype=torch.float32, device=device)
+    stamp = torch.empty((total, 8), dtype=torch.int32, device=device)
+    torch.ops.cvpce_amd.planogram_graphs(actuals.boxes, actuals.off2, actuals.thresh, min(sizes), max(sizes), nbr, weight, stamp)
+    parent = (nbr, weight, stamp)
+    return [Graph([None] * n, nbr[o:o + n], weight[o:o + n], stamp[o:o + n], parent + (o,)) for o, n in zip(_offsets(sizes), sizes)]
+
+
 def _packed(graphs, device):
     """-> (nbr, stamp) of the graphs packed back to back.  Graphs that are consecutive slices of one launch's tables are not copied."""
     first = graphs[0]._parent
@@ -113,28 +181,39 @@ def min_agree_for(min_score):
     return next((a for a in range(len(CARDINALS) + 1) if not -(a / len(CARDINALS)) > min_score), len(CARDINALS) + 1)
 
 
-def _prepare_match(expected, actual, min_score, stop_at_fraction):
-    """Everything `planogram_match` needs, uploaded -> (argument tuple of the op, its output tensor = pairs then counts, row offsets)."""
+def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, expected_ids=None):
+    """Everything `planogram_match` needs, uploaded -> (argument tuple of the op, its output tensor = pairs then counts, row offsets).
+    actuals (a `DeviceActuals`, with expected_ids = `expected_label_ids`' (ids, largest multiplicity) per planogram): the actual side's
+    ids and offsets are the pack's own, the expected ids come from the classifier's id space, and the hypothesis workspace is sized by
+    the host's bound n2 x (largest multiplicity of an expected label) -- the kernel counts the hypotheses itself."""
     device = actual[0].nbr.device
     if device.type != 'cuda':
         raise ValueError('common_subgraphs runs on device graphs (build_graphs)')
     for g in list(expected) + list(actual):
         if not 1 <= len(g) <= MAX_NODES:
             raise ValueError(f'a device graph has between 1 and {MAX_NODES} nodes, got {len(g)}')
-    ids = {}
-    lab1 = [ids.setdefault(l, len(ids)) for g in expected for l in g.labels]
-    lab2 = [ids.setdefault(l, len(ids)) for g in actual for l in g.labels]
     n1, n2 = [len(g) for g in expected], [len(g) for g in actual]
     off1, off2 = _offsets(n1), _offsets(n2)
     hyps, params = [], []
+    if actuals is None:
+        ids = {}
+        lab1 = [ids.setdefault(l, len(ids)) for g in expected for l in g.labels]
+        lab2 = [ids.setdefault(l, len(ids)) for g in actual for l in g.labels]
+    else:
+        if n2 != actuals.n2 or [len(e[0]) for e in expected_ids] != n1:
+            raise ValueError('the graphs of the detections, one id vector per expected graph')
+        lab1, lab2 = [v for e in expected_ids for v in e[0]], []
     for p, (a, b) in enumerate(zip(n1, n2)):
-        c1, c2 = Counter(lab1[off1[p]:off1[p + 1]]), Counter(lab2[off2[p]:off2[p + 1]])
-        hyps.append(sum(c * c2[l] for l, c in c1.items() if l in c2))
+        if actuals is None:
+            c1, c2 = Counter(lab1[off1[p]:off1[p + 1]]), Counter(lab2[off2[p]:off2[p + 1]])
+            hyps.append(sum(c * c2[l] for l, c in c1.items() if l in c2))
+        else:
+            hyps.append(b * expected_ids[p][1])
         params += [min_agree_for(min_score), int(min(a, b) * stop_at_fraction)]
     hyp_off, out_off = _offsets(hyps), _offsets([min(a, b) for a, b in zip(n1, n2)])
     if hyp_off[-1] >= 2 ** 31:
         raise ValueError('too many equal-label node pairs for one launch: split the batch')
-    parts = [lab1, lab2, off1, off2, params, hyp_off, out_off]
+    parts = [lab1, lab2, off1, off2 if actuals is None else [], params, hyp_off, out_off]
     small = _upload(torch.tensor([v for part in parts for v in part], dtype=torch.int32), device)      # one upload for all the small tables
     views, at = [], 0
     for part in parts:
@@ -145,6 +224,8 @@ def _prepare_match(expected, actual, min_score, stop_at_fraction):
     workspace = torch.empty(max(hyp_off[-1], 1), dtype=torch.int32, device=device)
     out = torch.empty(out_off[-1] * 2 + len(n1), dtype=torch.int32, device=device)      # the pairs, then the counts: one copy back
     pairs, count = out[:out_off[-1] * 2].view(-1, 2), out[out_off[-1] * 2:]
+    if actuals is not None:
+        views[1], views[3] = actuals.label, actuals.off2
     args = (nbr1, stamp1, views[0], views[2], nbr2, stamp2, views[1], views[3], views[4], views[5], views[6],
             max(n1), max(n2), hyp_off[-1], workspace, pairs, count)
     return args, out, out_off
@@ -181,11 +262,12 @@ class DeviceMatching:
     __slots__ = ('pairs', 'count', 'out_off', 'out', 'label1', 'off1', 'label2', 'off2', 'n1', 'n2', 'rows')
 
 
-def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
-    """The launch of `common_subgraphs` alone -> `DeviceMatching`; nothing is copied back and nothing is waited for."""
+def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, actuals=None, expected_ids=None):
+    """The launch of `common_subgraphs` alone -> `DeviceMatching`; nothing is copied back and nothing is waited for.
+    actuals / expected_ids: the actual side is a `DeviceActuals` (`actual` = its graphs), see `_prepare_match`."""
     if len(expected) != len(actual) or not expected:
         raise ValueError('one actual graph per expected graph, at least one pair')
-    args, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction)
+    args, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction, actuals, expected_ids)
     torch.ops.cvpce_amd.planogram_match(*args)
     m = DeviceMatching()
     m.label1, m.off1, m.label2, m.off2, m.out_off, m.pairs, m.count = args[2], args[3], args[6], args[7], args[10], args[15], args[16]
@@ -204,12 +286,27 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
         raise ValueError(f'between 1 and {torch_ops_homography.MAX_HYPOTHESES} hypotheses, got {hypotheses}')
     device = matching.pairs.device
     n1, n2 = matching.n1, matching.n2
-    for boxes, n in zip(list(expected_boxes) + list(actual_boxes), n1 + n2):
+    on_device = isinstance(actual_boxes, DeviceActuals)
+    if on_device and actual_boxes.n2 != n2:
+        raise ValueError('the detections that were matched')
+    for boxes, n in zip(list(expected_boxes) + ([] if on_device else list(actual_boxes)), n1 + n2):
         if boxes.dim() != 2 or boxes.shape[0] != n or boxes.shape[1] != 4:
             raise ValueError('the boxes of the graphs that were matched, (n, 4) each')
     sum1, sum2 = sum(n1), sum(n2)
-    host = torch.cat([bx.detach().to(device='cpu', dtype=torch.float32) for bx in list(expected_boxes) + list(actual_boxes)]).contiguous()
-    boxes = _upload(host, device)
+
+    def packed(sets):
+        """box sets back to back on the device: sets that lie there already (`expected_boxes_on_device`) are joined there"""
+        if all(bx.device == device and bx.dtype == torch.float32 for bx in sets):
+            return sets[0].contiguous() if len(sets) == 1 else torch.cat(sets)
+        return _upload(torch.cat([bx.detach().to(device='cpu', dtype=torch.float32) for bx in sets]).contiguous(), device)
+
+    if on_device:
+        boxes1, boxes2 = packed(list(expected_boxes)), actual_boxes.boxes
+    elif any(bx.device == device for bx in expected_boxes):
+        boxes1, boxes2 = packed(list(expected_boxes)), packed(list(actual_boxes))
+    else:                                         # (host boxes on both sides: one upload)
+        boxes = packed(list(expected_boxes) + list(actual_boxes))
+        boxes1, boxes2 = boxes[:sum1], boxes[sum1:]
     params = _upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
     workspace = torch.empty(max(torch_ops_homography.workspace_bytes(b, hypotheses), 8) // 4, dtype=torch.int32, device=device)
     at_h, at_i = 16 * sum1, 16 * sum1 + 72 * b
@@ -219,8 +316,8 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
     me, ma = i32[5 * b:5 * b + sum1], i32[5 * b + sum1:]
     max_pairs = max(1, max(min(a, c) for a, c in zip(n1, n2)))
     common = (matching.pairs, matching.count, matching.out_off, params)
-    ransac = (boxes[:sum1], matching.off1, boxes[sum1:], matching.off2, *common, max_pairs, seed, hypotheses, workspace)
-    finish = (boxes[:sum1], matching.label1, matching.off1, boxes[sum1:], matching.label2, matching.off2, *common, max(n1), max(n2), max_pairs,
+    ransac = (boxes1, matching.off1, boxes2, matching.off2, *common, max_pairs, seed, hypotheses, workspace)
+    finish = (boxes1, matching.label1, matching.off1, boxes2, matching.label2, matching.off2, *common, max(n1), max(n2), max_pairs,
               seed, hypotheses, workspace, status, hmat, winner, wcount, fcount, me, ma, pos)
     return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b])
 
@@ -298,7 +395,9 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
                    hypotheses=RANSAC_HYPOTHESES, reclass=None):
     """`planograms.finalize_via_ransac` for every image of a batch under the tail rule: two launches on the matchings
     as they lie on the device (`match_on_device`) and ONE pinned copy back.  expected / actual: the lists of `Graph` the matching was
-    made from; expected_boxes / actual_boxes: their (n, 4) boxes; reproj_thresholds: one per image, in pixels.
+    made from; expected_boxes / actual_boxes: their (n, 4) boxes; reproj_thresholds: one per image, in pixels.  Expected boxes that lie
+    on the device (`expected_boxes_on_device`) are not uploaded again; actual_boxes may be the `DeviceActuals` the matching was made
+    from: its boxes are read where they lie and its `status` comes back in the same wait (non-zero: RuntimeError).
     -> one record per image: {'status': 'ok' | 'none' | 'invalid', 'matched_expected', 'matched_actual' (bool), 'expected_positions'
     (float32 (n1, 4)), 'homography' (3 x 3 float64, None unless ok), 'inliers' (of the refit), 'points', 'matching' (its size),
     'winner', 'winner_inliers'}.
@@ -315,7 +414,13 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
     sum1 = sum(n1)
     back = torch.empty(blob.shape, dtype=torch.uint8).pin_memory()
     back.copy_(blob, non_blocking=True)
+    pack_status = None
+    if isinstance(actual_boxes, DeviceActuals):                   # (what `actuals_pack` reported comes back in the same wait)
+        pack_status = torch.empty(b, dtype=torch.int32).pin_memory()
+        pack_status.copy_(actual_boxes.status, non_blocking=True)
     torch.cuda.current_stream(blob.device).synchronize()
+    if pack_status is not None and any(pack_status.tolist()):
+        raise RuntimeError(f'actuals_pack: status {pack_status.tolist()} (1: the kept count is not the offsets\', 2: a gallery row outside the gallery)')
     if plan is not None:
         plan.counts = plan_counts.tolist()
     pos, hmat, i32 = back[:at_h].view(torch.float32).view(sum1, 4), back[at_h:at_i].view(torch.float64).view(b, 3, 3), back[at_i:].view(torch.int32)
@@ -371,3 +476,46 @@ def prepare(expected, thresh_size=0.5, device=None):
 def cached(expected, thresh_size):
     c = expected.get(CACHE_KEY) if isinstance(expected, dict) else None
     return c[1] if c is not None and c[0] == thresh_size else None
+
+
+def expected_boxes_on_device(expected, device):
+    """A planogram's boxes as the tail kernels read them -- float32 (n, 4) on `device` -- uploaded once and kept in the planogram's
+    dict under BOXES_KEY beside the cached graph (with the host tensor they were made from: other boxes, another upload)."""
+    boxes = expected['boxes']
+    c = expected.get(BOXES_KEY) if isinstance(expected, dict) else None
+    if c is None or c[0] is not boxes or c[1].device != device:
+        c = (boxes, _upload(boxes.detach().to(device='cpu', dtype=torch.float32).contiguous(), device))
+        if isinstance(expected, dict):
+            expected[BOXES_KEY] = c
+    return c[1]
+
+
+def expected_label_ids(planograms, classifier):
+    """The expected labels of a window as ids the match and claim kernels can compare with `DeviceActuals.label`: a label some gallery
+    item has gets its id of `classifier.label_ids`; a label no gallery item has gets len(label_ids) + r, r = its rank among such
+    labels in the window in order of appearance -- non-negative (the match kernel masks ids with INT_MAX), and equal id <=> equal
+    label across the window.  -> one (ids, largest multiplicity of a label) per planogram, or None where there is no id space or a
+    label cannot be hashed.  What does not depend on the window is cached in the planogram's dict under IDS_KEY with the classifier's
+    index generation, as `PlanogramComparator.LABEL_IDS_KEY` is."""
+    space, generation = getattr(classifier, 'label_ids', None), getattr(classifier, 'index_generation', None)
+    if space is None or generation is None:
+        return None
+    ranks, out = {}, []
+    for plano in planograms:
+        labels = plano['labels']
+        c = plano.get(IDS_KEY) if isinstance(plano, dict) else None
+        if c is None or c[0] != generation or len(c[1]) != len(labels):
+            try:
+                ids = [space.get(l, -1) for l in labels]
+                c = (generation, ids, [i for i, v in enumerate(ids) if v < 0], max(Counter(labels).values(), default=0))
+            except TypeError:
+                return None
+            if isinstance(plano, dict):
+                plano[IDS_KEY] = c
+        ids = c[1]
+        if c[2]:
+            ids = list(ids)
+            for i in c[2]:
+                ids[i] = len(space) + ranks.setdefault(labels[i], len(ranks))
+        out.append((ids, c[3]))
+    return out

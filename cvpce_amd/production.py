@@ -378,8 +378,14 @@ class PlanogramComparator:
         and one copy back; the host tail (homography, per-label claim, re-classification) runs per image -- with `device_tail` the
         homography and the claim are two more launches of the window and only the re-classification stays per image; with
         `device_reclass` that is one pass of the window as well (`_reclassified`: two waits, whatever the number of images with
-        positions to classify).  With `device_graphs` off it is the plain loop."""
+        positions to classify).  With `device_graphs` off it is the plain loop.  `actuals` may be a `planograms_device.DeviceActuals` --
+        a window's detections as `BatchedPipeline.run(actuals=True)` left them on the device -- where `device_graphs` and `device_tail`
+        are on (`_compare_device_actuals`)."""
         images = [None] * len(expecteds) if images is None else images
+        if not isinstance(actuals, (list, tuple)):
+            from . import planograms_device
+            if isinstance(actuals, planograms_device.DeviceActuals):          # (detections that never left the device)
+                return self._compare_device_actuals(expecteds, actuals, images, classifier)
         if not self.device_graphs:
             return [self._compare_host(e, a, img, classifier) for e, a, img in zip(expecteds, actuals, images)]
         from . import planograms_device as pd
@@ -403,7 +409,7 @@ class PlanogramComparator:
                 ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
                 if ids is not None:
                     return self._reclassified(results, todo, ge, ga, ids, expecteds, actuals, images, classifier)
-                records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [expecteds[i]['boxes'] for i in todo],
+                records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
                                             [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo])
                 for i, rec in zip(todo, records):
                     tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
@@ -412,6 +418,62 @@ class PlanogramComparator:
             matchings = pd.common_subgraphs(ge, ga)
             for i, matching in zip(todo, matchings):
                 results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
+        return results
+
+    def _compare_device_actuals(self, expecteds, actuals, images, classifier):
+        """`compare_batch` on detections that never left the device (`planograms_device.DeviceActuals`; the detections rule of
+        DESIGN.md 4b): the graph, match and tail kernels read the pack's boxes, label ids and thresholds where `actuals_pack` left
+        them; the host knows the box counts alone.  An image without detections is decided here; an image whose expected or actual
+        graph has no device form comes back through `to_host` and takes `_compare_host` (`host_routed`); so does a window whose
+        expected labels have no ids (a label that cannot be hashed)."""
+        from . import planograms_device as pd
+        if not (self.device_graphs and self.device_tail):
+            raise ValueError('device detections need device_graphs and device_tail: the kernels read the detections where they lie')
+        if classifier is None or len(actuals) != len(expecteds):
+            raise ValueError('one image of the pack per planogram, and the classifier whose id space the pack was labelled in')
+        if actuals.thresh_size != self.graph_threshold:
+            raise ValueError(f'the detections carry thresholds for graph_threshold {actuals.thresh_size}, the comparator has {self.graph_threshold}')
+        results, todo, routed = [None] * len(expecteds), [], []
+        for i, (e, n2) in enumerate(zip(expecteds, actuals.n2)):
+            if not n2:
+                results[i] = 0 if len(e['boxes']) else 1
+            elif not 1 <= len(e['boxes']) <= pd.MAX_NODES or n2 > pd.MAX_NODES:
+                routed.append(i)
+            else:
+                todo.append(i)
+        ids = pd.expected_label_ids([expecteds[i] for i in todo], classifier) if todo else None
+        if ids is None:
+            routed, todo = sorted(routed + todo), []
+        for i in routed:
+            self.host_routed += 1
+            boxes, labels = actuals.to_host(i, classifier.annotations)
+            results[i] = self._compare_host(expecteds[i], {'boxes': boxes, 'labels': labels}, images[i], classifier)
+        if not todo:
+            return results
+        pack = actuals.select(todo)
+        es, imgs = [expecteds[i] for i in todo], [images[i] for i in todo]
+        have = [pd.cached(e, self.graph_threshold) for e in es]
+        fresh = iter(pd.build_graphs([(e['boxes'], e['labels']) for e, h in zip(es, have) if h is None], self.graph_threshold))
+        ge = [h if h is not None else next(fresh) for h in have]
+        ga = pd.build_graphs(pack, self.graph_threshold)
+        matching = pd.match_on_device(ge, ga, actuals=pack, expected_ids=ids)
+        device = pack.boxes.device
+        boxes1 = [pd.expected_boxes_on_device(e, device) for e in es]
+        reproj = [self._reproj_threshold(img) for img in imgs]
+        reclass_ids = self._window_label_ids(es, classifier) if self.device_reclass else None
+        if reclass_ids is None:
+            records = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj)
+            found = None
+        else:
+            table = [datautils.image_hw(img) + (1,) if img is not None else (0, 0, 0) for img in imgs]
+            records, plan = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, reclass=table)
+            found = pd.reclassify_batch(plan, imgs, classifier, reclass_ids) if sum(plan.counts) else None
+        for p, (i, rec) in enumerate(zip(todo, records)):
+            if found is not None and rec['status'] == 'ok':
+                results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
+            else:                               # (`_finish` reads the actual side only where it has to compute the tail itself)
+                tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
+                results[i] = self._finish(rec['matching'], expecteds[i], None, images[i], classifier, tail)
         return results
 
     LABEL_IDS_KEY = 'reclass_label_ids'           # a planogram dict's cached id vector, beside planograms_device.CACHE_KEY
@@ -449,7 +511,7 @@ class PlanogramComparator:
         for i in todo:
             on = classifier is not None and images[i] is not None
             table.append(datautils.image_hw(images[i]) + (1,) if on else (0, 0, 0))
-        records, plan = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [expecteds[i]['boxes'] for i in todo],
+        records, plan = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
                                           [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], reclass=table)
         found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, ids) if sum(plan.counts) else None
         for p, (i, rec) in enumerate(zip(todo, records)):
@@ -497,10 +559,19 @@ class PlanogramComparator:
 class PlanogramEvaluator:
     """production.py:118-129 glue; `planogram_comparator` is any object with `.compare(expected, actual, image, classifier)`."""
 
-    def __init__(self, proposal_generator, classifier, planogram_comparator):
+    def __init__(self, proposal_generator, classifier, planogram_comparator, device_detections=False):
+        """device_detections (opt-in, needs a comparator with device_graphs and device_tail): a window's detections are never copied
+        to the host before the verdict (the detections rule of DESIGN.md 4b): `BatchedPipeline.run(actuals=True)` counts and packs
+        the confident, non-degenerate boxes with their label ids on the device, and the comparator's kernels read them there -- two
+        blocking copies and a Python lookup per detection less per size group.  `detections_host_routed` counts the windows that
+        took the host route with the switch on (a classifier without an id space)."""
+        if device_detections and not (getattr(planogram_comparator, 'device_graphs', False) and getattr(planogram_comparator, 'device_tail', False)):
+            raise ValueError('device_detections needs a comparator with device_graphs and device_tail: its kernels read the detections where they lie')
         self.proposal_generator = proposal_generator
         self.classifier = classifier
         self.planogram_comparator = planogram_comparator
+        self.device_detections = device_detections
+        self.detections_host_routed = 0
 
     def _float_image(self, image):
         """An 8-bit image becomes the device image here, ONCE (`ops.input_image`: the bytes themselves with ops.U8_KERNELS on, the float
@@ -514,6 +585,8 @@ class PlanogramEvaluator:
 
     def evaluate(self, image, planogram):
         image = self._float_image(image)
+        if self._on_device():
+            return self._evaluate_on_device([image], [planogram])[0]
         boxes, images = self.proposal_generator.generate_proposals_and_images(image)
         classes = [ann[0] for ann in self.classifier.classify(images)]
         return self.planogram_comparator.compare(planogram, {'boxes': boxes.detach().cpu(), 'labels': classes},
@@ -527,15 +600,9 @@ class PlanogramEvaluator:
         sizes are never mixed in a batch (the padded batch shape enters the anchors, like in torchvision), and the zero-area
         boxes `generate_proposals_and_images` drops are dropped here too."""
         pg = self.proposal_generator
-        pipe = self.__dict__.get('_pipe')
-        if pipe is None or pipe.detector is not pg.detector or pipe.classifier is not self.classifier:
-            pipe = self._pipe = BatchedPipeline(pg.detector, self.classifier, pg.condfidence_threshold)
-        pipe.confidence_threshold = pg.condfidence_threshold
+        pipe = self._pipeline()
         out = [None] * len(images)
-        groups = {}
-        for i, img in enumerate(images):
-            groups.setdefault(datautils.image_hw(ops.check_image_form(img)), []).append(i)
-        for idxs in groups.values():
+        for idxs in self._size_groups(images):
             res = pipe.run([ops.input_image(images[i], pg.device) for i in idxs])
             boxes, indices = res['boxes'].cpu(), res['indices'][:, :, 0].cpu()
             for j, i in enumerate(idxs):
@@ -547,11 +614,59 @@ class PlanogramEvaluator:
                 out[i] = (b, [self.classifier.annotations[k] for k in ix.tolist()])
         return out
 
+    def _pipeline(self):
+        pg = self.proposal_generator
+        pipe = self.__dict__.get('_pipe')
+        if pipe is None or pipe.detector is not pg.detector or pipe.classifier is not self.classifier:
+            pipe = self._pipe = BatchedPipeline(pg.detector, self.classifier, pg.condfidence_threshold)
+        pipe.confidence_threshold = pg.condfidence_threshold
+        return pipe
+
+    @staticmethod
+    def _size_groups(images):
+        """the indices of the images of each size, in order of first appearance (images of different sizes never share a batch)"""
+        groups = {}
+        for i, img in enumerate(images):
+            groups.setdefault(datautils.image_hw(ops.check_image_form(img)), []).append(i)
+        return list(groups.values())
+
+    def _on_device(self):
+        """Whether this window's detections stay on the device: the switch, and a classifier with an id space to label them in."""
+        if not self.device_detections:
+            return False
+        if getattr(self.classifier, 'label_ids', None) is None:
+            self.detections_host_routed += 1
+            return False
+        return True
+
+    def _evaluate_on_device(self, images, planograms):
+        """A window with `device_detections`: `run(actuals=True)` per size group, the packs joined on the device, ONE `compare_batch`
+        on them (in group order; the verdicts go back to the images' order)."""
+        from . import planograms_device as pd
+        pg, cmp = self.proposal_generator, self.planogram_comparator
+        pipe = self._pipeline()
+        pipe.actuals_thresh_size = cmp.graph_threshold
+        planograms = list(planograms)
+        if not images:
+            return []
+        order, packs = [], []
+        for idxs in self._size_groups(images):
+            packs.append(pipe.run([ops.input_image(images[i], pg.device) for i in idxs], actuals=True)['actuals'])
+            order += idxs
+        verdicts = cmp.compare_batch([planograms[i] for i in order], pd.DeviceActuals.concat(packs), [images[i] for i in order], self.classifier)
+        out = [None] * len(images)
+        for i, v in zip(order, verdicts):
+            out[i] = v
+        return out
+
     def evaluate_batch(self, images, planograms):
         """[evaluate(image, planogram) for image, planogram in zip(...)] with the detect / crop / embed / match half batched
         (`detect_and_classify_batch`); the comparator (CPU graph matching, RANSAC, re-classification of missing positions) runs
-        per image as in production.py:123-129."""
+        per image as in production.py:123-129.  With `device_detections` the detections go from the matcher to the comparator's
+        kernels on the device (`_evaluate_on_device`)."""
         images = [self._float_image(img) for img in images]
+        if self._on_device():
+            return self._evaluate_on_device(images, planograms)
         dets = self.detect_and_classify_batch(images)
         return self._compare_all(images, planograms, dets)
 
@@ -576,6 +691,10 @@ class PlanogramEvaluator:
         window = []
 
         def flush():
+            if self._on_device():
+                yield from self._evaluate_on_device([img for img, _ in window], [plano for _, plano in window])
+                window.clear()
+                return
             dets = self.detect_and_classify_batch([img for img, _ in window])
             if getattr(self.planogram_comparator, 'device_graphs', False):
                 yield from self._compare_all([img for img, _ in window], [plano for _, plano in window], dets)
@@ -685,13 +804,16 @@ class BatchedPipeline:
                 'indices': indices.view(n, dpi, k), 'gaussians': gauss, 'embeddings': emb, 'counts_host': counts}
 
     @torch.no_grad()
-    def run(self, images, stage_events=None, proposals=None):
+    def run(self, images, stage_events=None, proposals=None, actuals=False):
         """images: list of (3,H,W) f32 cuda tensors (or 8-bit (H,W,3) images: `ops.input_image`) -> dict of device tensors:
         boxes (N,dpi,4), scores (N,dpi), count (N,) = #scores > confidence, indices (N,dpi,k) (-1 beyond count).
         stage_events: optional list that receives (stage name, start event, end event) for detect / crop / embed / match.
         proposals: optional (boxes (N,dpi,4) f32, counts (N,) int32) device tensors that REPLACE the detector's confident boxes after
         the detector has run (stage-isolated benchmarks accept planted proposals, which pins P and the box shapes
         whatever the detector's weights emit); the detector's pass is still executed and timed.
+        actuals (opt-in; the detections rule of DESIGN.md 4b): the dict gains 'actuals', a `planograms_device.DeviceActuals` -- the
+        confident, non-degenerate boxes of every image with their label ids and graph thresholds (`actuals_thresh_size`), packed on the
+        device for the comparator: two more launches (csrc/actuals.hip), no further wait.  Off, the call launches what it always did.
         (Queueing the detector of call i + 1 on its own stream beside the embedder of call i was measured: +1.3 % at best, and
         the two stages' queues do not actually make progress side by side on this stack -- profiles/r03_rejected_experiments.md.)"""
         def mark():
@@ -724,14 +846,31 @@ class BatchedPipeline:
         # the copy has landed, i.e. while the crops still run, and queues the embedder's launches behind them.
         n = len(images)
         pin = self.__dict__.setdefault('_count_pins', {})
-        if n not in pin:
-            pin[n] = torch.empty(n, dtype=torch.int32).pin_memory()
-        pin[n].copy_(det_out[4], non_blocking=True)
+        if actuals:
+            # the kept counts -- how many of each image's confident boxes are non-degenerate -- are counted right behind the detector
+            # and travel in the same pinned copy as the confidence counts: still one wait
+            if getattr(self.classifier, 'gallery_label_id', None) is None:
+                raise ValueError('actuals=True needs a classifier with an id space (Classifier.label_ids)')
+            from . import torch_ops_actuals  # noqa: F401  (registers torch.ops.cvpce_amd.actuals_*)
+            det_boxes = det_out[0].contiguous()
+            both = torch.empty(2 * n, dtype=torch.int32, device=det_boxes.device)
+            both[:n].copy_(det_out[4])
+            torch.ops.cvpce_amd.actuals_count(det_boxes, both[:n], both[n:])
+            if ('actuals', n) not in pin:
+                pin['actuals', n] = torch.empty(2 * n, dtype=torch.int32).pin_memory()
+            pinned = pin['actuals', n]
+            pinned.copy_(both, non_blocking=True)
+        else:
+            if n not in pin:
+                pin[n] = torch.empty(n, dtype=torch.int32).pin_memory()
+            pinned = pin[n]
+            pinned.copy_(det_out[4], non_blocking=True)
         copied = torch.cuda.Event()
         copied.record()
         crops, ext, const_in, partial = self._crops(images, det_out)
         copied.synchronize()
-        counts = pin[n].tolist()
+        counts = pinned.tolist()
+        counts, kept = counts[:n], counts[n:]
         valid, sel, ext = self._select(crops, counts, ext)
         t2 = mark()
         if ext is not None:         # (an encoder with the work-list schedule: the tiles in the crops' constant padding are skipped)
@@ -743,4 +882,23 @@ class BatchedPipeline:
         t4 = mark()
         if stage_events is not None:
             stage_events += [('detect', t0, t1), ('crop', t1, t2), ('embed', t2, t3), ('match', t3, t4)]
-        return self._finish(images, det_out, counts, emb, idx, sel)
+        res = self._finish(images, det_out, counts, emb, idx, sel)
+        if actuals:
+            res['actuals'] = self._pack_actuals(det_boxes, both[:n], res['indices'], kept)
+        return res
+
+    actuals_thresh_size = 0.5          # the comparator's graph_threshold the packed thresholds are computed for
+
+    def _pack_actuals(self, boxes, count, indices, kept):
+        """`actuals_pack` behind the matcher: the kept boxes, their gallery rows, label ids and graph thresholds, packed on the device
+        with the host's prefix sums of the kept counts -> `planograms_device.DeviceActuals`.  Nothing is waited for."""
+        from . import planograms_device as pd
+        device, total = boxes.device, sum(kept)
+        off2 = pd._upload(torch.tensor(pd._offsets(kept), dtype=torch.int32), device)
+        out_boxes = torch.empty((total, 4), dtype=torch.float32, device=device)
+        small = torch.empty(2 * total + 2 * len(kept), dtype=torch.int32, device=device)
+        row, label, status = small[:total], small[total:2 * total], small[2 * total + len(kept):]
+        thresh = small[2 * total:2 * total + len(kept)].view(torch.float32)
+        torch.ops.cvpce_amd.actuals_pack(boxes, count, indices.contiguous(), self.classifier.gallery_label_id, off2, float(self.actuals_thresh_size),
+                                         out_boxes, row, label, thresh, status)
+        return pd.DeviceActuals(out_boxes, row, label, thresh, status, off2, kept, self.actuals_thresh_size)

@@ -21,8 +21,14 @@ Scenes: gridded planograms of 24 (4 x 6) and 200 (8 x 25) boxes (synthetic.plano
                   evaluate_iter images/s with `device_tail` alone and with `device_reclass` as well, in this one process, and what a
                   window costs in launches and waits on either path
 
+  detections leg  (--detections-markdown) `PlanogramEvaluator.evaluate_iter` with `device_detections` off and on over the comparator with
+                  all three switches on: the detector's confident boxes are replaced by the scene's detections inside the pipeline
+                  (`run(proposals=...)`), the planograms are the pipeline's own detections shrunk; images/s and what a window costs in
+                  launches and waits on either path
+
     python tools/bench_planogram_compare.py [--batch 8] [--launches 30] [--markdown profiles/r23_planogram_tail.md]
                                             [--reclass-markdown profiles/r25_reclass.md]
+                                            [--detections-only] [--detections-markdown profiles/r27_device_detections.md]
 """
 import argparse
 import json
@@ -301,6 +307,96 @@ def write_reclass(path, rows, args):
                     f" | {row['same_verdict']}/{row['batch']} / {row['same_verdict_iter']}/{row['batch']} |\n")
 
 
+class PlantedPipeline(production.BatchedPipeline):
+    """The detector runs as always; its confident boxes are replaced by the scene's detections (`run(proposals=...)`), so that both
+    paths of the detections leg -- which take their detections from the pipeline, not from the host -- see the scene."""
+    planted = None
+
+    def run(self, images, **kw):
+        assert len(images) == self.planted[0].shape[0]
+        return super().run(images, proposals=self.planted, **kw)
+
+
+class PlantedDetectionsEvaluator(production.PlanogramEvaluator):
+    def _pipeline(self):
+        pipe = self.__dict__.get('_planted_pipe')
+        if pipe is None:
+            pipe = self._planted_pipe = PlantedPipeline(self.proposal_generator.detector, self.classifier, self.proposal_generator.condfidence_threshold)
+        return pipe
+
+
+def time_detections(name, rows, cols, batch, det, enc, dev):
+    """The detections leg -> one row: `PlanogramEvaluator(device_detections=False)` against `True` over one comparator setting (all
+    three comparator switches on), same process, same inputs, the two paths alternating window by window."""
+    pairs, (h, w) = miss_scenes(rows, cols, batch)
+    gallery = synthetic.TensorGallery(synthetic.gallery_images(64, seed=100), [synthetic.PLANOGRAM_LABELS[i % len(synthetic.PLANOGRAM_LABELS)] for i in range(64)])
+    clf = production.Classifier(enc, gallery, device=dev, emb_device=dev, batch_size=32, match_dtype=torch.bfloat16)
+    pg = production.ProposalGenerator(det, device=dev, confidence_threshold=0.5)
+    images = [synthetic.shelf_image(400 + k, h, w).to(dev) for k in range(batch)]
+    dpi = det.detections_per_img
+    boxes, counts = torch.zeros((batch, dpi, 4)), []
+    for k, (_, a) in enumerate(pairs):
+        n = min(len(a['labels']), dpi)
+        boxes[k, :n] = a['boxes'][:n]
+        counts.append(n)
+    planted = (boxes.to(dev), torch.tensor(counts, dtype=torch.int32, device=dev))
+    switches = dict(device_graphs=True, device_tail=True, device_reclass=True)
+    evaluators = {'off': PlantedDetectionsEvaluator(pg, clf, production.PlanogramComparator(**switches)),
+                  'on': PlantedDetectionsEvaluator(pg, clf, production.PlanogramComparator(**switches), device_detections=True)}
+    for ev in evaluators.values():
+        ev._pipeline().planted = planted
+    # the planograms: what the pipeline itself makes of the planted boxes (the labels of noise crops are whatever is nearest), shrunk,
+    # every 11th label replaced by one no gallery item has -- so the comparator has matchings, homographies and positions to classify
+    dets = evaluators['off'].detect_and_classify_batch(images)
+    planos = [{'boxes': (b / 1.7).contiguous(), 'labels': [('not_in_the_gallery' if i % 11 == 5 else l) for i, l in enumerate(labels)]} for b, labels in dets]
+    row = {'scene': name, 'batch': batch, 'image': f'{h} x {w}', 'boxes': sum(counts) / batch}
+    rates, vals = {key: [] for key in evaluators}, {}
+    for r in range(REPEATS + 1):                            # (alternating; round 0 warms up)
+        for key, ev in evaluators.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vals[key] = list(ev.evaluate_iter(zip(images, planos), lookahead=batch))
+            dt = time.perf_counter() - t0
+            if r:
+                rates[key].append(batch / dt)
+    for key, ev in evaluators.items():
+        row[f'evaluate_iter_{key}'] = statistics.median(rates[key])
+        row[f'evaluate_iter_{key}_min_max'] = [min(rates[key]), max(rates[key])]
+        with WindowCounter() as c:
+            list(ev.evaluate_iter(zip(images, planos), lookahead=batch))
+        row.update({f'kernels_{key}': c.kernels, f'torch_ops_{key}': c.torch_device_ops, f'waits_{key}': c.waits})
+    row['same_verdict'] = sum(float(a) == float(b) and type(a) is type(b) for a, b in zip(vals['off'], vals['on']))
+    row['mean_verdict'] = sum(float(v) for v in vals['off']) / batch
+    row['host_routed'] = evaluators['on'].planogram_comparator.host_routed + evaluators['on'].detections_host_routed
+    return row
+
+
+DETECTIONS_COLS = ('image', 'boxes', 'mean_verdict', 'evaluate_iter_off', 'evaluate_iter_on', 'kernels_off', 'kernels_on', 'torch_ops_off', 'torch_ops_on',
+                   'waits_off', 'waits_on', 'host_routed')
+
+
+def write_detections(path, rows, args):
+    def fmt(row, c):
+        v = row[c]
+        if isinstance(v, str):
+            return v
+        lo_hi = row.get(c + '_min_max')
+        return f'{v:.4g}' + (f' ({lo_hi[0]:.4g} - {lo_hi[1]:.4g})' if lo_hi else '')
+    with open(path, 'w') as f:
+        f.write('# Planogram evaluator: detections kept on the device from the matcher to the comparator\n\n'
+                f'`python tools/bench_planogram_compare.py --batch {args.batch} --detections-only --detections-markdown ...`, one process, MI355X.  '
+                'The detector, the crops, the embedder and the matcher run on synthetic shelf images; the detector\'s confident boxes are replaced '
+                'by the scene\'s detections (`run(proposals=...)`), and the planograms are the pipeline\'s own detections shrunk by 1.7, every '
+                '11th label replaced by one no gallery item has.  `off` / `on`: `PlanogramEvaluator(device_detections=...)` over '
+                '`PlanogramComparator(device_graphs=True, device_tail=True, device_reclass=True)`.  `evaluate_iter_*`: images/s of '
+                f'`evaluate_iter` with the window of {args.batch} images as lookahead, median (min - max) of {REPEATS} windows per path, the two '
+                'paths alternating window by window.  Per window: `kernels` = launches of the project\'s own kernels, `torch_ops` = other torch '
+                'operators on device tensors (copies, gathers), `waits` = points at which the host waits for the device.\n\n')
+        f.write('| scene | ' + ' | '.join(DETECTIONS_COLS) + ' | same verdict |\n|---|' + '---|' * (len(DETECTIONS_COLS) + 1) + '\n')
+        for row in rows:
+            f.write(f"| {row['scene']} | " + ' | '.join(fmt(row, c) for c in DETECTIONS_COLS) + f" | {row['same_verdict']}/{row['batch']} |\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batch', type=int, default=8)
@@ -308,6 +404,8 @@ def main():
     ap.add_argument('--markdown', help='also write the table to this file')
     ap.add_argument('--reclass-markdown', help='run the re-classification leg and write its table to this file')
     ap.add_argument('--reclass-only', action='store_true', help='skip everything but the re-classification leg')
+    ap.add_argument('--detections-markdown', help='run the detections leg and write its table to this file')
+    ap.add_argument('--detections-only', action='store_true', help='skip everything but the detections leg')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     det = synthetic.synthetic_gln(seed=0, detections_per_img=200).to(dev)
@@ -321,6 +419,15 @@ def main():
     images = [synthetic.shelf_image(300 + k, 1024, 1024).to(dev) for k in range(args.batch)]
     rows = []
     grids = (('24 boxes (4 x 6)', (4, 6)), ('200 boxes (8 x 25)', (8, 25)))
+    if args.detections_markdown or args.detections_only:
+        detections_rows = []
+        for name, (r, c) in grids:
+            detections_rows.append(time_detections(name, r, c, args.batch, det, enc, dev))
+            print(json.dumps(detections_rows[-1]), flush=True)
+        if args.detections_markdown:
+            write_detections(args.detections_markdown, detections_rows, args)
+        if args.detections_only:
+            return 0
     if args.reclass_markdown:
         reclass_rows = []
         for name, (r, c) in grids:
