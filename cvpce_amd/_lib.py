@@ -2,7 +2,8 @@
 8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
 include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
 include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
-harness's kernel of include/cvpce_amd_classeval.h and the detections kernels of include/cvpce_amd_actuals.h).
+harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h and the compliance
+report kernels of include/cvpce_amd_report.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -148,8 +149,14 @@ ACTUALS_SIGNATURES = {
     'cvpce_actuals_pack': (c_int, [_fp, _ip, _vp, c_int, _ip, c_int, _ip, c_float, c_int, c_int, c_int, _fp, _ip, _ip, _fp, _ip, _vp]),
 }
 
+# include/cvpce_amd_report.h: the comparator's compliance report.  A table of its own, like the header.
+REPORT_SIGNATURES = {
+    'cvpce_report_positions': (c_int, [_ip, _ip, _ip, _fp, _fp, _ip, _ip, _ip, _ip, ctypes.c_double] + [c_int] * 3 + [_ip, _ip, _fp, _ip, _ip, _vp]),
+    'cvpce_report_reclass': (c_int, [_ip, _ip, _ip, _vp, _fp, _ip, _ip, _ip, _ip] + [c_int] * 6 + [_ip, _ip, _fp, _vp]),
+}
+
 for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES):
+               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

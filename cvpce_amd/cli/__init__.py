@@ -12,12 +12,14 @@ thread; the printed metrics are the same to the last digit, the inputs being the
 have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
 One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
 (default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `eval-planograms` takes
---device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`), and `dihe eval` takes --device-eval /
+--device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`) and --report FILE
+(one JSON line per image saying which positions are missing and what is there; `_ReportCommand`), and `dihe eval` takes --device-eval /
 --no-device-eval (default off: EVAL_WINDOW images at a time are cropped, embedded and matched in one pass and compared on the GPU;
 `_DeviceEvalCommand`).
 
     python -m cvpce_amd.cli --help
 """
+import json
 import os
 
 import click
@@ -200,6 +202,43 @@ class _DeviceDetectionsCommand(_DeviceReclassCommand):
 
 def _device_detections_switch():
     return bool(click.get_current_context().meta.get(_DeviceDetectionsCommand.DETECTIONS_KEY, False))
+
+
+class _ReportCommand(_DeviceDetectionsCommand):
+    """The four switches above, and --report FILE (default: none) beside them, arranged the same way."""
+    REPORT_OPTION = '--report'
+    REPORT_HELP = ('Also write one JSON line per image to FILE: which expected positions were detected, recovered, missing, out of view or '
+                   'unchecked, what sits there instead and which detections the planogram does not know '
+                   '(cvpce_amd.production.ComplianceReport.to_dict, plus the image index).  [default: none]')
+    REPORT_KEY = 'cvpce_amd.report'
+    REPORT_LABEL = '--report FILE'
+
+    def parse_args(self, ctx, args):
+        rest, args = [], list(args)
+        ctx.meta[self.REPORT_KEY] = None
+        i = 0
+        while i < len(args):
+            a = args[i]
+            if a == '--':
+                rest += args[i:]
+                break
+            if a == self.REPORT_OPTION:
+                if i + 1 >= len(args):
+                    raise click.UsageError('--report needs a file name', ctx)
+                ctx.meta[self.REPORT_KEY] = args[i + 1]
+                i += 1
+            elif a.startswith(self.REPORT_OPTION + '='):
+                ctx.meta[self.REPORT_KEY] = a[len(self.REPORT_OPTION) + 1:]
+            else:
+                rest.append(a)
+            i += 1
+        return super().parse_args(ctx, rest)
+
+    MORE = _DeviceDetectionsCommand.MORE + ((REPORT_LABEL, REPORT_HELP),)
+
+
+def _report_file():
+    return click.get_current_context().meta.get(_ReportCommand.REPORT_KEY)
 
 
 class _DeviceEvalCommand(_DeviceMetricsCommand):
@@ -393,7 +432,7 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command(cls=_DeviceDetectionsCommand)
+@cli.command(cls=_ReportCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -424,6 +463,8 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
                                                                                               device_tail=_device_tail_switch(),
                                                                                               device_reclass=_device_reclass_switch()),
                                               device_detections=_device_detections_switch())
+    report_path = _report_file()
+    report_out = open(report_path, 'w') if report_path else None
     total_a = total_e = 0.0
     # the reference evaluates one image at a time (cvpce/cli/eval.py:224-230); here the images are decoded ahead by the feeder's threads,
     # and EVAL_WINDOW of them are detected / embedded / matched together (PlanogramEvaluator.evaluate_batch: same per-image results,
@@ -431,7 +472,13 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     for s, data in enumerate(proposals_eval._batches(feeding.feed(planoset, dataloader_workers, generator.device), EVAL_WINDOW)):
         s *= EVAL_WINDOW
         pairs = [((d[0], d[3]) if datatype == 'gp' else tuple(d)) for d in data]
-        accs = evaluator.evaluate_batch([img for img, _ in pairs], [plano for _, plano in pairs])
+        if report_out is None:
+            accs = evaluator.evaluate_batch([img for img, _ in pairs], [plano for _, plano in pairs])
+        else:                                    # (the same route with its reasons: `.compliance` is evaluate_batch's value)
+            reports = evaluator.report_batch([img for img, _ in pairs], [plano for _, plano in pairs])
+            for i, rep in enumerate(reports, start=s):
+                report_out.write(json.dumps(dict(rep.to_dict(), image=i)) + '\n')
+            accs = [rep.compliance for rep in reports]
         for i, ((img, plano), acc) in enumerate(zip(pairs, accs), start=s):
             acc = float(acc)
             err = acc - plano['actual_accuracy']
@@ -441,6 +488,8 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
                 print(i)
             total_e += err ** 2
             total_a += acc
+    if report_out is not None:
+        report_out.close()
     print(f'--> Mean accuracy {total_a / len(planoset)}')
     print(f'--> MSE: {total_e / len(planoset)}')
 

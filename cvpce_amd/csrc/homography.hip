@@ -291,17 +291,7 @@ __device__ __forceinline__ double hg_pick(const double r[9], int i) {
     return i == 0 ? r[0] : i == 1 ? r[1] : i == 2 ? r[2] : i == 3 ? r[3] : i == 4 ? r[4] : i == 5 ? r[5] : i == 6 ? r[6] : i == 7 ? r[7] : r[8];
 }
 
-// IoU of an expected position a with a detection b: the expression evalmatch.hip holds to the bits of metrics.box_iou
-__device__ __forceinline__ float hg_iou(float4 a, float4 b) {
-#pragma clang fp contract(off)
-    const float area_a = (a.z - a.x) * (a.w - a.y), area_b = (b.z - b.x) * (b.w - b.y);
-    float w = fminf(a.z, b.z) - fmaxf(a.x, b.x);
-    float h = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-    w = w < 0.f ? 0.f : w;
-    h = h < 0.f ? 0.f : h;
-    const float inter = w * h;
-    return __fdiv_rn(inter, (area_a + area_b) - inter);
-}
+#include "iou.h"                              // hg_iou: the claim's IoU, shared with report.hip
 
 struct HgFinishLds { int pos, lab1, me, mask, total; };
 

@@ -249,3 +249,51 @@ def finalize_via_ransac(solution, b1, b2, l1, l2, reproj_threshold=10, iou_thres
     if return_matched_actual:
         return matched_expected, matched_actual, missing_expected, missing_positions, missing_labels
     return matched_expected, missing_expected, missing_positions, missing_labels
+
+
+# ---------------------------------------------------------------------------
+# The compliance report (the report rule): what became of every expected position.  The outcome codes are those of
+# include/cvpce_amd_report.h; PENDING never leaves the comparator.
+DETECTED, RECOVERED, MISSING, OUT_OF_VIEW, UNCHECKED, PENDING = range(6)
+OUTCOMES = ('detected', 'recovered', 'missing', 'out_of_view', 'unchecked', 'pending')
+
+
+def clamp_positions(positions, h, w):
+    """The comparator's clamp of projected positions to an h x w image and its validity test (more than a pixel wide and high)
+    -> (clamped (n,4), valid (n,) bool)"""
+    pos = positions.clone()
+    pos[:, 0::2] = pos[:, 0::2].clamp(min=0, max=w)
+    pos[:, 1::2] = pos[:, 1::2].clamp(min=0, max=h)
+    return pos, (pos[:, 2] - pos[:, 0] > 1) & (pos[:, 3] - pos[:, 1] > 1)
+
+
+def report_positions(matched_expected, matched_actual, expected_positions, actual_boxes, image_hw=None, iou_threshold=0.5):
+    """The first half of the report rule in plain torch, on `finalize_via_ransac(..., return_matched_actual=True,
+    return_expected_positions=True)`'s tensors.  image_hw: (h, w) of the image the positions will be re-classified in, None where
+    nothing will be classified.
+    -> (outcome (n1,) int32 -- DETECTED, UNCHECKED, OUT_OF_VIEW or PENDING --, occupant (n1,) int32, occupant_iou (n1,) float32,
+    stray (n2,) bool): the occupant of an undetected position is the unclaimed detection with the largest IoU >= iou_threshold, the
+    lowest index among equals (-1 / -1.0 where there is none, and for a detected position); a stray is an unclaimed detection that is
+    no position's occupant."""
+    n1, n2 = len(expected_positions), len(actual_boxes)
+    outcome = torch.full((n1,), DETECTED, dtype=torch.int32)
+    missing = ~matched_expected
+    if image_hw is None:
+        outcome[missing] = UNCHECKED
+    else:
+        valid = clamp_positions(expected_positions, *image_hw)[1]
+        outcome[missing & valid] = PENDING
+        outcome[missing & ~valid] = OUT_OF_VIEW
+    occupant = torch.full((n1,), -1, dtype=torch.int32)
+    occupant_iou = torch.full((n1,), -1.0, dtype=torch.float32)
+    if n1 and n2:
+        iou = metrics.box_iou(expected_positions.to(torch.float32), actual_boxes.to(torch.float32))
+        ok = (iou.to(torch.float64) >= iou_threshold) & ~matched_actual[None, :] & missing[:, None]        # (false on NaN)
+        best = torch.where(ok, iou, torch.full_like(iou, -1.0)).amax(dim=1)
+        first = torch.where(ok & (iou == best[:, None]), torch.arange(n2)[None, :], torch.full((1, 1), n2)).amin(dim=1)
+        has = ok.any(dim=1)
+        occupant[has] = first[has].to(torch.int32)
+        occupant_iou[has] = best[has]
+    stray = ~matched_actual.clone()
+    stray[occupant[occupant >= 0].to(torch.long)] = False
+    return outcome, occupant, occupant_iou, stray

@@ -275,10 +275,11 @@ def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, ac
     return m
 
 
-def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses):
+def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses, extra=0):
     """Everything the two tail launches need, uploaded -> (arguments of homography_ransac, of homography_finish, the output blob,
     its layout).  Every output lies in ONE allocation -- positions (f32), H (f64), then the int32 fields status, winner, winner count,
-    final count, matching size, matched_expected, matched_actual -- so that one copy brings it back."""
+    final count, matching size, matched_expected, matched_actual, then `extra` more int32 words (the compliance report's rows) -- so that
+    one copy brings it back.  The layout's last entry is the view of those extra words."""
     b = len(matching.n1)
     if not (b == len(expected_boxes) == len(actual_boxes) == len(reproj_thresholds)) or not b:
         raise ValueError('one entry per image, at least one image')
@@ -310,39 +311,43 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
     params = _upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
     workspace = torch.empty(max(torch_ops_homography.workspace_bytes(b, hypotheses), 8) // 4, dtype=torch.int32, device=device)
     at_h, at_i = 16 * sum1, 16 * sum1 + 72 * b
-    blob = torch.empty(at_i + 4 * (5 * b + sum1 + sum2), dtype=torch.uint8, device=device)
+    blob = torch.empty(at_i + 4 * (5 * b + sum1 + sum2 + extra), dtype=torch.uint8, device=device)
     pos, hmat, i32 = blob[:at_h].view(torch.float32).view(sum1, 4), blob[at_h:at_i].view(torch.float64), blob[at_i:].view(torch.int32)
     status, winner, wcount, fcount = (i32[k * b:(k + 1) * b] for k in range(4))
-    me, ma = i32[5 * b:5 * b + sum1], i32[5 * b + sum1:]
+    me, ma = i32[5 * b:5 * b + sum1], i32[5 * b + sum1:5 * b + sum1 + sum2]
     max_pairs = max(1, max(min(a, c) for a, c in zip(n1, n2)))
     common = (matching.pairs, matching.count, matching.out_off, params)
     ransac = (boxes1, matching.off1, boxes2, matching.off2, *common, max_pairs, seed, hypotheses, workspace)
     finish = (boxes1, matching.label1, matching.off1, boxes2, matching.label2, matching.off2, *common, max(n1), max(n2), max_pairs,
               seed, hypotheses, workspace, status, hmat, winner, wcount, fcount, me, ma, pos)
-    return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b])
+    return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b], i32[5 * b + sum1 + sum2:])
 
 
 class ReclassPlan:
     """What `reclass_plan` left on the device for a window, and the tail outputs the verdict kernel reads beside it: `boxes`
     [B][cap][4] f32, `expected_index` [B][cap] and `count` [B] int32 (slots at and beyond an image's count are unwritten), the views
     `status`, `matched_expected` and `off1` of the tail's tensors, and on the host `counts` (a list, brought back in the tail's own
-    synchronisation), the box counts `n1` and `cap` = max n1."""
-    __slots__ = ('boxes', 'expected_index', 'count', 'status', 'matched_expected', 'off1', 'counts', 'n1', 'cap')
+    synchronisation), the box counts `n1` and `cap` = max n1.  `outcome`: where `report_positions` left the window's outcomes on the
+    device (`finalize_batch(..., report=...)`), else None."""
+    __slots__ = ('boxes', 'expected_index', 'count', 'status', 'matched_expected', 'off1', 'counts', 'n1', 'cap', 'outcome')
 
 
-def _launch_plan(matching, finish, image_table):
-    """`reclass_plan` behind `homography_finish` on the same stream, and its counts on their way to pinned memory -> (ReclassPlan
-    without `counts`, the pinned tensor the counts land in once the stream has been waited for)."""
-    from . import torch_ops_reclass  # noqa: F401  (registers torch.ops.cvpce_amd.reclass_*)
-    b = len(matching.n1)
+def _image_table(image_table, b, device):
     if len(image_table) != b:
         raise ValueError('one (h, w, enabled) row per image')
+    return _upload(torch.tensor([[int(h), int(w), int(bool(on))] for h, w, on in image_table], dtype=torch.int32), device)
+
+
+def _launch_plan(matching, finish, table):
+    """`reclass_plan` behind `homography_finish` on the same stream, and its counts on their way to pinned memory -> (ReclassPlan
+    without `counts`, the pinned tensor the counts land in once the stream has been waited for).  table: `_image_table`'s."""
+    from . import torch_ops_reclass  # noqa: F401  (registers torch.ops.cvpce_amd.reclass_*)
+    b = len(matching.n1)
     status, me, pos = finish[16], finish[21], finish[23]
     device = status.device
     plan = ReclassPlan()
-    plan.n1, plan.cap = list(matching.n1), max(matching.n1)
+    plan.n1, plan.cap, plan.outcome = list(matching.n1), max(matching.n1), None
     plan.status, plan.matched_expected, plan.off1 = status, me, matching.off1
-    table = _upload(torch.tensor([[int(h), int(w), int(bool(on))] for h, w, on in image_table], dtype=torch.int32), device)
     plan.boxes = torch.empty((b, plan.cap, 4), dtype=torch.float32, device=device)
     slots = torch.empty(b * plan.cap + b, dtype=torch.int32, device=device)
     plan.expected_index, plan.count = slots[:b * plan.cap].view(b, plan.cap), slots[b * plan.cap:]
@@ -352,14 +357,18 @@ def _launch_plan(matching, finish, image_table):
     return plan, host
 
 
-def reclassify_batch(plan, images, classifier, expected_label_ids):
+def reclassify_batch(plan, images, classifier, expected_label_ids, report=False):
     """The window's second trip through the crop / embed / match kernels in one pass (the re-classification rule of DESIGN.md 4b):
     every image's planned positions are cropped straight to the embedder's bf16 input (`production.roi_crops`: boxes and counts are
     read on the device), compacted with the host's counts, embedded by ONE schedule and matched by ONE distance GEMM;
     `reclass_verdict` compares label ids and one pinned copy brings back the per-image found counts -- the only wait of this pass.
     plan: the `ReclassPlan` of `finalize_batch(..., reclass=...)` with at least one position; images: the window's images (either
     form; read only where the image's count is > 0); expected_label_ids: one list of ids per image (`Classifier.expected_label_ids`).
-    -> list of found counts, -1 for an image without a homography."""
+    -> list of found counts, -1 for an image without a homography.
+    report (the report rule of DESIGN.md 4b; a plan of `finalize_batch(..., report=...)`): the matcher also emits its distances,
+    `report_reclass` runs behind the verdict on a copy of the plan's outcomes, and the same pinned copy brings back the window's final
+    outcomes, seen rows and seen distances -> (found counts, outcome (sumN1,) int32, seen_row (sumN1,) int32, seen_distance (sumN1,)
+    float32), host tensors; the rows of an image without a homography hold nothing."""
     from . import ops, production
     b, cap, counts = len(plan.n1), plan.cap, plan.counts
     device = plan.count.device
@@ -381,6 +390,8 @@ def reclassify_batch(plan, images, classifier, expected_label_ids):
         ext = ext.index_select(0, sel) if ext is not None else None
     eng = classifier.encoder.engine()
     emb = eng.embed_packed(crops, ext=ext, const_in=const_in, partial=partial) if ext is not None else eng.embed_packed(crops)
+    if report:
+        return _verdict_and_report(plan, classifier, emb, slot_row, ids)
     indices = classifier.match(emb).contiguous()
     out = torch.empty(sum1 + b, dtype=torch.int32, device=device)
     torch.ops.cvpce_amd.reclass_verdict(plan.expected_index, plan.count, slot_row, indices, classifier.gallery_label_id, ids,
@@ -391,8 +402,31 @@ def reclassify_batch(plan, images, classifier, expected_label_ids):
     return host.tolist()
 
 
+def _verdict_and_report(plan, classifier, emb, slot_row, ids):
+    """The end of `reclassify_batch` with the report on: match with distances, `reclass_verdict`, `report_reclass`, ONE pinned copy of
+    {found counts, outcomes, seen rows, seen distances} and the pass's only wait."""
+    from . import torch_ops_report  # noqa: F401  (registers torch.ops.cvpce_amd.report_*)
+    b, sum1, device = len(plan.n1), sum(plan.n1), plan.count.device
+    if plan.outcome is None:
+        raise ValueError('a plan of finalize_batch(..., report=...)')
+    indices, distances = classifier.match(emb, return_distance=True)
+    indices, distances = indices.contiguous(), distances.contiguous()
+    out = torch.empty(b + 4 * sum1, dtype=torch.int32, device=device)            # found counts, outcome, seen_row, seen_distance | found
+    found_count, outcome, seen_row = out[:b], out[b:b + sum1], out[b + sum1:b + 2 * sum1]
+    seen_distance, found = out[b + 2 * sum1:b + 3 * sum1].view(torch.float32), out[b + 3 * sum1:]
+    outcome.copy_(plan.outcome)
+    torch.ops.cvpce_amd.reclass_verdict(plan.expected_index, plan.count, slot_row, indices, classifier.gallery_label_id, ids,
+                                        plan.matched_expected, plan.off1, plan.status, found, found_count)
+    torch.ops.cvpce_amd.report_reclass(plan.expected_index, plan.count, slot_row, indices, distances, classifier.gallery_label_id, ids,
+                                       plan.off1, plan.status, outcome, seen_row, seen_distance)
+    host = torch.empty(b + 3 * sum1, dtype=torch.int32).pin_memory()
+    host.copy_(out[:b + 3 * sum1], non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    return (host[:b].tolist(), host[b:b + sum1], host[b + sum1:b + 2 * sum1], host[b + 2 * sum1:].view(torch.float32))
+
+
 def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold=0.5, seed=0,
-                   hypotheses=RANSAC_HYPOTHESES, reclass=None):
+                   hypotheses=RANSAC_HYPOTHESES, reclass=None, report=None):
     """`planograms.finalize_via_ransac` for every image of a batch under the tail rule: two launches on the matchings
     as they lie on the device (`match_on_device`) and ONE pinned copy back.  expected / actual: the lists of `Graph` the matching was
     made from; expected_boxes / actual_boxes: their (n, 4) boxes; reproj_thresholds: one per image, in pixels.  Expected boxes that lie
@@ -402,16 +436,32 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
     (float32 (n1, 4)), 'homography' (3 x 3 float64, None unless ok), 'inliers' (of the refit), 'points', 'matching' (its size),
     'winner', 'winner_inliers'}.
     reclass (optional): one (image height, image width, enabled) per image -- `reclass_plan` is launched behind the tail and its counts
-    come back in the same synchronisation -> (records, `ReclassPlan`) for `reclassify_batch`."""
+    come back in the same synchronisation -> (records, `ReclassPlan`) for `reclassify_batch`.
+    report (optional; the report rule of DESIGN.md 4b): such a table too (with `reclass`: the same one) -- `report_positions` is
+    launched behind the tail (and the plan) and its rows come back in the same copy: every record gains 'outcome' (int32 (n1,), PENDING
+    where the position is to be re-classified), 'occupant', 'occupant_row' (int32 (n1,)), 'occupant_iou' (float32 (n1,)) and 'stray'
+    (bool (n2,)); meaningful for an 'ok' record only.  The detections' gallery rows are read from a `DeviceActuals`."""
     if not len(expected) == len(actual) == len(matching.n1) or [len(g) for g in expected] != matching.n1 or [len(g) for g in actual] != matching.n2:
         raise ValueError('the graphs the matching was made from')
-    ransac, finish, blob, (at_h, at_i, size) = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses)
+    b, n1, n2 = len(expected), matching.n1, matching.n2
+    sum1, sum2 = sum(n1), sum(n2)
+    if reclass is not None and report is not None and list(report) != list(reclass):
+        raise ValueError('the report reads the image table the plan reads')
+    ransac, finish, blob, (at_h, at_i, size, extra) = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed,
+                                                                    hypotheses, extra=4 * sum1 + sum2 if report is not None else 0)
     torch.ops.cvpce_amd.homography_ransac(*ransac)
     torch.ops.cvpce_amd.homography_finish(*finish)
-    plan, plan_counts = _launch_plan(matching, finish, reclass) if reclass is not None else (None, None)
+    table = _image_table(reclass if reclass is not None else report, b, blob.device) if (reclass is not None or report is not None) else None
+    plan, plan_counts = _launch_plan(matching, finish, table) if reclass is not None else (None, None)
+    if report is not None:
+        from . import torch_ops_report  # noqa: F401  (registers torch.ops.cvpce_amd.report_*)
+        rows = [extra[k * sum1:(k + 1) * sum1] for k in range(4)] + [extra[4 * sum1:]]          # outcome, occupant, IoU, row | stray
+        torch.ops.cvpce_amd.report_positions(finish[16], finish[21], finish[22], finish[23], finish[3], matching.off1, matching.off2, table,
+                                             actual_boxes.row if isinstance(actual_boxes, DeviceActuals) else None, float(iou_threshold),
+                                             rows[0], rows[1], rows[2].view(torch.float32), rows[3], rows[4])
+        if plan is not None:
+            plan.outcome = rows[0]
     size.copy_(matching.count)                                     # (the matching's size travels in the same copy)
-    b, n1, n2 = len(expected), matching.n1, matching.n2
-    sum1 = sum(n1)
     back = torch.empty(blob.shape, dtype=torch.uint8).pin_memory()
     back.copy_(blob, non_blocking=True)
     pack_status = None
@@ -425,7 +475,7 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
         plan.counts = plan_counts.tolist()
     pos, hmat, i32 = back[:at_h].view(torch.float32).view(sum1, 4), back[at_h:at_i].view(torch.float64).view(b, 3, 3), back[at_i:].view(torch.int32)
     head = i32[:5 * b].view(5, b).tolist()
-    me, ma = i32[5 * b:5 * b + sum1] != 0, i32[5 * b + sum1:] != 0
+    me, ma = i32[5 * b:5 * b + sum1] != 0, i32[5 * b + sum1:5 * b + sum1 + sum2] != 0
     off1, off2 = _offsets(n1), _offsets(n2)
     records = []
     for p in range(b):
@@ -434,6 +484,12 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
         records.append({'status': STATUS[head[0][p]], 'matched_expected': me[off1[p]:off1[p + 1]].clone(), 'matched_actual': ma[off2[p]:off2[p + 1]].clone(),
                         'expected_positions': pos[off1[p]:off1[p + 1]].clone(), 'homography': hmat[p].clone() if ok else None,
                         'inliers': head[3][p], 'points': 5 if m == 1 else 3 * m, 'matching': m, 'winner': head[1][p], 'winner_inliers': head[2][p]})
+    if report is not None:
+        more = i32[5 * b + sum1 + sum2:]
+        for p, rec in enumerate(records):
+            a, c = slice(off1[p], off1[p + 1]), slice(4 * sum1 + off2[p], 4 * sum1 + off2[p + 1])
+            rec.update(outcome=more[:sum1][a].clone(), occupant=more[sum1:2 * sum1][a].clone(), occupant_iou=more[2 * sum1:3 * sum1].view(torch.float32)[a].clone(),
+                       occupant_row=more[3 * sum1:4 * sum1][a].clone(), stray=more[c] != 0)
     return records if plan is None else (records, plan)
 
 

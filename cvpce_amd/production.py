@@ -299,28 +299,48 @@ class Classifier:
         idx = torch.load(pth)
         return idx['embedding'], idx['annotations']
 
-    def match(self, emb):
-        """(P,1024) f32 unit-norm on device -> (P,min(k,G)) int64 gallery indices, nearest first (any k: ops.match_topk)."""
+    def match(self, emb, return_distance=False):
+        """(P,1024) f32 unit-norm on device -> (P,min(k,G)) int64 gallery indices, nearest first (any k: ops.match_topk);
+        return_distance: -> (indices, their cosine distances (P,min(k,G)) float32 as the match kernel emits them)."""
         q = ops.pad_features(emb.to(self.match_dtype))
-        return ops.match_topk(q, self._gallery, self.k, g_norms=self._gallery_norms)
+        return ops.match_topk(q, self._gallery, self.k, g_norms=self._gallery_norms, return_distance=return_distance)
+
+    def _embed(self, batch):
+        """images (n,3,S,S) in [0,1] on the device -> their embeddings: one pass of the encoder's engine"""
+        eng = self.encoder.engine()
+        mean, std = getattr(self.encoder, 'input_mean', TANH_MEAN), getattr(self.encoder, 'input_std', TANH_STD)
+        packed = ops.pack_embed_input(batch, True, mean, std)  # scale_to_tanh + the encoder's own normalisation, fused
+        if hasattr(eng, 'skip_plan') and batch.dim() == 4 and batch.shape[2] == batch.shape[3] and eng.skip_plan(batch.shape[2]) is not None:
+            # crops made by resize_for_classification carry a constant 0.5 border below / right of the box content
+            # (datautils.py:232-239): the embedder skips the tiles that lie in it -- the extents are read off the crops
+            b32 = batch.to(torch.float32).contiguous()
+            return eng.embed_packed(packed, ext=ops.pad_extents(b32, 0.5), const_in=eng.const_crop(mean, std, 8, batch.shape[2]))
+        return eng.embed_packed(packed)
+
+    def classify_positions(self, image, boxes):
+        """The comparator's re-classification of one image's positions, with what the matcher saw: boxes (P,4) xyxy inside `image`
+        (either form) are cropped, embedded and matched as `PlanogramComparator._finish` has them classified
+        -> (the nearest gallery row of every box: list of P ints, its cosine distance as the match kernel emitted it: (P,) float32
+        on the host)."""
+        img = ops.input_image(image, self.device)
+        crops = ops.crop_resize(img, boxes.to(self.device), datautils.CLASSIFICATION_IMAGE_SIZE, mode=0)
+        rows, dist = [], [torch.empty(0, dtype=torch.float32)]
+        step = max(self.batch_size, ENGINE_BATCH)
+        for i in range(0, len(crops), step):
+            idx, d = self.match(self._embed(crops[i:i + step].to(device=self.device)), return_distance=True)
+            # one blocking copy per batch, as `classify` has one: the rows, and the distances' bits beside them
+            both = torch.stack((idx[:, 0], d[:, 0].contiguous().view(torch.int32).to(torch.int64))).cpu()
+            rows += both[0].tolist()
+            dist.append(both[1].to(torch.int32).view(torch.float32))
+        return rows, torch.cat(dist)
 
     def classify(self, images, return_embedding=False):
         """production.py:57-74: images (P,3,256,256) in [0,1] -> list[list[str]] (P x k).  (One device-to-host copy of the
         (P,k) indices per batch -- `.tolist()` -- whatever k is.)"""
         res, embs = [], []
-        eng = self.encoder.engine()
         step = max(self.batch_size, ENGINE_BATCH)
         for i in range(0, len(images), step):
-            batch = images[i:i + step].to(device=self.device)
-            mean, std = getattr(self.encoder, 'input_mean', TANH_MEAN), getattr(self.encoder, 'input_std', TANH_STD)
-            packed = ops.pack_embed_input(batch, True, mean, std)  # scale_to_tanh + the encoder's own normalisation, fused
-            if hasattr(eng, 'skip_plan') and batch.dim() == 4 and batch.shape[2] == batch.shape[3] and eng.skip_plan(batch.shape[2]) is not None:
-                # crops made by resize_for_classification carry a constant 0.5 border below / right of the box content
-                # (datautils.py:232-239): the embedder skips the tiles that lie in it -- the extents are read off the crops
-                b32 = batch.to(torch.float32).contiguous()
-                emb = eng.embed_packed(packed, ext=ops.pad_extents(b32, 0.5), const_in=eng.const_crop(mean, std, 8, batch.shape[2]))
-            else:
-                emb = eng.embed_packed(packed)
+            emb = self._embed(images[i:i + step].to(device=self.device))
             if return_embedding:
                 embs.append(emb.to(device=self.emb_device))
             nearest = self.match(emb).tolist()
@@ -330,6 +350,53 @@ class Classifier:
                 return res, torch.cat(embs)
             return res, torch.empty((0, self.encoder.embedding_size), dtype=torch.float, device=self.emb_device)
         return res
+
+
+class ComplianceReport:
+    """What `PlanogramComparator.report` says about one shelf image (the report rule of DESIGN.md 4b) -- the reference's
+    `# TODO: Also return which were actually missing` (production.py:105,116).
+      compliance          what `compare` returns for the same inputs, value and type
+      status              'ok' | 'no_detections' | 'no_matching' | 'no_homography'; every field below is None unless 'ok'
+      outcomes            (n1,) int8: DETECTED 0, RECOVERED 1 (by the re-classification), MISSING 2, OUT_OF_VIEW 3 (the projected
+                          position does not lie in the image), UNCHECKED 4 (no classifier or no image)
+      expected_positions  (n1, 4) float32: every expected box projected into the image
+      seen_labels         per position: the annotation of the nearest gallery row where it was re-classified, else None
+      seen_distance       (n1,) float32: that row's cosine distance as the match kernel emitted it, else -1
+      occupant            (n1,) int32: the unclaimed detection that sits on an undetected position (IoU >= the claim's threshold, the
+                          largest, the lowest index among equals), else -1; occupant_iou (n1,) float32 that IoU, else -1;
+                          occupant_labels per position: the occupant's label, else None
+      stray               (m,) int64: the unclaimed detections that are no position's occupant -- products the planogram does not know"""
+    FIELDS = ('outcomes', 'expected_positions', 'seen_labels', 'seen_distance', 'occupant', 'occupant_iou', 'occupant_labels', 'stray')
+    OUTCOMES = ('detected', 'recovered', 'missing', 'out_of_view', 'unchecked')
+
+    def __init__(self, compliance, status, outcomes=None, expected_positions=None, seen_labels=None, seen_distance=None, occupant=None,
+                 occupant_iou=None, occupant_labels=None, stray=None):
+        self.compliance, self.status = compliance, status
+        self.outcomes, self.expected_positions, self.seen_labels, self.seen_distance = outcomes, expected_positions, seen_labels, seen_distance
+        self.occupant, self.occupant_iou, self.occupant_labels, self.stray = occupant, occupant_iou, occupant_labels, stray
+
+    def missing(self):
+        """the expected positions that hold no product of theirs (MISSING, OUT_OF_VIEW or UNCHECKED) -> list of indices"""
+        return [] if self.outcomes is None else torch.where(self.outcomes >= 2)[0].tolist()
+
+    def substituted(self):
+        """the missing positions on which an unclaimed detection sits -> list of indices"""
+        return [i for i in self.missing() if int(self.occupant[i]) >= 0]
+
+    def to_dict(self):
+        """plain JSON-able types (a value that is not finite becomes None; labels go as they are)"""
+        def plain(v):
+            if torch.is_tensor(v):
+                v = v.tolist()
+            if isinstance(v, (list, tuple)):
+                return [plain(x) for x in v]
+            if isinstance(v, float) and (v != v or v in (float('inf'), float('-inf'))):
+                return None
+            return v
+        d = {'compliance': float(self.compliance), 'status': self.status}
+        d.update({name: plain(getattr(self, name)) for name in self.FIELDS})
+        d.update(missing=self.missing(), substituted=self.substituted())
+        return d
 
 
 class PlanogramComparator:
@@ -381,21 +448,43 @@ class PlanogramComparator:
         positions to classify).  With `device_graphs` off it is the plain loop.  `actuals` may be a `planograms_device.DeviceActuals` --
         a window's detections as `BatchedPipeline.run(actuals=True)` left them on the device -- where `device_graphs` and `device_tail`
         are on (`_compare_device_actuals`)."""
+        return self._batch(expecteds, actuals, images, classifier)
+
+    def report(self, expected, actual, image=None, classifier=None):
+        """`compare` with its reasons -> `ComplianceReport`: `.compliance` is what `compare` returns, the other fields say which
+        expected positions were detected, recovered by the re-classification, missing, out of view or unchecked, what the matcher saw
+        there, which unclaimed detection sits on an undetected position and which sit on none (the report rule of DESIGN.md 4b)."""
+        if self.device_graphs:
+            return self.report_batch([expected], [actual], [image], classifier)[0]
+        return self._report_host(expected, actual, image, classifier)
+
+    def report_batch(self, expecteds, actuals, images=None, classifier=None):
+        """[report(e, a, img, classifier) for ...] on the route `compare_batch` takes with the same switches, at its number of waits:
+        with `device_tail` the outcomes, occupants and strays come from `report_positions` behind the tail and travel in the tail's own
+        copy; with `device_reclass` `report_reclass` runs behind the verdict and its rows travel in the verdict's copy; an image that
+        `compare_batch` sends through the host gets the host report."""
+        return self._batch(expecteds, actuals, images, classifier, report=True)
+
+    def _host(self, expected, actual, image, classifier, report):
+        return self._report_host(expected, actual, image, classifier) if report else self._compare_host(expected, actual, image, classifier)
+
+    def _batch(self, expecteds, actuals, images, classifier, report=False):
+        """`compare_batch` (report off: verdicts) and `report_batch` (report on: `ComplianceReport`s) on one route."""
         images = [None] * len(expecteds) if images is None else images
         if not isinstance(actuals, (list, tuple)):
             from . import planograms_device
             if isinstance(actuals, planograms_device.DeviceActuals):          # (detections that never left the device)
-                return self._compare_device_actuals(expecteds, actuals, images, classifier)
+                return self._compare_device_actuals(expecteds, actuals, images, classifier, report)
         if not self.device_graphs:
-            return [self._compare_host(e, a, img, classifier) for e, a, img in zip(expecteds, actuals, images)]
+            return [self._host(e, a, img, classifier, report) for e, a, img in zip(expecteds, actuals, images)]
         from . import planograms_device as pd
         results, todo = [None] * len(expecteds), []
         for i, (e, a, img) in enumerate(zip(expecteds, actuals, images)):
             if not len(a['boxes']):
-                results[i] = 0 if len(e['boxes']) else 1
+                results[i] = self._no_detections(e, report)
             elif not 1 <= len(e['boxes']) <= pd.MAX_NODES or len(a['boxes']) > pd.MAX_NODES:
                 self.host_routed += 1
-                results[i] = self._compare_host(e, a, img, classifier)
+                results[i] = self._host(e, a, img, classifier, report)
             else:
                 todo.append(i)
         if todo:
@@ -408,19 +497,101 @@ class PlanogramComparator:
             if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
                 ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
                 if ids is not None:
-                    return self._reclassified(results, todo, ge, ga, ids, expecteds, actuals, images, classifier)
+                    return self._reclassified(results, todo, ge, ga, ids, expecteds, actuals, images, classifier, report)
+                table = [self._image_row(images[i], classifier) for i in todo] if report else None
                 records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
-                                            [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo])
+                                            [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], report=table)
                 for i, rec in zip(todo, records):
+                    if report:
+                        results[i] = self._report_record(rec, expecteds[i], actuals[i]['labels'], images[i], classifier)
+                        continue
                     tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
                     results[i] = self._finish(rec['matching'], expecteds[i], actuals[i], images[i], classifier, tail)
                 return results
             matchings = pd.common_subgraphs(ge, ga)
             for i, matching in zip(todo, matchings):
-                results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
+                if report:
+                    results[i] = self._report_host(expecteds[i], actuals[i], images[i], classifier, matching)
+                else:
+                    results[i] = self._finish(matching, expecteds[i], actuals[i], images[i], classifier)
         return results
 
-    def _compare_device_actuals(self, expecteds, actuals, images, classifier):
+    @staticmethod
+    def _no_detections(expected, report):
+        verdict = 0 if len(expected['boxes']) else 1
+        return ComplianceReport(verdict, 'no_detections') if report else verdict
+
+    @staticmethod
+    def _image_row(image, classifier):
+        """an image's {h, w, enabled} row of the plan and report kernels: enabled where there is something to classify with and in"""
+        on = classifier is not None and image is not None
+        return datautils.image_hw(image) + (1,) if on else (0, 0, 0)
+
+    # ---- the compliance report (DESIGN.md 4b, the report rule) --------------------------------------------------------------
+    def _report_host(self, expected, actual, image, classifier, matching=None):
+        """`_compare_host` with its reasons: the host tail with both of its optional returns, then `planograms.report_positions`.
+        matching: the common subgraph where it was found elsewhere (`device_graphs` alone)."""
+        from . import planograms
+        if not len(actual['boxes']):
+            return self._no_detections(expected, True)
+        if matching is None:
+            ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'], self.graph_threshold)
+            ga = planograms.build_graph(actual['boxes'], actual['labels'], self.graph_threshold)
+            matching = planograms.large_common_subgraph(ge, ga)
+        if not len(matching):
+            return ComplianceReport(0, 'no_matching')
+        tail = planograms.finalize_via_ransac(matching, expected['boxes'], actual['boxes'], expected['labels'], actual['labels'],
+                                              reproj_threshold=self._reproj_threshold(image), return_matched_actual=True,
+                                              return_expected_positions=True)
+        if tail[0] is None:                     # no homography (production.py:98-99)
+            return ComplianceReport(len(matching) / len(expected['boxes']), 'no_homography')
+        matched_expected, matched_actual, positions = tail[:3]
+        hw = datautils.image_hw(image) if classifier is not None and image is not None else None
+        outcome, occupant, occupant_iou, stray = planograms.report_positions(matched_expected, matched_actual, positions, actual['boxes'], hw)
+        return self._report_finish(outcome, positions, occupant, occupant_iou, stray, [actual['labels'][j] if j >= 0 else None for j in occupant.tolist()],
+                                   expected, image, classifier)
+
+    def _report_record(self, rec, expected, actual_labels, image, classifier, final=None, annotations=None):
+        """A record of `planograms_device.finalize_batch(..., report=...)` as a `ComplianceReport`.  final: (outcome, seen_row,
+        seen_distance) where the window's re-classification decided the pending positions on the device; else they are decided here,
+        per image.  actual_labels: the detections' labels, or None where `annotations` names them by the occupants' gallery rows."""
+        if not rec['matching']:
+            return ComplianceReport(0, 'no_matching')
+        if rec['status'] == 'invalid':
+            raise RuntimeError('finalize_batch: the matching does not belong to the graphs')
+        if rec['status'] != 'ok':
+            return ComplianceReport(rec['matching'] / len(expected['boxes']), 'no_homography')
+        occupant = rec['occupant']
+        if actual_labels is not None:
+            labels = [actual_labels[j] if j >= 0 else None for j in occupant.tolist()]
+        else:
+            labels = [annotations[r] if j >= 0 else None for j, r in zip(occupant.tolist(), rec['occupant_row'].tolist())]
+        return self._report_finish(rec['outcome'], rec['expected_positions'], occupant, rec['occupant_iou'], rec['stray'], labels, expected, image,
+                                   classifier, final)
+
+    def _report_finish(self, outcome, positions, occupant, occupant_iou, stray, occupant_labels, expected, image, classifier, final=None):
+        """The second half of the report rule and the report itself.  Positions that are still PENDING are re-classified here, through
+        `classifier.classify_positions`, as `_finish` has them classified; final: what the device made of them instead."""
+        from . import planograms
+        n1 = len(outcome)
+        if final is not None:
+            outcome, seen_row, seen_distance = final
+        else:
+            outcome = outcome.clone()
+            seen_row, seen_distance = torch.full((n1,), -1, dtype=torch.int32), torch.full((n1,), -1.0, dtype=torch.float32)
+            pending = torch.where(outcome == planograms.PENDING)[0]
+            if len(pending):
+                h, w = datautils.image_hw(image)
+                rows, dist = classifier.classify_positions(image, planograms.clamp_positions(positions[pending], h, w)[0])
+                seen_row[pending], seen_distance[pending] = torch.tensor(rows, dtype=torch.int32), dist.to(torch.float32)
+                same = torch.tensor([expected['labels'][i] == classifier.annotations[r] for i, r in zip(pending.tolist(), rows)])
+                outcome[pending] = torch.where(same, planograms.RECOVERED, planograms.MISSING).to(outcome.dtype)
+        found = outcome <= planograms.RECOVERED
+        seen = [classifier.annotations[r] if r >= 0 else None for r in seen_row.tolist()]
+        return ComplianceReport(found.sum() / len(found), 'ok', outcome.to(torch.int8), positions, seen, seen_distance, occupant.to(torch.int32),
+                                occupant_iou, occupant_labels, torch.where(stray)[0])
+
+    def _compare_device_actuals(self, expecteds, actuals, images, classifier, report=False):
         """`compare_batch` on detections that never left the device (`planograms_device.DeviceActuals`; the detections rule of
         DESIGN.md 4b): the graph, match and tail kernels read the pack's boxes, label ids and thresholds where `actuals_pack` left
         them; the host knows the box counts alone.  An image without detections is decided here; an image whose expected or actual
@@ -436,7 +607,7 @@ class PlanogramComparator:
         results, todo, routed = [None] * len(expecteds), [], []
         for i, (e, n2) in enumerate(zip(expecteds, actuals.n2)):
             if not n2:
-                results[i] = 0 if len(e['boxes']) else 1
+                results[i] = self._no_detections(e, report)
             elif not 1 <= len(e['boxes']) <= pd.MAX_NODES or n2 > pd.MAX_NODES:
                 routed.append(i)
             else:
@@ -447,7 +618,7 @@ class PlanogramComparator:
         for i in routed:
             self.host_routed += 1
             boxes, labels = actuals.to_host(i, classifier.annotations)
-            results[i] = self._compare_host(expecteds[i], {'boxes': boxes, 'labels': labels}, images[i], classifier)
+            results[i] = self._host(expecteds[i], {'boxes': boxes, 'labels': labels}, images[i], classifier, report)
         if not todo:
             return results
         pack = actuals.select(todo)
@@ -461,13 +632,15 @@ class PlanogramComparator:
         boxes1 = [pd.expected_boxes_on_device(e, device) for e in es]
         reproj = [self._reproj_threshold(img) for img in imgs]
         reclass_ids = self._window_label_ids(es, classifier) if self.device_reclass else None
+        table = [datautils.image_hw(img) + (1,) if img is not None else (0, 0, 0) for img in imgs]
         if reclass_ids is None:
-            records = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj)
+            records = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, report=table if report else None)
             found = None
         else:
-            table = [datautils.image_hw(img) + (1,) if img is not None else (0, 0, 0) for img in imgs]
-            records, plan = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, reclass=table)
-            found = pd.reclassify_batch(plan, imgs, classifier, reclass_ids) if sum(plan.counts) else None
+            records, plan = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, reclass=table, report=table if report else None)
+            found = pd.reclassify_batch(plan, imgs, classifier, reclass_ids, report=report) if sum(plan.counts) else None
+        if report:
+            return self._window_reports(results, todo, records, found, expecteds, None, images, classifier)
         for p, (i, rec) in enumerate(zip(todo, records)):
             if found is not None and rec['status'] == 'ok':
                 results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
@@ -501,19 +674,35 @@ class PlanogramComparator:
             out.append(ids)
         return out
 
-    def _reclassified(self, results, todo, ge, ga, ids, expecteds, actuals, images, classifier):
+    def _window_reports(self, results, todo, records, found, expecteds, actuals, images, classifier):
+        """The reports of a device window.  found: `reclassify_batch(..., report=True)`'s tuple, or None where the window had no
+        position to classify (then no outcome is pending) or the re-classification runs per image.  actuals None: the detections are
+        a `DeviceActuals`, their labels are the annotations of the occupants' gallery rows."""
+        off = [0]
+        for i in todo:
+            off.append(off[-1] + len(expecteds[i]['boxes']))
+        for p, (i, rec) in enumerate(zip(todo, records)):
+            final = None
+            if found is not None and rec['status'] == 'ok':
+                a = slice(off[p], off[p + 1])
+                final = (found[1][a].clone(), found[2][a].clone(), found[3][a].clone())
+            results[i] = self._report_record(rec, expecteds[i], actuals[i]['labels'] if actuals is not None else None, images[i], classifier, final,
+                                             None if classifier is None else classifier.annotations)
+        return results
+
+    def _reclassified(self, results, todo, ge, ga, ids, expecteds, actuals, images, classifier, report=False):
         """The `device_reclass` window: graphs -> match -> tail -> plan back to back and the first wait; where the plan holds
         positions, crops -> embedder -> match -> verdict and the second wait (`planograms_device.reclassify_batch`).  The verdict
         of an image with a homography is found_count / n1 -- the value and dtype of `_finish`'s found.sum() / len(found); every
         other image, and a window without positions, ends in `_finish` as with `device_tail` alone."""
         from . import planograms_device as pd
-        table = []
-        for i in todo:
-            on = classifier is not None and images[i] is not None
-            table.append(datautils.image_hw(images[i]) + (1,) if on else (0, 0, 0))
+        table = [self._image_row(images[i], classifier) for i in todo]
         records, plan = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
-                                          [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], reclass=table)
-        found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, ids) if sum(plan.counts) else None
+                                          [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], reclass=table,
+                                          report=table if report else None)
+        found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, ids, report=report) if sum(plan.counts) else None
+        if report:
+            return self._window_reports(results, todo, records, found, expecteds, actuals, images, classifier)
         for p, (i, rec) in enumerate(zip(todo, records)):
             if found is not None and rec['status'] == 'ok':
                 results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
@@ -584,13 +773,28 @@ class PlanogramEvaluator:
         return image
 
     def evaluate(self, image, planogram):
+        return self._evaluate(image, planogram, False)
+
+    def report(self, image, planogram):
+        """`evaluate` with its reasons -> `ComplianceReport` (`PlanogramComparator.report` on the image's detections)."""
+        return self._evaluate(image, planogram, True)
+
+    def report_batch(self, images, planograms):
+        """[report(image, planogram) for ...] on the route `evaluate_batch` takes with the same switches."""
+        return self._evaluate_batch(images, planograms, True)
+
+    def report_iter(self, pairs, lookahead=4):
+        """`report(image, planogram)` over an iterable of pairs, windowed as `evaluate_iter` windows them."""
+        return self._evaluate_iter(pairs, lookahead, True)
+
+    def _evaluate(self, image, planogram, report):
         image = self._float_image(image)
         if self._on_device():
-            return self._evaluate_on_device([image], [planogram])[0]
+            return self._evaluate_on_device([image], [planogram], report)[0]
         boxes, images = self.proposal_generator.generate_proposals_and_images(image)
         classes = [ann[0] for ann in self.classifier.classify(images)]
-        return self.planogram_comparator.compare(planogram, {'boxes': boxes.detach().cpu(), 'labels': classes},
-                                                 image, self.classifier)
+        cmp = self.planogram_comparator
+        return (cmp.report if report else cmp.compare)(planogram, {'boxes': boxes.detach().cpu(), 'labels': classes}, image, self.classifier)
 
     def detect_and_classify_batch(self, images):
         """[(boxes (P,4) cpu, labels list[str])] for a list of images -- what `evaluate` hands to the comparator, per image, but
@@ -639,7 +843,7 @@ class PlanogramEvaluator:
             return False
         return True
 
-    def _evaluate_on_device(self, images, planograms):
+    def _evaluate_on_device(self, images, planograms, report=False):
         """A window with `device_detections`: `run(actuals=True)` per size group, the packs joined on the device, ONE `compare_batch`
         on them (in group order; the verdicts go back to the images' order)."""
         from . import planograms_device as pd
@@ -653,7 +857,8 @@ class PlanogramEvaluator:
         for idxs in self._size_groups(images):
             packs.append(pipe.run([ops.input_image(images[i], pg.device) for i in idxs], actuals=True)['actuals'])
             order += idxs
-        verdicts = cmp.compare_batch([planograms[i] for i in order], pd.DeviceActuals.concat(packs), [images[i] for i in order], self.classifier)
+        verdicts = (cmp.report_batch if report else cmp.compare_batch)([planograms[i] for i in order], pd.DeviceActuals.concat(packs),
+                                                                       [images[i] for i in order], self.classifier)
         out = [None] * len(images)
         for i, v in zip(order, verdicts):
             out[i] = v
@@ -664,19 +869,24 @@ class PlanogramEvaluator:
         (`detect_and_classify_batch`); the comparator (CPU graph matching, RANSAC, re-classification of missing positions) runs
         per image as in production.py:123-129.  With `device_detections` the detections go from the matcher to the comparator's
         kernels on the device (`_evaluate_on_device`)."""
+        return self._evaluate_batch(images, planograms, False)
+
+    def _evaluate_batch(self, images, planograms, report):
         images = [self._float_image(img) for img in images]
         if self._on_device():
-            return self._evaluate_on_device(images, planograms)
+            return self._evaluate_on_device(images, planograms, report)
         dets = self.detect_and_classify_batch(images)
-        return self._compare_all(images, planograms, dets)
+        return self._compare_all(images, planograms, dets, report)
 
-    def _compare_all(self, images, planograms, dets):
-        """The comparator over a window: per image, or -- a comparator with `device_graphs` on -- its `compare_batch`."""
+    def _compare_all(self, images, planograms, dets, report=False):
+        """The comparator over a window: per image, or -- a comparator with `device_graphs` on -- its `compare_batch` (report on:
+        `report` and `report_batch`)."""
         cmp = self.planogram_comparator
         actuals = [{'boxes': b, 'labels': labels} for b, labels in dets]
         if getattr(cmp, 'device_graphs', False) and hasattr(cmp, 'compare_batch'):
-            return cmp.compare_batch(list(planograms), actuals, list(images), self.classifier)
-        return [cmp.compare(plano, actual, img, self.classifier) for img, plano, actual in zip(images, planograms, actuals)]
+            return (cmp.report_batch if report else cmp.compare_batch)(list(planograms), actuals, list(images), self.classifier)
+        one = cmp.report if report else cmp.compare
+        return [one(plano, actual, img, self.classifier) for img, plano, actual in zip(images, planograms, actuals)]
 
 
     def evaluate_iter(self, pairs, lookahead=4):
@@ -688,19 +898,23 @@ class PlanogramEvaluator:
         `evaluate(image, planogram)` returns for that pair (tests/test_gpu_harness.py): an image's detections and labels do not depend
         on what it is batched with.  lookahead = 1 is the serial loop.  `pairs` may be a `feeding.ImageFeeder` over such pairs: its
         device-resident 8-bit images are converted where they are, never copied again."""
+        return self._evaluate_iter(pairs, lookahead, False)
+
+    def _evaluate_iter(self, pairs, lookahead, report):
         window = []
 
         def flush():
             if self._on_device():
-                yield from self._evaluate_on_device([img for img, _ in window], [plano for _, plano in window])
+                yield from self._evaluate_on_device([img for img, _ in window], [plano for _, plano in window], report)
                 window.clear()
                 return
             dets = self.detect_and_classify_batch([img for img, _ in window])
             if getattr(self.planogram_comparator, 'device_graphs', False):
-                yield from self._compare_all([img for img, _ in window], [plano for _, plano in window], dets)
+                yield from self._compare_all([img for img, _ in window], [plano for _, plano in window], dets, report)
             else:
+                one = self.planogram_comparator.report if report else self.planogram_comparator.compare
                 for (img, plano), (b, labels) in zip(window, dets):
-                    yield self.planogram_comparator.compare(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
+                    yield one(plano, {'boxes': b, 'labels': labels}, img, self.classifier)
             window.clear()
 
         for image, planogram in pairs:
