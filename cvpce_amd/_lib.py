@@ -2,8 +2,8 @@
 8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
 include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
 include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
-harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h and the compliance
-report kernels of include/cvpce_amd_report.h).
+harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h, the compliance
+report kernels of include/cvpce_amd_report.h and the picture compositor of include/cvpce_amd_render.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -155,8 +155,14 @@ REPORT_SIGNATURES = {
     'cvpce_report_reclass': (c_int, [_ip, _ip, _ip, _vp, _fp, _ip, _ip, _ip, _ip] + [c_int] * 6 + [_ip, _ip, _fp, _vp]),
 }
 
+# include/cvpce_amd_render.h: the compliance pictures' compositor.  A table of its own, like the header.
+RENDER_SIGNATURES = {
+    'cvpce_render_canvases': (c_int, [_vp, c_int, c_longlong, _vp, c_longlong, _vp, c_longlong, _fp, _ip, _ip, _ip, c_int, _vp, c_longlong, _ip, c_int,
+                                      c_int, _vp]),
+}
+
 for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES):
+               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -2,7 +2,7 @@
 cli/dihe.py:257-309,382-423, cli/eval.py:12-71,168-240): the same command names, arguments, options and defaults as the
 reference for
 
-    cvpce gln eval | gln detect | dihe eval | dihe prebuild-index | eval-product-detection | eval-planograms
+    cvpce gln eval | gln detect | dihe eval | dihe prebuild-index | eval-product-detection | eval-planograms | rebuild-scene
 
 Training, hyper-parameter search, dataset visualisation and plotting commands are out of scope.  Options that only steer
 the reference's matplotlib (`--plots`, `--plot-res-reduction`) are accepted and ignored: every metric is printed.
@@ -13,7 +13,9 @@ have no such option in the reference: they read the same way, with CVPCE_DATALOA
 One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
 (default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `eval-planograms` takes
 --device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`) and --report FILE
-(one JSON line per image saying which positions are missing and what is there; `_ReportCommand`), and `dihe eval` takes --device-eval /
+(one JSON line per image saying which positions are missing and what is there; `_ReportCommand`) and --render DIR (the three compliance
+pictures of every image as PNG files; `_RenderCommand`), `rebuild-scene` writes those pictures for one image (--out PREFIX instead of the
+reference's matplotlib window), and `dihe eval` takes --device-eval /
 --no-device-eval (default off: EVAL_WINDOW images at a time are cropped, embedded and matched in one pass and compared on the GPU;
 `_DeviceEvalCommand`).
 
@@ -241,6 +243,42 @@ def _report_file():
     return click.get_current_context().meta.get(_ReportCommand.REPORT_KEY)
 
 
+class _RenderCommand(_ReportCommand):
+    """The switches and --report above, and --render DIR (default: none) beside them, arranged the same way."""
+    RENDER_OPTION = '--render'
+    RENDER_HELP = ('Also write the three compliance pictures of every image to DIR as <index>_annotated.png, <index>_observed.png and '
+                   '<index>_expected.png (cvpce_amd.rendering.CompliancePictures: composed on the GPU, encoded on the host).  [default: none]')
+    RENDER_KEY = 'cvpce_amd.render'
+    RENDER_LABEL = '--render DIR'
+
+    def parse_args(self, ctx, args):
+        rest, args = [], list(args)
+        ctx.meta[self.RENDER_KEY] = None
+        i = 0
+        while i < len(args):
+            a = args[i]
+            if a == '--':
+                rest += args[i:]
+                break
+            if a == self.RENDER_OPTION:
+                if i + 1 >= len(args):
+                    raise click.UsageError('--render needs a directory', ctx)
+                ctx.meta[self.RENDER_KEY] = args[i + 1]
+                i += 1
+            elif a.startswith(self.RENDER_OPTION + '='):
+                ctx.meta[self.RENDER_KEY] = a[len(self.RENDER_OPTION) + 1:]
+            else:
+                rest.append(a)
+            i += 1
+        return super().parse_args(ctx, rest)
+
+    MORE = _ReportCommand.MORE + ((RENDER_LABEL, RENDER_HELP),)
+
+
+def _render_dir():
+    return click.get_current_context().meta.get(_RenderCommand.RENDER_KEY)
+
+
 class _DeviceEvalCommand(_DeviceMetricsCommand):
     """The same arrangement for --device-eval / --no-device-eval (default: off) of `dihe eval`."""
     SWITCH = {'--device-eval': True, '--no-device-eval': False}
@@ -432,7 +470,70 @@ def eval_product_detection(img_dir, test_imgs, annotations, iou_threshold, coco,
     print(f'--> mAR300 {m_ar / len(thresholds)}')
 
 
-@cli.command(cls=_ReportCommand)
+def _plano_sets(datatype, img_dir, test_imgs, test_annotations, planograms):
+    if datatype == 'gp':
+        return (datautils.PlanogramTestSet(test_imgs, test_annotations, planograms, image_format='uint8'),
+                datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8'))
+    return datautils.InternalPlanoSet(planograms, image_format='uint8'), datautils.InternalTrainSet(img_dir[0], include_annotations=True, image_format='uint8')
+
+
+def _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index):
+    proposal_generator = proposals_eval.load_gln(gln_state, False)
+    proposal_generator.requires_grad_(False)
+    generator = production.ProposalGenerator(proposal_generator)
+    classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
+    return production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
+                                                                                          device_tail=_device_tail_switch(),
+                                                                                          device_reclass=_device_reclass_switch()),
+                                         device_detections=_device_detections_switch())
+
+
+def _scene_renderer(evaluator, sampleset, workers):
+    """the gallery's product images on the device, row by row the classifier's, and the compositor over them"""
+    from .. import rendering
+    atlas = rendering.ThumbnailAtlas(sampleset, evaluator.classifier.annotations, evaluator.proposal_generator.device, num_workers=workers)
+    return rendering.SceneRenderer(atlas)
+
+
+def _accuracy_line(acc, plano):
+    err = acc - plano['actual_accuracy']
+    return f'Detected accuracy: {acc:.3f}, Actual accuracy: {plano["actual_accuracy"]:.3f}, Error: {err:.3f}, SE: {err ** 2:.3f}'
+
+
+@cli.command(cls=_DeviceDetectionsCommand)
+@click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
+              help='Path to training image root')
+@click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
+@click.option('--test-annotations', type=click.Path(**_DIR), default=GP_ANN_DIR, show_default=True, help='Path to annotation root')
+@click.option('--planograms', type=click.Path(**_DIR), default=GP_PLANO_DIR, show_default=True, help='Path to planograms root')
+@click.option('--datatype', type=click.Choice(('gp', 'internal')), default='gp', show_default=True,
+              help='Dataset type; gp for Grocery Product, internal for our internal dataset')
+@click.option('--load-classifier-index', type=click.Path(),
+              help='Load pre-embedded images from given path instead of calculating the embedding on the fly')
+@click.option('--plano-idx', type=int, default=0, show_default=True, help='Rebuild the image with the given index')
+@click.option('--out', type=click.Path(writable=True), required=True,
+              help='Prefix of the pictures: PREFIX_annotated.png, PREFIX_observed.png and PREFIX_expected.png are written')
+@click.argument('gln-state', type=click.Path(**_FILE))
+@click.argument('dihe-state', type=click.Path(**_FILE))
+def rebuild_scene(img_dir, test_imgs, test_annotations, planograms, datatype, load_classifier_index, plano_idx, out, gln_state, dihe_state):
+    """Rebuild scene from product detections.
+
+    Writes the shelf image with the compliance report drawn on it, the observed planogram (every detection's product image where it
+    was detected) and the expected planogram rebuilt the same way, and prints the compliance."""
+    planoset, sampleset = _plano_sets(datatype, img_dir, test_imgs, test_annotations, planograms)
+    if not 0 <= plano_idx < len(planoset):
+        raise click.UsageError(f'--plano-idx {plano_idx}: the set has {len(planoset)} images')
+    evaluator = _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index)
+    renderer = _scene_renderer(evaluator, sampleset, _reader_threads())
+    d = planoset[plano_idx]
+    img, plano = (d[0], d[3]) if datatype == 'gp' else tuple(d)
+    report, pictures = evaluator.pictures(img, plano, renderer)
+    for path in pictures.save(out):
+        print(path)
+    print(_accuracy_line(float(report.compliance), plano))
+
+
+@cli.command(cls=_RenderCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
@@ -449,20 +550,14 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
                     dihe_state):
     """Evaluate planogram compliance evaluation."""
     dataloader_workers = _reader_threads()
-    if datatype == 'gp':
-        planoset = datautils.PlanogramTestSet(test_imgs, test_annotations, planograms, image_format='uint8')
-        sampleset = datautils.GroceryProductsDataset(img_dir, include_annotations=True, image_format='uint8')
-    else:
-        planoset = datautils.InternalPlanoSet(planograms, image_format='uint8')
-        sampleset = datautils.InternalTrainSet(img_dir[0], include_annotations=True, image_format='uint8')
-    proposal_generator = proposals_eval.load_gln(gln_state, False)
-    proposal_generator.requires_grad_(False)
-    generator = production.ProposalGenerator(proposal_generator)
-    classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
-    evaluator = production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
-                                                                                              device_tail=_device_tail_switch(),
-                                                                                              device_reclass=_device_reclass_switch()),
-                                              device_detections=_device_detections_switch())
+    planoset, sampleset = _plano_sets(datatype, img_dir, test_imgs, test_annotations, planograms)
+    evaluator = _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index)
+    generator = evaluator.proposal_generator
+    render_dir = _render_dir()
+    renderer = None
+    if render_dir:
+        os.makedirs(render_dir, exist_ok=True)
+        renderer = _scene_renderer(evaluator, sampleset, dataloader_workers)
     report_path = _report_file()
     report_out = open(report_path, 'w') if report_path else None
     total_a = total_e = 0.0
@@ -472,18 +567,24 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
     for s, data in enumerate(proposals_eval._batches(feeding.feed(planoset, dataloader_workers, generator.device), EVAL_WINDOW)):
         s *= EVAL_WINDOW
         pairs = [((d[0], d[3]) if datatype == 'gp' else tuple(d)) for d in data]
-        if report_out is None:
+        if report_out is None and renderer is None:
             accs = evaluator.evaluate_batch([img for img, _ in pairs], [plano for _, plano in pairs])
         else:                                    # (the same route with its reasons: `.compliance` is evaluate_batch's value)
-            reports = evaluator.report_batch([img for img, _ in pairs], [plano for _, plano in pairs])
-            for i, rep in enumerate(reports, start=s):
+            if renderer is None:
+                reports = evaluator.report_batch([img for img, _ in pairs], [plano for _, plano in pairs])
+            else:                                # (and with its pictures: one launch per window, then a host encode per file)
+                results = evaluator.pictures_batch([img for img, _ in pairs], [plano for _, plano in pairs], renderer)
+                reports = [rep for rep, _ in results]
+                for i, (_, pictures) in enumerate(results, start=s):
+                    pictures.save(os.path.join(render_dir, str(i)))
+            for i, rep in enumerate(reports, start=s) if report_out is not None else ():
                 report_out.write(json.dumps(dict(rep.to_dict(), image=i)) + '\n')
             accs = [rep.compliance for rep in reports]
         for i, ((img, plano), acc) in enumerate(zip(pairs, accs), start=s):
             acc = float(acc)
             err = acc - plano['actual_accuracy']
             if verbose:
-                print(f'Detected accuracy: {acc:.3f}, Actual accuracy: {plano["actual_accuracy"]:.3f}, Error: {err:.3f}, SE: {err ** 2:.3f}')
+                print(_accuracy_line(acc, plano))
             elif i % 10 == 0:
                 print(i)
             total_e += err ** 2

@@ -787,6 +787,62 @@ class PlanogramEvaluator:
         """`report(image, planogram)` over an iterable of pairs, windowed as `evaluate_iter` windows them."""
         return self._evaluate_iter(pairs, lookahead, True)
 
+    def pictures(self, image, planogram, renderer):
+        """`report` with its pictures -> (`ComplianceReport`, `rendering.CompliancePictures`): the photo with the report drawn on it,
+        the observed planogram (every detection's product image where it was detected) and the expected planogram rebuilt the same way,
+        composed on the device by `renderer` (a `rendering.SceneRenderer` over the `ThumbnailAtlas` of this classifier's gallery)."""
+        return self.pictures_batch([image], [planogram], renderer)[0]
+
+    def pictures_batch(self, images, planograms, renderer):
+        """[pictures(image, planogram, renderer) for ...] on the route `report_batch` takes with the same switches; the reports are
+        `report_batch`'s, and all pictures of the window come from ONE `renderer.render` call: one launch, no wait.  With
+        `device_detections` the detections' boxes and gallery rows are read from the window's device pack and never visit the host;
+        on the host routes a label becomes the first gallery row that carries it (`rendering.label_rows`), -1 -- an empty rectangle --
+        where the gallery has none."""
+        from . import rendering
+        images, planograms = [self._float_image(img) for img in images], list(planograms)
+        if not images:
+            return []
+        table = self._label_rows()
+        if self._on_device():
+            reports, dets = self._device_window(images, planograms, True)
+        else:
+            host = self.detect_and_classify_batch(images)
+            reports = self._compare_all(images, planograms, host, True)
+            dets = [(b, rendering.rows_of_labels(labels, table)) for b, labels in host]
+        lists, sizes, bases = [], [], []
+        for img, plano, rep, (boxes, rows) in zip(images, planograms, reports, dets):
+            hw = datautils.image_hw(img)
+            ehw = rendering.expected_canvas_hw(plano['boxes'], hw[1])
+            lists += [rendering.annotation_items(rep, boxes, rendering.ANNOTATION_THICKNESS, hw), rendering.observed_items(boxes, rows),
+                      rendering.expected_items(plano['boxes'], rendering.rows_of_labels(plano['labels'], table), ehw)]
+            sizes += [hw, hw, ehw]
+            bases += [img, None, None]
+        views = renderer.render(lists, sizes, bases)
+        return [(rep, rendering.CompliancePictures(*views[3 * k:3 * k + 3])) for k, rep in enumerate(reports)]
+
+    def pictures_iter(self, pairs, renderer, lookahead=4):
+        """`pictures(image, planogram, renderer)` over an iterable of pairs, windowed as `report_iter` windows them: one `render` call
+        per window."""
+        window = []
+        for image, planogram in pairs:
+            image = self._float_image(image)
+            if window and (len(window) >= max(1, lookahead) or datautils.image_hw(image) != datautils.image_hw(window[0][0])):
+                yield from self.pictures_batch([img for img, _ in window], [plano for _, plano in window], renderer)
+                window.clear()
+            window.append((image, planogram))
+        if window:
+            yield from self.pictures_batch([img for img, _ in window], [plano for _, plano in window], renderer)
+
+    def _label_rows(self):
+        """`rendering.label_rows` of the classifier's annotations, made once per index (`index_generation`)"""
+        from . import rendering
+        generation = getattr(self.classifier, 'index_generation', None)
+        cached = self.__dict__.get('_label_rows_cache')
+        if cached is None or generation is None or cached[0] != generation:
+            cached = self._label_rows_cache = (generation, rendering.label_rows(self.classifier.annotations))
+        return cached[1]
+
     def _evaluate(self, image, planogram, report):
         image = self._float_image(image)
         if self._on_device():
@@ -846,23 +902,29 @@ class PlanogramEvaluator:
     def _evaluate_on_device(self, images, planograms, report=False):
         """A window with `device_detections`: `run(actuals=True)` per size group, the packs joined on the device, ONE `compare_batch`
         on them (in group order; the verdicts go back to the images' order)."""
+        return self._device_window(images, planograms, report)[0]
+
+    def _device_window(self, images, planograms, report):
+        """`_evaluate_on_device`'s window -> (the verdicts in the images' order, per image the (boxes, gallery rows) of its detections
+        as views of the window's device pack: what the pictures are made of, never copied to the host)."""
         from . import planograms_device as pd
         pg, cmp = self.proposal_generator, self.planogram_comparator
         pipe = self._pipeline()
         pipe.actuals_thresh_size = cmp.graph_threshold
         planograms = list(planograms)
         if not images:
-            return []
+            return [], []
         order, packs = [], []
         for idxs in self._size_groups(images):
             packs.append(pipe.run([ops.input_image(images[i], pg.device) for i in idxs], actuals=True)['actuals'])
             order += idxs
-        verdicts = (cmp.report_batch if report else cmp.compare_batch)([planograms[i] for i in order], pd.DeviceActuals.concat(packs),
-                                                                       [images[i] for i in order], self.classifier)
-        out = [None] * len(images)
-        for i, v in zip(order, verdicts):
-            out[i] = v
-        return out
+        pack = pd.DeviceActuals.concat(packs)
+        verdicts = (cmp.report_batch if report else cmp.compare_batch)([planograms[i] for i in order], pack, [images[i] for i in order], self.classifier)
+        out, dets, at = [None] * len(images), [None] * len(images), 0
+        for i, v, n in zip(order, verdicts, pack.n2):
+            out[i], dets[i] = v, (pack.boxes[at:at + n], pack.row[at:at + n])
+            at += n
+        return out, dets
 
     def evaluate_batch(self, images, planograms):
         """[evaluate(image, planogram) for image, planogram in zip(...)] with the detect / crop / embed / match half batched
