@@ -3,7 +3,8 @@
 include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
 include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
 harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h, the compliance
-report kernels of include/cvpce_amd_report.h and the picture compositor of include/cvpce_amd_render.h).
+report kernels of include/cvpce_amd_report.h, the picture compositor of include/cvpce_amd_render.h and the Gaussian-map scoring
+kernels of include/cvpce_amd_gaussians.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -161,8 +162,16 @@ RENDER_SIGNATURES = {
                                       c_int, _vp]),
 }
 
+# include/cvpce_amd_gaussians.h: the Gaussian maps' targets and loss.  A table of its own, like the header.
+GAUSSIANS_SIGNATURES = {
+    'cvpce_gauss_kant_table': (c_int, [_fp, c_int, c_int, _vp]),
+    'cvpce_gauss_targets': (c_int, [_ip, _ip, _vp, _ip, _fp] + [c_int] * 7 + [POINTER(c_float), c_int, c_int, _fp, _vp]),
+    'cvpce_gauss_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'cvpce_gauss_loss': (c_int, [_fp, _fp, _ip, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, _vp, c_size_t, _fp, _ip, _vp]),
+}
+
 for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES):
+               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES, GAUSSIANS_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

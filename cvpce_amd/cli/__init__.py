@@ -11,7 +11,9 @@ form, decoded that many at a time ahead of the kernels and uploaded from pinned 
 thread; the printed metrics are the same to the last digit, the inputs being the same bits).  The two whole-pipeline commands
 have no such option in the reference: they read the same way, with CVPCE_DATALOADER_WORKERS threads (default 8).
 One switch goes beyond the reference: `gln eval` and `eval-product-detection` take --device-metrics / --no-device-metrics
-(default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `eval-planograms` takes
+(default off: the matching behind mAP runs on the GPU instead of on the host; `_DeviceMetricsCommand`), `gln eval` also
+--gaussian-loss / --no-gaussian-loss with --gaussian-outlier-threshold (default off: every image's Gaussian map is scored on the GPU
+against the map rendered from its ground-truth boxes, the reference's gaussian_loss; `_GaussianLossCommand`), `eval-planograms` takes
 --device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`) and --report FILE
 (one JSON line per image saying which positions are missing and what is there; `_ReportCommand`) and --render DIR (the three compliance
 pictures of every image as PNG files; `_RenderCommand`), `rebuild-scene` writes those pictures for one image (--out PREFIX instead of the
@@ -292,6 +294,56 @@ def _device_eval_switch():
     return bool(click.get_current_context().meta.get(_DeviceEvalCommand.KEY, False))
 
 
+class _GaussianLossCommand(_DeviceMetricsCommand):
+    """--device-metrics as above, and beside it --gaussian-loss / --no-gaussian-loss (default: off) with its
+    --gaussian-outlier-threshold VALUE (default 3), arranged the same way: taken off the argument list before click parses the
+    reference's options."""
+    GAUSS_SWITCH = {'--gaussian-loss': True, '--no-gaussian-loss': False}
+    GAUSS_HELP = ('Also score every image\'s Gaussian map against the map rendered from its ground-truth boxes, on the GPU behind the detector '
+                  '(cvpce_amd.device_gaussians; the reference\'s gaussian_loss).  SKU-110K only: its boxes are integers.  [default: off]')
+    GAUSS_KEY = 'cvpce_amd.gaussian_loss'
+    GAUSS_LABEL = '--gaussian-loss / --no-gaussian-loss'
+    THRESHOLD = '--gaussian-outlier-threshold'
+    THRESHOLD_HELP = 'An image is an outlier when its loss exceeds mean + FLOAT * std of all losses (with --gaussian-loss).  [default: 3]'
+    THRESHOLD_KEY = 'cvpce_amd.gaussian_outlier_threshold'
+
+    def parse_args(self, ctx, args):
+        rest, i = [], 0
+        ctx.meta[self.GAUSS_KEY], ctx.meta[self.THRESHOLD_KEY] = False, 3.0
+        while i < len(args):
+            a = args[i]
+            if a == '--':
+                rest += args[i:]
+                break
+            value = None
+            if a == self.THRESHOLD:
+                i += 1
+                value = args[i] if i < len(args) else None
+                if value is None and not ctx.resilient_parsing:
+                    raise click.UsageError(f'{self.THRESHOLD} needs a value', ctx)
+            elif a.startswith(self.THRESHOLD + '='):
+                value = a.split('=', 1)[1]
+            elif a in self.GAUSS_SWITCH:
+                ctx.meta[self.GAUSS_KEY] = self.GAUSS_SWITCH[a]
+            else:
+                rest.append(a)
+            if value is not None:
+                try:
+                    ctx.meta[self.THRESHOLD_KEY] = float(value)
+                except ValueError:
+                    raise click.UsageError(f'{self.THRESHOLD}: {value!r} is not a number', ctx)
+            i += 1
+        return super().parse_args(ctx, rest)
+
+    MORE = ((GAUSS_LABEL, GAUSS_HELP), (THRESHOLD + ' FLOAT', THRESHOLD_HELP))
+
+
+def _gaussian_loss_switch():
+    """-> the outlier threshold when --gaussian-loss is on, else None"""
+    meta = click.get_current_context().meta
+    return meta.get(_GaussianLossCommand.THRESHOLD_KEY, 3.0) if meta.get(_GaussianLossCommand.GAUSS_KEY, False) else None
+
+
 @click.group()
 def cli():
     """Computer vision based planogram compliance evaluation -- MI355X inference / evaluation commands."""
@@ -303,7 +355,7 @@ def gln():
     """Product proposal generation (GLN)."""
 
 
-@gln.command(cls=_DeviceMetricsCommand)
+@gln.command(cls=_GaussianLossCommand)
 @click.option('--dataset', type=click.Choice(('sku110k', 'gp180', 'gpbaseline')), default='sku110k', show_default=True,
               help='Dataset type that --imgs and --annotations points to')
 @click.option('--imgs', type=click.Path(**_DIR), default=SKU110K_IMG_DIR, show_default=True, help='Path to image dir')
@@ -327,6 +379,13 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
     """Evaluate product proposal generation performance.
 
     STATE_FILE should point to some GLN weights."""
+    outlier_threshold = _gaussian_loss_switch()
+    if outlier_threshold is not None and dataset != 'sku110k':
+        raise click.UsageError('--gaussian-loss needs --dataset sku110k: Gaussian targets are rendered from integer boxes')
+    gaussian_score = None
+    if outlier_threshold is not None:
+        from .. import device_gaussians
+        gaussian_score = lambda model: device_gaussians.GaussianScore(model, outlier_threshold=outlier_threshold)  # noqa: E731
     if dataset == 'sku110k':
         data = datautils.SKU110KDataset(imgs, annotations, skip=SKU110K_SKIP, include_gaussians=False, flip_chance=0, image_format='uint8')
     elif dataset == 'gp180':
@@ -336,7 +395,7 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
     thresholds = _coco_or(iou_threshold, coco)
     evaluation = proposals_eval.evaluate_gln(state_file, data, thresholds=thresholds, batch_size=batch_size,
                                              num_workers=dataloader_workers, num_metric_processes=metric_workers, trim_module_prefix=trim_module_prefix,
-                                             device_metrics=_device_metrics_switch())
+                                             device_metrics=_device_metrics_switch(), gaussian_score=gaussian_score)
     ap = ar = 0
     for t in thresholds:
         print(f'{t}:\t{evaluation[t]}')
@@ -344,6 +403,11 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
         ar += evaluation[t]['ar_300']
     print(f'--> AP {ap / len(thresholds)}')
     print(f'--> AR300 {ar / len(thresholds)}')
+    if gaussian_score is not None:
+        scored = evaluation['gaussians']
+        print(f'--> Gaussian loss {scored["mean"]} (std {scored["std"]})')
+        for i in scored['outliers']:
+            print(f'Outlier at index {i}: {data.index[i]["image_name"]}\t{float(scored["loss"][i])}')
 
 
 @gln.command()

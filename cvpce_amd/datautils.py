@@ -28,6 +28,73 @@ def image_hw(img):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Gaussian target maps (datautils.py:18-85), rendered on the GPU by csrc/gaussians.hip under the rule of DESIGN.md 4c.  The
+# reference's generate methods are closures and its join methods functions that run per box on the host; here both are
+# small descriptors the kernel is told about, under the reference's names and numeric defaults.
+# ---------------------------------------------------------------------------------------------------------------------
+class GenerateMethod:
+    """What `generate_via_*` returns: the method's name, its three kernel parameters and, for the kant method, (size, sigma)."""
+
+    def __init__(self, name, params, table=None):
+        self.name, self.params, self.table = name, tuple(float(p) for p in params), table
+
+    def __repr__(self):
+        return f'GenerateMethod({self.name!r}, {self.params}, table={self.table})'
+
+
+class JoinMethod:
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return f'JoinMethod({self.name!r})'
+
+
+def _scalar_only(value, func_name, scalar_name, default_form):
+    if value is not None:
+        raise TypeError(f'{func_name} is a callable in the reference ({default_form}); on the GPU it is the scalar of that form: '
+                        f'pass {scalar_name}=<number> instead')
+
+
+def generate_via_multivariate_normal(peak=1, variance_func=None, variance_scale=0.5):
+    """datautils.py:27-37 with `variance_func = lambda a: (a * variance_scale) ** 2` (the reference's default: a / 2)."""
+    _scalar_only(variance_func, 'variance_func', 'variance_scale', 'lambda a: (a/2)**2')
+    if not variance_scale > 0:
+        raise ValueError('variance_scale must be positive')
+    return GenerateMethod('multivariate_normal', (peak, variance_scale, 0))
+
+
+def generate_via_kant_method(size=120, sigma=40):
+    """datautils.py:39-54: a size x size table resampled to every clipped box."""
+    if int(size) != size or int(sigma) != sigma or not 1 <= size <= 4096 or sigma < 1:
+        raise ValueError('size is an integer in [1, 4096], sigma a positive integer')
+    return GenerateMethod('kant_method', (0, 0, 0), table=(int(size), int(sigma)))
+
+
+def generate_via_simple_and_scaled(minimum=-1, maximum=1, sigma_func=None, sigma_divisor=6):
+    """datautils.py:56-63 with `sigma_func = lambda c: c / sigma_divisor` (the reference's default: c / 6)."""
+    _scalar_only(sigma_func, 'sigma_func', 'sigma_divisor', 'lambda c: c / 6')
+    if not sigma_divisor > 0:
+        raise ValueError('sigma_divisor must be positive')
+    return GenerateMethod('simple_and_scaled', (minimum, maximum, sigma_divisor))
+
+
+join_via_max = JoinMethod('max')
+join_via_addition = JoinMethod('addition')
+join_via_replacement = JoinMethod('replacement')
+
+
+def generate_gaussians(w, h, boxes, size_reduction=1, generate_method=None, join_method=join_via_max, tanh=False):
+    """datautils.py:65-85 on the GPU -> (h // size_reduction, w // size_reduction) float32 on the device, one launch.
+
+    boxes: (B,4) INTEGER xyxy (as SKU110KDataset reads them), on the host or the device; float boxes raise TypeError.  A box with
+    zero reduced extent or nothing left after clipping contributes nothing (the reference raises there for two of its three
+    methods: DESIGN.md 4c)."""
+    from . import device_gaussians          # (kernel calls: the readers below stay host-only)
+    return device_gaussians.render_full(w, h, boxes, size_reduction, generate_method, join_method, tanh)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Dataset readers of the eval commands (SURVEY.md 8f next-4).  Host-side, CPU: csv / json / os / PIL like the reference.
 # Only what inference needs: index building + image loading; the training-time augmentations (gaussian target maps,
 # flips, random crops, alpha masks) are not rebuilt and raise if asked for.

@@ -256,6 +256,11 @@ def resized_hw(h, w, min_size=None, max_size=None):
     return int(math.floor(float(h) * scale)), int(math.floor(float(w) * scale))
 
 
+def padded_hw(h, w, size_divisible=SIZE_DIVISIBLE):
+    """GeneralizedRCNNTransform.batch_images: an extent rounded up to the size divisor."""
+    return (int(math.ceil(h / size_divisible) * size_divisible), int(math.ceil(w / size_divisible) * size_divisible))
+
+
 class GLNEngine:
     """Weights packed for the HIP kernels (bf16 [Cout][K], FrozenBN/BN folded) + the launch schedule."""
 
@@ -344,9 +349,7 @@ class GLNEngine:
         (min_size, max_size: resized_hw's)."""
         sizes = [image_hw(i) for i in images]               # (either form: float (3,H,W) or uint8 (H,W,3))
         rs = [resized_hw(h, w, min_size, max_size) for h, w in sizes]
-        hp = int(math.ceil(max(r[0] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
-        wp = int(math.ceil(max(r[1] for r in rs) / SIZE_DIVISIBLE) * SIZE_DIVISIBLE)
-        return sizes, rs, (hp, wp)
+        return sizes, rs, padded_hw(max(r[0] for r in rs), max(r[1] for r in rs))
 
     def transform(self, images, out=None):
         sizes, rs, (hp, wp) = self.batch_geometry(images, self.min_size, self.max_size)
@@ -845,6 +848,12 @@ class GaussianLayerNetwork(nn.Module):
         _check_detect_options(self.topk_candidates, self.score_thresh, self.nms_thresh, self.detections_per_img)
         return int(self.topk_candidates), float(self.score_thresh), float(self.nms_thresh)
 
+    def image_geometry(self, original_sizes):
+        """-> [(transformed (h, w), the same padded to the size divisor)] of images of these (H, W), by this model's transform: the
+        sizes the reference's transform records in `image_sizes`, and the extent a batch of that image alone is padded to."""
+        rs = [resized_hw(int(h), int(w), self.transform.min_size[-1], self.transform.max_size) for h, w in original_sizes]
+        return [(r, padded_hw(*r)) for r in rs]
+
     def load_state_dict(self, *args, **kwargs):
         self._engine = None
         return super().load_state_dict(*args, **kwargs)
@@ -905,6 +914,19 @@ class GaussianLayerNetwork(nn.Module):
         for r, g in zip(res, self.backbone.get_gaussians()):
             r['gaussians'] = g
         return res
+
+
+def gaussian_loss(predictions, targets, sizes, tanh=False, negative_threshold=0.0, positive_threshold=0.1, min_negatives=1000,
+                  negatives_per_positive=3):
+    """proposals.py:141-160 on the GPU (forward only) -> a 0-dim float32 device tensor; nothing is copied to the host.
+
+    predictions: (N,1,Hb,Wb) float32 on the device; targets: N full-resolution maps (H_i, W_i) float32 (uploaded when on the host);
+    sizes: the transformed (h, w) of every image -- its map is resized to (h // 2, w // 2) into a batch tensor whose padding holds the
+    background value (-1 with `tanh`, else 0).  One loss over the whole tensor, padding included: the sum of the positives' squared
+    errors and of the max(min_negatives, negatives_per_positive * positives) largest negatives', over their count."""
+    from .. import device_gaussians
+    return device_gaussians.reference_loss(predictions, targets, sizes, tanh, negative_threshold, positive_threshold, min_negatives,
+                                           negatives_per_positive)
 
 
 def gln_backbone(trainable_layers=5, pretrained=True):

@@ -6,10 +6,15 @@ scores).  By default the matching runs on the host as in the reference, in-proce
 the detector, no per-image copy to the host, no worker processes, one device-to-host copy when the data set is exhausted) and
 gives the same result wherever an image's confidences are pairwise distinct (equal confidences: see device_metrics).  `dataset` is any of the readers in datautils.py, or any iterable of `(image (3,H,W) f32 in [0,1] or (H,W,3) uint8,
 target dict with 'boxes' (T,4))`.  num_workers > 0 reads it through `feeding.ImageFeeder` with that many threads (the reference's
-DataLoader workers); 0, the default, reads it in the calling thread."""
+DataLoader workers); 0, the default, reads it in the calling thread.
+
+`gaussian_score` (a `device_gaussians.GaussianScore`, default None = exactly the code without it) also scores every batch's Gaussian
+maps against targets rendered from the ground-truth boxes, on the device behind the detector with no host wait; its `compute()` is
+returned under the extra key 'gaussians' of the result dict."""
 import torch
 
 from . import feeding, metrics, utils
+from .datautils import image_hw
 from .models import proposals
 
 
@@ -21,6 +26,16 @@ def load_gln(save_file, trim_module_prefix, **kwargs):
     model = proposals.gln(pretrained_backbone=False, **kwargs)
     model.load_state_dict(state_dict)
     return model.cuda().eval()
+
+
+def _score_gaussians(gaussian_score, result, batch):
+    gaussian_score.update(result, [t['boxes'] for _, t in batch], [image_hw(img) for img, _ in batch])
+
+
+def _with_gaussians(res, gaussian_score):
+    if gaussian_score is not None:
+        res['gaussians'] = gaussian_score.compute()
+    return res
 
 
 def _batches(dataset, batch_size):
@@ -36,23 +51,25 @@ def _batches(dataset, batch_size):
 
 @torch.no_grad()
 def evaluate_gln_sync(model, dataset, thresholds=(.5,), batch_size=1, num_workers=0, plots=False, silent=True,
-                      plot_res_reduction=1, device_metrics=False):
+                      plot_res_reduction=1, device_metrics=False, gaussian_score=None):
     if device_metrics:
-        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent)
+        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent, gaussian_score)
     predictions, targets, confidences = [], [], []
     for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
         if not silent and i % 100 == 0:
             print(f'{i}...')
         result = model([img.cuda(non_blocking=True) for img, _ in batch])
+        if gaussian_score is not None:
+            _score_gaussians(gaussian_score, result, batch)
         for r, (_, t) in zip(result, batch):
             predictions.append(r['boxes'].detach().cpu())
             targets.append(t['boxes'].detach().cpu())
             confidences.append(r['scores'].detach().cpu())
     res = metrics.calculate_metrics(targets, predictions, confidences, thresholds)
-    return {thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}
+    return _with_gaussians({thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}, gaussian_score)
 
 
-def _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent):
+def _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent, gaussian_score=None):
     from . import device_metrics
     accumulator = device_metrics.DetectionMetrics(thresholds)
     for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
@@ -60,23 +77,27 @@ def _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, si
             print(f'{i}...')
         result = model([img.cuda(non_blocking=True) for img, _ in batch])
         accumulator.update([t['boxes'] for _, t in batch], [r['boxes'] for r in result], [r['scores'] for r in result])
+        if gaussian_score is not None:
+            _score_gaussians(gaussian_score, result, batch)
     res = accumulator.compute()
-    return {thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}
+    return _with_gaussians({thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}, gaussian_score)
 
 
 @torch.no_grad()
 def evaluate_gln_async(model, dataset, thresholds=(.5,), batch_size=1, num_workers=0, num_metric_processes=4, plots=False,
-                       plot_res_reduction=1, silent=True, device_metrics=False):
+                       plot_res_reduction=1, silent=True, device_metrics=False, gaussian_score=None):
     """proposals_eval.py:50-87: detections are handed to `num_metric_processes` matching workers as they are produced.
     device_metrics=True: no workers are started, the matching is queued on the device behind each batch."""
     if device_metrics:
-        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent)
+        return _evaluate_gln_device(model, dataset, thresholds, batch_size, num_workers, silent, gaussian_score)
     # (the metric processes are started BEFORE the feeder's reader threads exist: a process forked beside running threads can deadlock)
     queue, mqueue, pipe = metrics.calculate_metrics_async(processes=num_metric_processes, iou_thresholds=thresholds)
     for i, batch in enumerate(_batches(feeding.feed(dataset, num_workers), batch_size)):
         if not silent and i % 100 == 0:
             print(f'GPU: {i}...')
         result = model([img.cuda(non_blocking=True) for img, _ in batch])
+        if gaussian_score is not None:
+            _score_gaussians(gaussian_score, result, batch)
         for r, (_, t) in zip(result, batch):
             queue.put((t['boxes'], r['boxes'], r['scores']))
     queue.join()
@@ -89,16 +110,19 @@ def evaluate_gln_async(model, dataset, thresholds=(.5,), batch_size=1, num_worke
     mqueue.join()
     if res is None:                               # empty dataset: what the synchronous routine returns
         res = metrics.calculate_metrics([], [], [], thresholds)
-    return {thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}
+    return _with_gaussians({thr: {k: v for k, v in itm.items() if k != 'raw'} for thr, itm in res.items()}, gaussian_score)
 
 
 def evaluate_gln(save_file, dataset, thresholds=(.5,), batch_size=1, num_workers=0, num_metric_processes=4, plots=False,
-                 trim_module_prefix=True, resolution_reduction=1, device_metrics=False):
+                 trim_module_prefix=True, resolution_reduction=1, device_metrics=False, gaussian_score=None):
     """proposals_eval.py:89-91.  num_metric_processes = 0 runs the matching in-process (evaluate_gln_sync); device_metrics=True
-    runs it on the device and ignores num_metric_processes."""
+    runs it on the device and ignores num_metric_processes.  gaussian_score: a `device_gaussians.GaussianScore`, or a callable
+    that makes one from the loaded model (the model does not exist before this call)."""
     model = load_gln(save_file, trim_module_prefix)
+    if gaussian_score is not None and not hasattr(gaussian_score, 'update'):
+        gaussian_score = gaussian_score(model)
     if device_metrics:
-        return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers, device_metrics=True)
+        return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers, device_metrics=True, gaussian_score=gaussian_score)
     if num_metric_processes and num_metric_processes > 0:
-        return evaluate_gln_async(model, dataset, thresholds, batch_size, num_workers, num_metric_processes)
-    return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers)
+        return evaluate_gln_async(model, dataset, thresholds, batch_size, num_workers, num_metric_processes, gaussian_score=gaussian_score)
+    return evaluate_gln_sync(model, dataset, thresholds, batch_size, num_workers, gaussian_score=gaussian_score)
