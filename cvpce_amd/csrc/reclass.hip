@@ -9,18 +9,12 @@
 //
 // Compiled with -ffp-contract=off like its neighbours: the two subtractions of the validity test are rounded on their own.
 #include "common.h"
+#include "window.h"
 #include "../../include/cvpce_amd_reclass.h"
 
 #define RC_THREADS CVPCE_RECLASS_THREADS
 #define RC_WAVES (RC_THREADS / WAVE)
 #define RC_MAX_NODES CVPCE_RECLASS_MAX_NODES
-#define RC_STATUS_OK 0                          // CVPCE_HOMOGRAPHY_OK
-
-// torch.clamp(min=lo, max=hi) on the host, comparison by comparison: a NaN fails both and stays, -0 is not below 0 and stays
-__device__ __forceinline__ float rc_clamp(float v, float lo, float hi) {
-    const float t = v < lo ? lo : v;
-    return hi < t ? hi : t;
-}
 
 __global__ __launch_bounds__(RC_THREADS) void reclass_plan_kernel(
     const int* __restrict__ status, const int* __restrict__ matched_expected, const float4* __restrict__ positions,
@@ -29,9 +23,9 @@ __global__ __launch_bounds__(RC_THREADS) void reclass_plan_kernel(
 #pragma clang fp contract(off)
     __shared__ int s_wave[RC_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int a0 = min(max(off1[p], 0), sumN1), a1 = min(max(off1[p + 1], a0), sumN1);
-    const int n1 = a1 - a0;
-    if (status[p] != RC_STATUS_OK || image[3 * p + 2] == 0 || n1 > cap) {      // (uniform)
+    const WnSlice expected = wn_slice(off1, p, sumN1);
+    const int a0 = expected.at, n1 = expected.n;
+    if (status[p] != CVPCE_HOMOGRAPHY_OK || image[3 * p + 2] == 0 || n1 > cap) {      // (uniform)
         if (tid == 0) count[p] = 0;
         return;
     }
@@ -43,12 +37,8 @@ __global__ __launch_bounds__(RC_THREADS) void reclass_plan_kernel(
         bool valid = false;
         float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < n1 && matched_expected[a0 + i] == 0) {
-            b = positions[a0 + i];
-            b.x = rc_clamp(b.x, 0.f, wf);
-            b.z = rc_clamp(b.z, 0.f, wf);
-            b.y = rc_clamp(b.y, 0.f, hf);
-            b.w = rc_clamp(b.w, 0.f, hf);
-            valid = (b.z - b.x > 1.f) && (b.w - b.y > 1.f);                   // (false on NaN)
+            b = wn_clamp_box(positions[a0 + i], wf, hf);
+            valid = wn_in_view(b);                                            // (false on NaN)
         }
         const unsigned long long ballot = __ballot(valid);
         if (lane == 0) s_wave[wave] = __popcll(ballot);
@@ -79,9 +69,9 @@ __global__ __launch_bounds__(RC_THREADS) void reclass_verdict_kernel(
     __shared__ int s_found[RC_MAX_NODES];
     __shared__ int s_sum[RC_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int a0 = min(max(off1[p], 0), sumN1), a1 = min(max(off1[p + 1], a0), sumN1);
-    const int n1 = a1 - a0;
-    if (status[p] != RC_STATUS_OK || n1 > cap) {                               // (uniform)
+    const WnSlice expected = wn_slice(off1, p, sumN1);
+    const int a0 = expected.at, n1 = expected.n;
+    if (status[p] != CVPCE_HOMOGRAPHY_OK || n1 > cap) {                        // (uniform)
         if (tid == 0) found_count[p] = -1;
         return;
     }
@@ -90,12 +80,9 @@ __global__ __launch_bounds__(RC_THREADS) void reclass_verdict_kernel(
     const int c = min(max(count[p], 0), cap);
     const size_t row0 = (size_t)p * cap;
     for (int s = tid; s < c; s += RC_THREADS) {
-        const int e = expected_index[row0 + s];
-        if (e < 0 || e >= n1) continue;
-        const int row = slot_row[row0 + s];
-        if (row < 0 || row >= M) continue;
-        const long long j = indices[(size_t)row * k];
-        if (j < 0 || j >= (long long)G) continue;
+        int e;
+        long long j;
+        if (!wn_slot_gallery_row(expected_index, slot_row, indices, row0, s, n1, M, k, G, e, j)) continue;
         const int want = expected_label_id[a0 + e];
         if (want >= 0 && gallery_label_id[j] == want) s_found[e] = 1;          // (two slots of one box store the same 1)
     }

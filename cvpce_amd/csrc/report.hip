@@ -12,22 +12,16 @@
 //   report_reclass_kernel    one workgroup per image: the lowest slot of every position by an LDS integer minimum, a recovered flag
 //                            (every writer stores 1), then one pass over the positions.
 //
-// Compiled with -ffp-contract=off like its neighbours: the validity test is reclass.hip's, the IoU is homography.hip's (iou.h).
+// Compiled with -ffp-contract=off like its neighbours: the validity test is reclass.hip's (window.h), the IoU is homography.hip's (iou.h).
 #include "common.h"
 #include "iou.h"
+#include "window.h"
 #include "../../include/cvpce_amd_report.h"
 #include <limits.h>
 
 #define RP_THREADS CVPCE_REPORT_THREADS
 #define RP_WAVES (RP_THREADS / WAVE)
 #define RP_MAX_NODES CVPCE_REPORT_MAX_NODES
-#define RP_STATUS_OK 0                          // CVPCE_HOMOGRAPHY_OK
-
-// reclass.hip's clamp, comparison by comparison: a NaN fails both and stays, -0 is not below 0 and stays
-__device__ __forceinline__ float rp_clamp(float v, float lo, float hi) {
-    const float t = v < lo ? lo : v;
-    return hi < t ? hi : t;
-}
 
 // whether candidate (iou, j) comes before (best, bj): larger IoU, then lower index; j == INT_MAX stands for "none" and loses to all
 __device__ __forceinline__ bool rp_before(float iou, int j, float best, int bj) {
@@ -45,10 +39,9 @@ __global__ __launch_bounds__(RP_THREADS) void report_positions_kernel(
     __shared__ int s_free[RP_MAX_NODES];            // matched_actual == 0
     __shared__ int s_occupant[RP_MAX_NODES];        // some position's occupant
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int a0 = min(max(off1[p], 0), sumN1), a1 = min(max(off1[p + 1], a0), sumN1);
-    const int b0 = min(max(off2[p], 0), sumN2), b1 = min(max(off2[p + 1], b0), sumN2);
-    const int n1 = a1 - a0, n2 = b1 - b0;
-    if (status[p] != RP_STATUS_OK || n1 > RP_MAX_NODES || n2 > RP_MAX_NODES) return;      // (uniform)
+    const WnSlice expected = wn_slice(off1, p, sumN1), actual = wn_slice(off2, p, sumN2);
+    const int a0 = expected.at, n1 = expected.n, b0 = actual.at, n2 = actual.n;
+    if (status[p] != CVPCE_HOMOGRAPHY_OK || n1 > RP_MAX_NODES || n2 > RP_MAX_NODES) return;      // (uniform)
     for (int j = tid; j < n2; j += RP_THREADS) {
         s_box[j] = boxes[b0 + j];
         s_free[j] = matched_actual[b0 + j] == 0;
@@ -92,9 +85,7 @@ __global__ __launch_bounds__(RP_THREADS) void report_positions_kernel(
                 if (enabled == 0) {
                     code = CVPCE_REPORT_UNCHECKED;
                 } else {
-                    const float x0 = rp_clamp(pos.x, 0.f, wf), x1 = rp_clamp(pos.z, 0.f, wf);
-                    const float y0 = rp_clamp(pos.y, 0.f, hf), y1 = rp_clamp(pos.w, 0.f, hf);
-                    code = (x1 - x0 > 1.f) && (y1 - y0 > 1.f) ? CVPCE_REPORT_PENDING : CVPCE_REPORT_OUT_OF_VIEW;      // (false on NaN)
+                    code = wn_in_view(wn_clamp_box(pos, wf, hf)) ? CVPCE_REPORT_PENDING : CVPCE_REPORT_OUT_OF_VIEW;      // (false on NaN)
                 }
             }
             const bool has = bj != INT_MAX;                                              // (then 0 <= bj < n2)
@@ -117,9 +108,9 @@ __global__ __launch_bounds__(RP_THREADS) void report_reclass_kernel(
     __shared__ int s_first[RP_MAX_NODES];           // the lowest slot of the position with an in-range row and index
     __shared__ int s_recovered[RP_MAX_NODES];
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int a0 = min(max(off1[p], 0), sumN1), a1 = min(max(off1[p + 1], a0), sumN1);
-    const int n1 = a1 - a0;
-    if (status[p] != RP_STATUS_OK || n1 > cap) return;                                  // (uniform)
+    const WnSlice expected = wn_slice(off1, p, sumN1);
+    const int a0 = expected.at, n1 = expected.n;
+    if (status[p] != CVPCE_HOMOGRAPHY_OK || n1 > cap) return;                           // (uniform)
     for (int i = tid; i < n1; i += RP_THREADS) {
         s_first[i] = INT_MAX;
         s_recovered[i] = 0;
@@ -128,12 +119,9 @@ __global__ __launch_bounds__(RP_THREADS) void report_reclass_kernel(
     const int c = min(max(count[p], 0), cap);
     const size_t row0 = (size_t)p * cap;
     for (int s = tid; s < c; s += RP_THREADS) {
-        const int e = expected_index[row0 + s];
-        if (e < 0 || e >= n1) continue;
-        const int row = slot_row[row0 + s];
-        if (row < 0 || row >= M) continue;
-        const long long j = indices[(size_t)row * k];
-        if (j < 0 || j >= (long long)G) continue;
+        int e;
+        long long j;
+        if (!wn_slot_gallery_row(expected_index, slot_row, indices, row0, s, n1, M, k, G, e, j)) continue;
         atomicMin(&s_first[e], s);                                                       // (LDS integer minimum: any order, one result)
         const int want = expected_label_id[a0 + e];
         if (want >= 0 && gallery_label_id[j] == want) s_recovered[e] = 1;                // (any writer: they all write 1)

@@ -28,7 +28,8 @@ tie-free, the device graph is the host graph.
 
 Graphs of more than MAX_NODES nodes are refused here; the comparator sends such an image through the host path.
 """
-from collections import Counter
+from collections import Counter, namedtuple
+from types import SimpleNamespace
 
 import networkx as nx
 import torch
@@ -118,6 +119,16 @@ def _offsets(lengths):
     return off
 
 
+def _upload_tables(device, **tables):
+    """Small int32 tables (lists) in ONE upload -> their views on the device by name; they lie in the order given."""
+    small = _upload(torch.tensor([v for table in tables.values() for v in table], dtype=torch.int32), device)
+    views, at = {}, 0
+    for name, table in tables.items():
+        views[name] = small[at:at + len(table)]
+        at += len(table)
+    return SimpleNamespace(**views)
+
+
 def build_graphs(items, thresh_size=0.5, device=None):
     """items: list of (boxes (n,4) xyxy, labels list of n) -> list of `Graph` on the device, built by one launch.  1 <= n <= MAX_NODES.
     Device work only: nothing is copied back.  items may be a `DeviceActuals` instead: its boxes, offsets and thresholds are read
@@ -181,8 +192,22 @@ def min_agree_for(min_score):
     return next((a for a in range(len(CARDINALS) + 1) if not -(a / len(CARDINALS)) > min_score), len(CARDINALS) + 1)
 
 
+def _launch_record(name):
+    """The arguments of the op `name` as a record type: one field per argument, under the op's own names and in its order (read off
+    its schema), so a record is filled by keyword, read by name and launched as a whole -- `launch()` -- whatever the order is."""
+    op = getattr(torch.ops.cvpce_amd, name)
+    record = namedtuple(name, [a.name for a in op.default._schema.arguments])
+    record.launch = lambda self: op(*self)
+    return record
+
+
+MatchLaunch = _launch_record('planogram_match')
+RansacLaunch = _launch_record('homography_ransac')
+FinishLaunch = _launch_record('homography_finish')          # (its outputs are `TailLayout.views` of the tail's blob)
+
+
 def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, expected_ids=None):
-    """Everything `planogram_match` needs, uploaded -> (argument tuple of the op, its output tensor = pairs then counts, row offsets).
+    """Everything `planogram_match` needs, uploaded -> (`MatchLaunch`, its output tensor = pairs then counts, row offsets).
     actuals (a `DeviceActuals`, with expected_ids = `expected_label_ids`' (ids, largest multiplicity) per planogram): the actual side's
     ids and offsets are the pack's own, the expected ids come from the classifier's id space, and the hypothesis workspace is sized by
     the host's bound n2 x (largest multiplicity of an expected label) -- the kernel counts the hypotheses itself."""
@@ -213,22 +238,18 @@ def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, 
     hyp_off, out_off = _offsets(hyps), _offsets([min(a, b) for a, b in zip(n1, n2)])
     if hyp_off[-1] >= 2 ** 31:
         raise ValueError('too many equal-label node pairs for one launch: split the batch')
-    parts = [lab1, lab2, off1, off2 if actuals is None else [], params, hyp_off, out_off]
-    small = _upload(torch.tensor([v for part in parts for v in part], dtype=torch.int32), device)      # one upload for all the small tables
-    views, at = [], 0
-    for part in parts:
-        views.append(small[at:at + len(part)])
-        at += len(part)
+    small = _upload_tables(device, label1=lab1, label2=lab2, off1=off1, off2=off2 if actuals is None else [], params=params,
+                           hyp_off=hyp_off, out_off=out_off)
+    label2, dev_off2 = (small.label2, small.off2) if actuals is None else (actuals.label, actuals.off2)
     nbr1, stamp1 = _packed(expected, device)
     nbr2, stamp2 = _packed(actual, device)
     workspace = torch.empty(max(hyp_off[-1], 1), dtype=torch.int32, device=device)
     out = torch.empty(out_off[-1] * 2 + len(n1), dtype=torch.int32, device=device)      # the pairs, then the counts: one copy back
     pairs, count = out[:out_off[-1] * 2].view(-1, 2), out[out_off[-1] * 2:]
-    if actuals is not None:
-        views[1], views[3] = actuals.label, actuals.off2
-    args = (nbr1, stamp1, views[0], views[2], nbr2, stamp2, views[1], views[3], views[4], views[5], views[6],
-            max(n1), max(n2), hyp_off[-1], workspace, pairs, count)
-    return args, out, out_off
+    match = MatchLaunch(nbr1=nbr1, stamp1=stamp1, label1=small.label1, off1=small.off1, nbr2=nbr2, stamp2=stamp2, label2=label2, off2=dev_off2,
+                        params=small.params, hyp_off=small.hyp_off, out_off=small.out_off, max_n1=max(n1), max_n2=max(n2),
+                        hypotheses=hyp_off[-1], workspace=workspace, pairs=pairs, count=count)
+    return match, out, out_off
 
 
 def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
@@ -267,19 +288,50 @@ def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, ac
     actuals / expected_ids: the actual side is a `DeviceActuals` (`actual` = its graphs), see `_prepare_match`."""
     if len(expected) != len(actual) or not expected:
         raise ValueError('one actual graph per expected graph, at least one pair')
-    args, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction, actuals, expected_ids)
-    torch.ops.cvpce_amd.planogram_match(*args)
+    match, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction, actuals, expected_ids)
+    match.launch()
     m = DeviceMatching()
-    m.label1, m.off1, m.label2, m.off2, m.out_off, m.pairs, m.count = args[2], args[3], args[6], args[7], args[10], args[15], args[16]
+    m.label1, m.off1, m.label2, m.off2 = match.label1, match.off1, match.label2, match.off2
+    m.out_off, m.pairs, m.count = match.out_off, match.pairs, match.count
     m.out, m.rows, m.n1, m.n2 = out, out_off, [len(g) for g in expected], [len(g) for g in actual]
     return m
 
 
-def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses, extra=0):
-    """Everything the two tail launches need, uploaded -> (arguments of homography_ransac, of homography_finish, the output blob,
-    its layout).  Every output lies in ONE allocation -- positions (f32), H (f64), then the int32 fields status, winner, winner count,
-    final count, matching size, matched_expected, matched_actual, then `extra` more int32 words (the compliance report's rows) -- so that
-    one copy brings it back.  The layout's last entry is the view of those extra words."""
+TailViews = namedtuple('TailViews', 'pos hmat status winner winner_count final_count size matched_expected matched_actual '
+                                    'outcome occupant occupant_iou occupant_row stray', defaults=(None,) * 5)
+
+
+class TailLayout:
+    """Where the outputs of a window's tail lie in their ONE allocation, so that one copy brings them back: positions (f32), H (f64),
+    then the int32 fields status, winner, winner count, final count, matching size, matched_expected, matched_actual and -- with
+    `extra`, for the compliance report -- outcome, occupant, occupant IoU (f32), occupant row and stray.  The byte offsets are here
+    and nowhere else: `views` is applied to the device blob for the launches and to its pinned copy for the records."""
+    __slots__ = ('b', 'sum1', 'sum2', 'extra', 'at_h', 'at_i', 'at_m', 'nbytes')
+
+    def __init__(self, b, sum1, sum2, extra=False):
+        self.b, self.sum1, self.sum2, self.extra = b, sum1, sum2, bool(extra)
+        self.at_h = 16 * sum1                           # bytes: H behind the positions
+        self.at_i = self.at_h + 72 * b                  # bytes: the int32 fields behind H
+        self.at_m = 5 * b                               # int32 words: the per-box fields behind the five per-image ones
+        self.nbytes = self.at_i + 4 * (self.at_m + sum1 + sum2 + (4 * sum1 + sum2 if self.extra else 0))
+
+    def views(self, blob):
+        """blob: a uint8 tensor of `nbytes`, on any device -> `TailViews`"""
+        b, sum1, sum2, m = self.b, self.sum1, self.sum2, self.at_m
+        pos, hmat = blob[:self.at_h].view(torch.float32).view(sum1, 4), blob[self.at_h:self.at_i].view(torch.float64)
+        i32 = blob[self.at_i:].view(torch.int32)
+        per_image = [i32[k * b:(k + 1) * b] for k in range(5)]
+        per_box = [i32[m:m + sum1], i32[m + sum1:m + sum1 + sum2]]
+        if not self.extra:
+            return TailViews(pos, hmat, *per_image, *per_box)
+        r = m + sum1 + sum2
+        rows = [i32[r + k * sum1:r + (k + 1) * sum1] for k in range(4)]
+        return TailViews(pos, hmat, *per_image, *per_box, rows[0], rows[1], rows[2].view(torch.float32), rows[3], i32[r + 4 * sum1:])
+
+
+def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses, report=False):
+    """Everything the two tail launches need, uploaded -> (`RansacLaunch`, `FinishLaunch`, the output blob, its `TailLayout`, the
+    layout's views of the blob).  report: the blob also holds the compliance report's rows."""
     b = len(matching.n1)
     if not (b == len(expected_boxes) == len(actual_boxes) == len(reproj_thresholds)) or not b:
         raise ValueError('one entry per image, at least one image')
@@ -310,17 +362,16 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
         boxes1, boxes2 = boxes[:sum1], boxes[sum1:]
     params = _upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
     workspace = torch.empty(max(torch_ops_homography.workspace_bytes(b, hypotheses), 8) // 4, dtype=torch.int32, device=device)
-    at_h, at_i = 16 * sum1, 16 * sum1 + 72 * b
-    blob = torch.empty(at_i + 4 * (5 * b + sum1 + sum2 + extra), dtype=torch.uint8, device=device)
-    pos, hmat, i32 = blob[:at_h].view(torch.float32).view(sum1, 4), blob[at_h:at_i].view(torch.float64), blob[at_i:].view(torch.int32)
-    status, winner, wcount, fcount = (i32[k * b:(k + 1) * b] for k in range(4))
-    me, ma = i32[5 * b:5 * b + sum1], i32[5 * b + sum1:5 * b + sum1 + sum2]
-    max_pairs = max(1, max(min(a, c) for a, c in zip(n1, n2)))
-    common = (matching.pairs, matching.count, matching.out_off, params)
-    ransac = (boxes1, matching.off1, boxes2, matching.off2, *common, max_pairs, seed, hypotheses, workspace)
-    finish = (boxes1, matching.label1, matching.off1, boxes2, matching.label2, matching.off2, *common, max(n1), max(n2), max_pairs,
-              seed, hypotheses, workspace, status, hmat, winner, wcount, fcount, me, ma, pos)
-    return ransac, finish, blob, (at_h, at_i, i32[4 * b:5 * b], i32[5 * b + sum1 + sum2:])
+    layout = TailLayout(b, sum1, sum2, extra=report)
+    blob = torch.empty(layout.nbytes, dtype=torch.uint8, device=device)
+    out = layout.views(blob)
+    common = dict(boxes1=boxes1, off1=matching.off1, boxes2=boxes2, off2=matching.off2, pairs=matching.pairs, count=matching.count,
+                  out_off=matching.out_off, params=params, max_pairs=max(1, max(min(a, c) for a, c in zip(n1, n2))), seed=seed,
+                  hypotheses=hypotheses, workspace=workspace)
+    finish = FinishLaunch(label1=matching.label1, label2=matching.label2, max_n1=max(n1), max_n2=max(n2), status=out.status, H=out.hmat,
+                          winner=out.winner, winner_count=out.winner_count, final_count=out.final_count,
+                          matched_expected=out.matched_expected, matched_actual=out.matched_actual, expected_positions=out.pos, **common)
+    return RansacLaunch(**common), finish, blob, layout, out
 
 
 class ReclassPlan:
@@ -343,15 +394,15 @@ def _launch_plan(matching, finish, table):
     without `counts`, the pinned tensor the counts land in once the stream has been waited for).  table: `_image_table`'s."""
     from . import torch_ops_reclass  # noqa: F401  (registers torch.ops.cvpce_amd.reclass_*)
     b = len(matching.n1)
-    status, me, pos = finish[16], finish[21], finish[23]
-    device = status.device
+    device = finish.status.device
     plan = ReclassPlan()
     plan.n1, plan.cap, plan.outcome = list(matching.n1), max(matching.n1), None
-    plan.status, plan.matched_expected, plan.off1 = status, me, matching.off1
+    plan.status, plan.matched_expected, plan.off1 = finish.status, finish.matched_expected, finish.off1
     plan.boxes = torch.empty((b, plan.cap, 4), dtype=torch.float32, device=device)
     slots = torch.empty(b * plan.cap + b, dtype=torch.int32, device=device)
     plan.expected_index, plan.count = slots[:b * plan.cap].view(b, plan.cap), slots[b * plan.cap:]
-    torch.ops.cvpce_amd.reclass_plan(status, me, pos, matching.off1, table, plan.boxes, plan.expected_index, plan.count)
+    torch.ops.cvpce_amd.reclass_plan(finish.status, finish.matched_expected, finish.expected_positions, finish.off1, table, plan.boxes,
+                                     plan.expected_index, plan.count)
     host = torch.empty(b, dtype=torch.int32).pin_memory()
     host.copy_(plan.count, non_blocking=True)
     return plan, host
@@ -383,8 +434,8 @@ def reclassify_batch(plan, images, classifier, expected_label_ids, report=False)
         rows += list(range(at, at + c)) + [-1] * (cap - c)
         sel += range(i * cap, i * cap + c)
         at += c
-    small = _upload(torch.tensor(rows + sel + [v for ids in expected_label_ids for v in ids], dtype=torch.int32), device)
-    slot_row, sel, ids = small[:b * cap].view(b, cap), small[b * cap:b * cap + total], small[b * cap + total:]
+    small = _upload_tables(device, slot_row=rows, sel=sel, ids=[v for ids in expected_label_ids for v in ids])
+    slot_row, sel, ids = small.slot_row.view(b, cap), small.sel, small.ids
     if total != b * cap:                        # (the embedder only runs over the valid crops, as BatchedPipeline._select has it)
         crops = crops.index_select(0, sel)
         ext = ext.index_select(0, sel) if ext is not None else None
@@ -402,6 +453,21 @@ def reclassify_batch(plan, images, classifier, expected_label_ids, report=False)
     return host.tolist()
 
 
+class VerdictLayout:
+    """The int32 words of `_verdict_and_report`'s one buffer: found counts [b], outcome, seen_row, seen_distance (f32) [sum1 each] --
+    the first `back` words, which the pinned copy brings back -- then found [sum1], which stays on the device."""
+    __slots__ = ('b', 'sum1', 'back', 'words')
+
+    def __init__(self, b, sum1):
+        self.b, self.sum1, self.back, self.words = b, sum1, b + 3 * sum1, b + 4 * sum1
+
+    def views(self, buf):
+        """buf: an int32 tensor of `words`, or of the first `back` of them (`found` is empty then), on any device"""
+        b, sum1 = self.b, self.sum1
+        return SimpleNamespace(found_count=buf[:b], outcome=buf[b:b + sum1], seen_row=buf[b + sum1:b + 2 * sum1],
+                               seen_distance=buf[b + 2 * sum1:self.back].view(torch.float32), found=buf[self.back:])
+
+
 def _verdict_and_report(plan, classifier, emb, slot_row, ids):
     """The end of `reclassify_batch` with the report on: match with distances, `reclass_verdict`, `report_reclass`, ONE pinned copy of
     {found counts, outcomes, seen rows, seen distances} and the pass's only wait."""
@@ -411,18 +477,19 @@ def _verdict_and_report(plan, classifier, emb, slot_row, ids):
         raise ValueError('a plan of finalize_batch(..., report=...)')
     indices, distances = classifier.match(emb, return_distance=True)
     indices, distances = indices.contiguous(), distances.contiguous()
-    out = torch.empty(b + 4 * sum1, dtype=torch.int32, device=device)            # found counts, outcome, seen_row, seen_distance | found
-    found_count, outcome, seen_row = out[:b], out[b:b + sum1], out[b + sum1:b + 2 * sum1]
-    seen_distance, found = out[b + 2 * sum1:b + 3 * sum1].view(torch.float32), out[b + 3 * sum1:]
-    outcome.copy_(plan.outcome)
+    layout = VerdictLayout(b, sum1)
+    buf = torch.empty(layout.words, dtype=torch.int32, device=device)
+    out = layout.views(buf)
+    out.outcome.copy_(plan.outcome)
     torch.ops.cvpce_amd.reclass_verdict(plan.expected_index, plan.count, slot_row, indices, classifier.gallery_label_id, ids,
-                                        plan.matched_expected, plan.off1, plan.status, found, found_count)
+                                        plan.matched_expected, plan.off1, plan.status, out.found, out.found_count)
     torch.ops.cvpce_amd.report_reclass(plan.expected_index, plan.count, slot_row, indices, distances, classifier.gallery_label_id, ids,
-                                       plan.off1, plan.status, outcome, seen_row, seen_distance)
-    host = torch.empty(b + 3 * sum1, dtype=torch.int32).pin_memory()
-    host.copy_(out[:b + 3 * sum1], non_blocking=True)
+                                       plan.off1, plan.status, out.outcome, out.seen_row, out.seen_distance)
+    host = torch.empty(layout.back, dtype=torch.int32).pin_memory()
+    host.copy_(buf[:layout.back], non_blocking=True)
     torch.cuda.current_stream(device).synchronize()
-    return (host[:b].tolist(), host[b:b + sum1], host[b + sum1:b + 2 * sum1], host[b + 2 * sum1:].view(torch.float32))
+    back = layout.views(host)
+    return back.found_count.tolist(), back.outcome, back.seen_row, back.seen_distance
 
 
 def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold=0.5, seed=0,
@@ -444,24 +511,22 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
     if not len(expected) == len(actual) == len(matching.n1) or [len(g) for g in expected] != matching.n1 or [len(g) for g in actual] != matching.n2:
         raise ValueError('the graphs the matching was made from')
     b, n1, n2 = len(expected), matching.n1, matching.n2
-    sum1, sum2 = sum(n1), sum(n2)
     if reclass is not None and report is not None and list(report) != list(reclass):
         raise ValueError('the report reads the image table the plan reads')
-    ransac, finish, blob, (at_h, at_i, size, extra) = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed,
-                                                                    hypotheses, extra=4 * sum1 + sum2 if report is not None else 0)
-    torch.ops.cvpce_amd.homography_ransac(*ransac)
-    torch.ops.cvpce_amd.homography_finish(*finish)
+    ransac, finish, blob, layout, out = _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou_threshold, seed, hypotheses,
+                                                      report=report is not None)
+    ransac.launch()
+    finish.launch()
     table = _image_table(reclass if reclass is not None else report, b, blob.device) if (reclass is not None or report is not None) else None
     plan, plan_counts = _launch_plan(matching, finish, table) if reclass is not None else (None, None)
     if report is not None:
         from . import torch_ops_report  # noqa: F401  (registers torch.ops.cvpce_amd.report_*)
-        rows = [extra[k * sum1:(k + 1) * sum1] for k in range(4)] + [extra[4 * sum1:]]          # outcome, occupant, IoU, row | stray
-        torch.ops.cvpce_amd.report_positions(finish[16], finish[21], finish[22], finish[23], finish[3], matching.off1, matching.off2, table,
-                                             actual_boxes.row if isinstance(actual_boxes, DeviceActuals) else None, float(iou_threshold),
-                                             rows[0], rows[1], rows[2].view(torch.float32), rows[3], rows[4])
+        torch.ops.cvpce_amd.report_positions(finish.status, finish.matched_expected, finish.matched_actual, finish.expected_positions, finish.boxes2,
+                                             finish.off1, finish.off2, table, actual_boxes.row if isinstance(actual_boxes, DeviceActuals) else None,
+                                             float(iou_threshold), out.outcome, out.occupant, out.occupant_iou, out.occupant_row, out.stray)
         if plan is not None:
-            plan.outcome = rows[0]
-    size.copy_(matching.count)                                     # (the matching's size travels in the same copy)
+            plan.outcome = out.outcome
+    out.size.copy_(matching.count)                                 # (the matching's size travels in the same copy)
     back = torch.empty(blob.shape, dtype=torch.uint8).pin_memory()
     back.copy_(blob, non_blocking=True)
     pack_status = None
@@ -473,23 +538,20 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
         raise RuntimeError(f'actuals_pack: status {pack_status.tolist()} (1: the kept count is not the offsets\', 2: a gallery row outside the gallery)')
     if plan is not None:
         plan.counts = plan_counts.tolist()
-    pos, hmat, i32 = back[:at_h].view(torch.float32).view(sum1, 4), back[at_h:at_i].view(torch.float64).view(b, 3, 3), back[at_i:].view(torch.int32)
-    head = i32[:5 * b].view(5, b).tolist()
-    me, ma = i32[5 * b:5 * b + sum1] != 0, i32[5 * b + sum1:5 * b + sum1 + sum2] != 0
+    host = layout.views(back)
+    status, winner, winner_count, final_count, size = (t.tolist() for t in (host.status, host.winner, host.winner_count, host.final_count, host.size))
+    me, ma, hmat = host.matched_expected != 0, host.matched_actual != 0, host.hmat.view(b, 3, 3)
     off1, off2 = _offsets(n1), _offsets(n2)
     records = []
     for p in range(b):
-        ok = head[0][p] == torch_ops_homography.OK
-        m = head[4][p]
-        records.append({'status': STATUS[head[0][p]], 'matched_expected': me[off1[p]:off1[p + 1]].clone(), 'matched_actual': ma[off2[p]:off2[p + 1]].clone(),
-                        'expected_positions': pos[off1[p]:off1[p + 1]].clone(), 'homography': hmat[p].clone() if ok else None,
-                        'inliers': head[3][p], 'points': 5 if m == 1 else 3 * m, 'matching': m, 'winner': head[1][p], 'winner_inliers': head[2][p]})
-    if report is not None:
-        more = i32[5 * b + sum1 + sum2:]
-        for p, rec in enumerate(records):
-            a, c = slice(off1[p], off1[p + 1]), slice(4 * sum1 + off2[p], 4 * sum1 + off2[p + 1])
-            rec.update(outcome=more[:sum1][a].clone(), occupant=more[sum1:2 * sum1][a].clone(), occupant_iou=more[2 * sum1:3 * sum1].view(torch.float32)[a].clone(),
-                       occupant_row=more[3 * sum1:4 * sum1][a].clone(), stray=more[c] != 0)
+        e, a, m = slice(off1[p], off1[p + 1]), slice(off2[p], off2[p + 1]), size[p]
+        rec = {'status': STATUS[status[p]], 'matched_expected': me[e].clone(), 'matched_actual': ma[a].clone(),
+               'expected_positions': host.pos[e].clone(), 'homography': hmat[p].clone() if status[p] == torch_ops_homography.OK else None,
+               'inliers': final_count[p], 'points': 5 if m == 1 else 3 * m, 'matching': m, 'winner': winner[p], 'winner_inliers': winner_count[p]}
+        if report is not None:
+            rec.update(outcome=host.outcome[e].clone(), occupant=host.occupant[e].clone(), occupant_iou=host.occupant_iou[e].clone(),
+                       occupant_row=host.occupant_row[e].clone(), stray=host.stray[a] != 0)
+        records.append(rec)
     return records if plan is None else (records, plan)
 
 

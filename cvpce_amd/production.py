@@ -444,7 +444,7 @@ class PlanogramComparator:
         """[compare(e, a, img, classifier) for ...] with the graph stages of the whole batch in two launches (all graphs, all matchings)
         and one copy back; the host tail (homography, per-label claim, re-classification) runs per image -- with `device_tail` the
         homography and the claim are two more launches of the window and only the re-classification stays per image; with
-        `device_reclass` that is one pass of the window as well (`_reclassified`: two waits, whatever the number of images with
+        `device_reclass` that is one pass of the window as well (`_device_window`: two waits, whatever the number of images with
         positions to classify).  With `device_graphs` off it is the plain loop.  `actuals` may be a `planograms_device.DeviceActuals` --
         a window's detections as `BatchedPipeline.run(actuals=True)` left them on the device -- where `device_graphs` and `device_tail`
         are on (`_compare_device_actuals`)."""
@@ -496,18 +496,7 @@ class PlanogramComparator:
             ga = built[len(build) - len(todo):]
             if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
                 ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
-                if ids is not None:
-                    return self._reclassified(results, todo, ge, ga, ids, expecteds, actuals, images, classifier, report)
-                table = [self._image_row(images[i], classifier) for i in todo] if report else None
-                records = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
-                                            [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], report=table)
-                for i, rec in zip(todo, records):
-                    if report:
-                        results[i] = self._report_record(rec, expecteds[i], actuals[i]['labels'], images[i], classifier)
-                        continue
-                    tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
-                    results[i] = self._finish(rec['matching'], expecteds[i], actuals[i], images[i], classifier, tail)
-                return results
+                return self._device_window(results, todo, ge, ga, expecteds, actuals, images, classifier, ids, report)
             matchings = pd.common_subgraphs(ge, ga)
             for i, matching in zip(todo, matchings):
                 if report:
@@ -622,31 +611,44 @@ class PlanogramComparator:
         if not todo:
             return results
         pack = actuals.select(todo)
-        es, imgs = [expecteds[i] for i in todo], [images[i] for i in todo]
+        es = [expecteds[i] for i in todo]
         have = [pd.cached(e, self.graph_threshold) for e in es]
         fresh = iter(pd.build_graphs([(e['boxes'], e['labels']) for e, h in zip(es, have) if h is None], self.graph_threshold))
         ge = [h if h is not None else next(fresh) for h in have]
         ga = pd.build_graphs(pack, self.graph_threshold)
-        matching = pd.match_on_device(ge, ga, actuals=pack, expected_ids=ids)
-        device = pack.boxes.device
-        boxes1 = [pd.expected_boxes_on_device(e, device) for e in es]
-        reproj = [self._reproj_threshold(img) for img in imgs]
+        # (two id vectors on purpose: `ids` above numbers a label outside the gallery len(space) + rank for the match and claim kernels,
+        # these give it -1 for the verdict kernel -- merging them would change what a kernel reads)
         reclass_ids = self._window_label_ids(es, classifier) if self.device_reclass else None
-        table = [datautils.image_hw(img) + (1,) if img is not None else (0, 0, 0) for img in imgs]
-        if reclass_ids is None:
-            records = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, report=table if report else None)
-            found = None
-        else:
-            records, plan = pd.finalize_batch(ge, ga, matching, boxes1, pack, reproj, reclass=table, report=table if report else None)
-            found = pd.reclassify_batch(plan, imgs, classifier, reclass_ids, report=report) if sum(plan.counts) else None
+        return self._device_window(results, todo, ge, ga, expecteds, pack, images, classifier, reclass_ids, report, expected_ids=ids)
+
+    def _device_window(self, results, todo, ge, ga, expecteds, actuals, images, classifier, reclass_ids, report, expected_ids=None):
+        """The device window of the images `todo`: match -> tail (-> plan) back to back on the graphs `ge` / `ga` and
+        the first wait; where the plan holds positions, crops -> embedder -> match -> verdict and the second wait
+        (`planograms_device.reclassify_batch`) -> `results`, filled at `todo`.
+        actuals: the host dicts of all images, or the `DeviceActuals` of the images `todo` with expected_ids, `expected_label_ids`' of
+        their planograms.  reclass_ids: `_window_label_ids`' where the window is to be re-classified on the device, else None: no plan
+        is asked for, and the re-classification runs per image in `_finish` / `_report_finish`.
+        The verdict of an image with a homography in a re-classified window is found_count / n1 -- the value and dtype of `_finish`'s
+        found.sum() / len(found); every other image, and a window without positions, ends in `_finish`."""
+        from . import planograms_device as pd
+        on_host = not isinstance(actuals, pd.DeviceActuals)
+        matching = pd.match_on_device(ge, ga) if on_host else pd.match_on_device(ge, ga, actuals=actuals, expected_ids=expected_ids)
+        table = [self._image_row(images[i], classifier) for i in todo] if report or reclass_ids is not None else None
+        out = pd.finalize_batch(ge, ga, matching, [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
+                                [actuals[i]['boxes'] for i in todo] if on_host else actuals, [self._reproj_threshold(images[i]) for i in todo],
+                                reclass=table if reclass_ids is not None else None, report=table if report else None)
+        records, plan = out if reclass_ids is not None else (out, None)
+        found = None
+        if plan is not None and sum(plan.counts):
+            found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, reclass_ids, report=report)
         if report:
-            return self._window_reports(results, todo, records, found, expecteds, None, images, classifier)
+            return self._window_reports(results, todo, records, found, expecteds, actuals if on_host else None, images, classifier)
         for p, (i, rec) in enumerate(zip(todo, records)):
             if found is not None and rec['status'] == 'ok':
                 results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
             else:                               # (`_finish` reads the actual side only where it has to compute the tail itself)
                 tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
-                results[i] = self._finish(rec['matching'], expecteds[i], None, images[i], classifier, tail)
+                results[i] = self._finish(rec['matching'], expecteds[i], actuals[i] if on_host else None, images[i], classifier, tail)
         return results
 
     LABEL_IDS_KEY = 'reclass_label_ids'           # a planogram dict's cached id vector, beside planograms_device.CACHE_KEY
@@ -688,27 +690,6 @@ class PlanogramComparator:
                 final = (found[1][a].clone(), found[2][a].clone(), found[3][a].clone())
             results[i] = self._report_record(rec, expecteds[i], actuals[i]['labels'] if actuals is not None else None, images[i], classifier, final,
                                              None if classifier is None else classifier.annotations)
-        return results
-
-    def _reclassified(self, results, todo, ge, ga, ids, expecteds, actuals, images, classifier, report=False):
-        """The `device_reclass` window: graphs -> match -> tail -> plan back to back and the first wait; where the plan holds
-        positions, crops -> embedder -> match -> verdict and the second wait (`planograms_device.reclassify_batch`).  The verdict
-        of an image with a homography is found_count / n1 -- the value and dtype of `_finish`'s found.sum() / len(found); every
-        other image, and a window without positions, ends in `_finish` as with `device_tail` alone."""
-        from . import planograms_device as pd
-        table = [self._image_row(images[i], classifier) for i in todo]
-        records, plan = pd.finalize_batch(ge, ga, pd.match_on_device(ge, ga), [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
-                                          [actuals[i]['boxes'] for i in todo], [self._reproj_threshold(images[i]) for i in todo], reclass=table,
-                                          report=table if report else None)
-        found = pd.reclassify_batch(plan, [images[i] for i in todo], classifier, ids, report=report) if sum(plan.counts) else None
-        if report:
-            return self._window_reports(results, todo, records, found, expecteds, actuals, images, classifier)
-        for p, (i, rec) in enumerate(zip(todo, records)):
-            if found is not None and rec['status'] == 'ok':
-                results[i] = torch.tensor(found[p]) / len(expecteds[i]['boxes'])
-            else:
-                tail = pd.finalize_result(rec, expecteds[i]['labels']) if rec['matching'] else None
-                results[i] = self._finish(rec['matching'], expecteds[i], actuals[i], images[i], classifier, tail)
         return results
 
     @staticmethod

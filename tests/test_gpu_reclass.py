@@ -398,6 +398,92 @@ def test_the_refactored_crop_helper_leaves_the_batched_pipeline_unchanged(cuda):
     assert all(torch.equal(out[key], again[key]) for key in ('indices', 'embeddings'))
 
 
+# The comparator's device window before its routes were folded into one (planograms_device's named launches and blob layouts,
+# `PlanogramComparator._device_window`): measured on commit f40041d on an MI355X, per route sha256 of compare_batch's verdicts and of
+# every field of report_batch's reports, and what the two calls cost together under `WindowCounter` (kernels, torch_device_ops, waits).
+WINDOW_ROUTES = {
+    'tail': (dict(), False),
+    'tail_reclass': (dict(device_reclass=True), False),
+    'actuals': (dict(), True),
+    'actuals_reclass': (dict(device_reclass=True), True),
+}
+WINDOW_DIGEST = 'e9eff137e882e015e012b760ef6550964bff73b6c1ad9ab66ab1cc0e9d11e1e1'                   # (the parent's on all four routes)
+WINDOW_PARENT = {
+    'tail': (WINDOW_DIGEST, 329, 829, 10),
+    'tail_reclass': (WINDOW_DIGEST, 104, 401, 4),
+    'actuals': (WINDOW_DIGEST, 331, 831, 10),
+    'actuals_reclass': (WINDOW_DIGEST, 106, 403, 4),
+}
+
+
+def _device_actuals(cuda, clf, actuals):
+    """host detections as the pack `actuals_pack` would leave of them: a label's gallery row is the first that carries it"""
+    from cvpce_amd import planograms_device as pd
+    n2 = [len(a['labels']) for a in actuals]
+    rows = [clf.annotations.index(l) for a in actuals for l in a['labels']]
+    i32 = lambda values: torch.tensor(values, dtype=torch.int32, device=cuda)
+    boxes = torch.cat([a['boxes'] for a in actuals]).to(torch.float32).contiguous().to(cuda)
+    thresh = torch.stack([pd.graph_threshold(a['boxes'].to(torch.float32), 0.5) for a in actuals]).to(torch.float32).to(cuda)
+    return pd.DeviceActuals(boxes, i32(rows), i32([clf.label_ids[clf.annotations[r]] for r in rows]), thresh, i32([0] * len(n2)),
+                            i32(pd._offsets(n2)), n2, 0.5)
+
+
+def _window_digest(verdicts, reports):
+    """sha256 over the verdicts of a window and over every field of its reports (tensors by shape, dtype and bytes)"""
+    h = hashlib.sha256()
+
+    def add(name, v):
+        if torch.is_tensor(v):
+            v = v.detach().cpu().contiguous()
+            h.update(name.encode() + str(tuple(v.shape)).encode() + str(v.dtype).encode())
+            h.update(v.reshape(-1).view(torch.uint8).numpy().tobytes())
+        else:
+            h.update(name.encode() + type(v).__name__.encode() + repr(v).encode())
+    for i, v in enumerate(verdicts):
+        add(f'verdict{i}', v)
+    for i, r in enumerate(reports):
+        add(f'compliance{i}', r.compliance)
+        add(f'reason{i}', r.status)
+        for field in r.FIELDS:
+            add(f'{field}{i}', getattr(r, field))
+    return h.hexdigest()
+
+
+def _window_route(cuda, name):
+    """one route of WINDOW_ROUTES over the window of `_pipeline` -> (digest, kernels, torch_device_ops, waits, verdicts, reports)"""
+    from cvpce_amd import production
+    from test_gpu_actuals import _window_counter
+    p = _pipeline(cuda)
+    clf, imgs, dets = p['clf'], p['imgs'], p['dets']
+    switches, on_device = WINDOW_ROUTES[name]
+    planos = _planograms(dets)                                    # (fresh dicts: every route fills its own caches in its first call)
+    actuals = [dict(zip(('boxes', 'labels'), _withheld(b, l))) for b, l in dets]
+    side = _device_actuals(cuda, clf, actuals) if on_device else actuals
+    cmp = production.PlanogramComparator(device_graphs=True, device_tail=True, **switches)
+    verdicts, reports = cmp.compare_batch(planos, side, imgs, clf), cmp.report_batch(planos, side, imgs, clf)
+    counter = _window_counter()
+    with counter:
+        cmp.compare_batch(planos, side, imgs, clf)
+        cmp.report_batch(planos, side, imgs, clf)
+    assert cmp.host_routed == 0 and cmp.reclass_host_routed == 0
+    return _window_digest(verdicts, reports), counter.kernels, counter.torch_device_ops, counter.waits, verdicts, reports
+
+
+def test_the_single_device_window_leaves_every_route_unchanged(cuda):
+    """the window of `test_all_three_switches_equal_the_tail_switch_exactly` (positions recovered and missing, verdicts strictly
+    between 0 and 1) on each device route: the outputs and the launches and waits are the parent's, the torch operators no more"""
+    got = {route: _window_route(cuda, route) for route in WINDOW_ROUTES}
+    for route, (digest, kernels, torch_ops, waits, verdicts, _) in got.items():
+        print(f'{route}: digest {digest}, kernels {kernels}, torch_device_ops {torch_ops}, waits {waits}, verdicts {[float(v) for v in verdicts]}')
+    for route, (digest, kernels, torch_ops, waits, verdicts, reports) in got.items():
+        assert any(0.0 < float(v) < 1.0 for v in verdicts) and all(r.status == 'ok' for r in reports), route
+        outcomes = torch.cat([r.outcomes for r in reports]).tolist()
+        assert 1 in outcomes and 2 in outcomes, route                                     # recovered and missing, both
+        want = WINDOW_PARENT[route]
+        assert digest == want[0], route
+        assert (kernels, waits) == (want[1], want[3]) and torch_ops <= want[2], route
+
+
 def _planted_proposals(cuda):
     """planted boxes for two 512 x 640 images of 40 slots, 17 and 33 of them counted: some small, some large, some at the image's edge"""
     g = torch.Generator().manual_seed(5)

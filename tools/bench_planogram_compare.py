@@ -102,8 +102,8 @@ def time_device(pairs, launches):
     out = [torch.empty_like(t) for t in (nbr, weight, stamp)]
     g_ms = events(lambda: torch.ops.cvpce_amd.planogram_graphs(boxes, offsets, thresh, min(sizes), max(sizes), *out), launches)
     assert all(torch.equal(a, b) for a, b in zip(out, (nbr, weight, stamp)))
-    args, _, _ = pd._prepare_match(graphs[:n], graphs[n:], -0.2, 0.5)
-    m_ms = events(lambda: torch.ops.cvpce_amd.planogram_match(*args), launches)
+    match, _, _ = pd._prepare_match(graphs[:n], graphs[n:], -0.2, 0.5)
+    m_ms = events(match.launch, launches)
     e2e = []
     for r in range(6):
         torch.cuda.synchronize()
@@ -118,9 +118,9 @@ def time_device(pairs, launches):
             planograms.finalize_via_ransac(m, e['boxes'], a['boxes'], e['labels'], a['labels'], reproj_threshold=10)
     tail = time.perf_counter() - t0
     on_device = pd.match_on_device(graphs[:n], graphs[n:])
-    ransac, finish, _, _ = pd._prepare_tail(on_device, [e['boxes'] for e, _ in pairs], [a['boxes'] for _, a in pairs], [10] * n, 0.5, 0,
-                                            pd.RANSAC_HYPOTHESES)
-    t_ms = events(lambda: (torch.ops.cvpce_amd.homography_ransac(*ransac), torch.ops.cvpce_amd.homography_finish(*finish)), launches)
+    ransac, finish, *_ = pd._prepare_tail(on_device, [e['boxes'] for e, _ in pairs], [a['boxes'] for _, a in pairs], [10] * n, 0.5, 0,
+                                          pd.RANSAC_HYPOTHESES)
+    t_ms = events(lambda: (ransac.launch(), finish.launch()), launches)
     cmp = production.PlanogramComparator(device_graphs=True, device_tail=True)
     e2e_tail, verdicts = [], None
     for r in range(6):
