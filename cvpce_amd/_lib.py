@@ -3,8 +3,8 @@
 include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
 include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
 harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h, the compliance
-report kernels of include/cvpce_amd_report.h, the picture compositor of include/cvpce_amd_render.h and the Gaussian-map scoring
-kernels of include/cvpce_amd_gaussians.h).
+report kernels of include/cvpce_amd_report.h, the picture compositor of include/cvpce_amd_render.h, the Gaussian-map scoring
+kernels of include/cvpce_amd_gaussians.h and the head-loss kernels of include/cvpce_amd_headloss.h).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -170,8 +170,16 @@ GAUSSIANS_SIGNATURES = {
     'cvpce_gauss_loss': (c_int, [_fp, _fp, _ip, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, _vp, c_size_t, _fp, _ip, _vp]),
 }
 
+# include/cvpce_amd_headloss.h: anchor matching and the two head losses.  A table of its own, like the header.
+HEADLOSS_SIGNATURES = {
+    'cvpce_headloss_workspace_bytes': (c_size_t, [POINTER(c_int), POINTER(c_int)] + [c_int] * 4),
+    'cvpce_headloss': (c_int, [POINTER(c_void_p), POINTER(c_void_p)] + [POINTER(c_int)] * 4 + [_fp, _fp, _ip, _ip, _fp] + [c_int] * 5
+                       + [_vp, c_size_t, _ip, _fp, _ip, _vp]),
+}
+
 for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES, GAUSSIANS_SIGNATURES):
+               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES, GAUSSIANS_SIGNATURES,
+               HEADLOSS_SIGNATURES):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -2,9 +2,11 @@
 cli/dihe.py:257-309,382-423, cli/eval.py:12-71,168-240): the same command names, arguments, options and defaults as the
 reference for
 
-    cvpce gln eval | gln detect | dihe eval | dihe prebuild-index | eval-product-detection | eval-planograms | rebuild-scene
+    cvpce gln eval | gln detect | gln seek-sku110k-outliers | dihe eval | dihe prebuild-index | eval-product-detection |
+    eval-planograms | rebuild-scene
 
-Training, hyper-parameter search, dataset visualisation and plotting commands are out of scope.  Options that only steer
+Training, hyper-parameter search, dataset visualisation and plotting commands are out of scope (`gln seek-sku110k-outliers` scores
+the three training losses forward only, in eval mode, and adds --batch-size and --dataloader-workers: cli/gln.py:309-377).  Options that only steer
 the reference's matplotlib (`--plots`, `--plot-res-reduction`) are accepted and ignored: every metric is printed.
 `--dataloader-workers` is the number of reader THREADS of `feeding.ImageFeeder`: the shelf images are opened in the 8-bit
 form, decoded that many at a time ahead of the kernels and uploaded from pinned memory (0 = read serially in the calling
@@ -408,6 +410,54 @@ def eval(dataset, imgs, annotations, batch_size, dataloader_workers, metric_work
         print(f'--> Gaussian loss {scored["mean"]} (std {scored["std"]})')
         for i in scored['outliers']:
             print(f'Outlier at index {i}: {data.index[i]["image_name"]}\t{float(scored["loss"][i])}')
+
+
+@gln.command(name='seek-sku110k-outliers')
+@click.option('--imgs', type=click.Path(**_DIR), default=SKU110K_IMG_DIR, show_default=True, help='Path to SKU-110K image dir')
+@click.option('--annotations', type=click.Path(exists=True), default=SKU110K_ANNOTATION_FILE, show_default=True,
+              help='Path to SKU-110K annotation file used in iteration')
+@click.option('--outlier-threshold', type=int, default=3, show_default=True,
+              help='The minimum number of standard deviations a loss needs to be above the average for an image to be considered an outlier')
+@click.option('--trim-module-prefix/--no-trim-module-prefix', default=False, show_default=True,
+              help='Trim "module." prefix from loaded model, legacy option, shouldn\'t be necessary')
+@click.option('--batch-size', type=int, default=1, show_default=True, help='Batch size (an image is scored over the anchors of its padded batch)')
+@click.option('--dataloader-workers', type=int, default=4, show_default=True, help='Number of data loading threads (0 = read in the calling thread)')
+@click.argument('state-file', type=click.Path(**_FILE))
+def seek_sku110k_outliers(imgs, annotations, outlier_threshold, trim_module_prefix, batch_size, dataloader_workers, state_file):
+    """Pass SKU110K data through GLN, print outliers.
+
+    Every image that is not in the skip list is scored by the three losses of the reference's compute_loss -- classification,
+    bbox_regression, gaussian -- on the GPU, in one pass over the data with one copy back at the end; images with a
+    loss more than --outlier-threshold standard deviations above its average are printed.  Eval-mode statistics, no flips
+    (INTEGRATION.md)."""
+    from .. import device_gaussians, device_headloss
+    data = datautils.SKU110KDataset(imgs, annotations, skip=SKU110K_SKIP, include_gaussians=False, flip_chance=0, image_format='uint8')
+    model = proposals_eval.load_gln(state_file, trim_module_prefix)
+    head_score = device_headloss.HeadScore(model, outlier_threshold=outlier_threshold)
+    gaussian_score = device_gaussians.GaussianScore(model, outlier_threshold=outlier_threshold)
+    model.keep_head_outputs(True)
+    done = 0
+    with torch.no_grad():
+        for batch in proposals_eval._batches(feeding.feed(data, dataloader_workers), batch_size):
+            if done % 200 < len(batch):
+                print(f'{done - done % 200}...')
+            done += len(batch)
+            sizes = [datautils.image_hw(img) for img, _ in batch]
+            result = model([img.cuda(non_blocking=True) for img, _ in batch])
+            head_score.update(model.head_outputs(), [t for _, t in batch], sizes)
+            gaussian_score.update(result, [t['boxes'] for _, t in batch], sizes)
+    scored = device_headloss.compute_together(head_score, gaussian_score)
+    names = ('classification', 'bbox_regression', 'gaussian')
+    print('-' * 10)
+    print('Mean loss:\t' + '\t'.join(str(scored[k]['mean']) for k in names))
+    print('Std loss:\t' + '\t'.join(str(scored[k]['std']) for k in names))
+    print('-' * 10)
+    outliers = sorted(set().union(*(scored[k]['outliers'] for k in names)))
+    if not outliers:
+        print('No outliers! Have a nice day!')
+    for i in outliers:
+        print(f'Outlier at index {i}: {data.index[i]["image_name"]}')
+        print('\t' + '\t'.join(str(float(scored[k]['loss'][i])) for k in names))
 
 
 @gln.command()

@@ -36,6 +36,7 @@
 // thread) so larger levels take the one-kernel decode, nms_sort holds L * topk keys in dynamic LDS (<= 80 KiB) and nms_scan
 // keeps 20 480 indices (80 KiB of static LDS) and fetches the rows of kept boxes after each chunk resolves.
 #include "common.h"
+#include "anchors.h"                          // grid_anchor: the anchor synthesis, shared with headloss.hip
 #include "../../include/cvpce_amd.h"
 #include <math.h>
 #include <stdlib.h>
@@ -123,9 +124,8 @@ __device__ __forceinline__ void decode_candidate(const DecodeArgs& a, int level,
     const int aidx = idx / a.K, label = idx - aidx * a.K;
     const int cell = aidx / a.A, an = aidx - cell * a.A;
     const int y = cell / gw, x = cell - y * gw;
-    const float shx = (float)x * (float)a.sw[level], shy = (float)y * (float)a.sh[level];
-    const float* ba = a.base_anchors + ((size_t)level * a.A + an) * 4;
-    const float ax1 = shx + ba[0], ay1 = shy + ba[1], ax2 = shx + ba[2], ay2 = shy + ba[3];
+    const float4 anchor = grid_anchor(a.base_anchors, level, a.A, an, x, y, a.sw[level], a.sh[level]);
+    const float ax1 = anchor.x, ay1 = anchor.y, ax2 = anchor.z, ay2 = anchor.w;
     const float w = ax2 - ax1, h = ay2 - ay1;
     const float cx = ax1 + 0.5f * w, cy = ay1 + 0.5f * h;
     const float4 r = *reinterpret_cast<const float4*>(rg + (size_t)aidx * 4);

@@ -149,6 +149,17 @@ def reference_loss(predictions, targets, sizes, tanh=False, negative_threshold=0
     return out_f[0, 0]
 
 
+def summarise(values, outlier_threshold):
+    """Per-image losses (n,) on the host -> {'loss', 'mean', 'std' (unbiased, the reference's torch.std), 'outliers': indices with
+    loss > mean + outlier_threshold * std}: the reference's outlier rule, shared with device_headloss."""
+    if not values.numel():
+        return {'loss': values, 'mean': float('nan'), 'std': float('nan'), 'outliers': []}
+    mean = float(values.mean())
+    std = float(values.std()) if values.numel() > 1 else float('nan')
+    outliers = [int(i) for i in (values > mean + outlier_threshold * std).nonzero().flatten()] if values.numel() > 1 else []
+    return {'loss': values, 'mean': mean, 'std': std, 'outliers': outliers}
+
+
 class GaussianScore:
     """Device-resident accumulator of per-image Gaussian losses: `update` per batch, `compute` once at the end.
 
@@ -194,15 +205,17 @@ class GaussianScore:
         self._losses.append(out_f)
         self.images += len(results)
 
+    def device_losses(self):
+        """The accumulated per-image losses (n,) still on the device, in the order given; None before the first update.  For a
+        caller that brings them to the host together with something else (device_headloss.compute_together); no copy is made here."""
+        return torch.cat(self._losses)[:, 0] if self._losses else None
+
     def compute(self):
         """The single device-to-host copy -> {'loss': (n,) per-image losses in the order given, 'mean', 'std' (unbiased, the
         reference's torch.std), 'outliers': indices with loss > mean + outlier_threshold * std}."""
-        if not self._losses:
-            empty = torch.zeros(0)
-            return {'loss': empty, 'mean': float('nan'), 'std': float('nan'), 'outliers': []}
-        values = torch.cat(self._losses)[:, 0].cpu()
+        values = self.device_losses()
+        if values is None:
+            return summarise(torch.zeros(0), self.outlier_threshold)
+        values = values.cpu()
         self.host_copies += 1
-        mean = float(values.mean())
-        std = float(values.std()) if values.numel() > 1 else float('nan')
-        outliers = [int(i) for i in (values > mean + self.outlier_threshold * std).nonzero().flatten()] if values.numel() > 1 else []
-        return {'loss': values, 'mean': mean, 'std': std, 'outliers': outliers}
+        return summarise(values, self.outlier_threshold)

@@ -310,6 +310,9 @@ class GLNEngine:
         self.side_streams = [torch.cuda.Stream(device=device) for _ in range(4)] if N_SIDE_STREAMS else []
         self.num_anchors = self.base_anchors.shape[1]
         self.device = device
+        # opt-in (GaussianLayerNetwork.keep_head_outputs): a pass also returns its per-level head outputs, set aside for `take_heads`
+        self.keep_heads = False
+        self.kept_heads = None
 
     def detect_options(self):
         """(topk_candidates, score_thresh, nms_thresh) of the model as they are now (validated), torchvision's defaults without
@@ -590,9 +593,26 @@ class GLNEngine:
         options = self.detect_options()
         _check_detections_per_img(detections_per_img, options[0])
         if USE_DETECT_GRAPH and not want_intermediates and ops.PROFILE is None:
-            return self._detect_graphed(images, num_classes, detections_per_img, conf_thresh, options)
+            return self._set_heads_aside(self._detect_graphed(images, num_classes, detections_per_img, conf_thresh, options), images)
         batch, original, resized = self.transform(images)
-        return self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates, options)
+        res = self._detect_tail(batch, original, resized, num_classes, detections_per_img, conf_thresh, want_intermediates, options)
+        if want_intermediates:
+            return self._set_heads_aside(res[0], images), res[1]
+        return self._set_heads_aside(res, images)
+
+    def _set_heads_aside(self, res, images):
+        """With `keep_heads` a pass returns its head outputs (L cls, then L reg tensors) behind its six results: they are kept, with
+        the batch's geometry, until `take_heads` hands them out; the caller gets the six results it always got."""
+        if len(res) == 6:
+            return res
+        levels = (len(res) - 6) // 2
+        _, resized, padded = self.batch_geometry(images, self.min_size, self.max_size)
+        self.kept_heads = {'cls': list(res[6:6 + levels]), 'reg': list(res[6 + levels:]), 'padded': tuple(padded), 'sizes': list(resized)}
+        return res[:6]
+
+    def take_heads(self):
+        kept, self.kept_heads = self.kept_heads, None
+        return kept
 
     def _detect_graphed(self, images, num_classes, detections_per_img, conf_thresh, options):
         """Graph cache policy (round-2 advisor finding): captured graphs live in an LRU of MAX_DETECT_GRAPHS entries; how often
@@ -604,6 +624,8 @@ class GLNEngine:
         original, resized, padded = self.batch_geometry(images, self.min_size, self.max_size)
         # (the post-processing options are kernel arguments baked into the capture: a change of one is another graph)
         key = (len(images), padded, tuple(resized), tuple(original), num_classes, detections_per_img, float(conf_thresh), options)
+        if self.keep_heads:                                 # (the kept tensors are outputs of that capture: another graph)
+            key += ('head_outputs',)
         graphs = self.__dict__.setdefault('_graphs', OrderedDict())
         entry = graphs.get(key)
         if entry is not None:                               # captured: replay
@@ -678,9 +700,10 @@ class GLNEngine:
         if gauss_done is not None:
             torch.cuda.current_stream().wait_event(gauss_done)
         gauss = gauss.permute(0, 3, 1, 2)  # (N,1,h,w) view of the NHWC buffer (C == 1)
+        kept = tuple(cls) + tuple(reg) if self.keep_heads else ()
         if want_intermediates:
-            return out + (gauss,), {'batch': batch, 'c': (c2, c3, c4, c5), 'features': feats, 'cls': cls, 'reg': reg}
-        return out + (gauss,)
+            return out + (gauss,) + kept, {'batch': batch, 'c': (c2, c3, c4, c5), 'features': feats, 'cls': cls, 'reg': reg}
+        return out + (gauss,) + kept
 
 
 # ---------------------------------------------------------------------------
@@ -841,6 +864,7 @@ class GaussianLayerNetwork(nn.Module):
         self.detections_per_img = detections_per_img
         self.gaussian_loss_params = gaussian_loss_params
         self._engine = None
+        self._keep_head_outputs = False
         self.eval()
 
     def _detect_options(self):
@@ -898,7 +922,66 @@ class GaussianLayerNetwork(nn.Module):
                                'No CPU fallback exists in cvpce_amd (the CPU restatement lives in oracle/ for tests).')
         if self._engine is None:
             self._engine = GLNEngine(self, dev, self.precision)
+        self._engine.keep_heads = self._keep_head_outputs
         return self._engine
+
+    def keep_head_outputs(self, flag=True):
+        """Opt-in: every following forward pass also keeps its head outputs -- the per-level classification logits and box
+        regressions the post-processing reads -- for `head_outputs`.  Off (the default), a pass launches, captures and replays
+        exactly what it always did; on, the kept tensors are outputs of the pass (of its captured graph too: the flag is part of
+        the graph key)."""
+        self._keep_head_outputs = bool(flag)
+        if self._engine is not None:
+            self._engine.keep_heads = self._keep_head_outputs
+        return self
+
+    def head_outputs(self):
+        """The head outputs of the last forward pass run with `keep_head_outputs(True)`, handed out once like `get_gaussians`:
+        {'cls': per-level (N,gh,gw,A*K) float32, 'reg': per-level (N,gh,gw,A*4) float32, 'padded': the batch's (Hp, Wp),
+        'sizes': the transformed (h, w) of every image}; None when there are none."""
+        return self._engine.take_heads() if self._engine is not None else None
+
+    @torch.no_grad()
+    def losses(self, images, targets):
+        """The reference's training-mode forward (proposals.py:169-181: RetinaNet's two head losses plus gaussian_loss) in
+        EVAL-mode statistics, forward only -> {'classification', 'bbox_regression', 'gaussian'} as 0-dim float32 device tensors;
+        nothing is copied to the host.
+
+        targets: one dict per image with 'boxes' (T,4) float xyxy in original pixels, 'labels' (T,) integers in
+        [0, num_classes) and optionally 'gaussians', a full-resolution (H,W) map.  Where no target has 'gaussians' the maps are
+        rendered from the boxes when those are integers (datautils.generate_gaussians' defaults); otherwise 'gaussian' is
+        omitted.  A ValueError for degenerate boxes, labels out of range or a length mismatch comes before anything is queued."""
+        from .. import device_gaussians, device_headloss
+        images = _image_list(images)
+        targets = list(targets)
+        if len(targets) != len(images):
+            raise ValueError('one target dict per image')
+        device_headloss.check_targets(targets, self.num_classes)
+        eng = self.engine()
+        images = [ops.input_image(i, eng.device) for i in images]
+        before = self._keep_head_outputs
+        self.keep_head_outputs(True)
+        try:
+            gauss = eng.detect(images, self.num_classes, self.detections_per_img)[5]
+        finally:
+            self.keep_head_outputs(before)
+        heads = eng.take_heads()
+        original = [image_hw(i) for i in images]
+        grids = [(c.shape[1], c.shape[2]) for c in heads['cls']]
+        strides = [(heads['padded'][0] // g[0], heads['padded'][1] // g[1]) for g in grids]
+        out_f, _, _ = device_headloss.head_losses(heads['cls'], heads['reg'], grids, strides, eng.base_anchors, [t['boxes'] for t in targets],
+                                                  [t['labels'] for t in targets], device_headloss.scale_factors(heads['sizes'], original))
+        res = {'classification': out_f[:, 0].mean(), 'bbox_regression': out_f[:, 1].mean()}
+        params = dict(self.gaussian_loss_params or {})
+        tanh = bool(params.pop('tanh', self.backbone.gaussian_subnet.tanh))
+        if all('gaussians' in t for t in targets):
+            res['gaussian'] = gaussian_loss(gauss, [t['gaussians'] for t in targets], heads['sizes'], tanh=tanh, **params)
+        elif not any('gaussians' in t for t in targets) and not any(torch.as_tensor(t['boxes']).is_floating_point() for t in targets):
+            hb, wb = gauss.shape[2:]
+            geom = [(h0, w0, 1, rh // 2, rw // 2) for (h0, w0), (rh, rw) in zip(original, heads['sizes'])]
+            maps = device_gaussians.render_boxes([torch.as_tensor(t['boxes']) for t in targets], geom, hb, wb, tanh=tanh, device=eng.device)
+            res['gaussian'] = device_gaussians.loss(gauss.to(torch.float32), maps, None, **params)[0][0, 0]
+        return res
 
     @torch.no_grad()
     def forward(self, images, targets=None):
