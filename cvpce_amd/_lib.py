@@ -1,10 +1,4 @@
-"""ctypes binding of the C ABI declared in include/cvpce_amd.h (and of the evaluation kernels of include/cvpce_amd_eval.h, the
-8-bit input kernels of include/cvpce_amd_input.h, the planogram comparator kernels of include/cvpce_amd_planogram.h and
-include/cvpce_amd_homography.h, the thin-strip launch of include/cvpce_amd_lists.h, the gallery kernel of
-include/cvpce_amd_gallery.h, the comparator's re-classification kernels of include/cvpce_amd_reclass.h, the classification
-harness's kernel of include/cvpce_amd_classeval.h, the detections kernels of include/cvpce_amd_actuals.h, the compliance
-report kernels of include/cvpce_amd_report.h, the picture compositor of include/cvpce_amd_render.h, the Gaussian-map scoring
-kernels of include/cvpce_amd_gaussians.h and the head-loss kernels of include/cvpce_amd_headloss.h).
+"""ctypes binding of the C ABI of libcvpce_hip.so: one signature table per header of include/, in `HEADERS`.
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -94,92 +88,94 @@ for _base, _twin in (('cvpce_conv2d_nhwc_bf16', 'cvpce_conv2d_nhwc_f16'), ('cvpc
                      ('cvpce_gln_transform', 'cvpce_gln_transform_f16'), ('cvpce_gln_transform_batch', 'cvpce_gln_transform_batch_f16')):
     SIGNATURES[_twin] = SIGNATURES[_base]
 
-# include/cvpce_amd_eval.h: the evaluation kernels.  A table of its own -- SIGNATURES mirrors the inference header alone.
-EVAL_SIGNATURES = {
+# One header of include/ <-> one table here <-> one op module (torch_ops.py), in the order the features arrived.  SIGNATURES is the
+# inference header's table.
+HEADERS = {'cvpce_amd.h': SIGNATURES}
+
+# the evaluation kernels.
+HEADERS['cvpce_amd_eval.h'] = {
     'cvpce_eval_match_detections': (c_int, [_fp, _ip, _ip, _ip, _fp, _ip, _ip, _fp] + [c_int] * 5 + [_ip, _vp, _vp]),
 }
 
-# include/cvpce_amd_input.h: the transform and the crop kernels reading (H,W,3) bytes.  A table of its own, like the header.
-INPUT_SIGNATURES = {
+# the transform and the crop kernels reading (H,W,3) bytes.
+HEADERS['cvpce_amd_input.h'] = {
     'cvpce_gln_transform_batch_u8': (c_int, [POINTER(c_void_p), POINTER(ctypes.c_ubyte), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
                                              _vp, c_int, c_int, POINTER(c_float), POINTER(c_float), _fp, _vp]),
     'cvpce_crop_resize_u8': (c_int, [_vp, _fp, _fp, _ip, c_int, _vp, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _vp]),
     'cvpce_crop_resize_content_u8': (c_int, [_vp, _fp, _fp, _ip, c_int, _vp, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _ip, _vp]),
 }
-INPUT_SIGNATURES['cvpce_gln_transform_batch_u8_f16'] = INPUT_SIGNATURES['cvpce_gln_transform_batch_u8']
+HEADERS['cvpce_amd_input.h']['cvpce_gln_transform_batch_u8_f16'] = HEADERS['cvpce_amd_input.h']['cvpce_gln_transform_batch_u8']
 
-# include/cvpce_amd_planogram.h: the comparator's graph stages.  A table of its own, like the header.
-PLANOGRAM_SIGNATURES = {
+# the comparator's graph stages.
+HEADERS['cvpce_amd_planogram.h'] = {
     'cvpce_planogram_graphs': (c_int, [_fp, _ip, _fp] + [c_int] * 4 + [_ip, _fp, _ip, _vp]),
     'cvpce_planogram_match_workspace_bytes': (c_size_t, [c_longlong]),
     'cvpce_planogram_match': (c_int, [_ip] * 11 + [c_int] * 6 + [c_longlong, _vp, c_size_t, _ip, _ip, _vp]),
 }
 
-# include/cvpce_amd_homography.h: the comparator's tail (homography, projection, claim).  A table of its own, like the header.
-HOMOGRAPHY_SIGNATURES = {
+# the comparator's tail (homography, projection, claim).
+HEADERS['cvpce_amd_homography.h'] = {
     'cvpce_homography_workspace_bytes': (c_size_t, [c_int, c_int]),
     'cvpce_homography_ransac': (c_int, [_fp, _ip, _fp, _ip, _ip, _ip, _ip, _vp] + [c_int] * 5 + [ctypes.c_uint, c_int, _vp, c_size_t, _vp]),
     'cvpce_homography_finish': (c_int, [_fp, _ip, _ip, _fp, _ip, _ip, _ip, _ip, _ip, _vp] + [c_int] * 7 + [ctypes.c_uint, c_int, _vp, c_size_t,
                                         _ip, _vp, _ip, _ip, _ip, _ip, _ip, _fp, _vp]),
 }
 
-# include/cvpce_amd_lists.h: the thin-strip companion of the work-list launches.  A table of its own, like the header.
-LISTS_SIGNATURES = {
+# the thin-strip companion of the work-list launches.
+HEADERS['cvpce_amd_lists.h'] = {
     'cvpce_conv3x3_halo_strips2': SIGNATURES['cvpce_conv3x3_halo_strips'],
 }
 
-# include/cvpce_amd_gallery.h: the gallery side's byte-reading kernel.  A table of its own, like the header.
-GALLERY_SIGNATURES = {
+# the gallery side's byte-reading kernel.
+HEADERS['cvpce_amd_gallery.h'] = {
     'cvpce_gallery_pack_u8': (c_int, [_vp, _ip, _vp, _vp, c_int, c_int, c_int, c_int, _ip, _vp]),
 }
 
-# include/cvpce_amd_reclass.h: the two ends of the comparator's re-classification.  A table of its own, like the header.
-RECLASS_SIGNATURES = {
+# the two ends of the comparator's re-classification.
+HEADERS['cvpce_amd_reclass.h'] = {
     'cvpce_reclass_plan': (c_int, [_ip, _ip, _fp, _ip, _ip] + [c_int] * 3 + [_fp, _ip, _ip, _vp]),
     'cvpce_reclass_verdict': (c_int, [_ip, _ip, _ip, _vp, _ip, _ip, _ip, _ip, _ip] + [c_int] * 6 + [_ip, _ip, _vp]),
 }
 
-# include/cvpce_amd_classeval.h: the classification harness's comparison.  A table of its own, like the header.
-CLASSEVAL_SIGNATURES = {
+# the classification harness's comparison.
+HEADERS['cvpce_amd_classeval.h'] = {
     'cvpce_classeval_rank': (c_int, [_vp, _ip, _ip] + [c_int] * 3 + [_ip, _vp]),
 }
 
-# include/cvpce_amd_actuals.h: a window's detections as the comparator's actual side.  A table of its own, like the header.
-ACTUALS_SIGNATURES = {
+# a window's detections as the comparator's actual side.
+HEADERS['cvpce_amd_actuals.h'] = {
     'cvpce_actuals_count': (c_int, [_fp, _ip, c_int, c_int, _ip, _vp]),
     'cvpce_actuals_pack': (c_int, [_fp, _ip, _vp, c_int, _ip, c_int, _ip, c_float, c_int, c_int, c_int, _fp, _ip, _ip, _fp, _ip, _vp]),
 }
 
-# include/cvpce_amd_report.h: the comparator's compliance report.  A table of its own, like the header.
-REPORT_SIGNATURES = {
+# the comparator's compliance report.
+HEADERS['cvpce_amd_report.h'] = {
     'cvpce_report_positions': (c_int, [_ip, _ip, _ip, _fp, _fp, _ip, _ip, _ip, _ip, ctypes.c_double] + [c_int] * 3 + [_ip, _ip, _fp, _ip, _ip, _vp]),
     'cvpce_report_reclass': (c_int, [_ip, _ip, _ip, _vp, _fp, _ip, _ip, _ip, _ip] + [c_int] * 6 + [_ip, _ip, _fp, _vp]),
 }
 
-# include/cvpce_amd_render.h: the compliance pictures' compositor.  A table of its own, like the header.
-RENDER_SIGNATURES = {
+# the compliance pictures' compositor.
+HEADERS['cvpce_amd_render.h'] = {
     'cvpce_render_canvases': (c_int, [_vp, c_int, c_longlong, _vp, c_longlong, _vp, c_longlong, _fp, _ip, _ip, _ip, c_int, _vp, c_longlong, _ip, c_int,
                                       c_int, _vp]),
 }
 
-# include/cvpce_amd_gaussians.h: the Gaussian maps' targets and loss.  A table of its own, like the header.
-GAUSSIANS_SIGNATURES = {
+# the Gaussian maps' targets and loss.
+HEADERS['cvpce_amd_gaussians.h'] = {
     'cvpce_gauss_kant_table': (c_int, [_fp, c_int, c_int, _vp]),
     'cvpce_gauss_targets': (c_int, [_ip, _ip, _vp, _ip, _fp] + [c_int] * 7 + [POINTER(c_float), c_int, c_int, _fp, _vp]),
     'cvpce_gauss_loss_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'cvpce_gauss_loss': (c_int, [_fp, _fp, _ip, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, _vp, c_size_t, _fp, _ip, _vp]),
 }
 
-# include/cvpce_amd_headloss.h: anchor matching and the two head losses.  A table of its own, like the header.
-HEADLOSS_SIGNATURES = {
+# anchor matching and the two head losses.
+HEADERS['cvpce_amd_headloss.h'] = {
     'cvpce_headloss_workspace_bytes': (c_size_t, [POINTER(c_int), POINTER(c_int)] + [c_int] * 4),
     'cvpce_headloss': (c_int, [POINTER(c_void_p), POINTER(c_void_p)] + [POINTER(c_int)] * 4 + [_fp, _fp, _ip, _ip, _fp] + [c_int] * 5
                        + [_vp, c_size_t, _ip, _fp, _ip, _vp]),
 }
 
-for _table in (SIGNATURES, EVAL_SIGNATURES, INPUT_SIGNATURES, PLANOGRAM_SIGNATURES, HOMOGRAPHY_SIGNATURES, LISTS_SIGNATURES, GALLERY_SIGNATURES,
-               RECLASS_SIGNATURES, CLASSEVAL_SIGNATURES, ACTUALS_SIGNATURES, REPORT_SIGNATURES, RENDER_SIGNATURES, GAUSSIANS_SIGNATURES,
-               HEADLOSS_SIGNATURES):
+for _table in HEADERS.values():
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -14,12 +14,9 @@ import torch
 
 from . import datautils, ops
 from .classification_eval import clip_boxes_to_image
+from . import staging
 
 LOG_ROWS = 4096           # records the log is first allocated for; it doubles when a window does not fit
-
-
-def _upload(host, device):
-    return host.pin_memory().to(device, non_blocking=True)
 
 
 class ClassificationTally:
@@ -91,7 +88,7 @@ class ClassificationTally:
             if c:
                 fb[i, :c] = clip_boxes_to_image(torch.as_tensor(b).cpu(), datautils.image_hw(img)).to(torch.float32)
                 sel += range(i * per, i * per + c)
-        small = _upload(torch.cat((fb.view(torch.int32).reshape(-1), torch.tensor(counts + sel + ids, dtype=torch.int32))), device)
+        small = staging.upload(torch.cat((fb.view(torch.int32).reshape(-1), torch.tensor(counts + sel + ids, dtype=torch.int32))), device)
         at = n * per * 4
         dev_boxes, dev_count = small[:at].view(torch.float32).view(n, per, 4), small[at:at + n]
         dev_sel, dev_ids = small[at + n:at + n + total], small[at + n + total:]

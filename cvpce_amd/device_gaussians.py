@@ -12,7 +12,7 @@ only -- the per-image sizes are known from the shapes, every upload goes through
 import torch
 
 from . import datautils, torch_ops_gaussians as G   # (registers torch.ops.cvpce_amd.gauss_*)
-from .device_metrics import _offsets, _pack, _upload
+from . import staging
 
 # stream operations `GaussianScore.update` queues per batch, whatever the number of boxes and pixels:
 #   launches: the stack of the predictions, the targets launch, the loss (a memset, five passes, the finish)     1 + 1 + 7
@@ -72,12 +72,12 @@ def render_boxes(boxes, geom, hb, wb, generate_method=None, join_method=None, ta
     if any(int(g[2]) < 1 for g in geom):
         raise ValueError('size_reduction is a positive integer')
     if any(b.is_cuda for b in boxes):
-        packed = _pack(boxes, torch.int32, device, (4,))
+        packed = staging.pack(boxes, torch.int32, device, (4,))
     else:                                                        # host boxes: packed on the host, one upload
         packed = torch.empty((0, 4), dtype=torch.int32, device=device) if not sum(b.numel() for b in boxes) else \
             torch.cat([b.reshape(-1, 4) for b in boxes]).to(torch.int32).pin_memory().to(device, non_blocking=True)
-    offsets = _upload(_offsets([b.numel() // 4 for b in boxes]), torch.int32, device)
-    g = _upload([[int(v) for v in row] for row in geom], torch.int32, device).reshape(len(geom), G.GEOM)
+    offsets = staging.upload_values(staging.offsets([b.numel() // 4 for b in boxes]), torch.int32, device)
+    g = staging.upload_values([[int(v) for v in row] for row in geom], torch.int32, device).reshape(len(geom), G.GEOM)
     table = _kant_table(device, *generate_method.table) if generate_method.table else None
     torch.ops.cvpce_amd.gauss_targets(packed, offsets, None, g, table, G.METHODS[generate_method.name], G.JOINS[join_method.name],
                                       *generate_method.params, int(bool(tanh)), int(bool(resize)), out)
@@ -94,8 +94,8 @@ def render_maps(maps, extents, hb, wb, tanh=False):
     for m in maps:
         if m.dim() != 2 or m.dtype != torch.float32 or not m.is_contiguous() or m.device != device:
             raise ValueError('targets are contiguous (H,W) float32 maps on one device')
-    ptrs = _upload([m.data_ptr() for m in maps], torch.int64, device)
-    g = _upload([[m.shape[0], m.shape[1], 1, int(h), int(w)] for m, (h, w) in zip(maps, extents)], torch.int32, device).reshape(len(maps), G.GEOM)
+    ptrs = staging.upload_values([m.data_ptr() for m in maps], torch.int64, device)
+    g = staging.upload_values([[m.shape[0], m.shape[1], 1, int(h), int(w)] for m, (h, w) in zip(maps, extents)], torch.int32, device).reshape(len(maps), G.GEOM)
     torch.ops.cvpce_amd.gauss_targets(None, None, ptrs, g, None, 0, 0, 0.0, 0.0, 0.0, int(bool(tanh)), 1, out)
     return out
 
@@ -200,7 +200,7 @@ class GaussianScore:
         geom = [(int(h0), int(w0), 1, rh // 2, rw // 2) for (h0, w0), ((rh, rw), _) in zip(original_sizes, geometry)]
         extents = [[min(ph // 2, hb), min(pw // 2, wb)] for _, (ph, pw) in geometry]
         targets = render_boxes(target_boxes, geom, hb, wb, self.generate_method, self.join_method, self.tanh, True, pred.device)
-        ext = _upload(extents, torch.int32, pred.device).reshape(len(extents), 2)
+        ext = staging.upload_values(extents, torch.int32, pred.device).reshape(len(extents), 2)
         out_f, _ = loss(pred, targets, ext, **self.loss_params)
         self._losses.append(out_f)
         self.images += len(results)

@@ -11,7 +11,7 @@ import torch
 
 from . import torch_ops_headloss as H   # (registers torch.ops.cvpce_amd.headloss)
 from .device_gaussians import summarise
-from .device_metrics import _offsets, _pack, _upload
+from . import staging
 
 # stream operations `HeadScore.update` queues per batch, whatever the number of boxes and anchors:
 #   launches: the memset of the boxes' best IoUs, headloss_match, headloss_terms, headloss_finish, the batch's result row   4 + 1
@@ -54,16 +54,6 @@ def scale_factors(transformed_sizes, original_sizes):
     return new / old
 
 
-def _pack_once(tensors, dtype, device, tail=()):
-    """Per-image host tensors -> packed on the host, ONE pinned upload; with a device tensor among them, `device_metrics._pack`."""
-    if any(t.is_cuda for t in tensors):
-        return _pack(tensors, dtype, device, tail)
-    host = torch.cat([t.detach().reshape((-1,) + tail).to(dtype) for t in tensors])
-    if not host.numel():
-        return torch.empty((0,) + tail, dtype=dtype, device=device)
-    return host.pin_memory().to(device, non_blocking=True)
-
-
 def head_losses(cls, reg, grids, strides, base_anchors, boxes, labels, scales):
     """The memset and the three launches of one batch -> (out_f (N,2) f32: classification, bbox_regression per image; out_i (N,3)
     i32: foreground, between, restored anchors; matched (N,A_total) i32: box index, -1 background, -2 between), all on the device.
@@ -91,12 +81,12 @@ def head_losses(cls, reg, grids, strides, base_anchors, boxes, labels, scales):
     nbytes = H.workspace_bytes([g[0] for g in grids], [g[1] for g in grids], num_anchors, n, sum_t)
     if nbytes == 0:
         raise ValueError(f'head losses: unsupported shape ({n} images, {sum(cells)} anchors, {sum_t} boxes: empty, or 2^31 elements and more)')
-    packed = _pack_once(boxes, torch.float32, device, (4,))
-    packed_labels = _pack_once(labels, torch.int32, device)
-    offsets = _upload(_offsets(counts), torch.int32, device)
+    packed = staging.pack_once(boxes, torch.float32, device, (4,))
+    packed_labels = staging.pack_once(labels, torch.int32, device)
+    offsets = staging.upload_values(staging.offsets(counts), torch.int32, device)
     scales = torch.as_tensor(scales, dtype=torch.float32).reshape(n, 2)
     if not scales.is_cuda:
-        scales = scales.pin_memory().to(device, non_blocking=True)
+        scales = staging.upload(scales, device)
     workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
     matched = torch.empty((n, sum(cells)), dtype=torch.int32, device=device)
     out_f = torch.empty((n, 2), dtype=torch.float32, device=device)

@@ -17,6 +17,7 @@ F-score are the host path's by construction.
 import torch
 
 from . import metrics, torch_ops_eval  # noqa: F401  (registers torch.ops.cvpce_amd.eval_match_detections)
+from . import staging
 
 MAX_THRESHOLDS = 16
 
@@ -27,32 +28,6 @@ def _device_of(*lists):
             if t.is_cuda:
                 return t.device
     return torch.device('cuda', torch.cuda.current_device())
-
-
-def _upload(values, dtype, device):
-    """A short host list -> device tensor through pinned memory: queued on the stream, the host does not wait."""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
-
-
-def _pack(tensors, dtype, device, tail=()):
-    """Per-image tensors (device or host) -> one packed device tensor."""
-    if not tensors:
-        return torch.zeros((0,) + tail, dtype=dtype, device=device)
-    parts = []
-    for t in tensors:
-        t = t.detach().reshape((-1,) + tail)
-        if not t.is_cuda:
-            t = t.to(dtype)
-            t = t.pin_memory() if t.numel() else t
-        parts.append(t.to(device=device, dtype=dtype, non_blocking=True))
-    return torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
-
-
-def _offsets(lengths):
-    off = [0]
-    for n in lengths:
-        off.append(off[-1] + n)
-    return off
 
 
 def _threshold_values(iou_thresholds):
@@ -75,18 +50,18 @@ def _match_packed(targets, predictions, confidences, thr, target_labels=None, pr
     for p, n in zip(predictions, n_pred):
         if p.numel() != 4 * n:
             raise ValueError('one confidence per predicted box')
-    pred = _pack(predictions, torch.float32, device, (4,))
-    conf = _pack(confidences, torch.float32, device)
-    tgt = _pack(targets, torch.float32, device, (4,))
+    pred = staging.pack(predictions, torch.float32, device, (4,))
+    conf = staging.pack(confidences, torch.float32, device)
+    tgt = staging.pack(targets, torch.float32, device, (4,))
     pcls = tcls = None
     if target_labels is not None:
         if [int(l.numel()) for l in target_labels] != n_tgt or [int(l.numel()) for l in prediction_labels] != n_pred:
             raise ValueError('one class id per box')
-        pcls = _pack(prediction_labels, torch.int32, device)
-        tcls = _pack(target_labels, torch.int32, device)
+        pcls = staging.pack(prediction_labels, torch.int32, device)
+        tcls = staging.pack(target_labels, torch.int32, device)
     sum_p, sum_t, k = sum(n_pred), sum(n_tgt), thr.numel()
-    poff = _upload(_offsets(n_pred), torch.int32, device)
-    toff = _upload(_offsets(n_tgt), torch.int32, device)
+    poff = staging.upload_values(staging.offsets(n_pred), torch.int32, device)
+    toff = staging.upload_values(staging.offsets(n_tgt), torch.int32, device)
     # rank = position in the image's stable descending confidence order: a stable sort by confidence over the whole batch, then
     # a stable sort of that by image number (already ascending in the packed layout) -- a segmented sort without a host loop
     pos = torch.arange(sum_p, dtype=torch.int32, device=device)
@@ -111,7 +86,7 @@ def match_detections(targets, predictions, confidences, iou_thresholds, target_l
     device = _device_of(predictions, confidences, targets)
     thr = torch.tensor(_threshold_values(iou_thresholds), dtype=torch.float32).to(device)
     m = _match_packed(targets, predictions, confidences, thr, target_labels, prediction_labels)
-    poff, toff = _offsets(m['n_pred']), _offsets(m['n_tgt'])
+    poff, toff = staging.offsets(m['n_pred']), staging.offsets(m['n_tgt'])
     return ([m['tp'][:, poff[i]:poff[i + 1]] for i in range(len(targets))],
             [m['first'][:, toff[i]:toff[i + 1]] for i in range(len(targets))])
 
@@ -140,7 +115,7 @@ class DetectionMetrics:
         if self._thr is None:
             if self._device is None:
                 self._device = _device_of(predictions, confidences, targets)
-            self._thr = _upload(self._values, torch.float32, self._device)
+            self._thr = staging.upload_values(self._values, torch.float32, self._device)
         m = _match_packed(targets, predictions, confidences, self._thr, target_labels, prediction_labels)
         self._labelled = labelled
         del m['first']

@@ -36,6 +36,7 @@ import torch
 
 from . import torch_ops_homography, torch_ops_planogram  # noqa: F401  (register torch.ops.cvpce_amd.planogram_* / homography_*)
 from .planograms import CARDINALS
+from . import staging
 from .torch_ops_planogram import MAX_NODES
 
 CACHE_KEY = 'device_graph'
@@ -84,7 +85,7 @@ class DeviceActuals:
         images = list(images)
         if images == list(range(len(self.n2))):
             return self
-        off = _offsets(self.n2)
+        off = staging.offsets(self.n2)
         return self.concat([DeviceActuals(self.boxes[off[i]:off[i + 1]], self.row[off[i]:off[i + 1]], self.label[off[i]:off[i + 1]],
                                           self.thresh[i:i + 1], self.status[i:i + 1], None, [self.n2[i]], self.thresh_size) for i in images])
 
@@ -98,7 +99,7 @@ class DeviceActuals:
             raise ValueError('at least one pack, all made with one thresh_size')
         n2 = [n for p in packs for n in p.n2]
         cat = lambda name: torch.cat([getattr(p, name) for p in packs])
-        off2 = _upload(torch.tensor(_offsets(n2), dtype=torch.int32), packs[0].boxes.device)
+        off2 = staging.upload(torch.tensor(staging.offsets(n2), dtype=torch.int32), packs[0].boxes.device)
         return DeviceActuals(cat('boxes'), cat('row'), cat('label'), cat('thresh'), cat('status'), off2, n2, packs[0].thresh_size)
 
 
@@ -108,20 +109,9 @@ def graph_threshold(boxes, thresh_size):
     return thresh_size * span
 
 
-def _upload(host, device):
-    return (host.pin_memory() if host.numel() else host).to(device, non_blocking=True)
-
-
-def _offsets(lengths):
-    off = [0]
-    for n in lengths:
-        off.append(off[-1] + n)
-    return off
-
-
 def _upload_tables(device, **tables):
     """Small int32 tables (lists) in ONE upload -> their views on the device by name; they lie in the order given."""
-    small = _upload(torch.tensor([v for table in tables.values() for v in table], dtype=torch.int32), device)
+    small = staging.upload(torch.tensor([v for table in tables.values() for v in table], dtype=torch.int32), device)
     views, at = {}, 0
     for name, table in tables.items():
         views[name] = small[at:at + len(table)]
@@ -146,10 +136,10 @@ def build_graphs(items, thresh_size=0.5, device=None):
             raise ValueError(f'a device graph has between 1 and {MAX_NODES} nodes, got {n}')
     host = [boxes.detach().to(device='cpu', dtype=torch.float32) for boxes, _ in items]
     thresh = torch.stack([graph_threshold(b, thresh_size) for b in host]).to(torch.float32)
-    off = _offsets(sizes)
-    boxes = _upload(torch.cat(host).contiguous(), device)
-    offsets = _upload(torch.tensor(off, dtype=torch.int32), device)
-    thresh = _upload(thresh, device)
+    off = staging.offsets(sizes)
+    boxes = staging.upload(torch.cat(host).contiguous(), device)
+    offsets = staging.upload(torch.tensor(off, dtype=torch.int32), device)
+    thresh = staging.upload(thresh, device)
     nbr = torch.empty((off[-1], 8), dtype=torch.int32, device=device)
     weight = torch.empty((off[-1], 8), dtype=torch.float32, device=device)
     stamp = torch.empty((off[-1], 8), dtype=torch.int32, device=device)
@@ -170,7 +160,7 @@ def _build_actual_graphs(actuals, thresh_size):
     stamp = torch.empty((total, 8), dtype=torch.int32, device=device)
     torch.ops.cvpce_amd.planogram_graphs(actuals.boxes, actuals.off2, actuals.thresh, min(sizes), max(sizes), nbr, weight, stamp)
     parent = (nbr, weight, stamp)
-    return [Graph([None] * n, nbr[o:o + n], weight[o:o + n], stamp[o:o + n], parent + (o,)) for o, n in zip(_offsets(sizes), sizes)]
+    return [Graph([None] * n, nbr[o:o + n], weight[o:o + n], stamp[o:o + n], parent + (o,)) for o, n in zip(staging.offsets(sizes), sizes)]
 
 
 def _packed(graphs, device):
@@ -218,7 +208,7 @@ def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, 
         if not 1 <= len(g) <= MAX_NODES:
             raise ValueError(f'a device graph has between 1 and {MAX_NODES} nodes, got {len(g)}')
     n1, n2 = [len(g) for g in expected], [len(g) for g in actual]
-    off1, off2 = _offsets(n1), _offsets(n2)
+    off1, off2 = staging.offsets(n1), staging.offsets(n2)
     hyps, params = [], []
     if actuals is None:
         ids = {}
@@ -235,7 +225,7 @@ def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, 
         else:
             hyps.append(b * expected_ids[p][1])
         params += [min_agree_for(min_score), int(min(a, b) * stop_at_fraction)]
-    hyp_off, out_off = _offsets(hyps), _offsets([min(a, b) for a, b in zip(n1, n2)])
+    hyp_off, out_off = staging.offsets(hyps), staging.offsets([min(a, b) for a, b in zip(n1, n2)])
     if hyp_off[-1] >= 2 ** 31:
         raise ValueError('too many equal-label node pairs for one launch: split the batch')
     small = _upload_tables(device, label1=lab1, label2=lab2, off1=off1, off2=off2 if actuals is None else [], params=params,
@@ -351,7 +341,7 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
         """box sets back to back on the device: sets that lie there already (`expected_boxes_on_device`) are joined there"""
         if all(bx.device == device and bx.dtype == torch.float32 for bx in sets):
             return sets[0].contiguous() if len(sets) == 1 else torch.cat(sets)
-        return _upload(torch.cat([bx.detach().to(device='cpu', dtype=torch.float32) for bx in sets]).contiguous(), device)
+        return staging.upload(torch.cat([bx.detach().to(device='cpu', dtype=torch.float32) for bx in sets]).contiguous(), device)
 
     if on_device:
         boxes1, boxes2 = packed(list(expected_boxes)), actual_boxes.boxes
@@ -360,7 +350,7 @@ def _prepare_tail(matching, expected_boxes, actual_boxes, reproj_thresholds, iou
     else:                                         # (host boxes on both sides: one upload)
         boxes = packed(list(expected_boxes) + list(actual_boxes))
         boxes1, boxes2 = boxes[:sum1], boxes[sum1:]
-    params = _upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
+    params = staging.upload(torch.tensor([[float(t), float(iou_threshold)] for t in reproj_thresholds], dtype=torch.float64), device)
     workspace = torch.empty(max(torch_ops_homography.workspace_bytes(b, hypotheses), 8) // 4, dtype=torch.int32, device=device)
     layout = TailLayout(b, sum1, sum2, extra=report)
     blob = torch.empty(layout.nbytes, dtype=torch.uint8, device=device)
@@ -386,7 +376,7 @@ class ReclassPlan:
 def _image_table(image_table, b, device):
     if len(image_table) != b:
         raise ValueError('one (h, w, enabled) row per image')
-    return _upload(torch.tensor([[int(h), int(w), int(bool(on))] for h, w, on in image_table], dtype=torch.int32), device)
+    return staging.upload(torch.tensor([[int(h), int(w), int(bool(on))] for h, w, on in image_table], dtype=torch.int32), device)
 
 
 def _launch_plan(matching, finish, table):
@@ -541,7 +531,7 @@ def finalize_batch(expected, actual, matching, expected_boxes, actual_boxes, rep
     host = layout.views(back)
     status, winner, winner_count, final_count, size = (t.tolist() for t in (host.status, host.winner, host.winner_count, host.final_count, host.size))
     me, ma, hmat = host.matched_expected != 0, host.matched_actual != 0, host.hmat.view(b, 3, 3)
-    off1, off2 = _offsets(n1), _offsets(n2)
+    off1, off2 = staging.offsets(n1), staging.offsets(n2)
     records = []
     for p in range(b):
         e, a, m = slice(off1[p], off1[p + 1]), slice(off2[p], off2[p + 1]), size[p]
@@ -602,7 +592,7 @@ def expected_boxes_on_device(expected, device):
     boxes = expected['boxes']
     c = expected.get(BOXES_KEY) if isinstance(expected, dict) else None
     if c is None or c[0] is not boxes or c[1].device != device:
-        c = (boxes, _upload(boxes.detach().to(device='cpu', dtype=torch.float32).contiguous(), device))
+        c = (boxes, staging.upload(boxes.detach().to(device='cpu', dtype=torch.float32).contiguous(), device))
         if isinstance(expected, dict):
             expected[BOXES_KEY] = c
     return c[1]

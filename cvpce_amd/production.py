@@ -14,6 +14,7 @@ import os
 import torch
 
 from . import datautils, ops
+from .staging import offsets, upload
 from .models.classification import TANH_MEAN, TANH_STD
 
 
@@ -1151,7 +1152,7 @@ class BatchedPipeline:
         with the host's prefix sums of the kept counts -> `planograms_device.DeviceActuals`.  Nothing is waited for."""
         from . import planograms_device as pd
         device, total = boxes.device, sum(kept)
-        off2 = pd._upload(torch.tensor(pd._offsets(kept), dtype=torch.int32), device)
+        off2 = upload(torch.tensor(offsets(kept), dtype=torch.int32), device)
         out_boxes = torch.empty((total, 4), dtype=torch.float32, device=device)
         small = torch.empty(2 * total + 2 * len(kept), dtype=torch.int32, device=device)
         row, label, status = small[:total], small[total:2 * total], small[2 * total + len(kept):]

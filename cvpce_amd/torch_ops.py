@@ -6,6 +6,10 @@ ROCm) dispatch key ONLY: there is no CPU kernel, so a CPU tensor fails in the di
 op level too).  All ops are out-variants -- the caller (cvpce_amd/ops.py) allocates, the op launches one hand-written
 kernel schedule on the current HIP stream through ctypes -> libcvpce_hip.so, no allocation, no synchronisation -- so they
 are safe under HIP stream capture (cvpce_amd.models.proposals captures the detector schedule in a hipGraph).
+
+One header of include/ <-> one table of `_lib.HEADERS` <-> one op module with one NAMES list.  The feature headers' modules are
+the `torch_ops_*.py` beside this one; each takes its list and its decorator from `registrar()`, so every op of the namespace is
+defined on the one library this module owns (a second DEF library for the namespace would raise) and under the rules above.
 """
 import ctypes
 
@@ -15,7 +19,33 @@ from . import _lib
 from ._lib import lib, check
 
 _L = torch.library.Library('cvpce_amd', 'DEF')
-NAMES = []
+
+
+def registrar():
+    """-> (names, op): `@op(schema)` defines the schema, registers the function as its CUDA kernel and appends the op's name to
+    `names`, in definition order."""
+    names = []
+
+    def op(schema):
+        def deco(fn):
+            name = schema.split('(')[0]
+            _L.define(schema)
+            _L.impl(name, fn, 'CUDA')
+            names.append(name)
+            return fn
+        return deco
+    return names, op
+
+
+NAMES, _op = registrar()
+
+
+def typed(what, f32=(), i32=(), i64=(), f64=(), u8=()):
+    """Every tensor of a group has the group's dtype and is contiguous, or RuntimeError; None entries are skipped."""
+    for dtype, tensors in ((torch.float32, f32), (torch.int32, i32), (torch.int64, i64), (torch.float64, f64), (torch.uint8, u8)):
+        for t in tensors:
+            if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+                raise RuntimeError(f'{what}: expected a contiguous {dtype} tensor, got {t.dtype} with strides {tuple(t.stride())}')
 
 
 def _stream():
@@ -35,16 +65,6 @@ def _by_dtype(x, bf16_name, f16_name, *same):
         if t is not None and t.dtype != x.dtype:
             raise RuntimeError(f'{bf16_name}: operand of type {t.dtype} with {x.dtype} activations')
     return getattr(lib, f16_name if x.dtype == torch.float16 else bf16_name)
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
 
 
 @_op('conv2d_nhwc(Tensor x, Tensor weight, Tensor? bias, Tensor? residual, Tensor(a!) out, int cout, int kh, int kw, int stride, '

@@ -1,25 +1,14 @@
 """PyTorch-ROCm custom op over the classification harness's kernel of include/cvpce_amd_classeval.h: `torch.ops.cvpce_amd.classeval_rank`.
 
-Kept apart from torch_ops_reclass.py and the other op modules, whose NAMES lists are pinned.  Same rules: defined on the library
-torch_ops owns, CUDA (= HIP on ROCm) dispatch key only -- no CPU kernel exists -- an out-variant that launches on the current stream
-through ctypes with no allocation and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 import torch
 
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar
 
-NAMES = []
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
+NAMES, _op = registrar()
 
 
 @_op('classeval_rank(Tensor indices, Tensor gallery_label_id, Tensor want, Tensor(a!) records) -> ()')

@@ -1,26 +1,14 @@
 """PyTorch-ROCm custom ops over the evaluation kernels of include/cvpce_amd_eval.h: `torch.ops.cvpce_amd.eval_*`.
 
-Kept apart from torch_ops.py, whose NAMES list mirrors the inference header entry point by entry point.  Same rules: defined
-on the library torch_ops owns (a second DEF library for the namespace would raise), CUDA (= HIP on ROCm) dispatch key only --
-no CPU kernel exists -- out-variants that launch on the current stream through ctypes with no allocation and no
-synchronisation, so they are safe under stream capture.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 import torch
 
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar
 
-NAMES = []
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
+NAMES, _op = registrar()
 
 
 @_op('eval_match_detections(Tensor pred, Tensor pred_off, Tensor rank, Tensor? pred_cls, Tensor tgt, Tensor tgt_off, '

@@ -1,28 +1,16 @@
 """PyTorch-ROCm custom op over the gallery kernel of include/cvpce_amd_gallery.h: `torch.ops.cvpce_amd.gallery_pack_u8`.
 
-Kept apart from torch_ops.py, whose NAMES list mirrors the inference header entry point by entry point, and from torch_ops_input.py,
-whose list mirrors the shelf side's byte kernels.  Same rules: defined on the library torch_ops owns (a second DEF library for the
-namespace would raise), CUDA (= HIP on ROCm) dispatch key only -- no CPU kernel exists -- an out-variant that launches on the current
-stream through ctypes with no allocation and no synchronisation, so it is safe under stream capture.  The op checks every tensor
-itself and raises before the library is called: `data` a flat contiguous uint8 buffer, `geom` (n,3) int32, `table` (3,257) bf16
-(ops.gallery_table), `out` (n,S,S,4|8) bf16, `ext` (n,2) int32, all contiguous and on one device.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.  The op checks every tensor itself and raises before the library is called: `data` a flat contiguous uint8
+buffer, `geom` (n,3) int32, `table` (3,257) bf16 (ops.gallery_table), `out` (n,S,S,4|8) bf16, `ext` (n,2) int32, all contiguous
+and on one device.
 """
 import torch
 
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar
 
-NAMES = []
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
+NAMES, _op = registrar()
 
 
 def _check(data, geom, table, out, ext):

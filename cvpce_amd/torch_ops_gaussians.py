@@ -1,32 +1,19 @@
 """PyTorch-ROCm custom ops over the Gaussian-map scoring kernels of include/cvpce_amd_gaussians.h: `torch.ops.cvpce_amd.gauss_kant_table`,
 `gauss_targets` and `gauss_loss`.
 
-Kept apart from the other op modules, whose NAMES lists are pinned.  Same rules: defined on the library torch_ops owns, CUDA (= HIP on
-ROCm) dispatch key only -- no CPU kernel exists -- out-variants that launch on the current stream through ctypes with no allocation and
-no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 import ctypes
 
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 GEOM = 5                                    # CVPCE_GAUSS_GEOM: H0, W0, r, h, w per image
 TILE, LIST = 16, 256                        # CVPCE_GAUSS_TILE, CVPCE_GAUSS_LIST
 METHODS = {'multivariate_normal': 0, 'kant_method': 1, 'simple_and_scaled': 2}
 JOINS = {'max': 0, 'addition': 1, 'replacement': 2}
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
 
 
 def loss_workspace_bytes(n, hb, wb):
@@ -34,16 +21,10 @@ def loss_workspace_bytes(n, hb, wb):
     return int(lib.cvpce_gauss_loss_workspace_bytes(int(n), int(hb), int(wb)))
 
 
-def _plain(what, dtype, *tensors):
-    for t in tensors:
-        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
-            raise RuntimeError(f'{what}: expected contiguous {dtype} tensors')
-
-
 @_op('gauss_kant_table(Tensor(a!) out, int sigma) -> ()')
 def _gauss_kant_table(out, sigma):
     what = 'cvpce_gauss_kant_table'
-    _plain(what, torch.float32, out)
+    typed(what, f32=(out,))
     if out.dim() != 2 or out.shape[0] != out.shape[1]:
         raise RuntimeError(f'{what}: the table is square')
     check(lib.cvpce_gauss_kant_table(_p(out), out.shape[0], sigma, _stream()), what)
@@ -53,9 +34,7 @@ def _gauss_kant_table(out, sigma):
      'float p0, float p1, float p2, int tanh, int resize, Tensor(a!) out) -> ()')
 def _gauss_targets(boxes, box_offsets, map_ptrs, geom, table, method, join, p0, p1, p2, tanh, resize, out):
     what = 'cvpce_gauss_targets'
-    _plain(what, torch.int32, boxes, box_offsets, geom)
-    _plain(what, torch.int64, map_ptrs)
-    _plain(what, torch.float32, table, out)
+    typed(what, i32=(boxes, box_offsets, geom), i64=(map_ptrs,), f32=(table, out))
     if out.dim() != 4 or out.shape[1] != 1:
         raise RuntimeError(f'{what}: the output is (N,1,Hb,Wb)')
     n, _, hb, wb = out.shape
@@ -84,9 +63,7 @@ def _gauss_targets(boxes, box_offsets, map_ptrs, geom, table, method, join, p0, 
 def _gauss_loss(pred, target, extent, negative_threshold, positive_threshold, min_negatives, negatives_per_positive, per_image, workspace,
                 out_f, out_i):
     what = 'cvpce_gauss_loss'
-    _plain(what, torch.float32, pred, target, out_f)
-    _plain(what, torch.int32, extent, out_i)
-    _plain(what, torch.uint8, workspace)
+    typed(what, f32=(pred, target, out_f), i32=(extent, out_i), u8=(workspace,))
     if pred.dim() != 4 or pred.shape[1] != 1 or pred.shape != target.shape:
         raise RuntimeError(f'{what}: predictions and targets are (N,1,Hb,Wb)')
     n, _, hb, wb = pred.shape

@@ -1,30 +1,16 @@
 """PyTorch-ROCm custom op over the head-loss kernels of include/cvpce_amd_headloss.h: `torch.ops.cvpce_amd.headloss` issues the memset
 and the three launches (headloss_match, headloss_terms, headloss_finish) of one batch.
 
-Kept apart from the other op modules, whose NAMES lists are pinned.  Same rules: defined on the library torch_ops owns, CUDA (= HIP on
-ROCm) dispatch key only -- no CPU kernel exists -- an out-variant that launches on the current stream through ctypes with no allocation
-and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 import ctypes
 
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
-from .torch_ops_gaussians import _plain
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 CHUNK, THREADS, MAX_LEVELS = 1024, 256, 8   # CVPCE_HEADLOSS_CHUNK, CVPCE_HEADLOSS_THREADS, CVPCE_HEADLOSS_MAX_LEVELS
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
 
 
 def _ints(values):
@@ -43,9 +29,7 @@ def _headloss(logits, regs, gh, gw, sh, sw, base_anchors, boxes, labels, box_off
               out_f, out_i):
     what = 'cvpce_headloss'
     L, n = len(logits), out_f.shape[0]
-    _plain(what, torch.float32, *logits, *regs, base_anchors, boxes, scales, out_f)
-    _plain(what, torch.int32, labels, box_offsets, matched, out_i)
-    _plain(what, torch.uint8, workspace)
+    typed(what, f32=(*logits, *regs, base_anchors, boxes, scales, out_f), i32=(labels, box_offsets, matched, out_i), u8=(workspace,))
     if not (1 <= L <= MAX_LEVELS and len(regs) == len(gh) == len(gw) == len(sh) == len(sw) == L):
         raise RuntimeError(f'{what}: one logits, regs, grid and stride entry per level, at most {MAX_LEVELS} levels')
     cells = [int(h) * int(w) * num_anchors for h, w in zip(gh, gw)]

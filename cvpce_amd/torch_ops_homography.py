@@ -1,39 +1,19 @@
 """PyTorch-ROCm custom ops over the comparator-tail kernels of include/cvpce_amd_homography.h: `torch.ops.cvpce_amd.homography_*`.
 
-Kept apart from torch_ops_planogram.py, whose NAMES list is pinned.  Same rules: defined on the library torch_ops owns, CUDA (= HIP on
-ROCm) dispatch key only -- no CPU kernel exists -- out-variants that launch on the current stream through ctypes with no allocation
-and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 MAX_PAIRS = 1024          # CVPCE_HOMOGRAPHY_MAX_PAIRS
 MAX_HYPOTHESES = 65536    # CVPCE_HOMOGRAPHY_MAX_HYPOTHESES
 OK, NONE, INVALID = 0, 1, 2
 
 
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
-
-
 def workspace_bytes(b, hypotheses):
     return lib.cvpce_homography_workspace_bytes(b, hypotheses)
-
-
-def _typed(what, f32, i32, f64):
-    if (any(t.dtype != torch.float32 for t in f32) or any(t.dtype != torch.int32 for t in i32) or any(t.dtype != torch.float64 for t in f64)):
-        raise RuntimeError(f'{what}: boxes and positions are float32, params and H float64, everything else int32')
-    if not all(t.is_contiguous() for t in tuple(f32) + tuple(i32) + tuple(f64)):
-        raise RuntimeError(f'{what}: contiguous tensors only')
 
 
 def _shapes(what, boxes1, off1, boxes2, off2, pairs, count, out_off, params, workspace):
@@ -48,7 +28,7 @@ def _shapes(what, boxes1, off1, boxes2, off2, pairs, count, out_off, params, wor
      'int max_pairs, int seed, int hypotheses, Tensor(a!) workspace) -> ()')
 def _homography_ransac(boxes1, off1, boxes2, off2, pairs, count, out_off, params, max_pairs, seed, hypotheses, workspace):
     what = 'cvpce_homography_ransac'
-    _typed(what, (boxes1, boxes2), (off1, off2, pairs, count, out_off), (params,))
+    typed(what, f32=(boxes1, boxes2), i32=(off1, off2, pairs, count, out_off), f64=(params,))
     b = _shapes(what, boxes1, off1, boxes2, off2, pairs, count, out_off, params, workspace)
     check(lib.cvpce_homography_ransac(_p(boxes1), _p(off1), _p(boxes2), _p(off2), _p(pairs), _p(count), _p(out_off), _p(params),
                                       b, boxes1.shape[0], boxes2.shape[0], pairs.shape[0], max_pairs, seed & 0xFFFFFFFF, hypotheses,
@@ -62,8 +42,8 @@ def _homography_ransac(boxes1, off1, boxes2, off2, pairs, count, out_off, params
 def _homography_finish(boxes1, label1, off1, boxes2, label2, off2, pairs, count, out_off, params, max_n1, max_n2, max_pairs, seed, hypotheses,
                        workspace, status, H, winner, winner_count, final_count, matched_expected, matched_actual, expected_positions):
     what = 'cvpce_homography_finish'
-    _typed(what, (boxes1, boxes2, expected_positions),
-           (label1, off1, label2, off2, pairs, count, out_off, status, winner, winner_count, final_count, matched_expected, matched_actual), (params, H))
+    typed(what, f32=(boxes1, boxes2, expected_positions), f64=(params, H),
+          i32=(label1, off1, label2, off2, pairs, count, out_off, status, winner, winner_count, final_count, matched_expected, matched_actual))
     b = _shapes(what, boxes1, off1, boxes2, off2, pairs, count, out_off, params, workspace)
     sum1, sum2 = boxes1.shape[0], boxes2.shape[0]
     if (label1.numel() != sum1 or label2.numel() != sum2 or matched_expected.numel() != sum1 or matched_actual.numel() != sum2

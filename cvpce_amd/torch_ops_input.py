@@ -1,11 +1,8 @@
 """PyTorch-ROCm custom ops over the 8-bit input kernels of include/cvpce_amd_input.h: `torch.ops.cvpce_amd.*_u8`.
 
-Kept apart from torch_ops.py, whose NAMES list mirrors the inference header entry point by entry point.  Same rules: defined
-on the library torch_ops owns (a second DEF library for the namespace would raise), CUDA (= HIP on ROCm) dispatch key only --
-no CPU kernel exists -- out-variants that launch on the current stream through ctypes with no allocation and no
-synchronisation, so they are safe under stream capture.  Every op checks its image arguments itself and raises before the
-library is called: a byte image is a contiguous (H,W,3) uint8 tensor on the device, `table` the 256 float32 values of the codes
-(ops.uint8_table) on the same device.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.  Every op checks its image arguments itself and raises before the library is called: a byte image is a
+contiguous (H,W,3) uint8 tensor on the device, `table` the 256 float32 values of the codes (ops.uint8_table) on the same device.
 """
 import ctypes
 
@@ -13,19 +10,9 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream, _by_dtype
+from .torch_ops import _p, _stream, _by_dtype, registrar
 
-NAMES = []
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
+NAMES, _op = registrar()
 
 
 def _is_bytes(what, img):

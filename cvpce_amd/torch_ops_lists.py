@@ -1,23 +1,12 @@
 """PyTorch-ROCm custom op over the thin-strip launch of include/cvpce_amd_lists.h: `torch.ops.cvpce_amd.conv3x3_halo_strips2`.
 
-Kept apart from torch_ops.py, whose NAMES list mirrors the inference header entry point by entry point.  Same rules as
-torch_ops_eval.py: defined on the library torch_ops owns, CUDA (= HIP on ROCm) dispatch key only -- no CPU kernel exists -- an
-out-variant that launches on the current stream through ctypes with no allocation and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 from ._lib import lib
-from .torch_ops import _L, _halo_list
+from .torch_ops import _halo_list, registrar
 
-NAMES = []
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
+NAMES, _op = registrar()
 
 
 @_op('conv3x3_halo_strips2(Tensor x, Tensor weight, Tensor? bias, Tensor(a!)? out, Tensor(b!)? mac, int mac_off, int cout, int k_pad, '

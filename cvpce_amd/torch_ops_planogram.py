@@ -1,40 +1,20 @@
 """PyTorch-ROCm custom ops over the planogram comparator kernels of include/cvpce_amd_planogram.h: `torch.ops.cvpce_amd.planogram_*`.
 
-Kept apart from torch_ops.py, whose NAMES list mirrors the inference header entry point by entry point.  Same rules as
-torch_ops_eval.py: defined on the library torch_ops owns, CUDA (= HIP on ROCm) dispatch key only -- no CPU kernel exists --
-out-variants that launch on the current stream through ctypes with no allocation and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 MAX_NODES = 1024          # CVPCE_PLANOGRAM_MAX_NODES
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
-
-
-def _typed(what, f32, i32):
-    if any(t.dtype != torch.float32 for t in f32) or any(t.dtype != torch.int32 for t in i32):
-        raise RuntimeError(f'{what}: boxes, thresholds and weights are float32, everything else int32')
-    if not all(t.is_contiguous() for t in tuple(f32) + tuple(i32)):
-        raise RuntimeError(f'{what}: contiguous tensors only')
 
 
 @_op('planogram_graphs(Tensor boxes, Tensor offsets, Tensor thresh, int min_n, int max_n, Tensor(a!) nbr, Tensor(b!) weight, '
      'Tensor(c!) stamp) -> ()')
 def _planogram_graphs(boxes, offsets, thresh, min_n, max_n, nbr, weight, stamp):
     what = 'cvpce_planogram_graphs'
-    _typed(what, (boxes, thresh, weight), (offsets, nbr, stamp))
+    typed(what, f32=(boxes, thresh, weight), i32=(offsets, nbr, stamp))
     b, sum_n = thresh.numel(), boxes.shape[0]
     if boxes.dim() != 2 or boxes.shape[1] != 4 or offsets.numel() != b + 1 or any(t.numel() != sum_n * 8 for t in (nbr, weight, stamp)):
         raise RuntimeError(f'{what}: inconsistent shapes')
@@ -47,7 +27,7 @@ def _planogram_graphs(boxes, offsets, thresh, min_n, max_n, nbr, weight, stamp):
 def _planogram_match(nbr1, stamp1, label1, off1, nbr2, stamp2, label2, off2, params, hyp_off, out_off, max_n1, max_n2, hypotheses,
                      workspace, pairs, count):
     what = 'cvpce_planogram_match'
-    _typed(what, (), (nbr1, stamp1, label1, off1, nbr2, stamp2, label2, off2, params, hyp_off, out_off, pairs, count))
+    typed(what, i32=(nbr1, stamp1, label1, off1, nbr2, stamp2, label2, off2, params, hyp_off, out_off, pairs, count))
     p, sum1, sum2 = count.numel(), label1.numel(), label2.numel()
     if (any(t.numel() != p + 1 for t in (off1, off2, hyp_off, out_off)) or params.numel() != 2 * p or pairs.dim() != 2 or pairs.shape[1] != 2
             or any(t.numel() != sum1 * 8 for t in (nbr1, stamp1)) or any(t.numel() != sum2 * 8 for t in (nbr2, stamp2))

@@ -1,33 +1,13 @@
 """PyTorch-ROCm custom ops over the comparator's re-classification kernels of include/cvpce_amd_reclass.h: `torch.ops.cvpce_amd.reclass_*`.
 
-Kept apart from torch_ops_homography.py and torch_ops_planogram.py, whose NAMES lists are pinned.  Same rules: defined on the library
-torch_ops owns, CUDA (= HIP on ROCm) dispatch key only -- no CPU kernel exists -- out-variants that launch on the current stream
-through ctypes with no allocation and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 MAX_NODES = 1024          # CVPCE_RECLASS_MAX_NODES
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
-
-
-def _typed(what, f32, i32, i64=()):
-    if (any(t.dtype != torch.float32 for t in f32) or any(t.dtype != torch.int32 for t in i32) or any(t.dtype != torch.int64 for t in i64)):
-        raise RuntimeError(f'{what}: positions and boxes are float32, the match indices int64, everything else int32')
-    if not all(t.is_contiguous() for t in tuple(f32) + tuple(i32) + tuple(i64)):
-        raise RuntimeError(f'{what}: contiguous tensors only')
 
 
 def _window(what, status, matched_expected, off1, slots):
@@ -43,7 +23,7 @@ def _window(what, status, matched_expected, off1, slots):
      'Tensor(b!) expected_index, Tensor(c!) count) -> ()')
 def _reclass_plan(status, matched_expected, expected_positions, off1, image, boxes, expected_index, count):
     what = 'cvpce_reclass_plan'
-    _typed(what, (expected_positions, boxes), (status, matched_expected, off1, image, expected_index, count))
+    typed(what, f32=(expected_positions, boxes), i32=(status, matched_expected, off1, image, expected_index, count))
     b, sum1, cap = _window(what, status, matched_expected, off1, (expected_index,))
     if (expected_positions.dim() != 2 or tuple(expected_positions.shape) != (sum1, 4) or tuple(boxes.shape) != (b, cap, 4)
             or tuple(image.shape) != (b, 3) or count.numel() != b):
@@ -57,8 +37,8 @@ def _reclass_plan(status, matched_expected, expected_positions, off1, image, box
 def _reclass_verdict(expected_index, count, slot_row, indices, gallery_label_id, expected_label_id, matched_expected, off1, status, found,
                      found_count):
     what = 'cvpce_reclass_verdict'
-    _typed(what, (), (expected_index, count, slot_row, gallery_label_id, expected_label_id, matched_expected, off1, status, found, found_count),
-           (indices,))
+    typed(what, i64=(indices,),
+          i32=(expected_index, count, slot_row, gallery_label_id, expected_label_id, matched_expected, off1, status, found, found_count))
     b, sum1, cap = _window(what, status, matched_expected, off1, (expected_index, slot_row))
     if (indices.dim() != 2 or indices.shape[1] < 1 or gallery_label_id.dim() != 1 or expected_label_id.numel() != sum1 or found.numel() != sum1
             or count.numel() != b or found_count.numel() != b):

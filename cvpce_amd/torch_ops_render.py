@@ -1,15 +1,14 @@
 """PyTorch-ROCm custom op over the compliance pictures' compositor of include/cvpce_amd_render.h: `torch.ops.cvpce_amd.render_canvases`.
 
-Kept apart from torch_ops_report.py, whose NAMES list is pinned.  Same rules: defined on the library torch_ops owns, CUDA (= HIP on
-ROCm) dispatch key only -- no CPU kernel exists -- an out-variant that launches on the current stream through ctypes with no
-allocation and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
 import torch
 
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar
 
-NAMES = []
+NAMES, _op = registrar()
 TILE_W, TILE_H = 64, 16           # CVPCE_RENDER_TILE_W, CVPCE_RENDER_TILE_H
 MAX_SIDE = 32768                  # CVPCE_RENDER_MAX_SIDE
 TABLE_COLS = 10                   # CVPCE_RENDER_TABLE_COLS
@@ -19,16 +18,6 @@ SRC_NONE, SRC_BASE = -1, -2       # CVPCE_RENDER_SRC_*
 def tiles(h, w):
     """CVPCE_RENDER_TILES: the workgroups an h x w canvas takes"""
     return ((int(h) + TILE_H - 1) // TILE_H) * ((int(w) + TILE_W - 1) // TILE_W)
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
 
 
 @_op('render_canvases(Tensor canvases, int total_tiles, Tensor? base, Tensor box, Tensor src, Tensor colour, Tensor thickness, Tensor atlas, '

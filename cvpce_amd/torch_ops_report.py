@@ -1,35 +1,15 @@
 """PyTorch-ROCm custom ops over the comparator's compliance report kernels of include/cvpce_amd_report.h: `torch.ops.cvpce_amd.report_*`.
 
-Kept apart from torch_ops_reclass.py, whose NAMES list is pinned.  Same rules: defined on the library torch_ops owns, CUDA (= HIP on
-ROCm) dispatch key only -- no CPU kernel exists -- out-variants that launch on the current stream through ctypes with no allocation
-and no synchronisation.
+The rules of torch_ops.py hold: CUDA (= HIP on ROCm) dispatch key only, out-variants on the current stream, no allocation, no
+synchronisation.
 """
-import torch
-
 from ._lib import lib, check
-from .torch_ops import _L, _p, _stream
+from .torch_ops import _p, _stream, registrar, typed
 
-NAMES = []
+NAMES, _op = registrar()
 MAX_NODES = 1024          # CVPCE_REPORT_MAX_NODES
 DETECTED, RECOVERED, MISSING, OUT_OF_VIEW, UNCHECKED, PENDING = range(6)          # CVPCE_REPORT_*
 OUTCOMES = ('detected', 'recovered', 'missing', 'out_of_view', 'unchecked', 'pending')
-
-
-def _op(schema):
-    def deco(fn):
-        name = schema.split('(')[0]
-        _L.define(schema)
-        _L.impl(name, fn, 'CUDA')
-        NAMES.append(name)
-        return fn
-    return deco
-
-
-def _typed(what, f32, i32, i64=()):
-    if (any(t.dtype != torch.float32 for t in f32) or any(t.dtype != torch.int32 for t in i32) or any(t.dtype != torch.int64 for t in i64)):
-        raise RuntimeError(f'{what}: positions, boxes, IoUs and distances are float32, the match indices int64, everything else int32')
-    if not all(t.is_contiguous() for t in tuple(f32) + tuple(i32) + tuple(i64)):
-        raise RuntimeError(f'{what}: contiguous tensors only')
 
 
 @_op('report_positions(Tensor status, Tensor matched_expected, Tensor matched_actual, Tensor expected_positions, Tensor actual_boxes, '
@@ -39,8 +19,8 @@ def _report_positions(status, matched_expected, matched_actual, expected_positio
                       outcome, occupant, occupant_iou, occupant_row, stray):
     what = 'cvpce_report_positions'
     rows = () if actual_row is None else (actual_row,)
-    _typed(what, (expected_positions, actual_boxes, occupant_iou),
-           (status, matched_expected, matched_actual, off1, off2, image, outcome, occupant, occupant_row, stray) + rows)
+    typed(what, f32=(expected_positions, actual_boxes, occupant_iou),
+          i32=(status, matched_expected, matched_actual, off1, off2, image, outcome, occupant, occupant_row, stray) + rows)
     b, sum1, sum2 = status.numel(), matched_expected.numel(), matched_actual.numel()
     if (off1.numel() != b + 1 or off2.numel() != b + 1 or tuple(image.shape) != (b, 3) or tuple(expected_positions.shape) != (sum1, 4)
             or tuple(actual_boxes.shape) != (sum2, 4) or any(t.numel() != sum1 for t in (outcome, occupant, occupant_iou, occupant_row))
@@ -56,8 +36,8 @@ def _report_positions(status, matched_expected, matched_actual, expected_positio
 def _report_reclass(expected_index, count, slot_row, indices, distances, gallery_label_id, expected_label_id, off1, status, outcome, seen_row,
                     seen_distance):
     what = 'cvpce_report_reclass'
-    _typed(what, (distances, seen_distance), (expected_index, count, slot_row, gallery_label_id, expected_label_id, off1, status, outcome, seen_row),
-           (indices,))
+    typed(what, f32=(distances, seen_distance), i64=(indices,),
+          i32=(expected_index, count, slot_row, gallery_label_id, expected_label_id, off1, status, outcome, seen_row))
     b, sum1 = status.numel(), outcome.numel()
     cap = expected_index.shape[1] if expected_index.dim() == 2 else 0
     if (off1.numel() != b + 1 or any(t.dim() != 2 or t.shape[0] != b or t.shape[1] != cap for t in (expected_index, slot_row))

@@ -3,22 +3,13 @@
 set; the case set has the properties the GPU tests rely on; the expected side's label ids; the kernels' header, signature table and
 torch ops stay apart from every other table and refuse CPU tensors; the switches."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import actuals_cases as ac
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_symbols(name):
-    text = open(os.path.join(ROOT, 'include', name)).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
 
 
 def _classifier(monkeypatch, annotations):
@@ -134,37 +125,13 @@ def test_expected_ids_are_equal_exactly_where_the_labels_are(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------------
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------
-OTHER_TABLES = ('SIGNATURES', 'EVAL_SIGNATURES', 'INPUT_SIGNATURES', 'PLANOGRAM_SIGNATURES', 'HOMOGRAPHY_SIGNATURES', 'LISTS_SIGNATURES',
-                'GALLERY_SIGNATURES', 'RECLASS_SIGNATURES', 'CLASSEVAL_SIGNATURES')
-OTHER_HEADERS = ('cvpce_amd.h', 'cvpce_amd_eval.h', 'cvpce_amd_input.h', 'cvpce_amd_planogram.h', 'cvpce_amd_homography.h', 'cvpce_amd_lists.h',
-                 'cvpce_amd_gallery.h', 'cvpce_amd_reclass.h', 'cvpce_amd_classeval.h')
-
-
 def test_actuals_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib, torch_ops_actuals
-    syms = _header_symbols('cvpce_amd_actuals.h')
-    assert syms == ['cvpce_actuals_count', 'cvpce_actuals_pack']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_actuals.h but not exported'
-    assert sorted(_lib.ACTUALS_SIGNATURES) == syms == sorted('cvpce_' + n for n in torch_ops_actuals.NAMES)
-    for table in OTHER_TABLES:
-        assert not set(syms) & set(getattr(_lib, table)) and not any('actuals' in s for s in getattr(_lib, table)), table
-    for header in OTHER_HEADERS:
-        assert not set(syms) & set(_header_symbols(header)), header
-    assert _header_symbols('cvpce_amd.h') == sorted(_lib.SIGNATURES)
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    assert abi.header_symbols('cvpce_amd_actuals.h') == ['cvpce_actuals_count', 'cvpce_actuals_pack']
 
 
 def test_actuals_ops_have_their_own_names_and_are_gpu_only():
-    from cvpce_amd import (torch_ops, torch_ops_actuals, torch_ops_classeval, torch_ops_eval, torch_ops_gallery, torch_ops_homography,
-                           torch_ops_input, torch_ops_planogram, torch_ops_reclass)
-    assert torch_ops_actuals.NAMES == ['actuals_count', 'actuals_pack']
-    for other in (torch_ops, torch_ops_classeval, torch_ops_eval, torch_ops_gallery, torch_ops_homography, torch_ops_input, torch_ops_planogram,
-                  torch_ops_reclass):
-        assert not set(torch_ops_actuals.NAMES) & set(other.NAMES) and not any('actuals' in n for n in other.NAMES)
-    for name in torch_ops_actuals.NAMES:
-        assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA')
-        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')
+    from cvpce_amd import torch_ops_actuals  # noqa: F401  (registers the ops; names and keys: test_abi_mirror_cpu.py)
     i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
     with pytest.raises(NotImplementedError, match='CPU'):
         torch.ops.cvpce_amd.actuals_count(torch.zeros(1, 2, 4), i32(1), i32(1))

@@ -4,22 +4,16 @@ the model's records, the kernel's header, signature table and torch op stay apar
 switch."""
 import ctypes
 import os
-import re
 import types
 
 import pytest
 import torch
 
+import abi
 import classeval_cases as cc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNN = (1, 2, 4, 9)          # 9 > K = 4
-
-
-def _header_symbols(name):
-    text = open(os.path.join(ROOT, 'include', name)).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
 
 
 def _case(seed):
@@ -104,43 +98,18 @@ def test_the_report_is_the_references():
 # ---------------------------------------------------------------------------------------------------------------------
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------
-OTHER_TABLES = ('SIGNATURES', 'EVAL_SIGNATURES', 'INPUT_SIGNATURES', 'PLANOGRAM_SIGNATURES', 'HOMOGRAPHY_SIGNATURES', 'LISTS_SIGNATURES',
-                'GALLERY_SIGNATURES', 'RECLASS_SIGNATURES')
-OTHER_HEADERS = ('cvpce_amd.h', 'cvpce_amd_eval.h', 'cvpce_amd_input.h', 'cvpce_amd_planogram.h', 'cvpce_amd_homography.h', 'cvpce_amd_lists.h',
-                 'cvpce_amd_gallery.h', 'cvpce_amd_reclass.h')
-
-
 def test_classeval_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib, torch_ops_classeval
-    syms = _header_symbols('cvpce_amd_classeval.h')
-    assert syms == ['cvpce_classeval_rank']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_classeval.h but not exported'
-    assert sorted(_lib.CLASSEVAL_SIGNATURES) == syms == sorted('cvpce_' + n for n in torch_ops_classeval.NAMES)
-    assert _lib.lib.cvpce_classeval_rank.argtypes == _lib.CLASSEVAL_SIGNATURES['cvpce_classeval_rank'][1]        # (the table is bound)
-    for table in OTHER_TABLES:
-        assert not set(syms) & set(getattr(_lib, table)) and not any('classeval' in s for s in getattr(_lib, table)), table
-    for header in OTHER_HEADERS:
-        assert not set(syms) & set(_header_symbols(header)), header
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    assert abi.header_symbols('cvpce_amd_classeval.h') == ['cvpce_classeval_rank']
 
 
 def test_the_pinned_header_and_names_are_unchanged():
-    from cvpce_amd import _lib, torch_ops
-    # the inference header mirrors SIGNATURES and torch_ops.NAMES, as tests/test_boundary_cpu.py pins them; none of the three knows the new entry
-    assert _header_symbols('cvpce_amd.h') == sorted(_lib.SIGNATURES)
-    assert not any('classeval' in n for n in torch_ops.NAMES)
-    assert 'classeval' not in open(os.path.join(ROOT, 'include', 'cvpce_amd.h')).read()
+    # the inference header does not know the new entry, not even in a comment (its symbols, table and op names: test_abi_mirror_cpu.py)
+    assert 'classeval' not in open(os.path.join(abi.INCLUDE, 'cvpce_amd.h')).read()
 
 
 def test_classeval_op_has_its_own_name_and_is_gpu_only():
-    from cvpce_amd import (torch_ops, torch_ops_classeval, torch_ops_eval, torch_ops_gallery, torch_ops_homography, torch_ops_input,
-                           torch_ops_planogram, torch_ops_reclass)
-    assert torch_ops_classeval.NAMES == ['classeval_rank']
-    for other in (torch_ops, torch_ops_eval, torch_ops_gallery, torch_ops_homography, torch_ops_input, torch_ops_planogram, torch_ops_reclass):
-        assert not set(torch_ops_classeval.NAMES) & set(other.NAMES) and not any('classeval' in n for n in other.NAMES)
-    assert torch._C._dispatch_has_kernel_for_dispatch_key('cvpce_amd::classeval_rank', 'CUDA')
-    assert not torch._C._dispatch_has_kernel_for_dispatch_key('cvpce_amd::classeval_rank', 'CPU')
+    from cvpce_amd import torch_ops_classeval  # noqa: F401  (registers the op; name and keys: test_abi_mirror_cpu.py)
     with pytest.raises(NotImplementedError, match='CPU'):
         torch.ops.cvpce_amd.classeval_rank(torch.zeros(2, 3, dtype=torch.int64), torch.zeros(4, dtype=torch.int32), torch.zeros(2, dtype=torch.int32),
                                            torch.zeros(2, 2, dtype=torch.int32))

@@ -3,19 +3,12 @@
 its own, and the host packing of a byte pass (`production.pack_gallery_bytes`) lays the images out back to back."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_symbols(name):
-    text = open(os.path.join(ROOT, 'include', name)).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
+import abi
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -120,27 +113,12 @@ def test_gallery_float_is_the_contract():
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------------------
 def test_library_exports_the_gallery_symbol():
-    from cvpce_amd import _lib
-    syms = header_symbols('cvpce_amd_gallery.h')
-    assert syms == ['cvpce_gallery_pack_u8']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_gallery.h but not exported'
-    assert sorted(_lib.GALLERY_SIGNATURES) == syms, 'ctypes signature table out of sync with the header'
-    for table in (_lib.SIGNATURES, _lib.EVAL_SIGNATURES, _lib.INPUT_SIGNATURES, _lib.PLANOGRAM_SIGNATURES, _lib.HOMOGRAPHY_SIGNATURES,
-                  _lib.LISTS_SIGNATURES):
-        assert not set(_lib.GALLERY_SIGNATURES) & set(table)
-    for other in ('cvpce_amd.h', 'cvpce_amd_eval.h', 'cvpce_amd_input.h', 'cvpce_amd_planogram.h', 'cvpce_amd_homography.h', 'cvpce_amd_lists.h'):
-        assert not set(syms) & set(header_symbols(other))
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    assert abi.header_symbols('cvpce_amd_gallery.h') == ['cvpce_gallery_pack_u8']
 
 
 def test_gallery_op_matches_the_header_on_the_gpu_only():
-    from cvpce_amd import torch_ops, torch_ops_input, torch_ops_gallery
-    assert sorted('cvpce_' + n for n in torch_ops_gallery.NAMES) == header_symbols('cvpce_amd_gallery.h')
-    assert not set(torch_ops_gallery.NAMES) & (set(torch_ops.NAMES) | set(torch_ops_input.NAMES))
-    for name in torch_ops_gallery.NAMES:
-        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')
-        assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA')
+    from cvpce_amd import torch_ops_gallery  # noqa: F401  (registers the op; name and keys: test_abi_mirror_cpu.py)
     with pytest.raises(NotImplementedError, match='CPU'):
         torch.ops.cvpce_amd.gallery_pack_u8(torch.zeros(48, dtype=torch.uint8), torch.zeros(1, 3, dtype=torch.int32),
                                             torch.zeros(3, 257, dtype=torch.bfloat16), torch.zeros(1, 4, 4, 4, dtype=torch.bfloat16), 0,

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 import gaussian_cases as gc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,16 +113,12 @@ def test_model_equals_the_reference_losses(golden):
 
 
 def test_header_table_and_op_names():
-    from cvpce_amd import _lib, torch_ops, torch_ops_gaussians as G
-    text = open(os.path.join(ROOT, 'include', 'cvpce_amd_gaussians.h')).read()
-    declared = re.findall(r'^(?:int|size_t)\s+(cvpce_\w+)\s*\(', text, re.M)
-    assert declared == list(_lib.GAUSSIANS_SIGNATURES) == ['cvpce_gauss_kant_table', 'cvpce_gauss_targets', 'cvpce_gauss_loss_workspace_bytes',
-                                                           'cvpce_gauss_loss']
-    for name in declared:
-        args = re.search(name + r'\((.*?)\);', text, re.S).group(1)
-        assert len(_lib.GAUSSIANS_SIGNATURES[name][1]) == len(re.sub(r'/\*.*?\*/', '', args).split(',')), name
-    assert G.NAMES == ['gauss_kant_table', 'gauss_targets', 'gauss_loss'] and len(torch_ops.NAMES) == 36
-    assert not set(G.NAMES) & set(torch_ops.NAMES)
+    """(exported, bound, compared argument by argument, the op names: test_abi_mirror_cpu.py)"""
+    from cvpce_amd import _lib, torch_ops_gaussians as G
+    header = 'cvpce_amd_gaussians.h'
+    text = open(os.path.join(abi.INCLUDE, header)).read()
+    assert list(abi.declarations(header)) == list(_lib.HEADERS[header]) == ['cvpce_gauss_kant_table', 'cvpce_gauss_targets',
+                                                                            'cvpce_gauss_loss_workspace_bytes', 'cvpce_gauss_loss']
     for macro, value in (('CVPCE_GAUSS_TILE', G.TILE), ('CVPCE_GAUSS_LIST', G.LIST), ('CVPCE_GAUSS_GEOM', G.GEOM)):
         assert int(re.search(rf'#define {macro} (\d+)', text).group(1)) == value
     assert G.METHODS == gc.METHODS and G.JOINS == gc.JOINS

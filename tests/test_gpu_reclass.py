@@ -418,14 +418,14 @@ WINDOW_PARENT = {
 
 def _device_actuals(cuda, clf, actuals):
     """host detections as the pack `actuals_pack` would leave of them: a label's gallery row is the first that carries it"""
-    from cvpce_amd import planograms_device as pd
+    from cvpce_amd import planograms_device as pd, staging
     n2 = [len(a['labels']) for a in actuals]
     rows = [clf.annotations.index(l) for a in actuals for l in a['labels']]
     i32 = lambda values: torch.tensor(values, dtype=torch.int32, device=cuda)
     boxes = torch.cat([a['boxes'] for a in actuals]).to(torch.float32).contiguous().to(cuda)
     thresh = torch.stack([pd.graph_threshold(a['boxes'].to(torch.float32), 0.5) for a in actuals]).to(torch.float32).to(cuda)
     return pd.DeviceActuals(boxes, i32(rows), i32([clf.label_ids[clf.annotations[r]] for r in rows]), thresh, i32([0] * len(n2)),
-                            i32(pd._offsets(n2)), n2, 0.5)
+                            i32(staging.offsets(n2)), n2, 0.5)
 
 
 def _window_digest(verdicts, reports):

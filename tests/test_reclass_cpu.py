@@ -2,23 +2,15 @@
 (tests/reclass_cases.py) equals `PlanogramComparator._finish`'s own torch lines on random and edge inputs; the kernels' header,
 signature table and torch ops stay apart from every other table and refuse CPU tensors; the switches and the label-id space."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import reclass_cases as rc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((480, 640), (333, 517), (1, 1), (7, 1000), (2161, 3847))          # (h, w): not multiples of anything
-
-
-def _header_symbols(name):
-    text = open(os.path.join(ROOT, 'include', name)).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(cvpce_[a-z0-9_]+)\s*\(', text)))
 
 
 def _bits(t):
@@ -101,29 +93,12 @@ def test_model_verdict_equals_the_loop_of_finish():
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------
 def test_reclass_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib
-    syms = _header_symbols('cvpce_amd_reclass.h')
-    assert syms == ['cvpce_reclass_plan', 'cvpce_reclass_verdict']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_reclass.h but not exported'
-    assert sorted(_lib.RECLASS_SIGNATURES) == syms, 'reclass signature table out of sync with the header'
-    for table in (_lib.SIGNATURES, _lib.EVAL_SIGNATURES, _lib.INPUT_SIGNATURES, _lib.PLANOGRAM_SIGNATURES, _lib.HOMOGRAPHY_SIGNATURES,
-                  _lib.LISTS_SIGNATURES, _lib.GALLERY_SIGNATURES):
-        assert not set(syms) & set(table) and not any('reclass' in s for s in table)
-    for header in ('cvpce_amd.h', 'cvpce_amd_eval.h', 'cvpce_amd_input.h', 'cvpce_amd_planogram.h', 'cvpce_amd_homography.h', 'cvpce_amd_lists.h',
-                   'cvpce_amd_gallery.h'):
-        assert not set(syms) & set(_header_symbols(header)), header
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    assert abi.header_symbols('cvpce_amd_reclass.h') == ['cvpce_reclass_plan', 'cvpce_reclass_verdict']
 
 
 def test_reclass_ops_have_their_own_names_and_are_gpu_only():
-    from cvpce_amd import torch_ops, torch_ops_eval, torch_ops_gallery, torch_ops_homography, torch_ops_input, torch_ops_planogram, torch_ops_reclass
-    assert torch_ops_reclass.NAMES == ['reclass_plan', 'reclass_verdict']
-    for other in (torch_ops, torch_ops_eval, torch_ops_gallery, torch_ops_homography, torch_ops_input, torch_ops_planogram):
-        assert not set(torch_ops_reclass.NAMES) & set(other.NAMES) and not any('reclass' in n for n in other.NAMES)
-    for name in torch_ops_reclass.NAMES:
-        assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA')
-        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')
+    from cvpce_amd import torch_ops_reclass  # noqa: F401  (registers the ops; names and keys: test_abi_mirror_cpu.py)
     i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
     with pytest.raises(NotImplementedError, match='CPU'):
         torch.ops.cvpce_amd.reclass_plan(i32(1), i32(2), torch.zeros(2, 4), i32(2), i32(1, 3), torch.zeros(1, 2, 4), i32(1, 2), i32(1))

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi
 import render_cases as rc
 import report_cases as rp
 from test_report_cpu import StubClassifier, _scenes, host_ops  # noqa: F401  (host_ops: a fixture)
@@ -231,21 +232,19 @@ def test_an_oversize_atlas_is_refused_by_the_size_arithmetic():
 # the header, the binding and the op
 # ---------------------------------------------------------------------------------------------------------------------
 def test_render_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib, torch_ops_render as R
-    text = open(os.path.join(ROOT, 'include', 'cvpce_amd_render.h')).read()
-    assert re.findall(r'\bint\s+(cvpce_\w+)\s*\(', text) == ['cvpce_render_canvases'] == list(_lib.RENDER_SIGNATURES)
+    """(exported, bound, compared argument by argument and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    from cvpce_amd import torch_ops_render as R
+    text = open(os.path.join(abi.INCLUDE, 'cvpce_amd_render.h')).read()
+    assert list(abi.declarations('cvpce_amd_render.h')) == ['cvpce_render_canvases']
     defines = dict(re.findall(r'#define\s+(CVPCE_RENDER_\w+)\s+\(?(-?\d+)\)?\s', text))
     assert (int(defines['CVPCE_RENDER_TILE_W']), int(defines['CVPCE_RENDER_TILE_H'])) == (R.TILE_W, R.TILE_H) == (rc.TILE_W, rc.TILE_H)
     assert int(defines['CVPCE_RENDER_MAX_SIDE']) == R.MAX_SIDE == rc.MAX_SIDE and int(defines['CVPCE_RENDER_TABLE_COLS']) == R.TABLE_COLS == rc.COLS
     assert (int(defines['CVPCE_RENDER_SRC_NONE']), int(defines['CVPCE_RENDER_SRC_BASE'])) == (R.SRC_NONE, R.SRC_BASE) == (rc.SRC_NONE, rc.SRC_BASE)
     assert int(defines['CVPCE_RENDER_CHUNK']) == rc.CHUNK and R.tiles(17, 65) == 4 == rc.tiles(17, 65)
-    assert len(_lib.RENDER_SIGNATURES['cvpce_render_canvases'][1]) == len(re.search(r'cvpce_render_canvases\((.*?)\);', text, re.S).group(1).split(','))
 
 
 def test_the_render_op_has_its_own_name_and_is_gpu_only():
-    from cvpce_amd import torch_ops, torch_ops_report, torch_ops_render
-    assert torch_ops_render.NAMES == ['render_canvases']
-    assert 'render_canvases' not in torch_ops.NAMES and 'render_canvases' not in torch_ops_report.NAMES
+    from cvpce_amd import torch_ops_render  # noqa: F401  (registers the op; name and keys: test_abi_mirror_cpu.py)
     z = lambda *s, dt=torch.int32: torch.zeros(*s, dtype=dt)
     with pytest.raises((NotImplementedError, RuntimeError)):
         torch.ops.cvpce_amd.render_canvases(z(1, 10, dt=torch.int64), 1, None, z(0, 4, dt=torch.float32), z(0), z(0), z(0), z(0, dt=torch.uint8), z(0, 3),

@@ -4,14 +4,15 @@ compliance is `compare`'s value on every status branch; the kernels' header, sig
 other table and refuse CPU tensors; the command line has the option."""
 import ctypes
 import json
+import os
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import reclass_cases as rc
 import report_cases as rp
-from test_reclass_cpu import _header_symbols
 
 GALLERY = 24
 
@@ -237,32 +238,18 @@ def test_the_edge_scenes_hold_what_they_are_named_for():
 # boundary
 # ---------------------------------------------------------------------------------------------------------------------
 def test_report_header_is_exported_and_mirrored():
-    from cvpce_amd import _lib
-    syms = _header_symbols('cvpce_amd_report.h')
-    assert syms == ['cvpce_report_positions', 'cvpce_report_reclass']
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(lib, s), f'{s} declared in include/cvpce_amd_report.h but not exported'
-    assert sorted(_lib.REPORT_SIGNATURES) == syms, 'report signature table out of sync with the header'
-    for table in (_lib.SIGNATURES, _lib.EVAL_SIGNATURES, _lib.INPUT_SIGNATURES, _lib.PLANOGRAM_SIGNATURES, _lib.HOMOGRAPHY_SIGNATURES,
-                  _lib.LISTS_SIGNATURES, _lib.GALLERY_SIGNATURES, _lib.RECLASS_SIGNATURES, _lib.CLASSEVAL_SIGNATURES, _lib.ACTUALS_SIGNATURES):
-        assert not set(syms) & set(table) and not any('report' in s for s in table)
+    """(exported, bound and disjoint from the other headers: test_abi_mirror_cpu.py)"""
+    assert abi.header_symbols('cvpce_amd_report.h') == ['cvpce_report_positions', 'cvpce_report_reclass']
     from cvpce_amd import planograms, torch_ops_report
     codes = ('DETECTED', 'RECOVERED', 'MISSING', 'OUT_OF_VIEW', 'UNCHECKED', 'PENDING')
-    text = open(_lib.os.path.join(_lib.os.path.dirname(_lib._HERE), 'include', 'cvpce_amd_report.h')).read()
+    text = open(os.path.join(abi.INCLUDE, 'cvpce_amd_report.h')).read()
     for value, name in enumerate(codes):
         assert f'#define CVPCE_REPORT_{name} {value} ' in text
         assert getattr(torch_ops_report, name) == getattr(planograms, name) == getattr(rp, name) == value
 
 
 def test_report_ops_have_their_own_names_and_are_gpu_only():
-    from cvpce_amd import torch_ops, torch_ops_actuals, torch_ops_homography, torch_ops_planogram, torch_ops_reclass, torch_ops_report
-    assert torch_ops_report.NAMES == ['report_positions', 'report_reclass']
-    for other in (torch_ops, torch_ops_actuals, torch_ops_homography, torch_ops_planogram, torch_ops_reclass):
-        assert not set(torch_ops_report.NAMES) & set(other.NAMES) and not any('report' in n for n in other.NAMES)
-    for name in torch_ops_report.NAMES:
-        assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA')
-        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CPU')
+    from cvpce_amd import torch_ops_report  # noqa: F401  (registers the ops; names and keys: test_abi_mirror_cpu.py)
     i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
     for rows in (None, i32(3)):
         with pytest.raises(NotImplementedError, match='CPU'):

@@ -76,13 +76,13 @@ def time_device(scenes, thresholds, device, batch=8, rounds=5):
 
 
 def time_kernel(scenes, thresholds, device, launches):
-    from cvpce_amd import device_metrics
+    from cvpce_amd import device_metrics, staging
     thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float32, device=device)
     dev = [[x.to(device) for x in col] for col in scenes]
     m = device_metrics._match_packed(dev[0], dev[1], dev[2], thr)
     pred, tgt = torch.cat(dev[1]), torch.cat(dev[0])
-    poff = torch.tensor(device_metrics._offsets(m['n_pred']), dtype=torch.int32, device=device)
-    toff = torch.tensor(device_metrics._offsets(m['n_tgt']), dtype=torch.int32, device=device)
+    poff = torch.tensor(staging.offsets(m['n_pred']), dtype=torch.int32, device=device)
+    toff = torch.tensor(staging.offsets(m['n_tgt']), dtype=torch.int32, device=device)
     first, tp = torch.empty_like(m['first']), torch.zeros_like(m['tp'])
     launch = lambda: torch.ops.cvpce_amd.eval_match_detections(pred, poff, m['rank'], None, tgt, toff, None, thr, max(m['n_tgt']), first, tp)
     for _ in range(5):

@@ -42,7 +42,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from cvpce_amd import planograms, planograms_device as pd, production, synthetic     # noqa: E402
+from cvpce_amd import planograms, planograms_device as pd, production, staging, synthetic     # noqa: E402
 
 
 def scenes(rows, cols, batch):
@@ -97,7 +97,7 @@ def time_device(pairs, launches):
     sizes = [len(l) for _, l in items]
     dev = nbr.device
     boxes = torch.cat([b for b, _ in items]).to(dev)
-    offsets = torch.tensor(pd._offsets(sizes), dtype=torch.int32, device=dev)
+    offsets = torch.tensor(staging.offsets(sizes), dtype=torch.int32, device=dev)
     thresh = torch.stack([pd.graph_threshold(b, 0.5) for b, _ in items]).float().to(dev)
     out = [torch.empty_like(t) for t in (nbr, weight, stamp)]
     g_ms = events(lambda: torch.ops.cvpce_amd.planogram_graphs(boxes, offsets, thresh, min(sizes), max(sizes), *out), launches)
