@@ -76,6 +76,7 @@ SIGNATURES = {
     'cvpce_match_set_core': (c_int, [c_int, c_int, c_int]),
     'cvpce_match_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_longlong)]),
     'cvpce_probe_l2_stream': (c_int, [_vp, c_longlong, c_int, _fp, c_int, _vp]),
+    'cvpce_probe_lds_fill': (c_int, [ctypes.c_uint, _ip, c_int, _vp]),
     'cvpce_probe_mfma_bf16': (c_int, [c_int, c_int, _vp, _fp, c_int, _vp]),
     'cvpce_match_topk': (c_int, [_vp, _vp, _fp, _fp, c_int, c_int, c_int, c_int, c_int, _vp, c_size_t, _vp, _fp, _vp]),
 }

@@ -166,6 +166,15 @@ __global__ __launch_bounds__(256, 1) void gauss_subnet_kernel(GaussSubnetArgs a)
         if (lane < 16) { bl[64 + lane] = a.b3 ? a.b3[lane] : 0.f; bl[80 + lane] = a.b4 ? a.b4[lane] : 0.f; }
     }
     const float bias5 = a.b5 ? a.b5[0] : 0.f;
+    // Pixel slots 32 .. 35 of the eight mid-ring rows are never stored to, and the unused columns of layers 2 and 3 (X + 28 ..) read
+    // slots 32 and 33.  Their values are dropped -- but column group 1's pixel l16 shares an MFMA column with group 0's in the 16 -> 1
+    // layer, under a weight row of zeros, and 0 x NaN is NaN: whatever bit patterns an earlier kernel left in LDS there must not be
+    // non-finite.  Zeros, once: 8 rows x 256 B, two 16-byte stores per lane (the two rings are adjacent).
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int c = lane + 64 * i;                                     // 16-byte chunk c & 15 of ring row c >> 4
+        *reinterpret_cast<u32x4*>(wbase + GS_L1_OFF + (c >> 4) * GS_MID_SLOT + 32 * 64 + (c & 15) * 16) = u32x4{0u, 0u, 0u, 0u};
+    }
 
     // ---- fragment addresses (LDS byte addresses of this lane inside ring slot 0; a slot base and, for column group 1, 1 024 are added).
     // x ring: L1 column group g, tap column kw reads the stored pixel under logical column X - 3 + 16 g + l16 + kw: patch pixel

@@ -105,3 +105,23 @@ extern "C" int cvpce_probe_l2_stream(const void* buf, long long bytes, int iters
     hipLaunchKernelGGL(l2_stream_probe_kernel, dim3(workgroups), dim3(512), 0, (hipStream_t)stream, (const u32x4*)buf, (unsigned)(bytes / 16), iters, sink);
     return cvpce_check_launch();
 }
+
+// Test probe: leaves one bit pattern in the whole LDS of the compute units its workgroups land on (160 KiB a workgroup, so one
+// per compute unit at a time).  LDS is not cleared between kernels: a kernel whose result depends on LDS it never wrote -- a ring slot
+// only read by columns that are dropped later, say -- is right as long as an earlier kernel left finite values there, and wrong after
+// one that left 0xFFFF (a NaN in every float type).  sink[workgroup] = 1 once its fill is done.
+#define LDS_FILL_BYTES (160 * 1024)
+__global__ __launch_bounds__(256, 1) void lds_fill_kernel(unsigned pattern, int* __restrict__ sink) {
+    extern __shared__ unsigned fill_lds[];
+    volatile unsigned* p = fill_lds;
+    for (int i = threadIdx.x; i < LDS_FILL_BYTES / 4; i += 256) p[i] = pattern;
+    __syncthreads();
+    if (threadIdx.x == 0) sink[blockIdx.x] = p[LDS_FILL_BYTES / 4 - 1] == pattern ? 1 : 0;
+}
+
+extern "C" int cvpce_probe_lds_fill(unsigned pattern, int* sink, int workgroups, void* stream) {
+    if (!sink || workgroups < 1) return CVPCE_ERR_ARG;
+    if (!cvpce_smem_attr_done<lds_fill_kernel>((const void*)lds_fill_kernel, LDS_FILL_BYTES)) return CVPCE_ERR_LAUNCH;
+    hipLaunchKernelGGL(lds_fill_kernel, dim3(workgroups), dim3(256), LDS_FILL_BYTES, (hipStream_t)stream, pattern, sink);
+    return cvpce_check_launch();
+}

@@ -1216,6 +1216,16 @@ def probe_mfma_bf16(shape, seconds=2.0, iters=20000, workgroups=256):
     return last        # the rate of the LAST group of launches: the settled clock, not the cold-start burst
 
 
+def probe_lds_fill(pattern, workgroups=2048):
+    """Leave the 32-bit `pattern` in the LDS of the compute units (csrc/probe.hip: 160 KiB a workgroup, one per compute unit at a time,
+    `workgroups` of them -- several rounds over the chip) -> how many workgroups ran.  For tests: no kernel's result may depend on LDS
+    it did not write."""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    sink = torch.zeros(workgroups, dtype=torch.int32, device=dev)
+    T.probe_lds_fill(int(pattern), sink, int(workgroups))
+    return int(sink.sum())
+
+
 def probe_l2_stream(mib=2, seconds=1.0, workgroups=512, iters=64):
     """TB/s at which all CUs together stream one L2-resident buffer of `mib` MiB into registers (csrc/probe.hip)."""
     import time

@@ -392,4 +392,9 @@ def _probe_l2_stream(buf, iters, sink, workgroups):
     check(lib.cvpce_probe_l2_stream(_p(buf), buf.numel() * buf.element_size(), iters, _p(sink), workgroups, _stream()), 'probe_l2_stream')
 
 
+@_op('probe_lds_fill(int pattern, Tensor(a!) sink, int workgroups) -> ()')
+def _probe_lds_fill(pattern, sink, workgroups):
+    check(lib.cvpce_probe_lds_fill(pattern, _p(sink), workgroups, _stream()), 'probe_lds_fill')
+
+
 T = torch.ops.cvpce_amd

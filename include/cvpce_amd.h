@@ -443,6 +443,11 @@ int cvpce_probe_mfma_bf16(int shape, int iters, const void* operands, float* sin
  * kernels can stream weights from L2 into registers.  Bytes moved = workgroups * iters * bytes.  sink: workgroups * 512 floats. */
 int cvpce_probe_l2_stream(const void* buf, long long bytes, int iters, float* sink, int workgroups, void* stream);
 
+/* Test probe: `workgroups` x 256 threads each fill the 160 KiB of LDS of the compute unit they run on with the 32-bit `pattern`
+ * (LDS is not cleared between kernels: what the next kernel finds in LDS it does not write).  sink: workgroups ints, 1 per
+ * workgroup that ran.  No result of any other function may depend on the pattern. */
+int cvpce_probe_lds_fill(unsigned pattern, int* sink, int workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@ and the only roundings left are the 16-bit stores.  The reference is float64 wit
   coarse (bf16)   i/8,  |i| <= 8     j/64,  |j| <= 4     k/8, |k| <= 8    2^-9
   fine   (fp16)   i/32, |i| <= 32    j/256, |j| <= 16    k/8, |k| <= 8    2^-13
   chain           i/8,  |i| <= m     +-1 (first: +-2^-3 / x's quantum)   k/8   2^-3 in every layer
+  the edges of fp16, on the recipes above (single layers: edge_scales; chains: EDGE_CHAINS; the table in front of EDGE_SINGLES has the rest):
+  big  (both)     the recipe's       the recipe's x 2^s  k 2^12; i 32, |i| <= 2047 (bf16: i 256, |i| <= 255)   the recipe's x 2^s
+  subw (fp16)     the fine recipe's  fine x 2^-14        (k/8) 2^-14                                           2^-27
+  subx (fp16)     i 2^-24, |i| <= 32 fine x 2^5          (k/8) 2^-14                                           2^-27
+  chain big, sub  x 2^xpow           +-2^p_i in layer i  k quanta of the layer's sums                          2^-3 x 2^(xpow + p_0 + .. + p_i)
 
 (The coarse recipe under fp16 would round almost nothing: 11 significant bits hold nearly every sum.)  In a fused chain the quantum of a
 layer's input is the quantum of the sums before it -- rounding a multiple of q to 16 bits leaves a multiple of q -- so the weights
@@ -24,7 +29,10 @@ budget.
 
 Budget: for every accumulation of a case, sum |products| + |bias| + |residual| in units of that layer's quantum is at most 2^22 -- fp32
 holds 2^24, the factor 4 is margin for a kernel that keeps more than one accumulator chain.  Single layers use the analytic worst case
-K max|x| max|w|; chains run every layer on the absolute values of its (rounded) input in float64.
+K max|x| max|w|; chains run every layer on the absolute values of its (rounded) input in float64.  The bias and the residual are
+checked on the grid of their own layer's sums, whatever power of two the regime put on it; a residual that sits on a finer grid than the
+sums (Layer.rq: +-65504 = 2047 x 32) makes that grid the quantum the accumulation is counted in; and behind an fp16 store a grid finer
+than 2^-24 is 2^-24 again (nothing finer is stored).
 """
 import math
 import zlib
@@ -37,6 +45,8 @@ BF, H16 = torch.bfloat16, torch.float16
 DTYPES = (BF, H16)
 IDS = {BF: 'bf16', H16: 'fp16'}
 F16_MAX = 65504.0
+F16_MIN_NORMAL, F16_SUB_Q = 2.0 ** -14, 2.0 ** -24       # below the first fp16 is subnormal, on multiples of the second
+STORE_MUTANTS = ('noclamp', 'clamp', 'flush', 'trunc')
 BUDGET_LOG2 = 22.0
 RECIPE = {BF: dict(xm=8, xq=2.0 ** -3, wm=4, wq=2.0 ** -6), H16: dict(xm=32, xq=2.0 ** -5, wm=16, wq=2.0 ** -8)}
 BIAS_Q = 2.0 ** -3
@@ -60,42 +70,73 @@ def signs(shape, q, g):
     return ((order < k // 2).double() * 2 - 1).reshape(tuple(shape)) * q
 
 
-def r16(t, dt):
+def ftz(t):
+    """fp16 subnormals flushed to zero"""
+    return torch.where(t.abs() < F16_MIN_NORMAL, torch.zeros_like(t), t)
+
+
+def r16(t, dt, model=None):
     """the kernels' 16-bit store on a tensor of exactly representable fp32 values held in any float type: fp16 clamps to +-65504, then
-    round-to-nearest-even; returned in t's type"""
+    round-to-nearest-even (also below 2^-14, where the quantum is 2^-24); returned in t's type.  model: a WRONG store, for
+    test_edge_mutants_differ -- 'noclamp' (fp16 overflows to infinity), 'clamp' (bf16 with fp16's clamp), 'flush' (a subnormal result
+    becomes zero), 'trunc' (below 2^-14 the value is cut towards zero instead of rounded)"""
+    assert model in STORE_MUTANTS + (None,)
     v = t.float()
-    assert torch.equal(v.to(t.dtype), t), 'a value to be stored is not an fp32 value: the case is over its budget'
-    if dt == H16:
+    known = ~t.isnan()                          # (behind a store without its clamp: infinity times zero)
+    assert torch.equal(v.to(t.dtype)[known], t[known]), 'a value to be stored is not an fp32 value: the case is over its budget'
+    if (dt == H16 and model != 'noclamp') or model == 'clamp':
         v = v.clamp(-F16_MAX, F16_MAX)
-    return v.to(dt).to(t.dtype)
+    out = v.to(dt).to(t.dtype)
+    if model == 'flush':
+        out = ftz(out)
+    elif model == 'trunc':
+        out = torch.where(t.abs() < F16_MIN_NORMAL, torch.trunc(t.double() / F16_SUB_Q).to(t.dtype) * F16_SUB_Q, out)
+    return out
 
 
 class Layer:
     """One accumulation and what the kernel does with it: conv(w, stride, pad) over the (2x nearest-upsampled if in_up) input + bias
     + residual ('same' size or stored at half size and nearest-upsampled), ReLU if act, one 16-bit store unless f32, then a max-pool
-    (k, stride, pad) of the stored values.  wq: the quantum of the weights."""
+    (k, stride, pad) of the stored values.  wq: the quantum of the weights.  rq: the quantum of the residual where it is not on the
+    grid of the sums (a residual at +-65504 lies on 32); the accumulation then counts in the finer of the two."""
 
-    def __init__(self, w, b, wq, stride=1, pad=0, act=1, f32=False, in_up=0, pool=None, res=None):
-        self.w, self.b, self.wq, self.stride, self.pad, self.act, self.f32, self.in_up, self.pool, self.res = w, b, wq, stride, pad, act, f32, in_up, pool, res
+    def __init__(self, w, b, wq, stride=1, pad=0, act=1, f32=False, in_up=0, pool=None, res=None, rq=None):
+        self.w, self.b, self.wq, self.stride, self.pad, self.act, self.f32, self.in_up, self.pool, self.res, self.rq = w, b, wq, stride, pad, act, f32, in_up, pool, res, rq
 
-    def accumulate(self, t, absolute=False):
-        ab = (lambda v: v.abs()) if absolute else (lambda v: v)
+    def but(self, **kw):
+        """a copy with some fields replaced"""
+        f = dict(w=self.w, b=self.b, wq=self.wq, stride=self.stride, pad=self.pad, act=self.act, f32=self.f32, in_up=self.in_up, pool=self.pool,
+                 res=self.res, rq=self.rq)
+        f.update(kw)
+        return Layer(**f)
+
+    def accumulate(self, t, absolute=False, flush=False):
+        """flush: the WRONG multiply of test_edge_mutants_differ -- the 16-bit operands (input, weights, residual) lose their fp16
+        subnormals before it"""
+        ab = (lambda v: v.abs()) if absolute else (ftz if flush else (lambda v: v))
         if self.in_up:
             t = F.interpolate(t, scale_factor=2.0, mode='nearest')
-        y = F.conv2d(ab(t), ab(self.w).to(t.dtype), ab(self.b).to(t.dtype) if self.b is not None else None, stride=self.stride, padding=self.pad)
+        bias = (self.b.abs() if absolute else self.b).to(t.dtype) if self.b is not None else None          # (fp32 in the kernels)
+        y = F.conv2d(ab(t), ab(self.w).to(t.dtype), bias, stride=self.stride, padding=self.pad)
         if self.res is not None:
             r = ab(self.res[:t.shape[0]]).to(t.dtype)
             y = y + (r if r.shape[-2:] == y.shape[-2:] else F.interpolate(r, size=y.shape[-2:], mode='nearest'))
         return y
 
-    def forward(self, t, dt):
-        """-> (what the next layer reads, the 16-bit values stored before the pool or None, the sums behind the activation they were rounded from)"""
-        y = sums = self.accumulate(t)
+    def forward(self, t, dt, mutant=None):
+        """-> (what the next layer reads, the 16-bit values stored before the pool or None, the sums behind the activation they were rounded from).
+        mutant: None | 'operands' (accumulate's flush) | 'input' (only the layer's input loses its subnormals) | a store model of r16
+        ('clamp' on an fp32 output clamps that)"""
+        if mutant == 'input':
+            t = ftz(t)
+        y = sums = self.accumulate(t, flush=mutant == 'operands')
         if self.act:
             y = sums = F.relu(y)
         stored = None
         if not self.f32:
-            y = stored = r16(y, dt)
+            y = stored = r16(y, dt, mutant if mutant in STORE_MUTANTS else None)
+        elif mutant == 'clamp':
+            y = y.clamp(-F16_MAX, F16_MAX)
         if self.pool:
             y = F.max_pool2d(y, *self.pool)
         return y, stored, sums
@@ -111,6 +152,16 @@ class Case:
         # the stored layers (indices into the 16-bit stores, in order) whose rounding this case is there to exercise: each must meet the
         # share conditions of test_exact_cases_cpu.py on its own.  Default: the last store
         self.covers = None
+        # None | 'big' | 'subw' | 'subx' | 'sub' (a chain): the edge of fp16 the case sits on
+        self.regime = None
+
+    def named_operands(self):
+        """the 16-bit operand tensors a sub regime names: their non-zero values are fp16 subnormals"""
+        if self.regime in ('subw', 'subx'):
+            return [self.layers[0].w] if self.regime == 'subw' else [self.x]
+        if self.regime == 'sub':                 # a chain: x or the first layer's weights, whichever the case put below 2^-14
+            return [t for t in (self.x, self.layers[0].w) if float(t.abs().max()) < F16_MIN_NORMAL]
+        return []
 
     def kept(self, t):
         return t[t.shape[0] - self.keep:]
@@ -118,18 +169,18 @@ class Case:
     def with_(self, x=None, layers=None):
         c = Case(self.family, self.name, self.dt, self.x if x is None else x, self.xq, self.layers if layers is None else layers, None)
         c.keep = min(self.keep, c.x.shape[0])
-        c.covers = self.covers
+        c.covers, c.regime = self.covers, self.regime
         return c
 
-    def reference(self, ftype=torch.float64, images=None, sums=False):
+    def reference(self, ftype=torch.float64, images=None, sums=False, mutant=None):
         """-> (final output NCHW in ftype, [stored 16-bit tensors]) over the kept images (or `images`, a slice of the batch); with
-        sums=True also the unrounded sums of the stored layers"""
+        sums=True also the unrounded sums of the stored layers.  mutant: (layer index, what Layer.forward does wrong there)"""
         sl = images if images is not None else slice(self.x.shape[0] - self.keep, None)
         t = self.x[sl].to(ftype)
         stored, unrounded = [], []
-        for L in self.layers:
+        for i, L in enumerate(self.layers):
             L = _sliced(L, sl)
-            t, s, y = L.forward(t, self.dt)
+            t, s, y = L.forward(t, self.dt, mutant[1] if mutant and mutant[0] == i else None)
             if s is not None:
                 stored.append(s)
                 unrounded.append(y)
@@ -146,10 +197,15 @@ class Case:
         for i, L0 in enumerate(self.layers):
             L = _sliced(L0, sl)
             _on_grid(L.w, L.wq, f'w{i}')
+            _on_grid(t, q, f'the input of layer {i}')          # (a store clamped to 65504 = 2047 x 32 stays on grids of 32 and finer only)
             q = q * L.wq
-            for name, v in (('bias', L.b), ('residual', L0.res)):
-                if v is not None:
-                    _on_grid(v, q, f'{name}{i}')
+            if L.b is not None:
+                _on_grid(L.b, q, f'bias{i}')
+            if L0.res is not None:
+                if L.rq is not None:
+                    q = min(q, L.rq)
+                _on_grid(L0.res, q, f'residual{i}')
+                assert torch.equal(L0.res.to(self.dt).double(), L0.res), f'residual{i} is not a value of the storage type'
             if len(self.layers) == 1:          # the analytic worst case: every product at the operands' maxima
                 k = L.w.shape[1] * L.w.shape[2] * L.w.shape[3]
                 total = k * float(self.x.abs().max()) * float(L.w.abs().max()) + (float(L.b.abs().max()) if L.b is not None else 0.0) \
@@ -159,13 +215,13 @@ class Case:
             worst = max(worst, total / q)
             if len(self.layers) > 1:
                 t = L.forward(t, self.dt)[0]
+            if self.dt == H16 and not L.f32:
+                q = max(q, F16_SUB_Q)               # (whatever fp16 stores is a multiple of 2^-24: a finer grid ends at the store)
         return math.log2(max(worst, 1.0)), q
 
 
 def _sliced(L, sl):
-    if L.res is None:
-        return L
-    return Layer(L.w, L.b, L.wq, L.stride, L.pad, L.act, L.f32, L.in_up, L.pool, L.res[sl])
+    return L if L.res is None else L.but(res=L.res[sl])
 
 
 def _on_grid(t, q, what):
@@ -194,28 +250,64 @@ def covered(case):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # builders
 # ---------------------------------------------------------------------------------------------------------------------------------
+PRODUCT_STD = {BF: 0.02468, H16: 0.02146}                # of one product x w on the recipe of the storage type
+BIG_RES = {BF: (255, 256.0), H16: (2047, 32.0)}          # a `big` residual: |i| <= m times q, all values of the storage type up to 65504
+BIG_BIAS_Q = 4096.0                                      # a `big` bias: k 2^12, |k| <= 8 -- on every grid of sums in use, and at most half of 65504
+REGIMES = ('big', 'subw', 'subx')
+
+
+def edge_scales(regime, dt, fan_in):
+    """-> (log2 of the factor on x, on the weights) of a single layer in an edge regime.  big: the sums' standard deviation stands at
+    about 65504 (17 at a fan-in of 576).  subw: 2^-14 makes every weight of the fine recipe an fp16 subnormal and the sums of 576 products
+    as well; a larger fan-in takes a smaller power, so that the sums stay below 2^-14.  subx: x on i 2^-24, and the weights times 2^5
+    (less at a larger fan-in): the sums lie on 2^-27, three bits below the subnormal quantum -- one store in 8 is an exact tie."""
+    over = max(0, math.floor(math.log2(math.sqrt(fan_in / 576.0))))
+    if regime == 'big':
+        return 0, round(math.log2(1.3 * F16_MAX / (math.sqrt(fan_in) * PRODUCT_STD[dt])))
+    assert dt == H16, 'bf16 has no subnormals within reach: its exponent range is that of fp32'
+    return {'subw': (0, -14 - over), 'subx': (-19, 5 - over)}[regime]
+
+
+def big_residual(shape, dt, g):
+    """a 16-bit residual for a `big` case: values of the storage type spread over +-65504 -- and in fp16 exactly +-65504 at one
+    position in 50: a sum added to a residual that already sits at the limit must still clamp"""
+    m, q = BIG_RES[dt]
+    r = grid(shape, m, q, g)
+    if dt == H16:
+        at_limit = torch.rand(tuple(shape), generator=g) < 0.02
+        sign = (torch.rand(tuple(shape), generator=g) < 0.5).double() * 2 - 1
+        r = torch.where(at_limit, sign * F16_MAX, r)
+    return r
+
+
 def single(family, name, dt, n, cin, h, w, cout, k, stride, pad, act=1, f32=False, in_up=0, pool=False, res=None, keep=None, bias=True,
-           wscale=None, salt=0):
+           wscale=None, salt=0, regime=None):
     """One conv layer on the recipe of its storage type.  res: None | 'same' | 'up' (stored at the output's half size, rounded up).
-    wscale: per-cout powers of two folded into the weights (a frozen batch norm's scale)."""
+    wscale: per-cout powers of two folded into the weights (a frozen batch norm's scale).  regime: None | 'big' | 'subw' | 'subx'
+    (edge_scales); the bias and the residual move with the grid of the sums."""
     rc = RECIPE[dt]
     g = seeded(family, name, *([salt] if salt else []))
-    x = grid((n, cin, h, w), rc['xm'], rc['xq'], g)
-    wgt = grid((cout, cin, k, k), rc['wm'], rc['wq'], g)
-    wq = rc['wq']
+    xs, ws = edge_scales(regime, dt, cin * k * k) if regime else (0, 0)
+    x = grid((n, cin, h, w), rc['xm'], rc['xq'], g) * 2.0 ** xs
+    wgt = grid((cout, cin, k, k), rc['wm'], rc['wq'], g) * 2.0 ** ws
+    xq, wq = rc['xq'] * 2.0 ** xs, rc['wq'] * 2.0 ** ws
     if wscale is not None:
         wgt = wgt * wscale[:, None, None, None]
         wq = wq * float(wscale.min())
-    b = grid((cout,), 8, BIAS_Q, g) if bias else None
+    b = grid((cout,), 8, BIG_BIAS_Q if regime == 'big' else BIAS_Q * 2.0 ** (xs + ws), g) if bias else None
     ho = ((h << in_up) + 2 * pad - k) // stride + 1
     wo = ((w << in_up) + 2 * pad - k) // stride + 1
-    r = None
-    if res == 'same':
-        r = grid((n, cout, ho, wo), 8, BIAS_Q, g)
-    elif res == 'up':
-        r = grid((n, cout, (ho + 1) // 2, (wo + 1) // 2), 8, BIAS_Q, g)
-    L = Layer(wgt, b, wq, stride, pad, act, f32, in_up, (2, 2, 0) if pool else None, r)
-    return Case(family, name, dt, x, rc['xq'], [L], keep)
+    r, rq = None, None
+    if res:
+        shape = (n, cout, ho, wo) if res == 'same' else (n, cout, (ho + 1) // 2, (wo + 1) // 2)
+        if regime == 'big':
+            r, rq = big_residual(shape, dt, g), BIG_RES[dt][1]
+        else:
+            r = grid(shape, 8, BIAS_Q, g) * 2.0 ** (xs + ws)
+    L = Layer(wgt, b, wq, stride, pad, act, f32, in_up, (2, 2, 0) if pool else None, r, rq)
+    case = Case(family, name, dt, x, xq, [L], keep)
+    case.regime = regime
+    return case
 
 
 CHAIN_X = {BF: (2, 2.0 ** -1), H16: (8, 2.0 ** -3)}      # |i| <= 2 halves | |i| <= 8 eighths: a chain's last store keeps a few bits more than it rounds to
@@ -233,30 +325,42 @@ def overflowing_x(dt, fan_in, bits_over):
     return m, BIAS_Q
 
 
-def chain(family, name, dt, n, cin, h, w, specs, keep=None, res_last=None, xgrid=None, first=None, covers=None):
+def chain(family, name, dt, n, cin, h, w, specs, keep=None, res_last=None, xgrid=None, first=None, covers=None, xpow=0, powers=None, regime=None, salt=0):
     """specs: per layer (cout, k, stride, pad, act, f32, in_up, pool) with weights +-1, the first layer's +-2^-3 / x's quantum; x:
     integers |i| <= xgrid[0] times xgrid[1] (default CHAIN_X of the storage type).  first: a RECIPE entry whose weight grid the first layer takes instead.
-    res_last: None | 'x' (the input itself) | 'sep' (a separate tensor on the k/8 grid) added in the last layer."""
-    g = seeded(family, name)
+    res_last: None | 'x' (the input itself) | 'sep' (a separate tensor on the k/8 grid) added in the last layer.
+    xpow, powers: x and layer i's weights take the factors 2^xpow and 2^powers[i] (the edge regimes); every bias, and a separate residual,
+    moves with the grid of its sums -- a `big` case's separate residual is big_residual's."""
+    g = seeded(family, name, *([salt] if salt else []))
     xm, xq = xgrid or CHAIN_X[dt]
-    x = grid((n, cin, h, w), xm, xq, g)
-    layers, c = [], cin
+    x = grid((n, cin, h, w), xm, xq, g) * 2.0 ** xpow
+    powers = powers or [0] * len(specs)
+    layers, c, total, qlog = [], cin, xpow, math.log2(xq) + xpow          # (qlog: log2 of the quantum of the sums)
     for i, (cout, k, stride, pad, act, f32, in_up, pool) in enumerate(specs):
         if i == 0 and first is not None:
             wgt, wq = grid((cout, c, k, k), first['wm'], first['wq'], g), first['wq']
         else:
             wq = BIAS_Q / xq if i == 0 else 1.0          # every layer's sums on the bias grid, 2^-3: a bias is at most 8 quanta of them
             wgt = signs((cout, c, k, k), wq, g)
-        b = grid((cout,), 8, BIAS_Q, g)
+        wgt, wq, total = wgt * 2.0 ** powers[i], wq * 2.0 ** powers[i], total + powers[i]
+        qlog += math.log2(wq)
+        b = grid((cout,), 8, BIAS_Q, g) * 2.0 ** total
         if cout == 1:
             b = b.abs()                            # (a single output channel with a negative bias would be dead behind its ReLU)
-        r = None
+        r, rq = None, None
         if i == len(specs) - 1 and res_last:
-            r = x if res_last == 'x' else grid((n, cout, h, w), 8, BIAS_Q, g)
-        layers.append(Layer(wgt, b, wq, stride, pad, act, f32, in_up, pool, r))
+            if res_last == 'x':
+                r, rq = x, xq * 2.0 ** xpow
+            elif regime == 'big':
+                r, rq = big_residual((n, cout, h, w), dt, g), BIG_RES[dt][1]
+            else:
+                r = grid((n, cout, h, w), 8, BIAS_Q, g) * 2.0 ** (max(total, -21) if dt == H16 else total)      # (16-bit: k 2^-24 at the finest)
+        layers.append(Layer(wgt, b, wq, stride, pad, act, f32, in_up, pool, r, rq))
         c = cout
-    case = Case(family, name, dt, x, xq, layers, keep)
-    case.covers = covers
+        if dt == H16 and not f32 and qlog < -24:    # (fp16 stores multiples of 2^-24: the next layer's grid starts from there)
+            total, qlog = total - 24 - qlog, -24
+    case = Case(family, name, dt, x, xq * 2.0 ** xpow, layers, keep)
+    case.covers, case.regime = covers, regime
     return case
 
 
@@ -434,20 +538,144 @@ def centre_tap(case):
     return case
 
 
-def vgg_stem_case(n, h, w, name=None):
+def vgg_stem_case(n, h, w, name=None, powers=None, regime=None):
     """conv1_1 (3 -> 64, +-1) + ReLU stored, conv1_2 (64 -> 64, +-1) + ReLU stored, MaxPool2d(2, 2); x large enough for conv1_1's 27
     products to stand one bit over bf16's significand -- conv1_2 then stands four over: one case exercises both stores"""
     return chain('vgg_stem', name or f'{n}x{h}x{w}', BF, n, 3, h, w, [(64, 3, 1, 1, 1, False, 0, None), (64, 3, 1, 1, 1, False, 0, (2, 2, 0))],
-                 xgrid=overflowing_x(BF, 27, 1.0), covers=(0, 1))
+                 xgrid=overflowing_x(BF, 27, 1.0), covers=(0, 1), powers=powers, regime=regime)
 
 
-def gln_stem_case(dt, n, h, w):
+def gln_stem_case(dt, n, h, w, regime=None):
     """conv 7x7 / 2 with a power-of-two frozen batch norm folded into the weights + ReLU, stored, then MaxPool2d(3, 2, 1) (exact)"""
-    c = single('gln_stem', f'{n}x{h}x{w}', dt, n, 3, h, w, 64, 7, 2, 3, wscale=gln_scale())
+    # (big: no scale above 1 -- a channel at twice the regime's size is saturated nearly everywhere behind the 3 x 3 pool, and shows nothing)
+    scale = gln_scale().clamp(max=1.0) if regime == 'big' else gln_scale()
+    c = single('gln_stem', f'{n}x{h}x{w}' + (f'_{regime}' if regime else ''), dt, n, 3, h, w, 64, 7, 2, 3, wscale=scale, regime=regime)
     c.layers[0].pool = (3, 2, 1)
-    c.scale = gln_scale()
+    c.scale = scale
     c.wt = c.layers[0].w / c.scale[:, None, None, None]          # what the model holds: the weight before the fold
     return c
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the edges of fp16: saturated stores (`big`) and subnormal operands and stores (`subw`, `subx`; a chain: `sub`)
+#
+#   regime   x                     w                          bias                  residual (16-bit)                 what it shows
+#   big      the recipe's          the recipe's times 2^s     k 2^12, |k| <= 8      fp16: i 32, |i| <= 2047, one in   fp16 stores clamp at +-65504, bf16 and fp32
+#            (fp16 and bf16)       (edge_scales: 17 at a      (on every grid of     50 exactly +-65504; bf16: i 256,  stores do not
+#                                  fan-in of 576)             sums in use)          |i| <= 255
+#   subw     the fine recipe's     the fine recipe's times    (k/8) 2^-14           (k/8) 2^-14: multiples of 2^-24   subnormal weights count at their value; a store
+#            (fp16)                2^-14: all subnormal                                                                rounds to nearest even on the 2^-24 grid
+#   subx     i 2^-24, |i| <= 32:   the fine recipe's times    (k/8) 2^-14           (k/8) 2^-14                       the same for subnormal activations
+#            all subnormal         2^5
+#   chain    layer i's +-1 weights take the factor 2^p_i and x the factor 2^xpow (EDGE_CHAINS); every bias is k quanta of its layer's sums
+#
+# A power of two on the weights changes no product's exactness and no count of quanta: the budget of a scaled single layer is that of the
+# plain one.  In a chain the clamp does not commute with the scale, and two things follow.  (1) 65504 = 2047 x 32 lies on the grids of 32
+# and finer only, so an fp16 store that saturates has a quantum of at most 32 and therefore sums of 2^11 quanta and more: a `big` chain
+# starts from an x of overflowing_x's size, on the grid 2^-3 x 2^8 = 32 (an identity residual is then on the grid of the last sums).
+# (2) Behind a store that saturates in part, the next layer's power brings the sums back to about 65504, on a finer grid; with it every
+# store of the three chains saturates in part inside the budget (measured: bneck at P = 256 2^21.8, the subnet 2^20.2), so NOT_EXERCISED_EDGE
+# is empty.  A `sub` chain keeps every store below 2^-14: whatever fp16 stores is a multiple of 2^-24, so each layer's power of about
+# 2^-3 puts its sums on 2^-27 again -- three bits to round, one store in eight an exact tie, at a budget below 2^18.
+# ---------------------------------------------------------------------------------------------------------------------------------
+# family -> [(existing case name, regimes: B = big in both types, w = subw, x = subx)]
+EDGE_SINGLES = {
+    'igemm': [('3x3_s2', 'Bwx'), ('residual', 'Bwx'), ('res_upsample', 'Bw'), ('in_upsample', 'Bx'), ('pool_generic', 'Bw'), ('cls_f32', 'B')],
+    'dma': [('dma128', 'Bwx'), ('dma_res_up', 'Bw')],
+    'splitk': [('512x25x25-512s1', 'Bwx'), ('512x25x25-512s1_res', 'Bw')],
+    'conv1x1': [('256x33x47-512s2', 'Bwx'), ('64x40x52-256s1same', 'Bwx'), ('64x30x31-128s1up', 'Bx')],
+    'halo': [('64x48x80-128', 'Bwx'), ('256x13x13-256', 'Bwx'), ('64x30x44-96_pool', 'Bw')],
+    'atlas': [('a', 'Bwx')],
+    'thin_out': [('128x48x48-9', 'Bwx')],
+    'thin3x3': [('2x37x45-32_act0', 'Bwx'), ('2x19x23-32_up_act1', 'Bx')],
+    'gln_stem': [('3x37x51', 'Bwx')],
+}
+EDGE_MAC, EDGE_VGG_STEM = (2, 64, 40, 24, 256), (1, 16, 32)       # bf16 only: `big`
+# chain family -> {(planes or None, regime, type): (x grid, xpow, powers)}; every case covers all of its stores
+EDGE_CHAINS = {
+    'gauss_tail': {(None, 'big', H16): (TAIL_X[H16], 0, [12, -17]), (None, 'big', BF): (TAIL_X[BF], 0, [15, -18]),
+                   (None, 'sub', H16): (TAIL_X[H16], -24, [4, 14])},
+    'gauss_subnet': {(None, 'big', H16): (overflowing_x(H16, 576, 0.0), 8, [0, -2, -3, 0, -17]), (None, 'big', BF): (CHAIN_X[BF], 14, [0, -3, -3, -2, -17]),
+                     (None, 'sub', H16): (overflowing_x(H16, 576, 0.0), 0, [-24, -3, -3, -2, 14])},
+    'bneck': {(64, 'big', H16): (overflowing_x(H16, 64, 0.0), 8, [0, -3, -1]), (64, 'big', BF): (BNECK_X[BF], 16, [0, -4, -2]),
+              (128, 'big', H16): (overflowing_x(H16, 512, 0.0), 8, [0, -3, -2]), (128, 'big', BF): (BNECK_X[BF], 15, [0, -4, -3]),
+              (256, 'big', H16): (overflowing_x(H16, 1024, 0.0), 8, [0, -4, -2]), (256, 'big', BF): (BNECK_X[BF], 15, [0, -5, -3]),
+              (64, 'sub', H16): (overflowing_x(H16, 64, -1.5), -21, [-2, -4, -3]), (128, 'sub', H16): (overflowing_x(H16, 512, -1.5), -21, [-2, -4, -3]),
+              (256, 'sub', H16): (overflowing_x(H16, 1024, -1.5), -21, [-2, -4, -3])},
+}
+EDGE_TAIL, EDGE_SUBNET, EDGE_BNECK = (1, 37, 41), (2, 19, 23), [(1, 64, 64, 37, 51, True), (1, 512, 128, 5, 9, False), (1, 1024, 256, 15, 29, False)]
+VGG_STEM_BIG = [10, -3]
+EDGE_TAIL_SALT = {('big', H16): 2, ('big', BF): 1, ('sub', H16): 1}          # (the seeds with which the one output channel is alive at pixel (0, 0), where test_case_is_sound changes its border pixel)
+# 16-bit stores of the chain families that neither a `big` nor a `sub` case can cover inside the budget: (family, type, planes or None,
+# regime) -> (stores, the measured budget)
+NOT_EXERCISED_EDGE = {}
+
+
+def edge_builders(plain):
+    """-> {case id: builder} of the edge cases: shapes of `plain` (builders()) under the name <existing name>_<regime>"""
+    out = {}
+    for family, rows in EDGE_SINGLES.items():
+        for name, codes in rows:
+            for regime, dt in [(r, dt) for code, r in (('B', 'big'), ('w', 'subw'), ('x', 'subx')) if code in codes for dt in ((H16, BF) if r == 'big' else (H16,))]:
+                assert f'{family}/{name}/{IDS[dt]}' in plain
+                out[f'{family}/{name}_{regime}/{IDS[dt]}'] = lambda family=family, name=name, regime=regime, dt=dt: _edge_single(family, name, regime, dt)
+    out[f'mac/{_mac_name()}_big/bf16'] = lambda: single('mac', _mac_name() + '_big', BF, *EDGE_MAC, 3, 1, 1, regime='big')
+    vname = '{}x{}x{}_big'.format(*EDGE_VGG_STEM)
+    out[f'vgg_stem/{vname}/bf16'] = lambda: vgg_stem_case(*EDGE_VGG_STEM, name=vname, powers=VGG_STEM_BIG, regime='big')
+    for (planes, regime, dt), (xg, xpow, powers) in EDGE_CHAINS['gauss_tail'].items():
+        n, h, w = EDGE_TAIL
+        name = f'{n}x{h}x{w}_{regime}'
+        out[f'gauss_tail/{name}/{IDS[dt]}'] = lambda name=name, regime=regime, dt=dt, xg=xg, xpow=xpow, powers=powers: chain(
+            'gauss_tail', name, dt, EDGE_TAIL[0], 16, *EDGE_TAIL[1:], tail_specs(), xgrid=xg, first=RECIPE[H16], covers=(0,), xpow=xpow, powers=powers, regime=regime, salt=EDGE_TAIL_SALT[regime, dt])
+    for (planes, regime, dt), (xg, xpow, powers) in EDGE_CHAINS['gauss_subnet'].items():
+        n, h, w = EDGE_SUBNET
+        name = f'{n}x{h}x{w}_act1_{regime}'
+        out[f'gauss_subnet/{name}/{IDS[dt]}'] = lambda name=name, regime=regime, dt=dt, xg=xg, xpow=xpow, powers=powers: chain(
+            'gauss_subnet', name, dt, EDGE_SUBNET[0], 64, *EDGE_SUBNET[1:], subnet_specs(1), xgrid=xg, covers=(0, 1, 2, 3), xpow=xpow, powers=powers, regime=regime)
+    for (n, cin, p, h, w, sep) in EDGE_BNECK:
+        for (planes, regime, dt), (xg, xpow, powers) in EDGE_CHAINS['bneck'].items():
+            if planes != p:
+                continue
+            name = f'{cin}-{p}x{h}x{w}' + ('_sep' if sep else '') + f'_{regime}'
+            out[f'bneck/{name}/{IDS[dt]}'] = lambda name=name, a=(n, cin, h, w), p=p, sep=sep, regime=regime, dt=dt, xg=xg, xpow=xpow, powers=powers: chain(
+                'bneck', name, dt, *a, bneck_specs(p), keep=1, res_last='sep' if sep else 'x', xgrid=xg, covers=(0, 1, 2), xpow=xpow, powers=powers, regime=regime)
+    return out
+
+
+def _mac_name():
+    n, cin, h, w, cout = EDGE_MAC
+    return f'{cin}x{h}x{w}-{cout}'
+
+
+def _edge_single(family, name, regime, dt):
+    """the single-layer case family/name of builders() in an edge regime, under the name <name>_<regime>"""
+    new = f'{name}_{regime}'
+    if family == 'igemm':
+        c = IGEMM[name]
+        return single(family, new, dt, *c[:8], regime=regime, **_opts(c[8]))
+    if family == 'dma':
+        c = DMA[name]
+        return single(family, new, dt, *c[:8], keep=1, regime=regime, **_opts(c[8]))
+    if family == 'splitk':
+        (n, cin, h, w, cout, k, stride, act) = SPLITK[0]
+        return single(family, new, dt, n, cin, h, w, cout, k, stride, k // 2, act=act, res='same' if name.endswith('_res') else None, keep=1, regime=regime)
+    if family == 'conv1x1':
+        (n, cin, h, w, cout, stride, res, act), = [c for c in C1X1 if f'{c[1]}x{c[2]}x{c[3]}-{c[4]}s{c[5]}{c[6]}' == name]
+        return single(family, new, dt, n, cin, h, w, cout, 1, stride, 0, act=act, res=res or None, regime=regime)
+    if family == 'halo':
+        (n, cin, h, w, cout, pool), = [c for c in HALO if f'{c[1]}x{c[2]}x{c[3]}-{c[4]}' + ('_pool' if c[5] else '') == name]
+        return single(family, new, dt, n, cin, h, w, cout, 3, 1, 1, pool=pool, regime=regime)
+    if family == 'atlas':
+        return single(family, new, dt, 3, 128, 21, 30, 256, 3, 1, 1, regime=regime)
+    if family == 'thin_out':
+        (cout, cin, h, w), = [c for c in THIN_OUT if f'{c[1]}x{c[2]}x{c[3]}-{c[0]}' == name]
+        return single(family, new, dt, 2, cin, h, w, cout, 3, 1, 1, act=0, f32=True, regime=regime)
+    if family == 'thin3x3':
+        (n, h, w, cout, up), act = [c for c in THIN3X3 if name.startswith(f'{c[0]}x{c[1]}x{c[2]}-{c[3]}' + ('_up' if c[4] else '') + '_act')][0], int(name[-1])
+        return single(family, new, dt, n, 64 if up else 32, h, w, cout, 3, 1, 1, act=act, in_up=up, regime=regime)
+    assert family == 'gln_stem'
+    n, h, w = (int(v) for v in name.split('x'))
+    return gln_stem_case(dt, n, h, w, regime)
 
 
 # the work-list launches of test_gpu_exact.py test_list_and_strip_launches: the S = 64 construction of tests/test_gpu_footprint.py
@@ -495,6 +723,18 @@ def _add_worklist(out):
 
 
 BUILDERS = _add_worklist(builders())
+EDGE_IDS = []                        # the ids of the edge cases, in the order of IDS_ALL
+
+
+def _add_edges(out):
+    edges = edge_builders(out)
+    assert all(cid.rsplit('_', 1)[0] + cid[cid.rindex('/'):] in out for cid in edges), 'an edge case is named after an existing case'
+    EDGE_IDS.extend(edges)
+    out.update(edges)
+    return out
+
+
+BUILDERS = _add_edges(BUILDERS)
 IDS_ALL = list(BUILDERS)
 
 

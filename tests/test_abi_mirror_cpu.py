@@ -22,7 +22,7 @@ def test_every_header_has_a_table_and_an_op_module():
     entry_points = sum(len(table) for table in _lib.HEADERS.values())
     ops = sum(len(abi.op_module(h).NAMES) for h in HEADERS)
     print(f'{len(on_disk)} headers, {entry_points} entry points, {ops} ops')
-    assert (len(on_disk), entry_points, ops) == (14, 87, 58)
+    assert (len(on_disk), entry_points, ops) == (14, 88, 59)
     declared = {s for h in HEADERS for s in abi.header_symbols(h)}
     assert abi.HOST_ONLY <= declared and {s for s in declared if s.endswith('_bytes')} <= abi.HOST_ONLY and len(abi.HOST_ONLY) == 12
 
@@ -86,12 +86,12 @@ def test_inference_ops_cover_the_inference_header():
     assert len(symbols) >= 13
     f16 = {s for s in symbols if s.endswith('_f16')}
     assert len(f16) == 16 and f16 == abi.twins(symbols)
-    assert len(torch_ops.NAMES) == len(abi.op_symbols(abi.INFERENCE)) == 36
+    assert len(torch_ops.NAMES) == len(abi.op_symbols(abi.INFERENCE)) == 37
 
 
 def test_op_names_are_distinct_and_gpu_only():
     names = [n for h in HEADERS for n in abi.op_module(h).NAMES]
-    assert len(names) == len(set(names)) == 58
+    assert len(names) == len(set(names)) == 59
     for name in names:
         assert hasattr(torch.ops.cvpce_amd, name)
         assert torch._C._dispatch_has_kernel_for_dispatch_key(f'cvpce_amd::{name}', 'CUDA'), name

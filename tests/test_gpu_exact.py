@@ -9,6 +9,11 @@ through ops.conv_route / ops.PROFILE which kernel ran.  The first two tests are 
 through one kernel on v_mfma_f32_32x32x16 (the register-staged implicit GEMM, 8 x 8 map) and one on v_mfma_f32_16x16x32 (the thin-output
 form of the wide halo kernel: it only runs 3 x 3 layers on maps of 48 x 48 and more, so the conv is a 3 x 3 whose off-centre taps are
 zero, on a 48 x 48 map) -- if the matrix units rounded sums of exactly representable values, these two would show it before any other test.
+
+The families' edge cases (exact_cases.EDGE_IDS: `_big`, `_subw`, `_subx`, `_sub`) run in the same family tests, on the same routes: fp16
+stores that saturate at +-65504 where bf16 and fp32 stores keep the value, and fp16 subnormal weights, activations, residuals and stored
+values -- a kernel that forgot a clamp on an intermediate store, clamped a bf16 store, flushed a subnormal or cut it instead of rounding
+differs from the reference (tests/test_exact_cases_cpu.py test_edge_mutants_differ shows it for every case on the host).
 """
 import contextlib
 
@@ -88,6 +93,26 @@ def launch_conv(cuda, c, **sw):
     return y, route, rec, layer
 
 
+# family -> (the ops switches its single-layer cases run under, what (case, route, kernel record, layer record) must satisfy)
+SINGLE = {
+    'igemm': (dict(FORCE_GENERIC_CONV=True), lambda c, route, rec, layer: route == 'igemm' and rec.startswith('conv_igemm_kernel')),
+    'dma': (dict(USE_HALO_3X3=False, USE_CONV1X1=False), lambda c, route, rec, layer: route == 'igemm' and rec.startswith('conv_dma')),
+    'splitk': ({}, lambda c, route, rec, layer: route == 'splitk' and 'split-K 4' in layer and rec.startswith('conv_igemm_kernel<128')),
+    'conv1x1': (dict(CONV1X1_ANY_SHAPE=True), lambda c, route, rec, layer: route == 'conv1x1' and rec == 'conv1x1_kernel'),
+    'halo': (dict(HALO_RAGGED=True), lambda c, route, rec, layer: route == 'halo' and rec == ('conv3x3_halo3_kernel' if c.layers[0].w.shape[0] <= 128 else 'conv3x3_halo2_kernel')),
+    'thin_out': ({}, lambda c, route, rec, layer: route == 'halo_thin_out' and layer.startswith('conv3x3_halo3 thin out')),
+    'thin3x3': ({}, lambda c, route, rec, layer: route == 'thin3x3' and rec == 'thin3x3_kernel'),
+}
+
+
+def run_single(cuda, c):
+    """a single-layer case through ops.conv2d under its family's switches, on the route and kernel the family is about -> output"""
+    sw, intended = SINGLE[c.family]
+    y, route, rec, layer = launch_conv(cuda, c, **sw)
+    assert intended(c, route, rec, layer), (c.id, route, rec, layer)
+    return y, rec
+
+
 @pytest.fixture(scope='module')
 def refs():
     """float64 references, computed once per case and shared by the tests that need them; never modified"""
@@ -132,9 +157,7 @@ def test_igemm_generic(cuda, refs, cid):
     """the register-staged implicit GEMM (every tile shape, K-step 32 and 64, stride 2, 7 x 7, residual same-size and upsampled, upsampled
     input, fp32 out, fused pool)"""
     c, ref = refs(cid)
-    y, route, rec, _ = launch_conv(cuda, c, FORCE_GENERIC_CONV=True)
-    assert route == 'igemm' and rec.startswith('conv_igemm_kernel'), (route, rec)
-    same(widen(y, c.keep), ref, cid)
+    same(widen(run_single(cuda, c)[0], c.keep), ref, cid)
 
 
 @pytest.mark.parametrize('cid', ec.ids('dma'))
@@ -143,8 +166,7 @@ def test_lds_dma_ring(cuda, refs, cid):
     dma_in_up: the 2-buffer 256 x 256 kernel, which takes the ring kernel's shapes on an upsampled input (its padding test runs on
     upsampled coordinates) -- no model has such a layer, so this is the only launch of that instance"""
     c, ref = refs(cid)
-    y, route, rec, _ = launch_conv(cuda, c, USE_HALO_3X3=False, USE_CONV1X1=False)
-    assert route == 'igemm' and rec.startswith('conv_dma'), (route, rec)
+    y, rec = run_single(cuda, c)
     if c.name == 'dma_in_up':
         assert rec == 'conv_dma_kernel<256,256,2,4,2>', rec
     same(widen(y, c.keep), ref, cid)
@@ -155,18 +177,14 @@ def test_splitk(cuda, refs, cid):
     """split-K launches: a partial sum lost or added twice in one tile moves that tile by whole quanta; 16-bit and fp32 out, with and
     without a residual"""
     c, ref = refs(cid)
-    y, route, rec, layer = launch_conv(cuda, c)
-    assert route == 'splitk' and 'split-K 4' in layer and rec.startswith('conv_igemm_kernel<128'), (route, rec, layer)
-    same(widen(y, c.keep), ref, cid)
+    same(widen(run_single(cuda, c)[0], c.keep), ref, cid)
 
 
 @pytest.mark.parametrize('cid', ec.ids('conv1x1'))
 def test_conv1x1(cuda, refs, cid):
     """the pointwise GEMM kernel: stride 2, both residual modes, K from 64 (one stage) to 2048, weights in registers and in LDS"""
     c, ref = refs(cid)
-    y, route, rec, _ = launch_conv(cuda, c, CONV1X1_ANY_SHAPE=True)
-    assert route == 'conv1x1' and rec == 'conv1x1_kernel', (route, rec)
-    same(widen(y, c.keep), ref, cid)
+    same(widen(run_single(cuda, c)[0], c.keep), ref, cid)
 
 
 @pytest.mark.parametrize('cid', ec.ids('halo'))
@@ -174,9 +192,7 @@ def test_halo(cuda, refs, cid):
     """the halo-patch kernels (16 x 16 tiles above 128 couts, 16 x 32 below): ragged tiles, ragged cout tiles (136, 264), the fused pool;
     and, both being exact, equal to the implicit-GEMM kernel on the same inputs"""
     c, ref = refs(cid)
-    y, route, rec, _ = launch_conv(cuda, c, HALO_RAGGED=True)
-    cout = c.layers[0].w.shape[0]
-    assert route == 'halo' and rec == ('conv3x3_halo3_kernel' if cout <= 128 else 'conv3x3_halo2_kernel'), (route, rec)
+    y, _ = run_single(cuda, c)
     same(widen(y, c.keep), ref, cid)
     y2, route2, rec2, _ = launch_conv(cuda, c, USE_HALO_3X3=False)
     assert route2 != 'halo' and not rec2.startswith('conv3x3_halo'), (route2, rec2)
@@ -187,26 +203,19 @@ def test_halo(cuda, refs, cid):
 def test_halo_thin_out(cuda, refs, cid):
     """the thin-output form of the wide halo kernel: Cout 1, 9, 36, fp32 out, no activation, 48 x 48 and a ragged 50 x 77"""
     c, ref = refs(cid)
-    y, route, rec, layer = launch_conv(cuda, c)
-    assert route == 'halo_thin_out' and layer.startswith('conv3x3_halo3 thin out'), (route, rec, layer)
-    same(widen(y, c.keep), ref, cid)
+    same(widen(run_single(cuda, c)[0], c.keep), ref, cid)
 
 
 @pytest.mark.parametrize('cid', ec.ids('thin3x3'))
 def test_thin3x3(cuda, refs, cid):
     """the thin 3 x 3 kernel (32 -> 16 | 32, and 64 -> 32 over the 2x upsampled input), with and without ReLU"""
     c, ref = refs(cid)
-    y, route, rec, _ = launch_conv(cuda, c)
-    assert route == 'thin3x3' and rec == 'thin3x3_kernel', (route, rec)
-    same(widen(y, c.keep), ref, cid)
+    same(widen(run_single(cuda, c)[0], c.keep), ref, cid)
 
 
-@pytest.mark.parametrize('cid', ec.ids('mac'))
-def test_conv2d_relu_mac(cuda, refs, cid):
-    """conv + ReLU with the MAC descriptor taken in the epilogue (stored, stored pooled, not stored): the descriptor is the maximum of
-    what the unfused schedule would have stored -- the 16-bit values (rounding is monotone, so also the rounded maximum of the sums)"""
+def run_mac(cuda, c):
+    """-> (the stored map or None, the descriptor rows with the layer's maxima from column 40)"""
     from cvpce_amd import ops
-    c, ref = refs(cid)
     L = c.layers[0]
     pool, store = '_pool' in c.name, '_nostore' not in c.name
     n, cout = c.x.shape[0], L.w.shape[0]
@@ -217,6 +226,16 @@ def test_conv2d_relu_mac(cuda, refs, cid):
         got = ops.conv2d_relu_mac(x, pc, mac, 40, store=store, pool=pool)
         assert prof.records[-1][0] == 'conv3x3_halo2_kernel'
     torch.cuda.synchronize()
+    return got, mac
+
+
+@pytest.mark.parametrize('cid', ec.ids('mac'))
+def test_conv2d_relu_mac(cuda, refs, cid):
+    """conv + ReLU with the MAC descriptor taken in the epilogue (stored, stored pooled, not stored): the descriptor is the maximum of
+    what the unfused schedule would have stored -- the 16-bit values (rounding is monotone, so also the rounded maximum of the sums)"""
+    c, ref = refs(cid)
+    pool, store = '_pool' in c.name, '_nostore' not in c.name
+    got, mac = run_mac(cuda, c)
     assert float(mac[:, :40].abs().max()) == 0.0
     assert torch.equal(mac[:, 40:].double().cpu(), ref.amax(dim=(-2, -1))), cid
     if not store:
@@ -230,10 +249,15 @@ def test_conv2d_relu_mac(cuda, refs, cid):
 def test_atlas_masked(cuda, refs, use_map, dt):
     """the masked atlas conv on two maps packed with a one-pixel zero gap (tests/test_gpu_kernels.py test_conv3x3_atlas_masked, n = 3):
     level pixels equal the conv of each map alone, gap pixels of computed tiles are exact zeros"""
+    check_atlas(cuda, refs, use_map, dt, '')
+
+
+def check_atlas(cuda, refs, use_map, dt, suffix):
+    """test_atlas_masked on the case atlas/a<suffix>: map b takes a's layer, and its x on a's grid"""
     from cvpce_amd import ops
-    ca, ra = refs(f'atlas/a/{ec.IDS[dt]}')
+    ca, ra = refs(f'atlas/a{suffix}/{ec.IDS[dt]}')
     cb, rb = refs(f'atlas/b/{ec.IDS[dt]}')
-    cb = cb.with_(layers=ca.layers)                                  # one layer over both maps
+    cb = cb.with_(x=cb.x * (ca.xq / cb.xq), layers=ca.layers)        # one layer over both maps
     rb = cb.reference()[0]
     n = 3
     pc = packed(ca.layers[0], dt, cuda)
@@ -262,52 +286,68 @@ def test_atlas_masked(cuda, refs, use_map, dt):
             computed[(t >> 16) * 16:(t >> 16) * 16 + 16, (t & 0xFFFF) * 16:(t & 0xFFFF) * 16 + 16] = True
     gap = (computed & (mask == 0))[None, :, :, None].expand(n, 21, 61, 256)
     assert int(gap.sum()) > 0 and float(y.cpu().double()[gap].abs().max()) == 0.0
+    return y[:, :, :30]
+
+
+ATLAS_EDGES = [c.split('/')[1][1:] + '/' + c.split('/')[2] for c in ec.ids('atlas') if c in ec.EDGE_IDS]
+
+
+@pytest.mark.parametrize('edge', ATLAS_EDGES)
+@pytest.mark.parametrize('use_map', [False, True], ids=['mask', 'mask+tile map'])
+def test_atlas_masked_edges(cuda, refs, use_map, edge):
+    """test_atlas_masked on the edge cases of map a (saturated stores in both types, subnormal weights, subnormal activations)"""
+    suffix, dt = edge.split('/')
+    check_atlas(cuda, refs, use_map, {v: k for k, v in ec.IDS.items()}[dt], suffix)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # fused chains: one rounding at each place the per-layer schedule stores
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('cstride', [4, 8])
-@pytest.mark.parametrize('cid', ec.ids('vgg_stem'))
-def test_vgg_stem(cuda, refs, cid, cstride):
-    """conv1_1 + ReLU + conv1_2 + ReLU + pool in one launch: conv1_1's output is rounded to bf16 before conv1_2 reads it, as the
-    unfused schedule stores it (tests/test_gpu_kernels.py test_vgg_stem_fused_parity); channel strides 4 and 8"""
+def run_vgg_stem(cuda, c, cstride=4):
     from cvpce_amd import ops
-    c, ref = refs(cid)
     l1, l2 = c.layers
     ps = ops.PackedStem(l1.w.float(), l1.b.float(), l2.w.float(), l2.b.float(), device=cuda)
     with switches() as prof:
         y = ops.vgg_stem(to_nhwc(c.x, BF, cstride).to(cuda), ps)
         assert prof.records[-1][0] == 'vgg_stem2_kernel'
     torch.cuda.synchronize()
-    same(widen(y), ref, cid)
+    return y
 
 
-@pytest.mark.parametrize('cid', ec.ids('gln_stem'))
-def test_gln_stem(cuda, refs, cid):
-    """conv 7 x 7 / 2 + frozen batch norm (power-of-two scales: the fold is exact) + ReLU + max-pool 3 x 3 / 2 in one launch: the conv
-    output is rounded before the pool, as the unfused schedule stores it (test_gln_stem_fused_parity); the pool is exact"""
-    from cvpce_amd import ops
+@pytest.mark.parametrize('cstride', [4, 8])
+@pytest.mark.parametrize('cid', ec.ids('vgg_stem'))
+def test_vgg_stem(cuda, refs, cid, cstride):
+    """conv1_1 + ReLU + conv1_2 + ReLU + pool in one launch: conv1_1's output is rounded to bf16 before conv1_2 reads it, as the
+    unfused schedule stores it (tests/test_gpu_kernels.py test_vgg_stem_fused_parity); channel strides 4 and 8"""
     c, ref = refs(cid)
+    same(widen(run_vgg_stem(cuda, c, cstride)), ref, cid)
+
+
+def run_gln_stem(cuda, c):
+    from cvpce_amd import ops
     L = c.layers[0]
     ps = ops.PackedGlnStem(c.wt.float(), c.scale.float(), L.b.float(), device=cuda, dtype=c.dt)
     with switches() as prof:
         y = ops.gln_stem(to_nhwc(c.x, c.dt).to(cuda), ps)
         assert prof.records[-1][0] == 'gln_stem_kernel'
     torch.cuda.synchronize()
-    same(widen(y), ref, cid)
+    return y
+
+
+@pytest.mark.parametrize('cid', ec.ids('gln_stem'))
+def test_gln_stem(cuda, refs, cid):
+    """conv 7 x 7 / 2 + frozen batch norm (power-of-two scales: the fold is exact) + ReLU + max-pool 3 x 3 / 2 in one launch: the conv
+    output is rounded before the pool, as the unfused schedule stores it (test_gln_stem_fused_parity); the pool is exact"""
+    c, ref = refs(cid)
+    same(widen(run_gln_stem(cuda, c)), ref, cid)
 
 
 def _chain_convs(c, cuda):
     return [packed(L, c.dt, cuda) for L in c.layers]
 
 
-@pytest.mark.parametrize('cid', ec.ids('gauss_tail'))
-def test_gauss_tail(cuda, refs, cid):
-    """the Gaussian subnet's two pointwise layers in one launch, ReLU: the hidden layer is rounded where the two-launch form stores it
-    (test_gauss_tail_parity)"""
+def run_gauss_tail(cuda, c):
     from cvpce_amd import ops
-    c, ref = refs(cid)
     c4, c5 = _chain_convs(c, cuda)
     x = to_nhwc(c.x, c.dt).to(cuda)
     with switches() as prof:
@@ -315,38 +355,67 @@ def test_gauss_tail(cuda, refs, cid):
         y = ops.gauss_tail(x, c4, c5, 1)
         assert prof.records[-1][0] == 'gauss_tail_kernel'
     torch.cuda.synchronize()
-    same(widen(y), ref, cid)
+    return y
+
+
+@pytest.mark.parametrize('cid', ec.ids('gauss_tail'))
+def test_gauss_tail(cuda, refs, cid):
+    """the Gaussian subnet's two pointwise layers in one launch, ReLU: the hidden layer is rounded where the two-launch form stores it
+    (test_gauss_tail_parity)"""
+    c, ref = refs(cid)
+    same(widen(run_gauss_tail(cuda, c)), ref, cid)
+
+
+def run_gauss_subnet(cuda, c, per_layer=False):
+    """-> the fused kernel's output (and that of the per-layer launches: three thin 3 x 3 layers and the fused tail)"""
+    from cvpce_amd import ops
+    act = c.layers[-1].act
+    convs = _chain_convs(c, cuda)
+    x = to_nhwc(c.x, c.dt).to(cuda)
+    y2 = None
+    with switches() as prof:
+        assert ops.can_fuse_gauss_subnet(x, convs)
+        y = ops.gauss_subnet(x, convs, act)
+        assert prof.records[-1][0] == 'gauss_subnet_kernel'
+        if per_layer:
+            t = ops.conv2d(x, convs[0], act=1, in_up_shift=1)
+            t = ops.conv2d(ops.conv2d(t, convs[1], act=1), convs[2], act=1)
+            assert [r[0] for r in prof.records[-3:]] == ['thin3x3_kernel'] * 3
+            y2 = ops.gauss_tail(t, convs[3], convs[4], act)
+    torch.cuda.synchronize()
+    return y, y2
 
 
 @pytest.mark.parametrize('cid', ec.ids('gauss_subnet'))
 def test_gauss_subnet(cuda, refs, cid):
     """the whole Gaussian subnet in one launch, no activation and ReLU behind the last layer: rounded at the four places _subnet_reference
     (tests/test_gpu_kernels.py) rounds -- and equal to the per-layer launches, of which the tolerance test can only demand atol"""
-    from cvpce_amd import ops
     c, ref = refs(cid)
-    act = c.layers[-1].act
-    convs = _chain_convs(c, cuda)
-    x = to_nhwc(c.x, c.dt).to(cuda)
-    with switches() as prof:
-        assert ops.can_fuse_gauss_subnet(x, convs)
-        y = ops.gauss_subnet(x, convs, act)
-        assert prof.records[-1][0] == 'gauss_subnet_kernel'
-        t = ops.conv2d(x, convs[0], act=1, in_up_shift=1)
-        t = ops.conv2d(ops.conv2d(t, convs[1], act=1), convs[2], act=1)
-        assert [r[0] for r in prof.records[-3:]] == ['thin3x3_kernel'] * 3
-        per_layer = ops.gauss_tail(t, convs[3], convs[4], act)
-    torch.cuda.synchronize()
+    y, per_layer = run_gauss_subnet(cuda, c, per_layer=True)
     same(widen(y), ref, cid)
     same(widen(per_layer), ref, cid + ' per-layer launches')
 
 
-@pytest.mark.parametrize('cid', ec.ids('bneck'))
-def test_bottleneck(cuda, refs, cid):
-    """the fused bottleneck (1 x 1 -> 3 x 3 -> 1 x 1 + residual, intermediates in LDS) against the reference with the two intermediate
-    layers rounded where the three-launch schedule stores them, and against that schedule; identity residual, and a separate residual
-    tensor for the projection-shortcut block.  The whole batch runs, the last image is compared with the reference."""
+STALE_LDS = ['gauss_subnet/2x64x15_act0/bf16', 'gauss_subnet/2x19x23_act1/fp16', 'gauss_tail/1x37x41/fp16', 'bneck/512-128x5x9/fp16', 'bneck/64-64x37x51_sep/bf16']
+
+
+@pytest.mark.parametrize('cid', STALE_LDS)
+def test_fused_chains_ignore_stale_lds(cuda, refs, cid):
+    """LDS is not cleared between kernels.  The fused chains keep rings and intermediate layers there and read slots beside the ones they
+    wrote (the subnet's unused columns X + 28 .. read pixel slots 32 and 33 of its rings, which no one stores to); what they read there
+    is dropped -- unless it is not finite: in the subnet's 16 -> 1 layer a dropped column shares an MFMA column with a kept one under a
+    weight row of zeros, and 0 x NaN is NaN.  So: every compute unit's LDS full of 0xFFFFFFFF (ops.probe_lds_fill), then the kernel, and
+    the result is the reference all the same."""
     from cvpce_amd import ops
     c, ref = refs(cid)
+    assert ops.probe_lds_fill(0xFFFFFFFF) == 2048
+    y = run_case(cuda, refs, c) if c.family != 'gauss_subnet' else run_gauss_subnet(cuda, c)[0]
+    same(widen(y, c.keep), ref, cid)
+
+
+def run_bottleneck(cuda, c, three_launches=False):
+    """-> the fused kernel's output (and the three-launch schedule's)"""
+    from cvpce_amd import ops
     pcs = _chain_convs(c, cuda)
     x = to_nhwc(c.x, c.dt).to(cuda)
     res = c.layers[-1].res
@@ -355,11 +424,66 @@ def test_bottleneck(cuda, refs, cid):
         assert ops.can_fuse_bottleneck(x, *pcs, r)
         y = ops.bottleneck(x, *pcs, r)
         assert prof.records[-1][0] == 'bneck_kernel'
-    with switches(USE_FUSED_BOTTLENECK=False):
-        y3 = ops.conv2d(ops.conv2d(ops.conv2d(x, pcs[0], act=1), pcs[1], act=1), pcs[2], act=1, residual=r)
+    y3 = None
+    if three_launches:
+        with switches(USE_FUSED_BOTTLENECK=False):
+            y3 = ops.conv2d(ops.conv2d(ops.conv2d(x, pcs[0], act=1), pcs[1], act=1), pcs[2], act=1, residual=r)
     torch.cuda.synchronize()
+    return y, y3
+
+
+@pytest.mark.parametrize('cid', ec.ids('bneck'))
+def test_bottleneck(cuda, refs, cid):
+    """the fused bottleneck (1 x 1 -> 3 x 3 -> 1 x 1 + residual, intermediates in LDS) against the reference with the two intermediate
+    layers rounded where the three-launch schedule stores them, and against that schedule; identity residual, and a separate residual
+    tensor for the projection-shortcut block.  The whole batch runs, the last image is compared with the reference."""
+    c, ref = refs(cid)
+    y, y3 = run_bottleneck(cuda, c, three_launches=True)
     same(widen(y, c.keep), ref, cid)
     same(widen(y), widen(y3), cid + ' against the three-launch schedule')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the edges of fp16, over every kernel at once
+# ---------------------------------------------------------------------------------------------------------------------------------
+def run_case(cuda, refs, c):
+    """the case's kernel, as its family's test launches it -> the output on the device"""
+    if c.family in SINGLE:
+        return run_single(cuda, c)[0]
+    if c.family == 'atlas':
+        return check_atlas(cuda, refs, False, c.dt, c.name[1:])
+    return {'mac': lambda: run_mac(cuda, c)[0], 'vgg_stem': lambda: run_vgg_stem(cuda, c), 'gln_stem': lambda: run_gln_stem(cuda, c),
+            'gauss_tail': lambda: run_gauss_tail(cuda, c), 'bneck': lambda: run_bottleneck(cuda, c)[0]}[c.family]()
+
+
+BIG_16BIT = [cid for cid in ec.EDGE_IDS if '_big/' in cid and cid.split('/')[0] not in ('gauss_tail', 'gauss_subnet', 'thin_out') and 'cls_f32' not in cid]
+BIG_F32 = [cid for cid in ec.EDGE_IDS if '_big/' in cid and (cid.split('/')[0] in ('gauss_tail', 'thin_out') or 'cls_f32' in cid)]
+
+
+@pytest.mark.parametrize('cid', [c for c in BIG_16BIT if c.endswith('/fp16')])
+def test_big_fp16_outputs_saturate(cuda, refs, cid):
+    """every `big` case with an fp16 output: the kernel's output is finite, and its largest magnitude is exactly 65504"""
+    c, _ = refs(cid)
+    y = run_case(cuda, refs, c)
+    assert y.dtype == H16 and bool(torch.isfinite(y).all()) and float(y.float().abs().max()) == ec.F16_MAX, cid
+
+
+@pytest.mark.parametrize('cid', [c for c in BIG_16BIT if c.endswith('/bf16')])
+def test_big_bf16_outputs_exceed_fp16(cuda, refs, cid):
+    """every `big` case with a bf16 output: the kernel's output is finite and exceeds 65504 somewhere -- no fp16 clamp in a bf16 instance"""
+    c, _ = refs(cid)
+    y = run_case(cuda, refs, c)
+    assert y.dtype == BF and bool(torch.isfinite(y).all()) and float(y.float().abs().max()) > ec.F16_MAX, cid
+
+
+@pytest.mark.parametrize('cid', BIG_F32)
+def test_big_f32_outputs_are_not_clamped(cuda, refs, cid):
+    """a `big` case with an fp32 output, in either storage type: values above 65504 arrive (the Gaussian tail's output lies behind a
+    layer that scales back down: there only finite)"""
+    c, ref = refs(cid)
+    y = run_case(cuda, refs, c)
+    assert y.dtype == F32 and bool(torch.isfinite(y).all()), cid
+    assert c.family == 'gauss_tail' or float(y.abs().max()) == float(ref.abs().max()) > ec.F16_MAX, cid
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
