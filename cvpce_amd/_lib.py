@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI of libcvpce_hip.so: one signature table per header of include/, in `HEADERS`.
+"""ctypes binding of the C ABI of libcvpce_hip.so: one signature table per header of include/, in `HEADERS` (include/ext/: in
+`EXTENSION_HEADERS`).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -176,7 +177,15 @@ HEADERS['cvpce_amd_headloss.h'] = {
                        + [_vp, c_size_t, _ip, _fp, _ip, _vp]),
 }
 
-for _table in HEADERS.values():
+# Headers of include/ext/: bound by the same loop, kept apart from HEADERS (the registry of the headers directly under include/).
+# Tonioni's matcher, the comparator's second one.
+EXTENSION_HEADERS = {'ext/cvpce_amd_tonioni.h': {
+    'cvpce_tonioni_workspace_bytes': (c_size_t, [c_longlong, c_int]),
+    'cvpce_tonioni_run': (c_int, [_ip] * 8 + [c_int] * 6 + [c_longlong, _vp, c_size_t, _vp]),
+    'cvpce_tonioni_select': (c_int, [_ip] * 7 + [c_int] * 7 + [c_longlong, _vp, c_size_t, _ip, _ip, _vp]),
+}}
+
+for _table in list(HEADERS.values()) + list(EXTENSION_HEADERS.values()):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -18,7 +18,8 @@ One switch goes beyond the reference: `gln eval` and `eval-product-detection` ta
 against the map rendered from its ground-truth boxes, the reference's gaussian_loss; `_GaussianLossCommand`), `eval-planograms` takes
 --device-graphs, --device-tail, --device-reclass and --device-detections (default off; `_DeviceDetectionsCommand`) and --report FILE
 (one JSON line per image saying which positions are missing and what is there; `_ReportCommand`) and --render DIR (the three compliance
-pictures of every image as PNG files; `_RenderCommand`), `rebuild-scene` writes those pictures for one image (--out PREFIX instead of the
+pictures of every image as PNG files; `_RenderCommand`) and --matcher [large|tonioni] (default large: the comparator's graph matcher;
+`_MatcherCommand`), `rebuild-scene` writes those pictures for one image (--out PREFIX instead of the
 reference's matplotlib window), and `dihe eval` takes --device-eval /
 --no-device-eval (default off: EVAL_WINDOW images at a time are cropped, embedded and matched in one pass and compared on the GPU;
 `_DeviceEvalCommand`).
@@ -281,6 +282,46 @@ class _RenderCommand(_ReportCommand):
 
 def _render_dir():
     return click.get_current_context().meta.get(_RenderCommand.RENDER_KEY)
+
+
+class _MatcherCommand(_RenderCommand):
+    """The switches, --report and --render above, and --matcher [large|tonioni] (default: large) beside them, arranged the same way."""
+    MATCHER_OPTION = '--matcher'
+    MATCHERS = production.PlanogramComparator.MATCHERS
+    MATCHER_HELP = ('The graph matcher of the comparator: large, the first sufficiently large common subgraph, or tonioni, the largest of '
+                    'the greedy runs from every hypothesis on (cvpce_amd.planograms.tonioni_mcs; with --device-graphs it runs on the GPU, the '
+                    'documented Tonioni rule): a larger matching on shelves with many facings of few products.  [default: large]')
+    MATCHER_KEY = 'cvpce_amd.matcher'
+    MATCHER_LABEL = '--matcher [large|tonioni]'
+
+    def parse_args(self, ctx, args):
+        rest, args = [], list(args)
+        ctx.meta[self.MATCHER_KEY] = self.MATCHERS[0]
+        i = 0
+        while i < len(args):
+            a = args[i]
+            if a == '--':
+                rest += args[i:]
+                break
+            if a == self.MATCHER_OPTION:
+                if i + 1 >= len(args):
+                    raise click.UsageError('--matcher needs a name', ctx)
+                ctx.meta[self.MATCHER_KEY] = args[i + 1]
+                i += 1
+            elif a.startswith(self.MATCHER_OPTION + '='):
+                ctx.meta[self.MATCHER_KEY] = a[len(self.MATCHER_OPTION) + 1:]
+            else:
+                rest.append(a)
+            i += 1
+        if ctx.meta[self.MATCHER_KEY] not in self.MATCHERS and not ctx.resilient_parsing:
+            raise click.UsageError(f'--matcher is one of {", ".join(self.MATCHERS)}', ctx)
+        return super().parse_args(ctx, rest)
+
+    MORE = _RenderCommand.MORE + ((MATCHER_LABEL, MATCHER_HELP),)
+
+
+def _matcher_name():
+    return click.get_current_context().meta.get(_MatcherCommand.MATCHER_KEY, _MatcherCommand.MATCHERS[0])
 
 
 class _DeviceEvalCommand(_DeviceMetricsCommand):
@@ -598,7 +639,8 @@ def _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index):
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
     return production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
                                                                                           device_tail=_device_tail_switch(),
-                                                                                          device_reclass=_device_reclass_switch()),
+                                                                                          device_reclass=_device_reclass_switch(),
+                                                                                          matcher=_matcher_name()),
                                          device_detections=_device_detections_switch())
 
 
@@ -647,7 +689,7 @@ def rebuild_scene(img_dir, test_imgs, test_annotations, planograms, datatype, lo
     print(_accuracy_line(float(report.compliance), plano))
 
 
-@cli.command(cls=_RenderCommand)
+@cli.command(cls=_MatcherCommand)
 @click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
               help='Path to training image root')
 @click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')

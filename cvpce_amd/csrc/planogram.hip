@@ -17,8 +17,8 @@
 #include "common.h"
 #include "../../include/cvpce_amd_planogram.h"
 #include <limits.h>
+#include "pg_hypotheses.h"
 
-#define PG_THREADS 256
 #define PG_MAX CVPCE_PLANOGRAM_MAX_NODES
 #define PG_TAN_PI_8 0.41421356f
 #define PG_TAN_3PI_8 2.41421356f
@@ -263,57 +263,8 @@ __global__ __launch_bounds__(PG_THREADS) void planogram_match_kernel(
     }
     __syncthreads();
 
-    // ---- hypotheses: count per (level, n1), prefix, place ----
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int a = tid; a < n1; a += PG_THREADS) {
-            int nl1[8];
-#pragma unroll
-            for (int d = 0; d < 8; ++d) {
-                const int e = nb1[a * 8 + d];
-                nl1[d] = e >= 0 ? lab1[e] : -1;
-            }
-            const int la = lab1[a];
-            for (int b = 0; b < n2; ++b) {
-                if (lab2[b] != la) continue;
-                int agree = 0;
-#pragma unroll
-                for (int d = 0; d < 8; ++d) agree += nl1[d] == nl2[b * 8 + d] ? 1 : 0;
-                const int at = (8 - agree) * n1 + a;                 // (this thread's own entry)
-                if (pass == 0) {
-                    un[at] += 1;
-                } else {
-                    const int pos = un[at]++;
-                    if (pos < hcap) hyp[(size_t)h0 + pos] = (agree << 20) | (a << 10) | b;
-                }
-            }
-        }
-        __syncthreads();
-        if (pass == 0) {
-            const int total = 9 * n1, chunk = (total + PG_THREADS - 1) / PG_THREADS;
-            const int e0 = min(tid * chunk, total), e1 = min(e0 + chunk, total);
-            int sum = 0;
-            for (int e = e0; e < e1; ++e) sum += un[e];
-            s_part[tid] = sum;
-            __syncthreads();
-            if (tid == 0) {
-                int run = 0;
-                for (int t = 0; t < PG_THREADS; ++t) {
-                    const int v = s_part[t];
-                    s_part[t] = run;
-                    run += v;
-                }
-                s_total = run;
-            }
-            __syncthreads();
-            int run = s_part[tid];
-            for (int e = e0; e < e1; ++e) {
-                const int v = un[e];
-                un[e] = run;
-                run += v;
-            }
-            __syncthreads();
-        }
-    }
+    // ---- hypotheses: count per (level, n1), prefix, place (pg_hypotheses.h) ----
+    pg_build_hypotheses(n1, n2, nb1, nb2, lab1, lab2, nl2, un, s_part, &s_total, hyp + h0, hcap);
     const int H = min(s_total, hcap);
     __syncthreads();                                                  // `un` becomes the queue
 

@@ -4,6 +4,7 @@
   build_graph             8-direction nearest-neighbour DiGraph over box centres (planograms.py:30-71)
   build_hypotheses /
   large_common_subgraph   hypothesis-seeded breadth-first common subgraph (planograms.py:73-132)
+  tonioni_mcs             Tonioni's greedy search from every suffix of the hypothesis list (planograms.py:134-169)
   finalize_via_ransac     homography planogram -> image from 3 points per matched box pair, projection of every
                           expected box, per-label IoU matching (planograms.py:171-245)
 
@@ -112,6 +113,60 @@ def large_common_subgraph(g1, g2, edge_label='dir', min_score=-0.2, stop_at_frac
         if len(grown) > len(best):
             best = grown
     return best
+
+
+NO_BOUND = 2 ** 31 - 1      # the running minimum of a Tonioni run that took no step
+
+
+def tonioni_run(hypotheses, steps_of, min_score=-0.2, give_up_below=0):
+    """One start of `tonioni_mcs` (the Tonioni rule of DESIGN.md 4b) on `hypotheses`, a best-first list of (score, n1, n2):
+    the head is taken, every hypothesis sharing a node with it is dropped, every survivor that is a same-direction neighbour pair of
+    it (`steps_of(n1, n2)`) gains a full point, and the rest is ordered again -- until nothing is left or the head's score is above
+    min_score.  After each step, `bound` = len(taken) + the number of survivors that are the first with their n1 AND the first with
+    their n2 (in the order before this step's points): the size of one greedy matching of what is left, not an upper bound.
+    -> (the pairs in the order they were taken, the minimum of `bound` over the steps; NO_BOUND without a step).
+    give_up_below: the run ends as soon as the minimum falls below it (the pairs are then of no use to `tonioni_mcs`)."""
+    live, taken, low = list(hypotheses), [], NO_BOUND
+    while live and not live[0][0] > min_score:
+        _, n1, n2 = live[0]
+        taken.append((n1, n2))
+        lifted = set(steps_of(n1, n2))
+        first1, first2, free, rest = set(), set(), 0, []
+        for s, x1, x2 in live[1:]:
+            if x1 == n1 or x2 == n2:
+                continue
+            free += x1 not in first1 and x2 not in first2
+            first1.add(x1); first2.add(x2)
+            rest.append((s - 1 if (x1, x2) in lifted else s, x1, x2))
+        low = min(low, len(taken) + free)
+        if low < give_up_below:
+            break
+        live = sorted(rest)
+    return taken, low
+
+
+def tonioni_pairs(g1, g2, edge_label='dir', min_score=-0.2):
+    """`tonioni_mcs` as a list: the adopted run's pairs in the order they were taken."""
+    hypotheses = build_hypotheses(g1, g2, edge_label)
+    steps_of = lambda n1, n2: _compatible_steps(g1, g2, n1, n2, edge_label)
+    best = []
+    for i in range(len(hypotheses)):
+        if len(best) > len(hypotheses) - i:
+            break
+        taken, low = tonioni_run(hypotheses[i:], steps_of, min_score, give_up_below=len(best))
+        if low >= len(best) and len(taken) > len(best):
+            best = taken
+    return best
+
+
+def tonioni_mcs(g1, g2, edge_label='dir', min_score=-0.2):
+    """Tonioni's common-subgraph search (cvpce/planograms.py:134-169): a greedy run from every suffix of the hypothesis list, the
+    largest kept.  A run is given up once its bound falls below the best size so far; equivalently start i is adopted
+    when min_i >= best and size_i > best.  The set is filled in the order the pairs were taken, as `large_common_subgraph`'s is."""
+    grown = set()
+    for pair in tonioni_pairs(g1, g2, edge_label, min_score):
+        grown.add(pair)
+    return grown
 
 
 # ---------------------------------------------------------------------------

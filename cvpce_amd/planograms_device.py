@@ -2,7 +2,9 @@
 `planograms.large_common_subgraph` (which stay as they are: host logic over networkx).
 
   build_graphs       8-direction nearest-neighbour graphs of a batch of box sets: one launch (csrc/planogram.hip)
-  common_subgraphs   hypothesis-seeded common subgraph of a batch of (expected, actual) graph pairs: one launch, one copy back
+  common_subgraphs   hypothesis-seeded common subgraph of a batch of (expected, actual) graph pairs: one launch, one copy back;
+                     matcher='tonioni': `planograms.tonioni_mcs` instead (csrc/tonioni.hip, the Tonioni rule of DESIGN.md 4b), three
+                     launches, the same copy back
   match_on_device    the same launch without the copy back: the matchings stay on the device for `finalize_batch`
   finalize_batch     RANSAC homography, refit, projection and per-label claim of a batch (csrc/homography.hip): two launches, one
                      copy back -- the opt-in counterpart of `planograms.finalize_via_ransac` (the tail rule of DESIGN.md 4b)
@@ -26,7 +28,8 @@ is unspecified.  The device uses d = sqrt(dx*dx + dy*dy) in fp32, every operatio
 `build_graph`'s own expression.  Everything else is `build_graph`'s greedy.  Where the host's distances are exact and its rows
 tie-free, the device graph is the host graph.
 
-Graphs of more than MAX_NODES nodes are refused here; the comparator sends such an image through the host path.
+Graphs of more than MAX_NODES nodes are refused here, and so is, with matcher='tonioni', a pair of more than
+TONIONI_MAX_HYPOTHESES hypotheses; the comparator sends such an image through the host path.
 """
 from collections import Counter, namedtuple
 from types import SimpleNamespace
@@ -34,10 +37,11 @@ from types import SimpleNamespace
 import networkx as nx
 import torch
 
-from . import torch_ops_homography, torch_ops_planogram  # noqa: F401  (register torch.ops.cvpce_amd.planogram_* / homography_*)
+from . import torch_ops_homography, torch_ops_planogram, torch_ops_tonioni  # noqa: F401  (register torch.ops.cvpce_amd.planogram_* / homography_* / tonioni_*)
 from .planograms import CARDINALS
 from . import staging
 from .torch_ops_planogram import MAX_NODES
+from .torch_ops_tonioni import MAX_HYPOTHESES as TONIONI_MAX_HYPOTHESES       # the most hypotheses of a pair the Tonioni matcher takes
 
 CACHE_KEY = 'device_graph'
 BOXES_KEY = 'device_boxes'        # a planogram dict's boxes on the device (`expected_boxes_on_device`)
@@ -191,13 +195,64 @@ def _launch_record(name):
     return record
 
 
+MATCHERS = ('large', 'tonioni')
+
+
+def check_matcher(matcher):
+    if matcher not in MATCHERS:
+        raise ValueError(f'matcher is one of {MATCHERS}, got {matcher!r}')
+    return matcher
+
+
+def score8_limit(min_score):
+    """The largest integer t for which the score t / 8 is NOT above min_score, by Python's own arithmetic (as `min_agree_for`): the
+    Tonioni kernels' integer test on score8 = -agree - 8 * bumps is `tonioni_mcs`'s float test."""
+    t = int(8 * min_score // 1)
+    while not (t + 1) / 8 > min_score:
+        t += 1
+    while t / 8 > min_score:
+        t -= 1
+    return max(min(t, 2 ** 31 - 1), -2 ** 31)
+
+
+def hypothesis_count(labels1, labels2):
+    """The number of equal-label node pairs of two label lists: the hypotheses of the pair."""
+    c1, c2 = Counter(labels1), Counter(labels2)
+    return sum(c * c2[l] for l, c in c1.items() if l in c2)
+
+
 MatchLaunch = _launch_record('planogram_match')
+TonioniRun = _launch_record('tonioni_run')
+TonioniSelect = _launch_record('tonioni_select')
+
+
+class TonioniLaunch:
+    """The launches of the Tonioni matcher as one: `run` (a `TonioniRun`: the hypotheses and every start's run) and `select` (a
+    `TonioniSelect`: the choice and the adopted run's pairs), with the fields `match_on_device` reads off a `MatchLaunch`.
+    `workspace` holds, as int32 words, the hypotheses [hypotheses], (M, F) per start [hypotheses][2] and the pairs' counts [P]."""
+    __slots__ = ('run', 'select', 'label1', 'off1', 'label2', 'off2', 'out_off', 'pairs', 'count', 'workspace', 'hyp_off')
+
+    def __init__(self, run, select, hyp_off):
+        self.run, self.select, self.hyp_off = run, select, hyp_off
+        self.label1, self.off1, self.label2, self.off2 = run.label1, run.off1, run.label2, run.off2
+        self.out_off, self.pairs, self.count, self.workspace = select.out_off, select.pairs, select.count, run.workspace
+
+    def launch(self):
+        self.run.launch()
+        self.select.launch()
+
+    def per_start(self, p):
+        """-> (M, F) of pair p's starts as an (H, 2) int32 device tensor (H: the host's count or bound of the pair)"""
+        total = self.hyp_off[-1]
+        return self.workspace[total:3 * total].view(-1, 2)[self.hyp_off[p]:self.hyp_off[p + 1]]
 RansacLaunch = _launch_record('homography_ransac')
 FinishLaunch = _launch_record('homography_finish')          # (its outputs are `TailLayout.views` of the tail's blob)
 
 
-def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, expected_ids=None):
+def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, expected_ids=None, matcher='large'):
     """Everything `planogram_match` needs, uploaded -> (`MatchLaunch`, its output tensor = pairs then counts, row offsets).
+    matcher='tonioni': everything `tonioni_run` and `tonioni_select` need instead -> (`TonioniLaunch`, ...): the same tables, one
+    score8 limit per pair as params, and the Tonioni workspace; stop_at_fraction is not read.
     actuals (a `DeviceActuals`, with expected_ids = `expected_label_ids`' (ids, largest multiplicity) per planogram): the actual side's
     ids and offsets are the pack's own, the expected ids come from the classifier's id space, and the hypothesis workspace is sized by
     the host's bound n2 x (largest multiplicity of an expected label) -- the kernel counts the hypotheses itself."""
@@ -224,33 +279,43 @@ def _prepare_match(expected, actual, min_score, stop_at_fraction, actuals=None, 
             hyps.append(sum(c * c2[l] for l, c in c1.items() if l in c2))
         else:
             hyps.append(b * expected_ids[p][1])
-        params += [min_agree_for(min_score), int(min(a, b) * stop_at_fraction)]
+        params += [min_agree_for(min_score), int(min(a, b) * stop_at_fraction)] if matcher == 'large' else [score8_limit(min_score)]
     hyp_off, out_off = staging.offsets(hyps), staging.offsets([min(a, b) for a, b in zip(n1, n2)])
     if hyp_off[-1] >= 2 ** 31:
         raise ValueError('too many equal-label node pairs for one launch: split the batch')
+    if matcher != 'large' and max(hyps) > TONIONI_MAX_HYPOTHESES:
+        raise ValueError(f'the Tonioni matcher takes at most {TONIONI_MAX_HYPOTHESES} hypotheses per pair, got {max(hyps)}')
     small = _upload_tables(device, label1=lab1, label2=lab2, off1=off1, off2=off2 if actuals is None else [], params=params,
                            hyp_off=hyp_off, out_off=out_off)
     label2, dev_off2 = (small.label2, small.off2) if actuals is None else (actuals.label, actuals.off2)
     nbr1, stamp1 = _packed(expected, device)
     nbr2, stamp2 = _packed(actual, device)
-    workspace = torch.empty(max(hyp_off[-1], 1), dtype=torch.int32, device=device)
+    words = max(hyp_off[-1], 1) if matcher == 'large' else max(torch_ops_tonioni.workspace_words(hyp_off[-1], len(n1)), 1)
+    workspace = torch.empty(words, dtype=torch.int32, device=device)
     out = torch.empty(out_off[-1] * 2 + len(n1), dtype=torch.int32, device=device)      # the pairs, then the counts: one copy back
     pairs, count = out[:out_off[-1] * 2].view(-1, 2), out[out_off[-1] * 2:]
+    if matcher != 'large':
+        common = dict(nbr1=nbr1, off1=small.off1, nbr2=nbr2, off2=dev_off2, params=small.params, hyp_off=small.hyp_off, max_n1=max(n1),
+                      max_n2=max(n2), max_hyp=max(hyps), hypotheses=hyp_off[-1], workspace=workspace)
+        run = TonioniRun(label1=small.label1, label2=label2, **common)
+        return TonioniLaunch(run, TonioniSelect(out_off=small.out_off, pairs=pairs, count=count, **common), hyp_off), out, out_off
     match = MatchLaunch(nbr1=nbr1, stamp1=stamp1, label1=small.label1, off1=small.off1, nbr2=nbr2, stamp2=stamp2, label2=label2, off2=dev_off2,
                         params=small.params, hyp_off=small.hyp_off, out_off=small.out_off, max_n1=max(n1), max_n2=max(n2),
                         hypotheses=hyp_off[-1], workspace=workspace, pairs=pairs, count=count)
     return match, out, out_off
 
 
-def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
+def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, matcher='large'):
     """`planograms.large_common_subgraph(g1, g2)` for every (g1, g2) of zip(expected, actual) -- lists of `Graph` -- in one launch
     and one device-to-host copy -> list of sets of (expected node, actual node).  A set is filled in the order its pairs grew, as
-    the host's is (the order a set is built in decides the order it is iterated in)."""
+    the host's is (the order a set is built in decides the order it is iterated in).
+    matcher='tonioni': `planograms.tonioni_mcs(g1, g2)` instead, in the same copy and wait; stop_at_fraction has no meaning for that
+    search and is ignored."""
     if len(expected) != len(actual):
         raise ValueError('one actual graph per expected graph')
     if not expected:
         return []
-    matching = match_on_device(expected, actual, min_score, stop_at_fraction)
+    matching = match_on_device(expected, actual, min_score, stop_at_fraction, matcher=matcher)
     out, out_off = matching.out, matching.rows
     host = torch.empty(out.shape, dtype=torch.int32).pin_memory()
     host.copy_(out, non_blocking=True)
@@ -269,18 +334,21 @@ def common_subgraphs(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2):
 class DeviceMatching:
     """The matchings of a batch as the match kernel left them on the device: `pairs` [rows][2], `count` [P], `out_off` [P+1] (int32,
     views of `out` = pairs then counts), the label-id tables `label1` / `label2` with their offsets `off1` / `off2`, and on the host
-    the node counts `n1` / `n2` and the row offsets `rows`."""
-    __slots__ = ('pairs', 'count', 'out_off', 'out', 'label1', 'off1', 'label2', 'off2', 'n1', 'n2', 'rows')
+    the node counts `n1` / `n2` and the row offsets `rows`.  `launch`: the `MatchLaunch` or `TonioniLaunch` that made it."""
+    __slots__ = ('pairs', 'count', 'out_off', 'out', 'label1', 'off1', 'label2', 'off2', 'n1', 'n2', 'rows', 'launch')
 
 
-def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, actuals=None, expected_ids=None):
+def match_on_device(expected, actual, min_score=-0.2, stop_at_fraction=1 / 2, actuals=None, expected_ids=None, matcher='large'):
     """The launch of `common_subgraphs` alone -> `DeviceMatching`; nothing is copied back and nothing is waited for.
-    actuals / expected_ids: the actual side is a `DeviceActuals` (`actual` = its graphs), see `_prepare_match`."""
+    actuals / expected_ids: the actual side is a `DeviceActuals` (`actual` = its graphs), see `_prepare_match`.
+    matcher='tonioni': the launches of the Tonioni matcher instead, the same `DeviceMatching` (stop_at_fraction is ignored); with a
+    `DeviceActuals` the launch is sized by the host's bound and the workgroups beyond a pair's real hypothesis count exit."""
     if len(expected) != len(actual) or not expected:
         raise ValueError('one actual graph per expected graph, at least one pair')
-    match, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction, actuals, expected_ids)
+    match, out, out_off = _prepare_match(expected, actual, min_score, stop_at_fraction, actuals, expected_ids, check_matcher(matcher))
     match.launch()
     m = DeviceMatching()
+    m.launch = match
     m.label1, m.off1, m.label2, m.off2 = match.label1, match.off1, match.label2, match.off2
     m.out_off, m.pairs, m.count = match.out_off, match.pairs, match.count
     m.out, m.rows, m.n1, m.n2 = out, out_off, [len(g) for g in expected], [len(g) for g in actual]

@@ -404,8 +404,16 @@ class PlanogramComparator:
     """production.py:76-116: graph matching -> RANSAC homography -> per-label IoU matching -> optional re-classification
     of the expected-but-undetected positions (a second trip through the crop / embed / match kernels)."""
 
-    def __init__(self, graph_threshold=0.5, device_graphs=False, device_tail=False, device_reclass=False):
-        """device_graphs (opt-in): the neighbour graphs and the common subgraph come from the kernels of `planograms_device` (its
+    MATCHERS = ('large', 'tonioni')
+
+    def __init__(self, graph_threshold=0.5, device_graphs=False, device_tail=False, device_reclass=False, matcher='large'):
+        """matcher: 'large' -- `planograms.large_common_subgraph`, the first sufficiently large common subgraph, the default -- or
+        'tonioni' -- `planograms.tonioni_mcs`, the largest of the greedy runs from every hypothesis on: a larger matching on shelves
+        with many facings of few products, at a much higher cost on the host (the Tonioni rule of DESIGN.md 4b).  On every device
+        route the matching then comes from the Tonioni kernels; an image with more hypotheses (equal-label node pairs; with device
+        detections: the bound n2 x the largest multiplicity of an expected label) than `planograms_device.TONIONI_MAX_HYPOTHESES`
+        takes the host path and counts in `host_routed`.
+        device_graphs (opt-in): the neighbour graphs and the common subgraph come from the kernels of `planograms_device` (its
         documented rule at equal distances); the homography and everything after it stay the host's.  `host_routed`
         counts the images that took the host path with the switch on (a graph of more than 1024 nodes).
         device_tail (opt-in, needs device_graphs): the homography, the projection and the per-label claim run on the device too
@@ -416,6 +424,8 @@ class PlanogramComparator:
         planned behind the tail, cropped to bf16 embedder input, embedded by one schedule, matched by one GEMM and compared as label
         ids; a window costs two waits.  `reclass_host_routed` counts the windows that took the per-image re-classification with the
         switch on (an annotation or an expected label that cannot be hashed into the id space)."""
+        if matcher not in self.MATCHERS:
+            raise ValueError(f'matcher is one of {self.MATCHERS}, got {matcher!r}')
         if device_tail and not device_graphs:
             raise ValueError('device_tail needs device_graphs: the tail kernels read the matching where the match kernel left it')
         if device_reclass and not device_tail:
@@ -424,6 +434,7 @@ class PlanogramComparator:
         self.device_graphs = device_graphs
         self.device_tail = device_tail
         self.device_reclass = device_reclass
+        self.matcher = matcher
         self.host_routed = 0
         self.reclass_host_routed = 0
 
@@ -439,7 +450,16 @@ class PlanogramComparator:
         ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'],
                                                                                   self.graph_threshold)
         ga = planograms.build_graph(actual['boxes'], actual['labels'], self.graph_threshold)
-        return self._finish(planograms.large_common_subgraph(ge, ga), expected, actual, image, classifier)
+        return self._finish(self._host_matching(ge, ga), expected, actual, image, classifier)
+
+    def _host_matching(self, ge, ga):
+        from . import planograms
+        return planograms.tonioni_mcs(ge, ga) if self.matcher == 'tonioni' else planograms.large_common_subgraph(ge, ga)
+
+    def _over_limit(self, hypotheses):
+        """whether a pair of `hypotheses` hypotheses (or that bound) has no device form under this comparator's matcher"""
+        from . import planograms_device as pd
+        return self.matcher == 'tonioni' and hypotheses > pd.TONIONI_MAX_HYPOTHESES
 
     def compare_batch(self, expecteds, actuals, images=None, classifier=None):
         """[compare(e, a, img, classifier) for ...] with the graph stages of the whole batch in two launches (all graphs, all matchings)
@@ -483,7 +503,8 @@ class PlanogramComparator:
         for i, (e, a, img) in enumerate(zip(expecteds, actuals, images)):
             if not len(a['boxes']):
                 results[i] = self._no_detections(e, report)
-            elif not 1 <= len(e['boxes']) <= pd.MAX_NODES or len(a['boxes']) > pd.MAX_NODES:
+            elif (not 1 <= len(e['boxes']) <= pd.MAX_NODES or len(a['boxes']) > pd.MAX_NODES
+                  or (self.matcher != 'large' and self._over_limit(pd.hypothesis_count(e['labels'], a['labels'])))):
                 self.host_routed += 1
                 results[i] = self._host(e, a, img, classifier, report)
             else:
@@ -498,7 +519,7 @@ class PlanogramComparator:
             if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
                 ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
                 return self._device_window(results, todo, ge, ga, expecteds, actuals, images, classifier, ids, report)
-            matchings = pd.common_subgraphs(ge, ga)
+            matchings = pd.common_subgraphs(ge, ga, matcher=self.matcher)
             for i, matching in zip(todo, matchings):
                 if report:
                     results[i] = self._report_host(expecteds[i], actuals[i], images[i], classifier, matching)
@@ -527,7 +548,7 @@ class PlanogramComparator:
         if matching is None:
             ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'], self.graph_threshold)
             ga = planograms.build_graph(actual['boxes'], actual['labels'], self.graph_threshold)
-            matching = planograms.large_common_subgraph(ge, ga)
+            matching = self._host_matching(ge, ga)
         if not len(matching):
             return ComplianceReport(0, 'no_matching')
         tail = planograms.finalize_via_ransac(matching, expected['boxes'], actual['boxes'], expected['labels'], actual['labels'],
@@ -605,6 +626,10 @@ class PlanogramComparator:
         ids = pd.expected_label_ids([expecteds[i] for i in todo], classifier) if todo else None
         if ids is None:
             routed, todo = sorted(routed + todo), []
+        elif self.matcher != 'large':           # (the launch is sized by the bound n2 x largest multiplicity: that is what must fit)
+            over = [self._over_limit(actuals.n2[i] * e[1]) for i, e in zip(todo, ids)]
+            routed = sorted(routed + [i for i, o in zip(todo, over) if o])
+            todo, ids = [i for i, o in zip(todo, over) if not o], [e for e, o in zip(ids, over) if not o]
         for i in routed:
             self.host_routed += 1
             boxes, labels = actuals.to_host(i, classifier.annotations)
@@ -633,7 +658,10 @@ class PlanogramComparator:
         found.sum() / len(found); every other image, and a window without positions, ends in `_finish`."""
         from . import planograms_device as pd
         on_host = not isinstance(actuals, pd.DeviceActuals)
-        matching = pd.match_on_device(ge, ga) if on_host else pd.match_on_device(ge, ga, actuals=actuals, expected_ids=expected_ids)
+        if on_host:
+            matching = pd.match_on_device(ge, ga, matcher=self.matcher)
+        else:
+            matching = pd.match_on_device(ge, ga, actuals=actuals, expected_ids=expected_ids, matcher=self.matcher)
         table = [self._image_row(images[i], classifier) for i in todo] if report or reclass_ids is not None else None
         out = pd.finalize_batch(ge, ga, matching, [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
                                 [actuals[i]['boxes'] for i in todo] if on_host else actuals, [self._reproj_threshold(images[i]) for i in todo],
