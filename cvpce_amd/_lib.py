@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI of libcvpce_hip.so: one signature table per header of include/, in `HEADERS` (include/ext/: in
-`EXTENSION_HEADERS`).
+`EXTENSION_HEADERS` and `PICTURE_EXTENSION_HEADERS`).
 
 The HIP library is the product: there is NO CPU fallback.  Importing this
 module without a built `libcvpce_hip.so` raises immediately (build it with
@@ -185,7 +185,13 @@ EXTENSION_HEADERS = {'ext/cvpce_amd_tonioni.h': {
     'cvpce_tonioni_select': (c_int, [_ip] * 7 + [c_int] * 7 + [c_longlong, _vp, c_size_t, _ip, _ip, _vp]),
 }}
 
-for _table in list(HEADERS.values()) + list(EXTENSION_HEADERS.values()):
+# The step pictures' strokes.  A registry of its own beside EXTENSION_HEADERS: tests/test_tonioni_cpu.py pins that one to the
+# matcher's header alone, as tests/test_abi_mirror_cpu.py pins HEADERS; a change that is free to edit both folds the three together.
+PICTURE_EXTENSION_HEADERS = {'ext/cvpce_amd_strokes.h': {
+    'cvpce_strokes_draw': (c_int, [_vp, c_int, c_longlong, _vp, c_longlong, _fp, _ip, _ip, c_int, _vp]),
+}}
+
+for _table in list(HEADERS.values()) + list(EXTENSION_HEADERS.values()) + list(PICTURE_EXTENSION_HEADERS.values()):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(lib, _name)   # AttributeError here = header/library mismatch: fail loudly
         _fn.restype = _res

@@ -3,9 +3,11 @@ cli/dihe.py:257-309,382-423, cli/eval.py:12-71,168-240): the same command names,
 reference for
 
     cvpce gln eval | gln detect | gln seek-sku110k-outliers | dihe eval | dihe prebuild-index | eval-product-detection |
-    eval-planograms | rebuild-scene
+    eval-planograms | rebuild-scene | plot-planogram-eval | misc pipeline-demo
 
-Training, hyper-parameter search, dataset visualisation and plotting commands are out of scope (`gln seek-sku110k-outliers` scores
+(the last two write the step pictures of `rendering.StepPictures` to --out PREFIX instead of opening matplotlib windows; the demo's
+embedding scatter plots are not drawn, and `misc pipeline-demo --scale-gallery` goes beyond the reference, see its help text).
+Training, hyper-parameter search, dataset visualisation and the other plotting commands are out of scope (`gln seek-sku110k-outliers` scores
 the three training losses forward only, in eval mode, and adds --batch-size and --dataloader-workers: cli/gln.py:309-377).  Options that only steer
 the reference's matplotlib (`--plots`, `--plot-res-reduction`) are accepted and ignored: every metric is printed.
 `--dataloader-workers` is the number of reader THREADS of `feeding.ImageFeeder`: the shelf images are opened in the 8-bit
@@ -632,22 +634,24 @@ def _plano_sets(datatype, img_dir, test_imgs, test_annotations, planograms):
     return datautils.InternalPlanoSet(planograms, image_format='uint8'), datautils.InternalTrainSet(img_dir[0], include_annotations=True, image_format='uint8')
 
 
-def _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index):
+def _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index, graph_threshold=0.5):
     proposal_generator = proposals_eval.load_gln(gln_state, False)
     proposal_generator.requires_grad_(False)
     generator = production.ProposalGenerator(proposal_generator)
     classifier = production.Classifier(_load_encoder(dihe_state), sampleset, batch_size=8, load=load_classifier_index)
-    return production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(device_graphs=_device_graphs_switch(),
+    return production.PlanogramEvaluator(generator, classifier, production.PlanogramComparator(graph_threshold=graph_threshold,
+                                                                                          device_graphs=_device_graphs_switch(),
                                                                                           device_tail=_device_tail_switch(),
                                                                                           device_reclass=_device_reclass_switch(),
                                                                                           matcher=_matcher_name()),
                                          device_detections=_device_detections_switch())
 
 
-def _scene_renderer(evaluator, sampleset, workers):
+def _scene_renderer(evaluator, sampleset, workers, **atlas_options):
     """the gallery's product images on the device, row by row the classifier's, and the compositor over them"""
     from .. import rendering
-    atlas = rendering.ThumbnailAtlas(sampleset, evaluator.classifier.annotations, evaluator.proposal_generator.device, num_workers=workers)
+    atlas = rendering.ThumbnailAtlas(sampleset, evaluator.classifier.annotations, evaluator.proposal_generator.device, num_workers=workers,
+                                     **atlas_options)
     return rendering.SceneRenderer(atlas)
 
 
@@ -749,6 +753,104 @@ def eval_planograms(img_dir, test_imgs, test_annotations, planograms, datatype, 
         report_out.close()
     print(f'--> Mean accuracy {total_a / len(planoset)}')
     print(f'--> MSE: {total_e / len(planoset)}')
+
+
+_STEP_NAMES = 'detections, positions, expected_graph, observed_graph, expected_matched, observed_matched, annotated, observed and expected'
+
+
+@cli.command(cls=_DeviceDetectionsCommand)
+@click.option('--img-dir', type=click.Path(**_DIR), multiple=True, default=GP_TRAIN_FOLDERS, show_default=True,
+              help='Path to training image root')
+@click.option('--test-imgs', type=click.Path(**_DIR), default=GP_TEST_DIR, show_default=True, help='Path to test image root')
+@click.option('--test-annotations', type=click.Path(**_DIR), default=GP_ANN_DIR, show_default=True, help='Path to annotation root')
+@click.option('--planos', type=click.Path(**_DIR), default=GP_PLANO_DIR, show_default=True, help='Path to planograms root')
+@click.option('--datatype', type=click.Choice(('gp', 'internal')), default='gp', show_default=True,
+              help='Dataset type; gp for Grocery Product, internal for our internal dataset')
+@click.option('--load-classifier-index', type=click.Path(),
+              help='Load pre-embedded images from given path instead of calculating the embedding on the fly')
+@click.option('--plano-idx', type=int, help='Visualize image with given index instead of choosing randomly')
+@click.option('--out', type=click.Path(writable=True), required=True,
+              help=f'Prefix of the pictures: PREFIX_<name>.png is written for {_STEP_NAMES}')
+@click.argument('gln-state', type=click.Path(**_FILE))
+@click.argument('dihe-state', type=click.Path(**_FILE))
+def plot_planogram_eval(img_dir, test_imgs, test_annotations, planos, datatype, load_classifier_index, plano_idx, out, gln_state, dihe_state):
+    """Visualize planogram compliance evaluation steps.
+
+    Does the proposed planogram compliance evaluation procedure step by step and writes a picture for each step: the detections and
+    the projected expected positions on the shelf image, the neighbour graphs and the matched common subgraph drawn over the rebuilt
+    expected and observed planograms, and the pictures of rebuild-scene.  Prints the compliance."""
+    import random
+    planoset, sampleset = _plano_sets(datatype, img_dir, test_imgs, test_annotations, planos)
+    if plano_idx is None:
+        plano_idx = random.randrange(len(planoset))
+    if not 0 <= plano_idx < len(planoset):
+        raise click.UsageError(f'--plano-idx {plano_idx}: the set has {len(planoset)} images')
+    evaluator = _plano_evaluator(gln_state, dihe_state, sampleset, load_classifier_index)
+    renderer = _scene_renderer(evaluator, sampleset, _reader_threads())
+    d = planoset[plano_idx]
+    img, plano = (d[0], d[3]) if datatype == 'gp' else tuple(d)
+    report, pictures = evaluator.step_pictures(img, plano, renderer)
+    for path in pictures.save(out):
+        print(path)
+    print(_accuracy_line(float(report.compliance), plano))
+
+
+@cli.group()
+def misc():
+    """Miscellaneous commands."""
+
+
+PIPELINE_DEMO_GRAPH_THRESHOLD = 0.7       # cli/misc.py:177-178
+
+
+@misc.command(cls=_DeviceDetectionsCommand)
+@click.option('--out', type=click.Path(writable=True), required=True,
+              help=f'Prefix of the pictures: PREFIX_<name>.png is written for {_STEP_NAMES}')
+@click.option('--scale-gallery/--no-scale-gallery', default=False, show_default=True,
+              help='Embed the product photos in [-1, 1] (scale_to_tanh), the range the encoder sees its queries in.  Off, the default, '
+                   'is what the reference does: it embeds this gallery in [0, 1] although the queries are in [-1, 1].')
+@click.argument('gln-state', type=click.Path(**_FILE))
+@click.argument('dihe-state', type=click.Path(**_FILE))
+@click.argument('dataset-folder', type=click.Path(**_DIR))
+@click.argument('image-file', type=click.Path(**_FILE))
+@click.argument('plano-file', type=click.Path(**_FILE))
+def pipeline_demo(out, scale_gallery, gln_state, dihe_state, dataset_folder, image_file, plano_file):
+    """Demonstrate the CVPCE pipeline.
+
+    The dataset folder is expected to contain .png, .jpg and .jpeg files,
+    one for each class, with the class label set as the filename.
+
+    The planogram file should be a JSON file formatted in a manner such as
+
+    \b
+    [
+        {
+            "label": "class1",
+            "box": [0, 0, 5, 5]
+        },
+        {
+            "label": "class2",
+            "box": [5, 0, 10, 5]
+        }
+    ]
+
+    (in this case, the dataset folder should contain files for class1 and class2,
+    such as class1.png and class2.jpg)
+
+    Writes the step pictures of plot-planogram-eval and prints the compliance.  The two embedding scatter plots of the reference's
+    demo are not drawn."""
+    dataset = datautils.SimpleFolderSet(dataset_folder, scale=scale_gallery)
+    rebuildset = datautils.SimpleFolderSet(dataset_folder, train=False)
+    if not len(dataset):
+        raise click.UsageError(f'{dataset_folder} holds no .png, .jpg or .jpeg file')
+    evaluator = _plano_evaluator(gln_state, dihe_state, dataset, None, graph_threshold=PIPELINE_DEMO_GRAPH_THRESHOLD)
+    renderer = _scene_renderer(evaluator, rebuildset, _reader_threads(), float_items='unit')
+    img = datautils._image_reader('uint8')(datautils._open_image(image_file))
+    plano = datautils.read_planogram_json(plano_file)
+    report, pictures = evaluator.step_pictures(img, plano, renderer)
+    for path in pictures.save(out):
+        print(path)
+    print(f'Compliance: {float(report.compliance):.3f} ({report.status})')
 
 
 if __name__ == '__main__':

@@ -536,3 +536,60 @@ class InternalTrainSet(GroceryProductsDataset):
         if self.include_annotations:
             return t, t, self.categories[i], self.annotations[i]
         return t, t, self.categories[i]
+
+
+class SimpleFolderSet:
+    """datautils.py:484-512, the bring-your-own-data gallery of `misc pipeline-demo`: a folder of product photos named after their
+    label -- `<label>.png`, `.jpg` or `.jpeg` (`types`; the label is the file name without that ending, whatever else it holds).
+    Items: (img, img, label, label), doubled as the other sets' are; transparent pixels (alpha 0) become white and the alpha plane is
+    dropped.  train=False: the image as it is, float (3, h, w) in [0, 1] of any size -- what the scene is rebuilt from
+    (`rendering.ThumbnailAtlas(..., float_items='unit')`).  train=True: `resize_for_classification` of it, (3, 256, 256) in [0, 1] on
+    `device` (the kernel has no host form) -- what the reference embeds as its gallery, although the encoder's queries are in [-1, 1]
+    (SURVEY.md Appendix B); scale=True applies `scale_to_tanh` (x * 2 - 1) to such an item, the range the encoder was trained on.
+    Directory entries are visited in sorted order, as this module's other sets visit them (the reference takes os.scandir order)."""
+
+    def __init__(self, root, train=True, types=('.png', '.jpg', '.jpeg'), device='cuda', scale=False):
+        self.paths, self.classes = self.build_index(root, types)
+        self.train, self.device, self.scale = train, device, scale
+
+    @staticmethod
+    def build_index(root, types):
+        name_re = _re.compile('^(.*)(' + '|'.join(_re.escape(t) for t in types) + ')$')
+        paths, classes = [], []
+        for name in sorted(_os.listdir(root)):
+            m = name_re.match(name)
+            if m is None or not _os.path.isfile(_os.path.join(root, name)):
+                continue
+            paths.append(_os.path.join(root, name))
+            classes.append(m.group(1))
+        return paths, classes
+
+    def index_for_ann(self, ann):
+        return self.classes.index(ann)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        c = self.classes[i]
+        img = pil_to_tensor(_open_image(self.paths[i]))
+        if len(img) > 3:
+            img[:, img[3] == 0] = 1
+            img = img[:3]                       # drop alpha
+        elif len(img) == 1:
+            img = img.expand(3, -1, -1).contiguous()
+        if self.train:
+            img = resize_for_classification(img.to(self.device))
+            if self.scale:
+                img = img * 2 - 1
+        return img, img, c, c
+
+
+def read_planogram_json(path):
+    """The planogram file of `misc pipeline-demo` (cli/misc.py:127-139, 171-174): a JSON list of {"label": ..., "box": [x1, y1, x2, y2]}
+    -> {'boxes': float32 (n, 4), 'labels': list of n} as the comparator takes it."""
+    with open(path) as f:
+        plano = _json.load(f)
+    if not isinstance(plano, list) or not all(isinstance(o, dict) and 'label' in o and 'box' in o and len(o['box']) == 4 for o in plano):
+        raise ValueError(f'{path}: a planogram is a JSON list of {{"label": ..., "box": [x1, y1, x2, y2]}}')
+    return {'boxes': torch.tensor([o['box'] for o in plano], dtype=torch.float32).reshape(-1, 4), 'labels': [o['label'] for o in plano]}

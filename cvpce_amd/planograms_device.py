@@ -12,6 +12,8 @@
                      embed / match pass): one more wait -- the opt-in counterpart of the per-image loop of `PlanogramComparator._finish`
   finalize_result    a record of `finalize_batch` as the tuple `finalize_via_ransac` returns
   to_networkx        a device graph as the DiGraph the host functions expect (node order 0..n-1, adjacency in stamp order)
+  nbr_table, matched_of_pairs, matched_nodes    what the step pictures draw: a host graph's neighbour table, and the matched nodes of a
+                     host matching and of a `DeviceMatching` (the latter on the device, without a wait)
   prepare            caches a planogram's device graph in its dict, as `expected['graph']` caches the host graph
   DeviceActuals      a window's detections as `BatchedPipeline.run(actuals=True)` left them on the device (csrc/actuals.hip): the actual
                      side of `build_graphs`, `match_on_device` and `finalize_batch` without a copy to the host (the detections rule of
@@ -638,6 +640,37 @@ def to_networkx(graph):
     for i, s in sorted(filled, key=lambda e: int(stamp[e[0], e[1]])):
         g.add_edge(i, int(nbr[i, s]), dir=CARDINALS[s], weight=weight[i, s])
     return g
+
+
+def nbr_table(g):
+    """`to_networkx` backwards, the neighbours alone: a host DiGraph of `planograms.build_graph` (nodes 0..n-1, at most one edge per node
+    and direction) -> its `nbr` [n][8] int32 table on the host, -1 = empty: what the step pictures draw (`rendering.graph_strokes`)."""
+    table = torch.full((g.number_of_nodes(), len(CARDINALS)), -1, dtype=torch.int32)
+    for i, j, d in g.edges(data='dir'):
+        table[i, CARDINALS.index(d)] = j
+    return table
+
+
+def matched_of_pairs(pairs, n1, n2):
+    """a matching as the host has it -- (expected node, actual node) pairs -> (matched expected nodes (n1,), matched actual nodes (n2,)),
+    bool, on the host"""
+    me, ma = torch.zeros(n1, dtype=torch.bool), torch.zeros(n2, dtype=torch.bool)
+    for a, b in pairs:
+        me[a], ma[b] = True, True
+    return me, ma
+
+
+def matched_nodes(matching, p):
+    """`matched_of_pairs` for pair p of a `DeviceMatching`, on the device and without a wait: the rows of `pairs` beyond the pair's
+    count hold -1 and mark nothing."""
+    rows = matching.pairs[matching.rows[p]:matching.rows[p + 1]].to(torch.int64)
+    out = []
+    for col, n in ((0, matching.n1[p]), (1, matching.n2[p])):
+        node = rows[:, col]
+        marks = torch.zeros(n + 1, dtype=torch.bool, device=rows.device)                   # (slot n: the rows that name no node)
+        marks.index_fill_(0, torch.where((node >= 0) & (node < n), node, torch.full_like(node, n)), True)
+        out.append(marks[:n])
+    return tuple(out)
 
 
 def prepare(expected, thresh_size=0.5, device=None):

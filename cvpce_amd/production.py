@@ -400,6 +400,22 @@ class ComplianceReport:
         return d
 
 
+class ComparisonSteps:
+    """What the step pictures need of one comparison beside its report (`PlanogramComparator.steps`): the two neighbour graphs as
+    `nbr` [n][8] int32 tables (-1 = empty; `planograms_device.Graph.nbr`) and the nodes the matcher paired, bool (n1,) and (n2,) --
+    each on the device where the route left it (the device routes never copy them back), on the host from the host routes."""
+    __slots__ = ('expected_nbr', 'actual_nbr', 'matched_expected', 'matched_actual')
+
+    def __init__(self, expected_nbr, actual_nbr, matched_expected, matched_actual):
+        self.expected_nbr, self.actual_nbr, self.matched_expected, self.matched_actual = expected_nbr, actual_nbr, matched_expected, matched_actual
+
+    @classmethod
+    def of_host(cls, ge, ga, matching):
+        """from the host's networkx graphs and its set of (expected node, actual node) pairs"""
+        from . import planograms_device as pd
+        return cls(pd.nbr_table(ge), pd.nbr_table(ga), *pd.matched_of_pairs(matching, ge.number_of_nodes(), ga.number_of_nodes()))
+
+
 class PlanogramComparator:
     """production.py:76-116: graph matching -> RANSAC homography -> per-label IoU matching -> optional re-classification
     of the expected-but-undetected positions (a second trip through the crop / embed / match kernels)."""
@@ -486,18 +502,33 @@ class PlanogramComparator:
         `compare_batch` sends through the host gets the host report."""
         return self._batch(expecteds, actuals, images, classifier, report=True)
 
-    def _host(self, expected, actual, image, classifier, report):
-        return self._report_host(expected, actual, image, classifier) if report else self._compare_host(expected, actual, image, classifier)
+    def steps(self, expected, actual, image=None, classifier=None):
+        """`report` with what the step pictures draw -> (`ComplianceReport`, `ComparisonSteps`, or None for an image without
+        detections: it has no graph to draw)."""
+        return self.steps_batch([expected], [actual], [image], classifier)[0]
 
-    def _batch(self, expecteds, actuals, images, classifier, report=False):
-        """`compare_batch` (report off: verdicts) and `report_batch` (report on: `ComplianceReport`s) on one route."""
+    def steps_batch(self, expecteds, actuals, images=None, classifier=None):
+        """[steps(e, a, img, classifier) for ...] on the route `report_batch` takes with the same switches, its reports, launches and
+        waits: the graphs and the matching are kept where the route has them anyway -- the device routes' stay on the device."""
+        kept = [None] * len(expecteds)
+        return list(zip(self._batch(expecteds, actuals, images, classifier, report=True, steps=kept), kept))
+
+    def _host(self, expected, actual, image, classifier, report, steps=None, at=None):
+        """steps, at: the list `steps_batch` fills and this image's place in it (report on)"""
+        if not report:
+            return self._compare_host(expected, actual, image, classifier)
+        return self._report_host(expected, actual, image, classifier, steps=steps, at=at)
+
+    def _batch(self, expecteds, actuals, images, classifier, report=False, steps=None):
+        """`compare_batch` (report off: verdicts) and `report_batch` (report on: `ComplianceReport`s) on one route.  steps: a list with
+        one place per image where `steps_batch` wants the graphs and the matching kept (`ComparisonSteps`)."""
         images = [None] * len(expecteds) if images is None else images
         if not isinstance(actuals, (list, tuple)):
             from . import planograms_device
             if isinstance(actuals, planograms_device.DeviceActuals):          # (detections that never left the device)
-                return self._compare_device_actuals(expecteds, actuals, images, classifier, report)
+                return self._compare_device_actuals(expecteds, actuals, images, classifier, report, steps)
         if not self.device_graphs:
-            return [self._host(e, a, img, classifier, report) for e, a, img in zip(expecteds, actuals, images)]
+            return [self._host(e, a, img, classifier, report, steps, i) for i, (e, a, img) in enumerate(zip(expecteds, actuals, images))]
         from . import planograms_device as pd
         results, todo = [None] * len(expecteds), []
         for i, (e, a, img) in enumerate(zip(expecteds, actuals, images)):
@@ -506,7 +537,7 @@ class PlanogramComparator:
             elif (not 1 <= len(e['boxes']) <= pd.MAX_NODES or len(a['boxes']) > pd.MAX_NODES
                   or (self.matcher != 'large' and self._over_limit(pd.hypothesis_count(e['labels'], a['labels'])))):
                 self.host_routed += 1
-                results[i] = self._host(e, a, img, classifier, report)
+                results[i] = self._host(e, a, img, classifier, report, steps, i)
             else:
                 todo.append(i)
         if todo:
@@ -518,9 +549,11 @@ class PlanogramComparator:
             ga = built[len(build) - len(todo):]
             if self.device_tail:                # graphs -> match -> tail back to back: the matching never leaves the device in between
                 ids = self._window_label_ids([expecteds[i] for i in todo], classifier) if self.device_reclass else None
-                return self._device_window(results, todo, ge, ga, expecteds, actuals, images, classifier, ids, report)
+                return self._device_window(results, todo, ge, ga, expecteds, actuals, images, classifier, ids, report, steps=steps)
             matchings = pd.common_subgraphs(ge, ga, matcher=self.matcher)
-            for i, matching in zip(todo, matchings):
+            for p, (i, matching) in enumerate(zip(todo, matchings)):
+                if steps is not None:
+                    steps[i] = ComparisonSteps(ge[p].nbr, ga[p].nbr, *pd.matched_of_pairs(matching, len(ge[p]), len(ga[p])))
                 if report:
                     results[i] = self._report_host(expecteds[i], actuals[i], images[i], classifier, matching)
                 else:
@@ -539,9 +572,10 @@ class PlanogramComparator:
         return datautils.image_hw(image) + (1,) if on else (0, 0, 0)
 
     # ---- the compliance report (the report rule) --------------------------------------------------------------
-    def _report_host(self, expected, actual, image, classifier, matching=None):
+    def _report_host(self, expected, actual, image, classifier, matching=None, steps=None, at=None):
         """`_compare_host` with its reasons: the host tail with both of its optional returns, then `planograms.report_positions`.
-        matching: the common subgraph where it was found elsewhere (`device_graphs` alone)."""
+        matching: the common subgraph where it was found elsewhere (`device_graphs` alone).  steps, at: the list `steps_batch` fills and this
+        image's place in it: it takes the `ComparisonSteps` of the graphs and the matching made here."""
         from . import planograms
         if not len(actual['boxes']):
             return self._no_detections(expected, True)
@@ -549,6 +583,8 @@ class PlanogramComparator:
             ge = expected['graph'] if 'graph' in expected else planograms.build_graph(expected['boxes'], expected['labels'], self.graph_threshold)
             ga = planograms.build_graph(actual['boxes'], actual['labels'], self.graph_threshold)
             matching = self._host_matching(ge, ga)
+            if steps is not None:
+                steps[at] = ComparisonSteps.of_host(ge, ga, matching)
         if not len(matching):
             return ComplianceReport(0, 'no_matching')
         tail = planograms.finalize_via_ransac(matching, expected['boxes'], actual['boxes'], expected['labels'], actual['labels'],
@@ -602,7 +638,7 @@ class PlanogramComparator:
         return ComplianceReport(found.sum() / len(found), 'ok', outcome.to(torch.int8), positions, seen, seen_distance, occupant.to(torch.int32),
                                 occupant_iou, occupant_labels, torch.where(stray)[0])
 
-    def _compare_device_actuals(self, expecteds, actuals, images, classifier, report=False):
+    def _compare_device_actuals(self, expecteds, actuals, images, classifier, report=False, steps=None):
         """`compare_batch` on detections that never left the device (`planograms_device.DeviceActuals`; the detections rule of
         DESIGN.md 4b): the graph, match and tail kernels read the pack's boxes, label ids and thresholds where `actuals_pack` left
         them; the host knows the box counts alone.  An image without detections is decided here; an image whose expected or actual
@@ -633,7 +669,7 @@ class PlanogramComparator:
         for i in routed:
             self.host_routed += 1
             boxes, labels = actuals.to_host(i, classifier.annotations)
-            results[i] = self._host(expecteds[i], {'boxes': boxes, 'labels': labels}, images[i], classifier, report)
+            results[i] = self._host(expecteds[i], {'boxes': boxes, 'labels': labels}, images[i], classifier, report, steps, i)
         if not todo:
             return results
         pack = actuals.select(todo)
@@ -645,9 +681,9 @@ class PlanogramComparator:
         # (two id vectors on purpose: `ids` above numbers a label outside the gallery len(space) + rank for the match and claim kernels,
         # these give it -1 for the verdict kernel -- merging them would change what a kernel reads)
         reclass_ids = self._window_label_ids(es, classifier) if self.device_reclass else None
-        return self._device_window(results, todo, ge, ga, expecteds, pack, images, classifier, reclass_ids, report, expected_ids=ids)
+        return self._device_window(results, todo, ge, ga, expecteds, pack, images, classifier, reclass_ids, report, expected_ids=ids, steps=steps)
 
-    def _device_window(self, results, todo, ge, ga, expecteds, actuals, images, classifier, reclass_ids, report, expected_ids=None):
+    def _device_window(self, results, todo, ge, ga, expecteds, actuals, images, classifier, reclass_ids, report, expected_ids=None, steps=None):
         """The device window of the images `todo`: match -> tail (-> plan) back to back on the graphs `ge` / `ga` and
         the first wait; where the plan holds positions, crops -> embedder -> match -> verdict and the second wait
         (`planograms_device.reclassify_batch`) -> `results`, filled at `todo`.
@@ -662,6 +698,9 @@ class PlanogramComparator:
             matching = pd.match_on_device(ge, ga, matcher=self.matcher)
         else:
             matching = pd.match_on_device(ge, ga, actuals=actuals, expected_ids=expected_ids, matcher=self.matcher)
+        if steps is not None:                   # (views and a few device operators: nothing is copied back, nothing waited for)
+            for p, i in enumerate(todo):
+                steps[i] = ComparisonSteps(ge[p].nbr, ga[p].nbr, *pd.matched_nodes(matching, p))
         table = [self._image_row(images[i], classifier) for i in todo] if report or reclass_ids is not None else None
         out = pd.finalize_batch(ge, ga, matching, [pd.expected_boxes_on_device(expecteds[i], ga[0].nbr.device) for i in todo],
                                 [actuals[i]['boxes'] for i in todo] if on_host else actuals, [self._reproj_threshold(images[i]) for i in todo],
@@ -844,6 +883,71 @@ class PlanogramEvaluator:
         if window:
             yield from self.pictures_batch([img for img, _ in window], [plano for _, plano in window], renderer)
 
+    def step_pictures(self, image, planogram, renderer):
+        """`pictures` step by step -> (`ComplianceReport`, `rendering.StepPictures`): the detections and the projected positions on
+        the photo, the two neighbour graphs and the common subgraph the matcher found drawn over the rebuilt planograms, and the three
+        pictures of `pictures` -- what the reference's `plot-planogram-eval` and `misc pipeline-demo` show in matplotlib windows."""
+        return self.step_pictures_batch([image], [planogram], renderer)[0]
+
+    def step_pictures_batch(self, images, planograms, renderer):
+        """[step_pictures(image, planogram, renderer) for ...] on the route `report_batch` takes with the same switches; the reports are
+        `report_batch`'s, the last three pictures `pictures_batch`'s byte for byte, and all pictures of the window come from ONE
+        `renderer.render` call: the compositor's launch and the stroke launch over its output, no wait.  The graphs and the matching
+        are drawn from where the comparator's route left them (`PlanogramComparator.steps_batch`); an image whose report says
+        'no_detections' or 'no_matching' has no strokes, one that is not 'ok' no rings on `positions`."""
+        from . import rendering
+        images, planograms = [self._float_image(img) for img in images], list(planograms)
+        if not images:
+            return []
+        if not hasattr(self.planogram_comparator, 'steps_batch'):
+            raise TypeError('step pictures need a comparator that keeps its graphs and its matching (`PlanogramComparator.steps_batch`)')
+        table = self._label_rows()
+        if self._on_device():
+            both, dets = self._device_window(images, planograms, True, steps=True)
+        else:
+            host = self.detect_and_classify_batch(images)
+            both = self._compare_all(images, planograms, host, True, steps=True)
+            dets = [(b, rendering.rows_of_labels(labels, table)) for b, labels in host]
+        # the photos as bytes, each made once (float planes by `render`'s own rule) and joined into ONE allocation: `render` reads bases that
+        # are views of one allocation where they lie, so a photo that is the base of three canvases is not copied three times
+        photos = [(img if img.dtype == torch.uint8 else rendering.float_image_bytes(img.to(renderer.device))).to(renderer.device) for img in images]
+        pool, at = torch.cat([p.reshape(-1) for p in photos]), 0
+        lists, sizes, bases, strokes = [], [], [], []
+        for img, photo, plano, (rep, steps), (boxes, rows) in zip(images, photos, planograms, both, dets):
+            base, at = pool[at:at + photo.numel()].view(photo.shape), at + photo.numel()
+            hw = datautils.image_hw(img)
+            ehw = rendering.expected_canvas_hw(plano['boxes'], hw[1])
+            # (a list that several canvases share goes to the device once, not once per canvas)
+            annotated = rendering.annotation_items(rep, boxes, rendering.ANNOTATION_THICKNESS, hw).to(renderer.device)
+            observed = rendering.observed_items(boxes, rows).to(renderer.device)
+            expected = rendering.expected_items(plano['boxes'], rendering.rows_of_labels(plano['labels'], table), ehw).to(renderer.device)
+            ringed = lambda b, colour: rendering.ring_items(b, colour, rendering.ANNOTATION_THICKNESS, hw, boxes.device).to(renderer.device)
+            lists += [ringed(boxes, rendering.DETECTION_COLOUR), ringed(rep.expected_positions if rep.status == 'ok' else None, rendering.POSITION_COLOUR),
+                      expected, observed, expected, observed, annotated, observed, expected]
+            sizes += [hw, hw, ehw, hw, ehw, hw, hw, hw, ehw]
+            bases +=[base, base, None, None, None, None, base, None, None]
+            if steps is None or rep.status in ('no_detections', 'no_matching'):
+                strokes += [None] * 9
+            else:
+                on_canvas = rendering.expected_boxes_on_canvas(plano['boxes'], ehw)
+                ge, ga = rendering.graph_strokes(steps.expected_nbr, on_canvas), rendering.graph_strokes(steps.actual_nbr, boxes)
+                strokes += [None, None, ge, ga, rendering.matched_strokes(steps.expected_nbr, on_canvas, steps.matched_expected, whole=ge),
+                            rendering.matched_strokes(steps.actual_nbr, boxes, steps.matched_actual, whole=ga), None, None, None]
+        views = renderer.render(lists, sizes, bases, strokes=strokes)
+        return [(rep, rendering.StepPictures(*views[9 * k:9 * k + 9])) for k, (rep, _) in enumerate(both)]
+
+    def step_pictures_iter(self, pairs, renderer, lookahead=4):
+        """`step_pictures(image, planogram, renderer)` over an iterable of pairs, windowed as `pictures_iter` windows them."""
+        window = []
+        for image, planogram in pairs:
+            image = self._float_image(image)
+            if window and (len(window) >= max(1, lookahead) or datautils.image_hw(image) != datautils.image_hw(window[0][0])):
+                yield from self.step_pictures_batch([img for img, _ in window], [plano for _, plano in window], renderer)
+                window.clear()
+            window.append((image, planogram))
+        if window:
+            yield from self.step_pictures_batch([img for img, _ in window], [plano for _, plano in window], renderer)
+
     def _label_rows(self):
         """`rendering.label_rows` of the classifier's annotations, made once per index (`index_generation`)"""
         from . import rendering
@@ -914,9 +1018,10 @@ class PlanogramEvaluator:
         on them (in group order; the verdicts go back to the images' order)."""
         return self._device_window(images, planograms, report)[0]
 
-    def _device_window(self, images, planograms, report):
+    def _device_window(self, images, planograms, report, steps=False):
         """`_evaluate_on_device`'s window -> (the verdicts in the images' order, per image the (boxes, gallery rows) of its detections
-        as views of the window's device pack: what the pictures are made of, never copied to the host)."""
+        as views of the window's device pack: what the pictures are made of, never copied to the host).  steps: the verdicts are
+        `PlanogramComparator.steps_batch`'s pairs."""
         from . import planograms_device as pd
         pg, cmp = self.proposal_generator, self.planogram_comparator
         pipe = self._pipeline()
@@ -929,7 +1034,8 @@ class PlanogramEvaluator:
             packs.append(pipe.run([ops.input_image(images[i], pg.device) for i in idxs], actuals=True)['actuals'])
             order += idxs
         pack = pd.DeviceActuals.concat(packs)
-        verdicts = (cmp.report_batch if report else cmp.compare_batch)([planograms[i] for i in order], pack, [images[i] for i in order], self.classifier)
+        compare = cmp.steps_batch if steps else cmp.report_batch if report else cmp.compare_batch
+        verdicts = compare([planograms[i] for i in order], pack, [images[i] for i in order], self.classifier)
         out, dets, at = [None] * len(images), [None] * len(images), 0
         for i, v, n in zip(order, verdicts, pack.n2):
             out[i], dets[i] = v, (pack.boxes[at:at + n], pack.row[at:at + n])
@@ -950,14 +1056,15 @@ class PlanogramEvaluator:
         dets = self.detect_and_classify_batch(images)
         return self._compare_all(images, planograms, dets, report)
 
-    def _compare_all(self, images, planograms, dets, report=False):
+    def _compare_all(self, images, planograms, dets, report=False, steps=False):
         """The comparator over a window: per image, or -- a comparator with `device_graphs` on -- its `compare_batch` (report on:
-        `report` and `report_batch`)."""
+        `report` and `report_batch`; steps on: `steps` and `steps_batch`)."""
         cmp = self.planogram_comparator
         actuals = [{'boxes': b, 'labels': labels} for b, labels in dets]
         if getattr(cmp, 'device_graphs', False) and hasattr(cmp, 'compare_batch'):
-            return (cmp.report_batch if report else cmp.compare_batch)(list(planograms), actuals, list(images), self.classifier)
-        one = cmp.report if report else cmp.compare
+            batch = cmp.steps_batch if steps else cmp.report_batch if report else cmp.compare_batch
+            return batch(list(planograms), actuals, list(images), self.classifier)
+        one = cmp.steps if steps else cmp.report if report else cmp.compare
         return [one(plano, actual, img, self.classifier) for img, plano, actual in zip(images, planograms, actuals)]
 
 

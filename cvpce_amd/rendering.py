@@ -7,12 +7,21 @@ launch of csrc/render.hip by the picture rule of DESIGN.md 4b instead of one mat
                         its inputs live;
   * `SceneRenderer`     any number of canvases in one launch and no wait;
   * `CompliancePictures`    the three pictures of a shelf image, `.save(prefix)` writes them as PNG (a host copy and a host encode).
+
+The step pictures of `plot-planogram-eval` and `misc pipeline-demo` (cvpce/utils.py:181-189 `draw_planograph`: `nx.draw` at the box
+centres) add straight strokes over those canvases, drawn in place by one launch of csrc/strokes.hip by the stroke rule of DESIGN.md 4b:
+
+  * `Strokes`, `graph_strokes`, `matched_strokes`    the stroke lists of a neighbour graph and of the subgraph its matched nodes induce,
+                        pure tensor code that runs where the graph's table lives; every size is known to the host;
+  * `SceneRenderer.render(..., strokes=...)`    the second launch, over the same flat buffer;
+  * `StepPictures`      the nine pictures of a shelf image, the last three `CompliancePictures`' own.
 """
 import types
 
 import torch
 
 from . import torch_ops_render as R
+from . import torch_ops_strokes as S
 
 BLACK = 0x000000
 WHITE = 0xFFFFFF
@@ -31,6 +40,14 @@ STRAY_COLOUR = rgb(200, 0, 200)
 OUT_OF_VIEW = 3                    # the code of 'out_of_view' in ComplianceReport.outcomes
 ANNOTATION_THICKNESS = 3           # the rings of the annotated picture, in pixels
 ATLAS_MAX_BYTES = 2 ** 31 - 1      # the atlas rows' offsets are int32
+# the step pictures: the rings of the `detections` and `positions` pictures, and the graph drawings in networkx's default colours
+# (black edges under blue nodes).  A stroke's radius is in HALF pixels: a stroke of radius t is t pixels thick.
+DETECTION_COLOUR = rgb(255, 0, 0)
+POSITION_COLOUR = rgb(0, 0, 255)
+GRAPH_EDGE_COLOUR = BLACK
+GRAPH_NODE_COLOUR = rgb(31, 120, 180)
+GRAPH_EDGE_RADIUS = 2              # a 2-pixel line
+GRAPH_NODE_RADIUS = 10             # a disc 10 pixels across
 
 
 class Items:
@@ -108,15 +125,21 @@ def expected_items(planogram_boxes, rows, canvas_hw):
     """`observed_items` for the planogram itself: its boxes are mapped into the (H, W) canvas by `(b - origin) * scale`, two separately
     rounded fp32 operations, with origin = (min x1, min y1) of the planogram and scale = min(W / ew, H / eh) of its extents ew x eh (the
     aspect ratio is kept; fp32).  rows: the first gallery row of each expected label, -1 where the gallery has none."""
+    return observed_items(expected_boxes_on_canvas(planogram_boxes, canvas_hw), rows)
+
+
+def expected_boxes_on_canvas(planogram_boxes, canvas_hw):
+    """`expected_items`' mapping alone: the planogram's boxes in the pixels of the (H, W) canvas, float32 (n, 4) where the boxes live --
+    what the expected picture pastes into and what the expected graph is drawn between."""
     b = planogram_boxes.to(torch.float32).reshape(-1, 4)
     if not b.shape[0]:
-        return observed_items(b, rows)
+        return b
     h, w = canvas_hw
     origin = torch.stack([b[:, 0].min(), b[:, 1].min()])
     ext = torch.stack([b[:, 2].max(), b[:, 3].max()]) - origin
     scale = torch.minimum(torch.tensor(float(w), dtype=torch.float32, device=b.device) / ext[0],
                           torch.tensor(float(h), dtype=torch.float32, device=b.device) / ext[1])
-    return observed_items((b - origin.repeat(2)) * scale, rows)
+    return (b - origin.repeat(2)) * scale
 
 
 def annotation_items(report, actual_boxes, thickness=3, canvas_hw=None):
@@ -137,6 +160,85 @@ def annotation_items(report, actual_boxes, thickness=3, canvas_hw=None):
     colours = torch.tensor([OUTCOME_COLOURS[name] for name in report.OUTCOMES], dtype=torch.int32)[outcomes[order]]
     positions = _items(report.expected_positions[order].to(dev), R.SRC_NONE, colours, thickness)
     return Items.cat([base, stray, positions])
+
+
+def ring_items(boxes, colour, thickness=3, canvas_hw=None, device=None):
+    """The photo with boxes ringed (`utils.show(img, boxes)`): the base image over the whole (H, W) canvas, then every box as a ring of
+    `colour` with nothing inside.  boxes None: the base alone.  The items live where the boxes live (`device` where there are none)."""
+    h, w = canvas_hw
+    dev = boxes.device if torch.is_tensor(boxes) else torch.device('cpu' if device is None else device)
+    base = _items(torch.tensor([[0.0, 0.0, float(w), float(h)]], device=dev), R.SRC_BASE, BLACK, 0)
+    if boxes is None or not boxes.numel():
+        return base
+    return Items.cat([base, _items(boxes, R.SRC_NONE, colour, thickness)])
+
+
+class Strokes:
+    """A stroke list of the stroke rule: `ends` (n, 4) float32 ax ay bx by in canvas pixels, `colour`, `radius` (n,) int32 (the radius
+    in half pixels, <= 0: the stroke is skipped), all on one device."""
+    __slots__ = ('ends', 'colour', 'radius')
+
+    def __init__(self, ends, colour, radius):
+        self.ends, self.colour, self.radius = ends, colour, radius
+
+    def __len__(self):
+        return int(self.radius.numel())
+
+    def to(self, device):
+        return Strokes(*(getattr(self, n).to(device) for n in self.__slots__))
+
+    @staticmethod
+    def cat(lists):
+        lists = list(lists)
+        return Strokes(*(torch.cat([getattr(l, n) for l in lists]) for n in Strokes.__slots__))
+
+
+def graph_strokes(graph, boxes, keep=None, edge_colour=GRAPH_EDGE_COLOUR, node_colour=GRAPH_NODE_COLOUR, edge_radius=GRAPH_EDGE_RADIUS,
+                  node_radius=GRAPH_NODE_RADIUS):
+    """The drawing of a neighbour graph over its boxes (`utils.draw_planograph`): one stroke slot per (node, direction slot) of the
+    graph's `nbr` [n][8] table, node-major, then one disc -- a stroke of length zero -- per node, so the nodes lie over the edges and
+    the list has 9 n strokes whatever the graph holds: the host knows every size and no count is read back.  An empty slot (-1, or a
+    neighbour outside the graph) carries radius 0 and zero ends.  A node's position is its box's centre, ((x1 + x2) / 2, (y1 + y2) / 2)
+    in fp32.  graph: a `planograms_device.Graph` or its `nbr` table; boxes (n, 4) in canvas pixels -- the expected side's through
+    `expected_boxes_on_canvas`.  keep (n,) bool: only these nodes' discs and the edges between two of them (`matched_strokes`).  Pure
+    tensor code where the table lives (the boxes are brought there), without a wait."""
+    nbr = getattr(graph, 'nbr', graph)
+    dev = nbr.device
+    b = boxes.to(device=dev, dtype=torch.float32).reshape(-1, 4)
+    n = b.shape[0]
+    nbr = nbr.to(torch.int64).reshape(-1, 8)
+    if nbr.shape[0] != n:
+        raise ValueError(f'one box per node: {n} boxes for a graph of {nbr.shape[0]} nodes')
+    centre = torch.stack([(b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2], dim=1)
+    filled = (nbr >= 0) & (nbr < n)
+    to = nbr.clamp(0, max(n - 1, 0))
+    nodes = torch.ones(n, dtype=torch.bool, device=dev) if keep is None else keep.to(device=dev, dtype=torch.bool).reshape(n)
+    if keep is not None:
+        filled = filled & nodes[:, None] & nodes[to]
+    edges = torch.cat([centre[:, None, :].expand(n, 8, 2), centre[to]], dim=2)
+    edges = torch.where(filled[:, :, None], edges, torch.zeros_like(edges)).reshape(-1, 4)
+    i32 = lambda mask, value: torch.where(mask, int(value), 0).to(torch.int32).reshape(-1)
+    ends = torch.cat([edges, centre.repeat(1, 2)]).contiguous()
+    colour = torch.cat([torch.full((8 * n,), int(edge_colour), dtype=torch.int32, device=dev),
+                        torch.full((n,), int(node_colour), dtype=torch.int32, device=dev)])
+    return Strokes(ends, colour, torch.cat([i32(filled, edge_radius), i32(nodes, node_radius)]))
+
+
+def matched_strokes(graph, boxes, matched, whole=None, **style):
+    """`graph_strokes` of the subgraph the matched nodes induce (`ge.subgraph(nodes_e)`, cli/eval.py:335-342): the edges whose two ends
+    are matched and the matched nodes' discs, in the same 9 n slots.  matched (n,) bool, on any device
+    (`planograms_device.matched_nodes` makes it from a `DeviceMatching` without a wait).
+    whole: `graph_strokes(graph, boxes, **style)` where the caller has it -- the list is then that one with the radii of the slots that
+    leave the matched set zeroed (the same strokes painted; a slot of radius 0 keeps its ends)."""
+    if whole is None:
+        return graph_strokes(graph, boxes, keep=matched, **style)
+    nbr = getattr(graph, 'nbr', graph).to(torch.int64).reshape(-1, 8)
+    n = nbr.shape[0]
+    if len(whole) != 9 * n:
+        raise ValueError(f'the strokes of another graph: {len(whole)} for {n} nodes')
+    nodes = matched.to(device=nbr.device, dtype=torch.bool).reshape(n)
+    inside = nodes[:, None] & nodes[nbr.clamp(0, max(n - 1, 0))]          # (an empty slot has radius 0 in `whole` already)
+    return Strokes(whole.ends, whole.colour, torch.where(torch.cat([inside.reshape(-1), nodes]), whole.radius, torch.zeros_like(whole.radius)))
 
 
 def float_image_bytes(planes):
@@ -179,8 +281,9 @@ class ThumbnailAtlas:
 
     The set is read the way `Classifier._gallery_items` reads it (`num_workers` reader threads, in order).  An item's image is a
     gallery byte image, uint8 (h, w, 3), or the float (3, 256, 256) form in [-1, 1], quantised by
-    clamp(floor((x * 0.5 + 0.5) * 255 + 0.5), 0, 255) (`gallery_float_bytes`).  annotations: the classifier's, where given the set's
-    must equal them row by row (ValueError).
+    clamp(floor((x * 0.5 + 0.5) * 255 + 0.5), 0, 255) (`gallery_float_bytes`).  float_items='unit': a float item is (3, h, w) of any size
+    in [0, 1] instead -- what `datautils.SimpleFolderSet(train=False)` yields -- quantised by floor(clamp(x, 0, 1) * 255 + 0.5)
+    (`float_image_bytes`).  annotations: the classifier's, where given the set's must equal them row by row (ValueError).
 
     max_side: an image whose larger side exceeds it is reduced on the device by the compositor itself, rendered as one item into a
     canvas of `reduced_hw(h, w, max_side)` = (max(1, (h * max_side + m // 2) // m), max(1, (w * max_side + m // 2) // m)), m = max(h, w);
@@ -189,11 +292,16 @@ class ThumbnailAtlas:
     ValueError (`atlas_layout`)."""
     PASS = 256          # images reduced per launch
 
-    def __init__(self, sample_set, annotations=None, device=torch.device('cuda'), num_workers=0, max_side=128):
+    FLOAT_ITEMS = ('tanh', 'unit')
+
+    def __init__(self, sample_set, annotations=None, device=torch.device('cuda'), num_workers=0, max_side=128, float_items='tanh'):
         from .production import Classifier, is_gallery_bytes
         self.device, self.max_side = torch.device(device), max_side
         if max_side is not None and max_side < 1:
             raise ValueError('max_side is None or at least 1')
+        if float_items not in self.FLOAT_ITEMS:
+            raise ValueError(f'float_items is one of {self.FLOAT_ITEMS}, got {float_items!r}')
+        to_bytes = gallery_float_bytes if float_items == 'tanh' else float_image_bytes
         reader = types.SimpleNamespace(num_workers=num_workers, batch_size=self.PASS)
         chunks, hws, pending = [], [], []
 
@@ -209,7 +317,7 @@ class ThumbnailAtlas:
             if not is_gallery_bytes(img):
                 if not (torch.is_tensor(img) and img.is_floating_point() and img.dim() == 3 and img.shape[0] == 3):
                     raise TypeError(f'a gallery item is a uint8 (h,w,3) or a float (3,S,S) image, got {type(img).__name__} {tuple(getattr(img, "shape", ()))}')
-                img = gallery_float_bytes(img)
+                img = to_bytes(img)
             if img.shape[0] < 1 or img.shape[1] < 1:
                 raise ValueError(f'gallery item {r} is empty')
             hws.append(reduced_hw(img.shape[0], img.shape[1], max_side))
@@ -259,14 +367,35 @@ class SceneRenderer:
         self.device = atlas.data.device
         self.align = align          # canvases start at multiples of this many bytes of the flat output (4: dword stores where W * 3 allows)
 
-    def render(self, item_lists, canvas_hws, bases=None, background=WHITE):
+    def render(self, item_lists, canvas_hws, bases=None, background=WHITE, strokes=None):
         """item_lists[c] (`Items`, on any device) painted into a canvas of canvas_hws[c] = (H, W), over `background` -> a list of device
         uint8 (H, W, 3) views of ONE flat buffer.  One launch, no wait: the host knows every size.  bases[c]: the base image `src = -2`
         names, or None.  A byte image (H, W, 3) is used where it lies when all bases of the call are views of one allocation (else
         their bytes are joined by one copy); float planes (3, H, W) become bytes first by floor(clamp(x, 0, 1) * 255 + 0.5)
-        (`float_image_bytes`, torch operations on the device)."""
+        (`float_image_bytes`, torch operations on the device).
+        strokes[c] (`Strokes`, on any device, or None): drawn over canvas c by a second launch on the same flat buffer
+        (csrc/strokes.hip), again without a wait; None, or no stroke in any list: exactly the call above."""
         out, table = self._launch(item_lists, canvas_hws, bases, background)
+        if strokes is not None:
+            self._draw(out, table, strokes)
         return [out[row[1]:row[1] + row[2] * row[3] * 3].view(row[2], row[3], 3) for row in table]
+
+    def _draw(self, out, table, strokes):
+        """the stroke launch over the canvases of `table` that have strokes: only their tiles are in its grid"""
+        if len(strokes) != len(table):
+            raise ValueError('one stroke list or None per canvas')
+        rows, lists, tile, k = [], [], 0, 0
+        for row, s in zip(table, strokes):
+            if s is not None and len(s):
+                rows.append((tile, row[1], row[2], row[3], k, k + len(s)))
+                lists.append(s if s.radius.device == self.device else s.to(self.device))
+                tile, k = tile + S.tiles(row[2], row[3]), k + len(s)
+        if not rows:
+            return
+        every = Strokes.cat(lists)
+        canvases = torch.tensor(rows, dtype=torch.int64).to(self.device, non_blocking=True)
+        self.last_strokes = (canvases, tile, every.ends, every.colour, every.radius)   # (the op's inputs: tools/bench_step_pictures.py times the launch alone)
+        torch.ops.cvpce_amd.strokes_draw(*self.last_strokes, out)
 
     def _launch(self, item_lists, canvas_hws, bases, background):
         """-> (the flat output, the canvas table as host rows)"""
@@ -341,3 +470,19 @@ class CompliancePictures:
             Image.fromarray(getattr(self, name).cpu().numpy(), 'RGB').save(path)
             paths.append(path)
         return paths
+
+
+class StepPictures(CompliancePictures):
+    """The comparison of one shelf image step by step, device uint8 (H, W, 3), in the order `plot-planogram-eval` and
+    `misc pipeline-demo` show them: `detections` (the photo with every detection ringed), `positions` (the photo with every projected
+    expected position ringed: `utils.show(img, expected_positions)`), `expected_graph` and `observed_graph` (the rebuilt planograms with
+    their neighbour graphs drawn over them), `expected_matched` and `observed_matched` (the same with the common subgraph the matcher
+    found), then `CompliancePictures`' three, byte for byte.  An image without a matching has no strokes on its graph pictures, and one
+    without a homography no rings on `positions`."""
+    NAMES = ('detections', 'positions', 'expected_graph', 'observed_graph', 'expected_matched', 'observed_matched') + CompliancePictures.NAMES
+
+    def __init__(self, *pictures):
+        if len(pictures) != len(self.NAMES):
+            raise ValueError(f'{len(self.NAMES)} pictures: {", ".join(self.NAMES)}')
+        for name, picture in zip(self.NAMES, pictures):
+            setattr(self, name, picture)
